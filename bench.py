@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - throughput of the SAMAudio.separate() hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (ranks read
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) and as a plain `python bench.py --gpus N`, which re-executes
@@ -58,6 +58,7 @@ import os
 import socket
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -137,7 +138,14 @@ def parse(argv=None):
                          "on the same weights reuse the main run's oracle pass for their parity_check")
     ap.add_argument("--selftest-spawn", action="store_true",
                     help="CPU-only: exercise the self-launch + sharding + gather plumbing on gloo (tests/test_bench_spawn_cpu.py)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller (target and residual waveforms, "
+                         "the noise it drew) as DIR/<name>.npy in float32, at most 64 MB in all (see dump_outputs); the inputs "
+                         "are seeded, so two builds run with the same arguments can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def log(msg):
@@ -523,6 +531,33 @@ def other_configs(args):
     return out
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(res, out_dir, rank=0, world=1):
+    """--dump-outputs: the SeparationResult of the last timed step - target and residual waveforms [clips, ...] and the noise
+    separate() drew [rows, T, 256] - as out_dir/{target,residual,noise}.npy in float32 (`_rank<r>` appended with N > 1 ranks).
+    When the whole result is over this rank's share of DUMP_BYTES (the default workload's is 131 MB), every array keeps the
+    same fraction of its elements: the flat indices np.sort(np.random.default_rng(0).choice(numel, k, replace=False)), which
+    depend only on the array's size, so two runs of the same arguments store the same positions."""
+    import numpy as np
+    import torch
+    arrays = {"target": torch.stack(res.target), "residual": torch.stack(res.residual), "noise": res.noise}
+    total = 4 * sum(a.numel() for a in arrays.values())
+    budget = DUMP_BYTES // world - 1024 * len(arrays)   # room for the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        a = a.detach().float()
+        if total > budget:
+            k = a.numel() * budget // total
+            idx = np.sort(np.random.default_rng(0).choice(a.numel(), size=k, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        out = a.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), out)
+        log(f"dump-outputs: {name}{suffix}.npy {list(out.shape)}" + (" (seeded sample)" if total > budget else ""))
+
+
 def hip_classes():
     from sam_audio_amd import hip
     return hip.CLASSES
@@ -542,7 +577,8 @@ class _HashTokenizer:
 
     def __call__(self, text, return_tensors="pt", padding="longest", max_length=512, truncation=True, **_):
         import torch
-        rows = [[1] + [3 + (hash(w) % 30000) for w in t.split()][: max_length - 1] for t in text]
+        # crc32, not hash(): str hashes are salted per process, and the same prompt must give the same ids in every run
+        rows = [[1] + [3 + (zlib.crc32(w.encode()) % 30000) for w in t.split()][: max_length - 1] for t in text]
         width = max(len(r) for r in rows)
         ids = torch.zeros(len(rows), width, dtype=torch.long)
         att = torch.zeros(len(rows), width, dtype=torch.long)
@@ -871,7 +907,7 @@ def run(args):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         assert all(torch.isfinite(w).all() for w in res.target), "non-finite output"
-        return elapsed, step
+        return elapsed, step, res
 
     # ---- the timed run ------------------------------------------------------------------------------------
     if args.scaling == "weak":
@@ -888,7 +924,12 @@ def run(args):
     model.tail_split = (n_streams == 1) if os.environ.get("SAMAUDIO_BENCH_TAIL_SPLIT") is None else bool(int(os.environ["SAMAUDIO_BENCH_TAIL_SPLIT"]))
     SPLIT_MODE[0] = n_streams == 1
     log(f"inputs resident ({len(my_ids)} clips on this rank, {n_streams} stream(s)); warm-up")
-    elapsed, step = timed(batch, args.steps, args.warmup, args.scaling)
+    # the noise separate() draws on the device: seeded, so that the same arguments give the same inputs in every run
+    torch.cuda.manual_seed(1234 + rank)
+    elapsed, step, res = timed(batch, args.steps, args.warmup, args.scaling)
+    if args.dump_outputs:   # before any later separate() call reuses the buffers the result may live in
+        dump_outputs(res, args.dump_outputs, rank, world)
+    del res
     value = clips_total * CLIP_SECONDS * args.steps / elapsed
     log(f"timed {args.steps} steps in {elapsed:.3f} s -> {value:.2f} s-audio/s")
 
@@ -940,7 +981,7 @@ def run(args):
         o_batch = make_batch(o_ids)[0]
         o_steps = max(2, min(args.steps, 5))
         model.streams = auto_streams(len(o_ids))
-        o_elapsed, _ = timed(o_batch, o_steps, 1, other)
+        o_elapsed, _, _ = timed(o_batch, o_steps, 1, other)
         strong = {"scaling": other, "global_batch": o_total, "clips_per_gpu": len(o_ids), "steps": o_steps,
                   "ms_per_step": round(1e3 * o_elapsed / o_steps, 2), "streams_per_gpu": model.streams,
                   "value": round(o_total * CLIP_SECONDS * o_steps / o_elapsed, 3), "unit": "s-audio/s"}

@@ -11,9 +11,11 @@ For each case it
   4. stores the REFERENCE outputs (not the oracle's) as the fixture.
 Integer fixture: Batch.process_anchors (processor.py:78-124) on a table of (start, end) spans that
 includes exact multiples of the 0.04 s frame period.
+Key fixture: the state-dict keys of the reference's own module tree at 'tiny' dims (ref_keys_tiny.json).
 """
 from __future__ import annotations
 
+import json
 import os
 import sys
 
@@ -158,6 +160,34 @@ def run_anchor_table():
              ids_none=none_batch.anchor_ids.numpy(), alignment_none=none_batch.anchor_alignment.numpy())
 
 
+def reference_state_dict_keys(size="tiny"):
+    """The non-codec state-dict keys of the reference's own module tree at `size` dims: its DiT, AlignModalities,
+    EmbedAnchors and the two Linear layers under the attribute names of reference model.py:80-93 (the reference SAMAudio
+    itself cannot be instantiated offline: dacvae / perception_models are absent)."""
+    ref_import.import_reference()
+    from sam_audio.model.align import AlignModalities
+    from sam_audio.model.config import TransformerConfig as RefTC
+    from sam_audio.model.model import EmbedAnchors
+    from sam_audio.model.transformer import DiT
+    cfg = preset_config(size)
+    t = cfg.transformer
+    with torch.device("meta"):
+        dit = DiT(RefTC(dim=t.dim, n_heads=t.n_heads, n_layers=t.n_layers, context_dim=t.context_dim))
+        align = AlignModalities(cfg.vision_encoder.dim, t.dim)
+        anchors = EmbedAnchors(cfg.num_anchors, cfg.anchor_embedding_dim, t.dim)
+    keys = {"transformer." + k for k in dit.state_dict()}
+    keys |= {"align_masked_video." + k for k in align.state_dict()}
+    keys |= {"embed_anchors." + k for k in anchors.state_dict()}
+    keys |= {"proj.weight", "proj.bias", "memory_proj.weight", "memory_proj.bias"}   # model.py:84,91
+    return sorted(keys)
+
+
+def run_ref_keys():
+    with open(os.path.join(GOLDEN_DIR, "ref_keys_tiny.json"), "w") as f:
+        json.dump(reference_state_dict_keys("tiny"), f, indent=0)
+        f.write("\n")
+
+
 def main():
     os.makedirs(GOLDEN_DIR, exist_ok=True)
     torch.set_num_threads(max(1, os.cpu_count() or 1))
@@ -166,6 +196,8 @@ def main():
         print(name, {k: f"{e:.2e}/{s:.2f}" for k, (e, s) in rep.items()})
     run_anchor_table()
     print("anchor table OK")
+    run_ref_keys()
+    print("reference state-dict keys OK")
 
 
 if __name__ == "__main__":
