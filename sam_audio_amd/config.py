@@ -181,6 +181,8 @@ class TransformerConfig:
             problems.append("t_block_non_linearity must be 'silu'")
         if self.frequency_embedding_dim % 64:
             problems.append("frequency_embedding_dim must be a multiple of 64")
+        if self.ffn_hidden % 64:   # w2's K axis: every GEMM form (fp32, 16-bit, split operands over K' = 3F) steps K by 64
+            problems.append(f"ffn_hidden must be a multiple of 64 (got {self.ffn_hidden}: multiple_of={self.multiple_of})")
         if problems:
             raise NotImplementedError(
                 "TransformerConfig outside the HIP path's supported family: " + "; ".join(problems)

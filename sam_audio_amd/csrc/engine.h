@@ -97,10 +97,15 @@ class Engine {
   // whole K (A rows [lo | hi | hi], W rows [W_hi | W_lo | W_hi]: the launch may share operand tiles, common.h GEMM_FLAG_X3_SHARE); mode 3: the same
   // with K' split per input block (the convolutions of gemm_codec_x3 / the patcher: [block][3 Cin]) - a plain walk over K' only
   Status gemm(const GemmParams& p, hipStream_t st, double alg_flops = -1.0, int cls = 0, int mode = 0);
+  GemmParams launch_params(const GemmParams& p_in, int cls, int mode) const;   // the tag / flags gemm() launches p_in with
   // SAMAUDIO_OPT_X3_CLASSES: `p` = the fp32 context's plain launch (fp32 A rows, fp32-typed outputs) of a class that is switched
   // on; `w3` = its "<name>.x3" weight.  Splits A into the scratch operand [lo | hi | hi] and runs ONE 16-bit GEMM over K' = 3K.
   // `presplit`: the activation operand is already in its split form at that address (written by the kernel that produced it)
-  Status gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, int cls, const void* presplit = nullptr);
+  // `presplit`: A already split; otherwise gemm_x3 splits it into x3a, or into x3u when `ffn_wide` (w2's F-wide operand)
+  Status gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, int cls, const void* presplit = nullptr, bool ffn_wide = false);
+  static void x3_operands(GemmParams& p, const void* a3, const void* w3, bool ktm);
+  // the launch gemm_x3 would make of `p` with GEMM_FLAG_OUT_SPLIT3 passes gemm_check (the 8-phase family takes it)
+  bool x3_split3_out_ok(GemmParams p, const void* w3, bool ktm, void* out3) const;
   bool x3(int cls) const { return !bf16_ && (x3_classes_ & cls) != 0; }
   // SAMAUDIO_OPT_X3_CLASSES bit CODEC, convolutions with >= 256 output channels whose weight has a registered "<name>.x3" twin
   // ([N, K / Cin, 3 Cin]: every Cin-block of a weight row as [W_hi | W_lo | W_hi]): the fp32 activation buffer is split row by row
@@ -210,6 +215,7 @@ class Engine {
     float *temb32, *tu32, *tsilu32, *xn32, *prep32, *mem32, *yu32, *yemb32;  // fp32 operands of the f32 classes (16-bit contexts)
     unsigned char *pad_mask, *text_mask;
     double* gn_part;
+    size_t x3a_bytes, x3u_bytes;   // capacities of x3a / x3u (gemm_x3 refuses a split that would not fit)
   } d_;
 };
 

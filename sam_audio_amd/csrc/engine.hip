@@ -392,7 +392,8 @@ Status Engine::plan_dit(Bump& b, int rows, int T, int Lt, bool assign) {
   auto act = [&](long n) { return b.take((size_t)n * esz_); };
   auto& d = d_;
   float* ymid = f32(M * C2); float* aligned = f32(M * D); float* cond = f32(M * D); float* h = f32(M * D);
-  float* hp1 = f32(M * D); float* text_proj = f32(Mt * D); float* t_emb = f32(nt * D); float* t0 = f32(nt * 6 * D);
+  // (hp1 also stages the per-clip text projection of a prepare with candidates: B * Lt <= rows * Lt rows of it)
+  float* hp1 = f32((M > Mt ? M : Mt) * D); float* text_proj = f32(Mt * D); float* t_emb = f32(nt * D); float* t0 = f32(nt * 6 * D);
   float* tsin = f32(nt * D); float* vtmp = f32(M * D); float* times = f32(4096);
   float* modgs = f32(2L * cfg_.n_layers * nt * 2 * D);   // pre-combined RMSNorm + modulate operands of an evaluation
   void* ybf = act(M * C2); void* xn = act(M * D); void* qkv = act(M * 3 * D);
@@ -421,10 +422,14 @@ Status Engine::plan_dit(Bump& b, int rows, int T, int Lt, bool assign) {
   const bool fold_all = cfg_.n_layers <= kMaxFoldLayers;
   void* ut = fold ? act((long)rows * D * kp * (fold_all ? cfg_.n_layers : 1)) : nullptr;
   // SAMAUDIO_OPT_X3_CLASSES: the split activation operand [lo | hi | hi] of the widest GEMM input (16-bit, 3 K elements per row)
-  // (x3a: D-wide operands and the patcher's halo-padded rows; x3u: the SwiGLU hidden, written by the w13 launch while it reads x3a)
+  // (x3a: D-wide operands - the M frame rows, the Mt text rows of class CKV - and the patcher's halo-padded rows; x3u: the SwiGLU
+  // hidden, written by the w13 launch while it reads x3a)
   const bool x3g = !bf16_ && (x3_classes_ & ~(SAMAUDIO_X3_ATTENTION | SAMAUDIO_CLS_CODEC));
-  void* x3a = x3g ? b.take((size_t)rows * (T + 2) * 3 * (size_t)D * 2) : nullptr;
-  void* x3u = x3g ? b.take((size_t)M * 3 * (size_t)F * 2) : nullptr;
+  const long x3a_rows = (long)rows * (T + 2) > Mt ? (long)rows * (T + 2) : Mt;
+  const size_t x3a_bytes = x3g ? (size_t)x3a_rows * 3 * (size_t)D * 2 : 0;
+  void* x3a = x3g ? b.take(x3a_bytes) : nullptr;
+  const size_t x3u_bytes = x3g ? (size_t)M * 3 * (size_t)F * 2 : 0;
+  void* x3u = x3g ? b.take(x3u_bytes) : nullptr;
   // folded cross-attention on compensated operands (class CWO of an x3 context, short memory, 128-wide heads): probabilities
   // [M][3 kp] and the per-batch operands of all layers [L][rows][D][3 kp]
   const bool fold3 = x3g && (x3_classes_ & SAMAUDIO_CLS_CWO) && Lt <= 16 && D / cfg_.n_heads == 128 && cfg_.n_layers <= kMaxFoldLayers &&
@@ -440,7 +445,7 @@ Status Engine::plan_dit(Bump& b, int rows, int T, int Lt, bool assign) {
     d.Vt = Vt; d.attn = attn; d.hbf = hbf; d.qc = qc; d.ca = ca; d.u = u; d.gnbuf = gnbuf; d.mem = mem; d.yu = yu;
     d.yemb = yemb; d.kvc = kvc; d.temb = temb; d.tu = tu; d.tsilu = tsilu; d.feats = feats; d.text = text;
     d.video = video; d.anch = anch; d.temb32 = temb32; d.tu32 = tu32; d.tsilu32 = tsilu32; d.xn32 = xn32; d.prep32 = prep32;
-    d.mem32 = mem32; d.yu32 = yu32; d.yemb32 = yemb32; d.probs = probs; d.ut = ut; d.x3a = x3a; d.x3u = x3u; d.x3p = x3p; d.ut3 = ut3; d.pad_mask = pad_mask; d.text_mask = text_mask; d.gn_part = gn_part;
+    d.mem32 = mem32; d.yu32 = yu32; d.yemb32 = yemb32; d.probs = probs; d.ut = ut; d.x3a = x3a; d.x3a_bytes = x3a_bytes; d.x3u = x3u; d.x3u_bytes = x3u_bytes; d.x3p = x3p; d.ut3 = ut3; d.pad_mask = pad_mask; d.text_mask = text_mask; d.gn_part = gn_part;
   }
   return Status{};
 }
@@ -644,6 +649,27 @@ static int cls_slot(int cls) {
   return bit;
 }
 
+// the tag and flags a launch of gemm() runs with (x3_split3_out_ok dry-runs gemm_check on them)
+GemmParams Engine::launch_params(const GemmParams& p_in, int cls, int mode) const {
+  const bool f32 = mode == 1;
+  GemmParams p = p_in;
+  p.tag = prof_cls_[0] == 'c' ? 1 : 0;  // codec launches run under their own kernel symbols
+  // bit 1: no tail split (gemm.hip gemm_tail_split); bit 9 (from the caller): 16-bit output in the alt format; bit 10: operands
+  // in the alt format (SAMAUDIO_OPT_ALT16_CLASSES, mixed mode)
+  // bit 11 (from the caller): W is K-tile-major
+  p.flags = (p_in.flags & (512 | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split_ ? 0 : 2) | (alt16(cls) && !f32 ? 1024 : 0);
+  if (p.tag) cls = SAMAUDIO_CLS_CODEC;
+  // an x3 launch on K-concatenated split operands: let the 8-phase kernels share the operand tiles the three products have in common
+  // (common.h GEMM_FLAG_X3_SHARE) wherever the launch qualifies; debug flag 38 = 1: the plain walk over K' (A/B, tests)
+  // mode 3 (the convolutions: every Cin-block of K' is its own [hi | lo | hi]) never qualifies
+  if (mode == 2 && debug_flag(38) != 1 && (debug_flag(38) < 2 || (cls & (debug_flag(38) >> 1)))) {   // (flag 38 >= 2: class mask << 1, diagnosis)
+    GemmParams q = p;
+    q.flags |= GEMM_FLAG_X3_SHARE;
+    if (q.kc == q.K && q.K % 192 == 0 && !gemm_check(q, true)) p = q;
+  }
+  return p;
+}
+
 Status Engine::gemm(const GemmParams& p_in, hipStream_t st, double alg_flops, int cls, int mode) {
   const bool f32 = mode == 1, x3m = mode == 2 || mode == 3;   // mode 3: an x3 launch whose K' is split per input block, not as a whole
   const bool is16 = bf16_ || x3m;   // the launch's operand format (an X3 launch: 16-bit operands inside an fp32 context)
@@ -674,21 +700,8 @@ Status Engine::gemm(const GemmParams& p_in, hipStream_t st, double alg_flops, in
         return gemm_codec_x3(p_in, it->second, st, alg_flops);
     }
   }
-  GemmParams p = p_in;
-  p.tag = prof_cls_[0] == 'c' ? 1 : 0;  // codec launches run under their own kernel symbols
-  // bit 1: no tail split (gemm.hip gemm_tail_split); bit 9 (from the caller): 16-bit output in the alt format; bit 10: operands
-  // in the alt format (SAMAUDIO_OPT_ALT16_CLASSES, mixed mode)
-  // bit 11 (from the caller): W is K-tile-major
-  p.flags = (p_in.flags & (512 | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split_ ? 0 : 2) | (alt16(cls) && !f32 ? 1024 : 0);
+  GemmParams p = launch_params(p_in, cls, mode);
   if (p.tag) cls = SAMAUDIO_CLS_CODEC;
-  // an x3 launch on K-concatenated split operands: let the 8-phase kernels share the operand tiles the three products have in common
-  // (common.h GEMM_FLAG_X3_SHARE) wherever the launch qualifies; debug flag 38 = 1: the plain walk over K' (A/B, tests)
-  // mode 3 (the convolutions: every Cin-block of K' is its own [hi | lo | hi]) never qualifies
-  if (mode == 2 && debug_flag(38) != 1 && (debug_flag(38) < 2 || (cls & (debug_flag(38) >> 1)))) {   // (flag 38 >= 2: class mask << 1, diagnosis)
-    GemmParams q = p;
-    q.flags |= GEMM_FLAG_X3_SHARE;
-    if (q.kc == q.K && q.K % 192 == 0 && !gemm_check(q, true)) p = q;
-  }
   if (f32) {  // a class of SAMAUDIO_OPT_F32_CLASSES: exact-fp32 kernel inside a 16-bit context
     if (!p.W) return fail(SAMAUDIO_ERR_WEIGHT, "SAMAUDIO_OPT_F32_CLASSES: the class's \"<name>.f32\" weight copy is not registered");
     if (const char* why = gemm_check(p, false)) return fail(SAMAUDIO_ERR_ARG, why);
@@ -740,15 +753,27 @@ Status Engine::gemm(const GemmParams& p_in, hipStream_t st, double alg_flops, in
   return Status{};
 }
 
-Status Engine::gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, int cls, const void* presplit) {
+Status Engine::gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, int cls, const void* presplit, bool ffn_wide) {
   if (!w3 || !d_.x3a) return fail(SAMAUDIO_ERR_STATE, "SAMAUDIO_OPT_X3_CLASSES: split weight or scratch operand missing (set the option before samaudio_prepare)");
   if (p.nbatch != 1 || p.kc != p.K || p.a_off || p.tap_stride || (p.out_act && p.out_f32))
     return fail(SAMAUDIO_ERR_ARG, "SAMAUDIO_OPT_X3_CLASSES: plain single-batch launches with one output only");
   const int K = p.K;
-  // algorithmic bytes of the split: the fp32 row in, three 16-bit copies out
-  if (!presplit)
-    SA_TRY(op("split3", (double)p.M * K * (4 + 6), 0, st, [&] { return launch_split3((const float*)p.A, p.lda, d_.x3a, p.M, K, st); }));
-  p.A = presplit ? presplit : d_.x3a; p.lda = 3L * K; p.K = 3 * K; p.kc = 3 * K; p.W = w3;
+  if (!presplit) {   // split the fp32 operand here: into x3a (D-wide rows), or - w2's F-wide hidden - into x3u
+    void* const dst = ffn_wide ? d_.x3u : d_.x3a;
+    if ((size_t)p.M * 3 * K * 2 > (ffn_wide ? d_.x3u_bytes : d_.x3a_bytes))
+      return fail(SAMAUDIO_ERR_WORKSPACE, "SAMAUDIO_OPT_X3_CLASSES: the split operand does not fit the scratch the workspace plan holds");
+    // algorithmic bytes of the split: the fp32 row in, three 16-bit copies out
+    SA_TRY(op("split3", (double)p.M * K * (4 + 6), 0, st, [&] { return launch_split3((const float*)p.A, p.lda, dst, p.M, K, st); }));
+    presplit = dst;
+  }
+  x3_operands(p, presplit, w3, ktm);
+  return gemm(p, st, 2.0 * p.M * (double)p.N * K, cls, 2);   // flops as the reference counts them: one product over K
+}
+
+// the 16-bit launch over K' = 3K that an x3 class makes of its fp32 GemmParams: A = the split operand, W = the split weight
+void Engine::x3_operands(GemmParams& p, const void* a3, const void* w3, bool ktm) {
+  const int K = p.K;
+  p.A = a3; p.lda = 3L * K; p.K = 3 * K; p.kc = 3 * K; p.W = w3;
   if (p.out_act) {   // an fp32 context's "activation" outputs are fp32 tensors: the 16-bit kernel writes them as its fp32 output
     p.out_f32 = (float*)p.out_act; p.f32_ld = p.act_ld; p.f32_bstride = p.act_bstride; p.f32_off = p.act_off;
     p.f32_act = p.act != ACT_NONE;
@@ -759,7 +784,13 @@ Status Engine::gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, i
     p.out_act = p.out_f32; p.act_ld = 3L * (p.swiglu ? p.N / 2 : p.N); p.act_bstride = p.act_off = 0;
     p.out_f32 = nullptr; p.f32_ld = p.f32_bstride = p.f32_off = 0; p.f32_act = 0;
   }
-  return gemm(p, st, 2.0 * p.M * (double)p.N * K, cls, 2);   // flops as the reference counts them: one product over K
+}
+
+bool Engine::x3_split3_out_ok(GemmParams p, const void* w3, bool ktm, void* out3) const {
+  p.out_act = out3;
+  p.flags |= GEMM_FLAG_OUT_SPLIT3;
+  x3_operands(p, d_.x3a, w3, ktm);
+  return gemm_check(launch_params(p, SAMAUDIO_CLS_W13, 2), true) == nullptr;   // the parameters gemm() would launch
 }
 
 Status Engine::gemm_codec_x3(const GemmParams& p_in, const X3CodecW& w, hipStream_t st, double alg_flops) {
@@ -928,7 +959,8 @@ Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float*
   const int D = cfg_.dim, C2 = cfg_.latent_channels;
   const long M = (long)rows * T, Mt = (long)rows * Lt;
   // the conditioning is computed once per CLIP (B = rows / candidates of them) and then repeated for the clip's candidates: the
-  // per-clip results live in buffers the evaluations overwrite anyway (aligned, hp1) until the repeat kernels have read them
+  // per-clip results live in buffers the evaluations overwrite anyway (aligned, hp1 - which plan_dit sizes for Lt > T too) until the
+  // repeat kernels have read them
   const int B = rows / cand;
   const long Mb = (long)B * T, Mtb = (long)B * Lt;
   float* const cond_b = cand > 1 ? d_.aligned : d_.cond;
@@ -1155,8 +1187,11 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
   }
   trace("kvc", d_.kvc, (size_t)Mt * kv_ld, bf16_, st);
   // folded cross-attention: U_l = Wo_l V_l of EVERY layer in one launch (it depends on the text memory only, not on h)
-  const bool fold_all = fold_ltp_ && !fold3_ && cfg_.n_layers <= kMaxFoldLayers && !debug_flag(31);   // flag 31: one launch per layer (A/B, tests)
-  if (fold3_) {   // x3 context: U = Wo V of every layer on split operands, [L][rows][D][3 kp] = [U_hi | U_lo | U_hi]
+  // the fold on compensated operands as prepare() set it up - unless class CWO was switched off since: then the unfolded path
+  const bool fold3 = fold3_ && x3(SAMAUDIO_CLS_CWO);
+  const int fold_ltp = fold3_ && !fold3 ? 0 : fold_ltp_;
+  const bool fold_all = fold_ltp && !fold3 && cfg_.n_layers <= kMaxFoldLayers && !debug_flag(31);   // flag 31: one launch per layer (A/B, tests)
+  if (fold3) {   // x3 context: U = Wo V of every layer on split operands, [L][rows][D][3 kp] = [U_hi | U_lo | U_hi]
     const float* wos[kMaxFoldLayers];
     for (int l = 0; l < cfg_.n_layers; ++l) wos[l] = (const float*)layers_[l].c_wo;
     SA_TRY(op("cross_attn_fold3", ((double)D * D * 4 + (double)rows * D * fold_kp_ * 6 + (double)Mt * D * 4) * cfg_.n_layers, 0, st, [&] {
@@ -1187,7 +1222,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     // compensated operands (fp32 contexts): the producers write the split form [lo | hi | hi] themselves where they can
     const bool qkv_pre = x3(SAMAUDIO_CLS_QKV) && mod_gs, w13_pre = x3(SAMAUDIO_CLS_W13) && mod_gs;
     const bool wo_pre = x3(SAMAUDIO_CLS_WO) && x3(SAMAUDIO_X3_ATTENTION);
-    const bool w2_pre = x3(SAMAUDIO_CLS_W2) && x3(SAMAUDIO_CLS_W13) && F % 16 == 0;
+    bool w2_pre = false;   // (decided with the w13 launch below)
     SA_TRY(op("rmsnorm_mod", MD * (4 + (qkv_pre ? 6 : esz_)), 0, st, [&] {
       if (qkv_pre)
         return launch_rmsnorm_gs_split3(d_.h, d_.modgs + (2L * l) * nt * 2 * D, gs_ld, d_.x3a, (int)M, D, T, eps, st);
@@ -1256,7 +1291,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_CWQ));
     }
     const void* kv_l = (const char*)d_.kvc + (size_t)l * 2 * D * esz_;
-    if (fold3_) {
+    if (fold3) {
       // h += P . U on compensated operands: K' = 3 kp = 576 instead of 3 D
       SA_TRY(op("cross_attn_probs3", (MD * 4 + (double)M * fold_kp_ * 6 + (double)Mt * 2 * D * 4), 0, st, [&] {
         return launch_cross_attn_probs3((const float*)d_.qc, w.c_q_norm, (const float*)kv_l, kv_ld, d_.text_mask, d_.x3p, fold_kp_, rows, T, Lt,
@@ -1272,7 +1307,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       out_f32(p, d_.h, D);
       p.f32_bstride = (long)T * D;
       SA_TRY(gemm(p, st, 2.0 * M * (double)D * H * Lt, SAMAUDIO_CLS_CWO, 2));
-    } else if (fold_ltp_) {
+    } else if (fold_ltp) {
       // h += P . U with U = Wo V folded per (batch, head, token): K = H*Lt instead of D (see attention.hip)
       SA_TRY(op("cross_attn_probs", (MD + (double)M * fold_kp_ + (double)Mt * 2 * D) * esz_, 0, st, [&] {
         return launch_cross_attn_probs(d_.qc, w.c_q_norm, kv_l, kv_ld, d_.text_mask, d_.probs, fold_kp_, rows, T, Lt,
@@ -1325,7 +1360,10 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       ktm(p, w, 3);
       prefetch(p, w.w2, (double)D * F);
       if (x3(SAMAUDIO_CLS_W13)) {
-        if (w2_pre) { p.out_act = d_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }   // the SwiGLU epilogue writes w2's split operand itself
+        // the SwiGLU epilogue writes w2's split operand itself where the 8-phase family takes the launch (F % 32 == 0 among others);
+        // otherwise w2 splits u with the stand-alone kernel
+        w2_pre = x3(SAMAUDIO_CLS_W2) && x3_split3_out_ok(p, w.w13_3, w.ktm3 & 16, d_.x3u);
+        if (w2_pre) { p.out_act = d_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
         SA_TRY(gemm_x3(p, w.w13_3, w.ktm3 & 16, st, SAMAUDIO_CLS_W13, w13_pre ? d_.x3a : nullptr));
       }
       else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_W13));
@@ -1337,7 +1375,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       out_f32(p, d_.h, D);
       ktm(p, w, 4);
       if (l + 1 < cfg_.n_layers) prefetch(p, layers_[l + 1].wqkv, 3.0 * D * D);
-      if (x3(SAMAUDIO_CLS_W2)) SA_TRY(gemm_x3(p, w.w2_3, w.ktm3 & 32, st, SAMAUDIO_CLS_W2, w2_pre ? d_.x3u : nullptr));
+      if (x3(SAMAUDIO_CLS_W2)) SA_TRY(gemm_x3(p, w.w2_3, w.ktm3 & 32, st, SAMAUDIO_CLS_W2, w2_pre ? d_.x3u : nullptr, true));
       else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_W2));
       trace("  h after ffn", d_.h, (size_t)M * D, false, st);
     }

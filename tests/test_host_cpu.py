@@ -38,6 +38,9 @@ def test_config_defaults_match_reference_rule():
     SAMAudioConfig(transformer=dict(dim=2048, n_heads=32)).check_supported()   # head_dim 64: built since round 5
     with pytest.raises(NotImplementedError):
         SAMAudioConfig(transformer=dict(dim=2048, n_heads=64)).check_supported()   # head_dim 32 is not
+    # F = 688 ('tiny' with multiple_of=16): refused up front, not with an assertion deep in the weight conversion
+    with pytest.raises(NotImplementedError, match="ffn_hidden"):
+        preset_config("tiny", transformer=dict(multiple_of=16)).check_supported()
     with pytest.raises(TypeError):
         SAMAudioConfig(transformer=dict(bogus=1))
 

@@ -1,5 +1,7 @@
 """Helpers shared by the GPU parity tests: thin ctypes callers of the per-kernel C-ABI hooks."""
+import contextlib
 import ctypes as C
+import os
 
 import torch
 
@@ -69,3 +71,41 @@ def report(name, got, want, tol):
     print(f"{name}: max-abs err {err:.3e} (ref max {scale:.3f}, tol {tol:.1e})")
     assert err <= tol, f"{name}: {err} > {tol}"
     return err
+
+
+@contextlib.contextmanager
+def workspace_guard(model, guard: int = 4 << 20):
+    """Hand every engine context of `model` (its own and its stream lanes') exactly the workspace it asks for, followed by `guard`
+    bytes the test owns, and assert on exit that no kernel wrote into them.
+
+    Replaces `model._ensure_workspace` for the duration: each call allocates need + 256 + guard bytes filled with the poison byte
+    (conftest.py: SAMAUDIO_POISON), passes the engine the 256-byte aligned `need` bytes only - the codec sizes its chunks by the
+    workspace it is handed, so it must not see the guard - and keeps the buffer alive.  An out-of-bounds write past the workspace
+    plan then lands in memory of this test and becomes an assertion instead of a fault or a corrupted neighbour tensor."""
+    fill = int(os.environ.get("SAMAUDIO_POISON_BYTE", "255"), 0)
+    handed = []   # (buffer, offset of the aligned start, need)
+    owners = []   # whom each workspace went to (the model or one of its stream lanes): what the context manager yields
+
+    def ensure(rows, frames, text_len, codec_items, samples, lane=None):
+        own = lane if lane is not None else model
+        need = model._lib.samaudio_workspace_bytes(own._ctx, rows, frames, max(1, text_len), codec_items, samples)
+        ws = torch.full((need + 256 + guard,), fill, dtype=torch.uint8, device=model.device)
+        base = ws.data_ptr()
+        aligned = (base + 255) // 256 * 256
+        own._workspace = ws
+        handed.append((ws, aligned - base, need))
+        owners.append(own)
+        hip.check(model._lib.samaudio_set_workspace(own._ctx, C.c_void_p(aligned), need))
+
+    model._ensure_workspace = ensure
+    try:
+        yield owners
+        torch.cuda.synchronize()
+        for ws, off, need in handed:
+            host = ws.cpu()
+            for what, part in (("in front of", host[:off]), ("behind", host[off + need:])):
+                bad = (part != fill).nonzero()
+                assert bad.numel() == 0, (f"{bad.numel()} guard bytes {what} a {need}-byte workspace were written (first at "
+                                          f"{int(bad[0])} of {part.numel()})")
+    finally:
+        del model._ensure_workspace
