@@ -28,7 +28,11 @@ typedef void* samaudio_stream; /* hipStream_t */
 
 enum { SAMAUDIO_F32 = 0, SAMAUDIO_BF16 = 1 };           /* compute precision == dtype of GEMM operands */
 enum { SAMAUDIO_DT_F32 = 0, SAMAUDIO_DT_BF16 = 1, SAMAUDIO_DT_I64 = 2, SAMAUDIO_DT_U8 = 3 };
-enum { SAMAUDIO_ODE_EULER = 0, SAMAUDIO_ODE_MIDPOINT = 1 };
+/* ODE methods of samaudio_ode_solve, torchdiffeq's fixed-grid solvers.  EULER and MIDPOINT fold each
+ * step into the output GEMM's epilogue; RK4 (torchdiffeq's "rk4": the 3/8-rule variant, 4 evaluations per step, the last at the grid
+ * point t1) and HEUN3 (Heun's third-order method, 3 evaluations) write every stage's field into a stage buffer of their own
+ * (samaudio_set_ode_stages) and combine them in ode_stage_kernel. */
+enum { SAMAUDIO_ODE_EULER = 0, SAMAUDIO_ODE_MIDPOINT = 1, SAMAUDIO_ODE_RK4 = 2, SAMAUDIO_ODE_HEUN3 = 3 };
 
 enum {
   SAMAUDIO_OK = 0,
@@ -204,11 +208,22 @@ int samaudio_prepare_latent(samaudio_ctx* ctx, int rows, int frames, int text_le
 int samaudio_forward(samaudio_ctx* ctx, const float* noisy, const float* time, int n_time, float* out,
                      samaudio_stream stream);
 
-/* Fixed-grid ODE solve, replaces torchdiffeq.odeint at model.py:285-290 (method "midpoint" | "euler").
- * grid_host: n_grid increasing time points on the HOST (t0 .. t1); state [rows, frames, 256] f32 is updated
- * in place from the noise to states[-1]. */
+/* Fixed-grid ODE solve, replaces torchdiffeq.odeint at model.py:285-290 (method SAMAUDIO_ODE_*: "euler" | "midpoint" | "rk4" |
+ * "heun3").  grid_host: n_grid strictly increasing time points on the HOST (t0 .. t1); state [rows, frames, 256] f32 is updated
+ * in place from the noise to states[-1].  The evaluation times of a solve are handed to the device as kernel arguments into a
+ * table of 4096 floats: midpoint and euler take 2 * n_grid of them, rk4 / heun3 one per stage and step (4 resp. 3 * (n_grid - 1));
+ * a longer grid is SAMAUDIO_ERR_ARG.  rk4 / heun3 need the context's stage buffers (below): missing or too small =
+ * SAMAUDIO_ERR_WORKSPACE; a library built without ode_stage_kernel (the CPU launcher emulation) refuses them with
+ * SAMAUDIO_ERR_STATE. */
 int samaudio_ode_solve(samaudio_ctx* ctx, float* state, int method, const float* grid_host, int n_grid,
                        samaudio_stream stream);
+/* Stage buffers of the Runge-Kutta methods, borrowed from the caller like the workspace and apart from it (the workspace plan, and
+ * so samaudio_workspace_bytes, is the same for every method): one fp32 array of rows * frames * 256 elements per stage, each on a
+ * 256-byte boundary.  samaudio_ode_stage_bytes = what a solve of `method` over [rows, frames] needs (0 for euler and midpoint,
+ * which use none).  samaudio_set_ode_stages hands the context its buffer (256-byte aligned; NULL withdraws it); it must not overlap
+ * the workspace or the state, and each context of a process needs its own. */
+size_t samaudio_ode_stage_bytes(samaudio_ctx* ctx, int method, int rows, int frames);
+int samaudio_set_ode_stages(samaudio_ctx* ctx, void* stages, size_t bytes);
 
 /* DAC-VAE.  encode (codec.py:65-70): wav [items, samples] f32, samples % hop == 0 -> mean latent
  * [items, samples/hop, codec_dim] f32 (channels-last).  decode (codec.py:86-89):

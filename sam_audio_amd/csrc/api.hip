@@ -118,6 +118,16 @@ int samaudio_ode_solve(samaudio_ctx* ctx, float* state, int method, const float*
   return ret(ctx->engine->ode_solve(state, method, grid_host, n_grid, (hipStream_t)stream));
 }
 
+size_t samaudio_ode_stage_bytes(samaudio_ctx* ctx, int method, int rows, int frames) {
+  if (!ctx) return 0;
+  return ctx->engine->ode_stage_bytes(method, rows, frames);
+}
+
+int samaudio_set_ode_stages(samaudio_ctx* ctx, void* stages, size_t bytes) {
+  if (!ctx) return bad("null context");
+  return ret(ctx->engine->set_ode_stages(stages, bytes));
+}
+
 int samaudio_codec_encode(samaudio_ctx* ctx, const float* wav, int items, int64_t samples, float* latent,
                           samaudio_stream stream) {
   if (!ctx) return bad("null context");

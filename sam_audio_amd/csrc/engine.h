@@ -62,6 +62,10 @@ class Engine {
                  const uint8_t* pad_mask, hipStream_t st, int candidates = 1, bool latent_feats = false);
   Status forward(const float* noisy, const float* time, int n_time, float* out, hipStream_t st);
   Status ode_solve(float* state, int method, const float* grid_host, int n_grid, hipStream_t st);
+  // stage buffers of the Runge-Kutta methods (samaudio_set_ode_stages): borrowed, apart from the workspace
+  struct RkTableau;   // engine.hip: rk4 / heun3
+  size_t ode_stage_bytes(int method, int rows, int frames) const;
+  Status set_ode_stages(void* p, size_t bytes);
   Status codec_encode(const float* wav, int items, int64_t samples, float* latent, hipStream_t st);
   // `pairs`: latent is the ODE state [items / 2, frames, 2 * codec_dim] - item 2b = the first codec_dim channels of row b (target),
   // 2b + 1 the second (residual): reference model.py:291-295 without the transposed copy
@@ -149,6 +153,9 @@ class Engine {
   int prefetch_rows_ = 0;   // SAMAUDIO_OPT_PREFETCH_ROWS (16-bit contexts)
   int x3_classes_ = 0;      // SAMAUDIO_OPT_X3_CLASSES (fp32 contexts)
   Status solve_launches(float* y, int method, const float* grid, int n_grid, hipStream_t st);   // the launches of one solve
+  Status solve_rk(float* y, const RkTableau& tab, const float* grid, int n_grid, hipStream_t st);   // ... of rk4 / heun3
+  float* stages_ = nullptr;   // samaudio_set_ode_stages
+  size_t stages_bytes_ = 0;
   bool sentinel_on_ = false;   // SAMAUDIO_OPT_SENTINEL
   float* sentinel_dev_ = nullptr;   // [SAMAUDIO_SENTINEL_SLOTS][2] slots + [kSentinelPartials][2] partials (debug_device_alloc)
   // fold the scan of a tensor into `slot` (no-op unless the sentinel is on); fmt as launch_sentinel

@@ -1404,14 +1404,99 @@ Status Engine::forward(const float* noisy, const float* time, int n_time, float*
   return s;
 }
 
+// Explicit Runge-Kutta methods of torchdiffeq's fixed-grid family.  Stage i of a step t0 -> t1 = t0 + dt
+// evaluates k_i = f(t0 + c_i dt, y0 + dt * sum_j a_ij k_j); then y1 = y0 + dt * bscale * sum_j b_j k_j.  Coefficients in torchdiffeq's
+// grouping: rk4 is its rk4_alt_step_func (the 3/8 rule, last stage at the grid point t1), heun3 its Heun3 tableau.
+struct Engine::RkTableau {
+  int stages;
+  float c[4];
+  float a[4][4];
+  float b[4], bscale;
+  bool last_at_t1;
+};
+static const Engine::RkTableau* rk_tableau(int method) {
+  static const Engine::RkTableau rk4 = {4, {0.f, 1.f / 3, 2.f / 3, 1.f}, {{}, {1.f / 3}, {-1.f / 3, 1.f}, {1.f, -1.f, 1.f}},
+                                        {1.f, 3.f, 3.f, 1.f}, 0.125f, true};
+  static const Engine::RkTableau heun3 = {3, {0.f, 1.f / 3, 2.f / 3}, {{}, {1.f / 3}, {0.f, 2.f / 3}}, {0.25f, 0.f, 0.75f}, 1.f,
+                                          false};
+  return method == SAMAUDIO_ODE_RK4 ? &rk4 : method == SAMAUDIO_ODE_HEUN3 ? &heun3 : nullptr;
+}
+static size_t stage_stride(int rows, int frames, int C2) { return ((size_t)rows * frames * C2 * 4 + 255) & ~size_t(255); }
+
+size_t Engine::ode_stage_bytes(int method, int rows, int frames) const {
+  const RkTableau* tab = rk_tableau(method);
+  if (!tab || rows <= 0 || frames <= 0) return 0;
+  return (size_t)tab->stages * stage_stride(rows, frames, cfg_.latent_channels);
+}
+
+Status Engine::set_ode_stages(void* p, size_t bytes) {
+  if (reinterpret_cast<uintptr_t>(p) & 255) return fail(SAMAUDIO_ERR_WORKSPACE, "ode stage buffer must be 256-byte aligned");
+  stages_ = (float*)p;
+  stages_bytes_ = p ? bytes : 0;
+  return Status{};
+}
+
+static bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+  const char *pa = (const char*)a, *pb = (const char*)b;
+  return pa && pb && pa < pb + nb && pb < pa + na;
+}
+
 Status Engine::ode_solve(float* y, int method, const float* grid, int n_grid, hipStream_t st) {
   if (!prepared_) return fail(SAMAUDIO_ERR_STATE, "ode_solve: call samaudio_prepare first");
-  if (method != SAMAUDIO_ODE_EULER && method != SAMAUDIO_ODE_MIDPOINT)
+  const RkTableau* rk = rk_tableau(method);
+  if (method != SAMAUDIO_ODE_EULER && method != SAMAUDIO_ODE_MIDPOINT && !rk)
     return fail(SAMAUDIO_ERR_ARG, "ode_solve: unsupported method");
-  if (!y || !grid || n_grid < 2 || 2 * n_grid > 4096) return fail(SAMAUDIO_ERR_ARG, "ode_solve: bad grid");
+  // the evaluation times go into d_.times (4096 floats): two per grid point for euler / midpoint, one per stage and step for rk4 / heun3
+  const bool fits = rk ? (long)rk->stages * (n_grid - 1) <= 4096 : 2 * n_grid <= 4096;
+  if (!y || !grid || n_grid < 2 || !fits) return fail(SAMAUDIO_ERR_ARG, "ode_solve: bad grid");
   for (int k = 0; k + 1 < n_grid; ++k)
     if (!(grid[k + 1] > grid[k])) return fail(SAMAUDIO_ERR_ARG, "ode_solve: grid must be increasing");
-  return solve_launches(y, method, grid, n_grid, st);
+  if (!rk) return solve_launches(y, method, grid, n_grid, st);
+  if (!launch_ode_stage) return fail(SAMAUDIO_ERR_STATE, "ode_solve: rk4 / heun3 are not available in this build (no ode_stage_kernel)");
+  const size_t need = ode_stage_bytes(method, rows_, frames_);
+  if (!stages_ || stages_bytes_ < need)
+    return fail(SAMAUDIO_ERR_WORKSPACE, "ode_solve: rk4 / heun3 need samaudio_ode_stage_bytes() of stage buffers (samaudio_set_ode_stages)");
+  if (overlaps(stages_, need, ws_, ws_bytes_) || overlaps(stages_, need, y, (size_t)rows_ * frames_ * cfg_.latent_channels * 4))
+    return fail(SAMAUDIO_ERR_WORKSPACE, "ode_solve: the stage buffers overlap the workspace or the state");
+  return solve_rk(y, *rk, grid, n_grid, st);
+}
+
+Status Engine::solve_rk(float* y, const RkTableau& tab, const float* grid, int n_grid, hipStream_t st) {
+  const int s = tab.stages, steps = n_grid - 1;
+  const long n = (long)rows_ * frames_ * cfg_.latent_channels;
+  // stage times in torchdiffeq's float arithmetic (t0 + dt * c); all of them as kernel arguments: no host synchronisation
+  std::vector<float> ev((size_t)s * steps);
+  for (int k = 0; k < steps; ++k) {
+    const float t0 = grid[k], dt = grid[k + 1] - grid[k];
+    for (int i = 0; i < s; ++i)
+      ev[(size_t)s * k + i] = i == 0 ? t0 : (i == s - 1 && tab.last_at_t1) ? grid[k + 1] : t0 + dt * tab.c[i];
+  }
+  SA_HIP(launch_set_floats(d_.times, ev.data(), (int)ev.size(), st));
+  float* kbuf[4];
+  for (int i = 0; i < s; ++i) kbuf[i] = (float*)((char*)stages_ + i * stage_stride(rows_, frames_, cfg_.latent_channels));
+  for (int k = 0; k < steps; ++k) {
+    const float dt = grid[k + 1] - grid[k];
+    for (int i = 0; i < s; ++i) {
+      // k_i = f(t_i, stage input): stage 0 reads y0 itself, the others the combination the previous stage left in d_.ymid
+      SA_TRY(eval_field(i == 0 ? y : d_.ymid, d_.times + (size_t)s * k + i, 1, kbuf[i], nullptr, 1.f, st));
+      // then the next stage's input, or after the last stage y1 written over y0
+      const bool last = i == s - 1;
+      OdeStageArgs a{};
+      for (int j = 0; j <= i; ++j) {
+        const float c = last ? tab.b[j] : tab.a[i + 1][j];
+        if (c != 0.f) {
+          a.k[a.n_src] = kbuf[j];
+          a.coef[a.n_src++] = c;
+        }
+      }
+      const float scale = last ? dt * tab.bscale : dt;
+      float* out = last ? y : d_.ymid;
+      SA_TRY(op("ode_stage", (a.n_src + 2.0) * n * 4, 2.0 * (a.n_src + 1) * n, st,
+                [&] { return launch_ode_stage(y, a, scale, out, n, st); }));
+    }
+  }
+  if (hash_on()) hash_flush((HashTrace*)hash_, this, st);
+  return Status{};
 }
 
 Status Engine::solve_launches(float* y, int method, const float* grid, int n_grid, hipStream_t st) {

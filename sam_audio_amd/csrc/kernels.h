@@ -179,6 +179,18 @@ struct FloatPack {
 };
 hipError_t launch_set_floats(float* dst, const float* host_values, int n, hipStream_t st);
 
+// one combination of an explicit Runge-Kutta step (engine.hip solve_rk): out[i] = y0[i] + scale * sum_j coef[j] * k[j][i] for i < n
+// (fp32, n % 4 == 0, 16-byte aligned), 1..4 sources.  `out` may be `y0` itself: the last combination of a step writes y1 over y0.
+struct OdeStageArgs {
+  const float* k[4];
+  float coef[4];
+  int n_src;
+};
+// weak: the CPU emulation of the launchers (oracle/emu) does not define it, and a library linked against that emulation must still
+// load - ode_solve then refuses the Runge-Kutta methods (SAMAUDIO_ERR_STATE) instead of the whole library failing to bind
+__attribute__((weak)) hipError_t launch_ode_stage(const float* y0, const OdeStageArgs& a, float scale, float* out, long n,
+                                                  hipStream_t st);
+
 // out[r,:] = AT(x[r,:] + vec[(r / rows_per_b) * vec_ld + :])
 hipError_t launch_add_rowvec(const float* x, const float* vec, long vec_ld, void* out, bool bf16, int rows, int D,
                              int rows_per_b, hipStream_t st);

@@ -766,6 +766,43 @@ hipError_t launch_set_floats(float* dst, const float* host_values, int n, hipStr
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// explicit Runge-Kutta combination (engine.hip solve_rk): out = y0 + scale * (coef0 k0 + coef1 k1 + ...), fp32, float4 per lane.
+// The last combination of a step writes y1 over y0, so `y0` and `out` may be the same array: neither is __restrict__ (each lane reads
+// its y0 element before it writes the same element, and no lane touches another's).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ode_stage_kernel(const float4* y0, const OdeStageArgs a, const float scale, float4* out,
+                                                        const long n4) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    float4 k[4];   // every load first (n_src is uniform: the branches are scalar), then the arithmetic
+    k[0] = ((const float4*)a.k[0])[i];
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+      if (j < a.n_src) k[j] = ((const float4*)a.k[j])[i];
+    const float4 y = y0[i];
+    float4 s = make_float4(a.coef[0] * k[0].x, a.coef[0] * k[0].y, a.coef[0] * k[0].z, a.coef[0] * k[0].w);
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+      if (j < a.n_src) {
+        s.x += a.coef[j] * k[j].x;
+        s.y += a.coef[j] * k[j].y;
+        s.z += a.coef[j] * k[j].z;
+        s.w += a.coef[j] * k[j].w;
+      }
+    out[i] = make_float4(y.x + scale * s.x, y.y + scale * s.y, y.z + scale * s.z, y.w + scale * s.w);
+  }
+}
+
+hipError_t launch_ode_stage(const float* y0, const OdeStageArgs& a, float scale, float* out, long n, hipStream_t st) {
+  if (a.n_src < 1 || a.n_src > 4 || n % 4) return hipErrorInvalidValue;
+  const long n4 = n / 4;
+  long gx = (n4 + 255) / 256;
+  if (gx > 2048) gx = 2048;
+  if (gx < 1) gx = 1;
+  hipLaunchKernelGGL(ode_stage_kernel, dim3((unsigned)gx), dim3(256), 0, st, (const float4*)y0, a, scale, (float4*)out, n4);
+  return hipGetLastError();
+}
+
 hipError_t launch_time_features(const float* t, int nt, const float* freqs, int fdim, const float* inv_freq, int D,
                                 void* temb, float* tsin, bool bf16, hipStream_t st) {
   if (bf16)

@@ -77,7 +77,9 @@ def dtype_code(dtype, operands: Optional[str] = None, alt_ok: bool = False) -> i
         if dtype != want:
             raise TypeError(f"{dtype} tensor handed to the {operands}-operand build of libsamaudio_hip")
     return {torch.float32: DT_F32, torch.bfloat16: DT_BF16, torch.float16: DT_BF16}[dtype]
-ODE_EULER, ODE_MIDPOINT = 0, 1
+ODE_EULER, ODE_MIDPOINT, ODE_RK4, ODE_HEUN3 = 0, 1, 2, 3
+ODE_STAGES = {ODE_RK4: 4, ODE_HEUN3: 3}   # field evaluations per step of the methods that keep stage buffers
+ODE_TIME_SLOTS = 4096                     # the engine's table of evaluation times (samaudio.h samaudio_ode_solve)
 OPT_TAIL_SPLIT, OPT_F32_CLASSES, OPT_QUANT_CLASSES, OPT_QUANT_FORMAT, OPT_ALT16_CLASSES, OPT_PREFETCH_ROWS, OPT_SENTINEL = 1, 2, 3, 4, 5, 6, 7
 OPT_X3_CLASSES = 9
 SENTINEL_SLOTS = 16
@@ -244,6 +246,8 @@ _PROTOS = {
     "samaudio_codec_decode_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_ode_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "samaudio_ode_stage_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "samaudio_set_ode_stages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_codec_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "samaudio_codec_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_profile_begin": (C.c_int, [C.c_void_p]),

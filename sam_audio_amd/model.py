@@ -38,20 +38,64 @@ class SeparationResult:  # reference model.py:68-72
     noise: torch.Tensor
 
 
-def ode_grid(ode_opt: Dict[str, Any], t0: float = 0.0, t1: float = 1.0):
-    """(method id, grid) for the fixed-grid solvers torchdiffeq would run for `ode_opt`
-    (reference model.py:285-290; quirk Q11).  Anything but midpoint/euler + step_size is rejected."""
+# torchdiffeq's fixed-grid solvers the engine runs (samaudio.h SAMAUDIO_ODE_*).  Its adaptive solvers size every step from the error
+# norm of the whole batch, so a row's result would depend on which rows share the call (sharding, streams=2 and the candidate repeat rely
+# on rows being independent), and the Adams family's warm-up cannot be restated without its source: DESIGN.md section 1 row a6.
+ODE_METHODS = {"euler": hip.ODE_EULER, "midpoint": hip.ODE_MIDPOINT, "rk4": hip.ODE_RK4, "heun3": hip.ODE_HEUN3}
+
+
+def _field_stand_in(t, y):
+    raise NotImplementedError("grid_constructor: the HIP path passes a stand-in for the vector field; a grid constructor that "
+                              "evaluates the field is not supported")
+
+
+def ode_grid(ode_opt: Dict[str, Any], t0: float = 0.0, t1: float = 1.0, y0: Optional[torch.Tensor] = None):
+    """(method id, grid) for the fixed-grid solvers torchdiffeq would run for `ode_opt` (reference model.py:285-290; quirk Q11).
+    method: euler | midpoint | rk4 | heun3.  options, with the semantics of torchdiffeq's FixedGridODESolver:
+      {"step_size": h}        t0, t0 + h, ... with the last point clamped to t1;
+      {"grid_constructor": g} g(func, y0, t) with t = tensor([t0, t1]) on y0's device and `func` a stand-in that raises if called;
+                              1-D, strictly increasing (also as float32, what the engine integrates over), from t0 to t1 exactly;
+      none / {}               one step over [t0, t1].
+    Everything else - other methods, other keys, step_size together with grid_constructor - is a ValueError."""
     method = ode_opt.get("method", "midpoint")
-    if method not in ("midpoint", "euler"):
-        raise ValueError(f"ode method {method!r} is not supported by the HIP path (midpoint | euler)")
-    options = dict(ode_opt.get("options", {}))
+    if method not in ODE_METHODS:
+        raise ValueError(f"ode method {method!r} is not supported by the HIP path ({' | '.join(ODE_METHODS)}; the adaptive and "
+                         "Adams solvers are not: DESIGN.md section 1 row a6)")
+    options = dict(ode_opt.get("options") or {})
     step = options.pop("step_size", None)
-    if step is None or options:
-        raise ValueError("ode_opt['options'] must be exactly {'step_size': float}")
-    n = int(math.ceil((t1 - t0) / step + 1))
-    grid = [min(t0 + k * step, t1) for k in range(n)]
-    grid[-1] = t1
-    return (hip.ODE_MIDPOINT if method == "midpoint" else hip.ODE_EULER), grid
+    constructor = options.pop("grid_constructor", None)
+    if options:
+        raise ValueError(f"ode_opt['options']: unsupported {sorted(options)} (step_size | grid_constructor)")
+    if step is not None and constructor is not None:
+        raise ValueError("ode_opt['options']: step_size and grid_constructor are mutually exclusive")
+    if step is not None:
+        n = int(math.ceil((t1 - t0) / step + 1))
+        grid = [min(t0 + k * step, t1) for k in range(n)]
+        grid[-1] = t1
+    elif constructor is not None:
+        grid = _constructed_grid(constructor, y0, t0, t1)
+    else:
+        grid = [t0, t1]
+    stages = hip.ODE_STAGES.get(ODE_METHODS[method])
+    if stages is not None and stages * (len(grid) - 1) > hip.ODE_TIME_SLOTS:
+        raise ValueError(f"ode grid of {len(grid) - 1} steps: {method} evaluates the field {stages} times per step, the engine's "
+                         f"time table holds {hip.ODE_TIME_SLOTS} evaluations")
+    return ODE_METHODS[method], grid
+
+
+def _constructed_grid(constructor: Callable, y0: Optional[torch.Tensor], t0: float, t1: float) -> List[float]:
+    t = torch.tensor([t0, t1], device=y0.device if y0 is not None else None)
+    g = torch.as_tensor(constructor(_field_stand_in, y0, t)).detach()
+    if g.dim() != 1 or g.numel() < 2:
+        raise ValueError(f"grid_constructor must return a 1-D grid of at least two points (got shape {tuple(g.shape)})")
+    g = g.to("cpu")
+    if float(g[0]) != t0 or float(g[-1]) != t1:
+        raise ValueError(f"grid_constructor: the grid must start at {t0} and end at {t1} exactly "
+                         f"(got {float(g[0])} .. {float(g[-1])})")
+    g32 = g.to(torch.float32)
+    if not bool((g32[1:] > g32[:-1]).all()):
+        raise ValueError("grid_constructor: the grid must be strictly increasing (as float32)")
+    return g32.tolist()
 
 
 class _Codec16:
@@ -94,6 +138,7 @@ class _Lane:
         if model._has_codec:   # the lane also decodes its own row group (SAMAudio._solve_concurrent)
             hip.check(self.lib.samaudio_finalize(self._ctx, 1))
         self._workspace: Optional[torch.Tensor] = None
+        self._stages: Optional[torch.Tensor] = None   # rk4 / heun3 stage buffers of this context (SAMAudio._ensure_stages)
         self._live = None
         self._codec16: Optional[_Codec16] = None
         self.stream = torch.cuda.Stream(device=model.device)
@@ -175,6 +220,7 @@ class SAMAudio:
         self._ctx = C.c_void_p()
         self._tensors: Dict[str, torch.Tensor] = {}
         self._workspace: Optional[torch.Tensor] = None
+        self._stages: Optional[torch.Tensor] = None
         self._has_dit = self._has_codec = False
         if int(streams) not in (1, 2) and not os.environ.get("SAMAUDIO_ALLOW_STREAMS"):
             # measured on MI355X: 2 groups +3 %, 3-4 groups no further gain
@@ -469,6 +515,24 @@ class SAMAudio:
         hip.check(self._lib.samaudio_set_workspace(own._ctx, C.c_void_p(aligned),
                                                    own._workspace.numel() - (aligned - base)))
 
+    def _ensure_stages(self, method: int, rows: int, frames: int, lane: Optional[_Lane] = None) -> None:
+        """Stage buffers of a Runge-Kutta solve (samaudio_set_ode_stages), owned per engine context like the workspace and apart from
+        it; euler and midpoint need none and allocate nothing."""
+        own = lane if lane is not None else self
+        need = self._lib.samaudio_ode_stage_bytes(own._ctx, method, rows, frames)
+        if need == 0:
+            return
+        if own._stages is None or own._stages.numel() < need + 256:
+            own._stages = None
+            if os.environ.get("SAMAUDIO_POISON"):   # as the workspace: a stage read before it was written shows up as NaN
+                fill = int(os.environ.get("SAMAUDIO_POISON_BYTE", "255"), 0)
+                own._stages = torch.full((need + 256,), fill, dtype=torch.uint8, device=self.device)
+            else:
+                own._stages = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        base = own._stages.data_ptr()
+        aligned = (base + 255) // 256 * 256
+        hip.check(self._lib.samaudio_set_ode_stages(own._ctx, C.c_void_p(aligned), own._stages.numel() - (aligned - base)))
+
     def _codec_chunk(self, items: int) -> int:
         return min(items, int(os.environ.get("SAMAUDIO_CODEC_CHUNK", "16")))
 
@@ -607,10 +671,11 @@ class SAMAudio:
 
     def solve(self, noise: torch.Tensor, ode_opt: Dict[str, Any] = DFLT_ODE_OPT) -> torch.Tensor:
         """Integrate the flow ODE from `noise` with the conditioning of the last `_prepare` call."""
-        method, grid = ode_grid(ode_opt)
         state = noise.to(self.device, torch.float32).clone().contiguous()
+        method, grid = ode_grid(ode_opt, y0=state)
         g = (C.c_float * len(grid))(*grid)
         with torch.cuda.device(self.device):
+            self._ensure_stages(method, state.size(0), state.size(1))
             hip.check(self._lib.samaudio_ode_solve(self._ctx, hip.ptr(state), method, g, len(grid),
                                                    hip.current_stream_ptr()))
         return state
@@ -629,9 +694,9 @@ class SAMAudio:
         latent state, and with `decode` also the waveforms [rows, 2, samples] (model.py:291-295)."""
         import threading
         from .dist import shard_range
-        method, grid = ode_grid(ode_opt)
-        g = (C.c_float * len(grid))(*grid)
         state = noise.to(self.device, torch.float32).clone().contiguous()
+        method, grid = ode_grid(ode_opt, y0=state)   # one grid for the whole batch (a grid_constructor sees all rows)
+        g = (C.c_float * len(grid))(*grid)
         rows, frames, C2 = state.shape
         wavs = (torch.empty(rows * 2, frames * self.cfg.audio_codec.hop_length, device=self.device)
                 if decode else None)
@@ -666,6 +731,7 @@ class SAMAudio:
                 with torch.inference_mode(), torch.cuda.device(self.device), torch.cuda.stream(stream):
                     self._prepare(*part, lane=lane, anchors_validated=anchors_validated, candidates=candidates, latent=latent)
                     ctx = self._ctx if lane is None else lane._ctx
+                    self._ensure_stages(method, len(rr), frames, lane)
                     hip.check(self._lib.samaudio_ode_solve(ctx, hip.ptr(state[sl]), method, g, len(grid),
                                                            hip.current_stream_ptr()))
                     if decode:   # waveforms (2b, 2b+1) = (target, residual) of row b, gathered from the state inside the engine
