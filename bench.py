@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py - throughput of the SAMAudio.separate() hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+JSON line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, `config`, ...; the keys of the sections below are there and null).
+`--full` adds everything else this file measures or checks - the sections listed under "The JSON line also carries", the other
+scaling mode at N > 1, the configs[3] breakdown and the vision tower's own timing - after the timed steps, which are the same
+in both forms; the --no-* switches trim a --full run.
 
 N > 1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (ranks read
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) and as a plain `python bench.py --gpus N`, which re-executes
@@ -24,9 +30,9 @@ Scaling.  BASELINE configs[2] is ONE batch of 32 clips sharded over the GPUs ("b
 batch-sharded"; north_star: >= 7.5x at 8 vs 1 GPU on that batch), so with N > 1 the line's `value` is `--scaling strong`: the
 global batch of --batch clips is split contiguously over the ranks (32 -> 8 x 4).  `--scaling weak`:
 every rank processes its own batch of --batch clips.  With N > 1 the run also times the other mode and reports it under
-"other_scaling", so one driver invocation per N yields both curves.  At N = 1 the two coincide.
+"other_scaling" (--full), so one invocation per N yields both curves.  At N = 1 the two coincide.
 
-The JSON line also carries
+The JSON line also carries, with --full,
   roofline       - bf16 MFMA roofline of the dominant DiT GEMM kernel symbol: algorithmic flops of its launches / their
                    HIP-event time, measured on the launch stream in one extra instrumented step (single stream); plus the
                    aggregate over every DiT GEMM launch ("dit_gemm_all"), the whole-step figure ("whole_step": executed
@@ -69,6 +75,11 @@ PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA peak, MI355X_MICROARCH.md "Chip-lev
 PEAK_HBM_GBS = 8000.0      # HBM3E peak, same table (6.29 TB/s measured achievable)
 
 
+# the switches that trim a --full run; a plain run sets them all (the configs[3] breakdown and the vision tower's own timing
+# have no switch: run() asks args.full)
+EXTRAS = ("no_cpu_baseline", "no_roofline", "no_verify", "no_parity_mode", "no_hostile", "no_other", "no_other_configs")
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -88,7 +99,7 @@ def parse(argv=None):
                          "fastest mode that holds the 1e-3 parity bound on the benign AND the trained-like weights | fp16 = IEEE "
                          "half operands (one product per multiply; inside the bound on benign weights only) | mixed = bfloat16 on "
                          "the five big GEMM classes, fp16 elsewhere | bf16 everywhere (BASELINE's nominal dtype; outside the bound) "
-                         "| fp32 (exact-fp32 MFMA) | bf16x3.  Plain fp16 and bf16 are timed side by side (--no-parity-mode skips it)")
+                         "| fp32 (exact-fp32 MFMA) | bf16x3.  With --full, plain fp16 and bf16 are timed side by side (--no-parity-mode skips it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-verify", action="store_true", help="skip parity_check (it shares the oracle run with cpu_baseline)")
@@ -96,7 +107,7 @@ def parse(argv=None):
                     help="skip the side-by-side timing of the other 16-bit mode (fp16 runs: \"mixed_mode\"; mixed / bf16 runs: "
                          "\"fp16_mode\")")
     ap.add_argument("--verify", action="store_true", help="run parity_check even with --no-cpu-baseline")
-    ap.add_argument("--no-hostile", action="store_true", help="skip hostile_check (the main line of the default workload runs it)")
+    ap.add_argument("--no-hostile", action="store_true", help="skip hostile_check (the --full main line of the default workload runs it)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all host cores")
     ap.add_argument("--streams", type=int, default=0,
                     help="row groups of the batch solved concurrently on separate HIP streams (default 0 = auto: 2 with >= 16 "
@@ -127,7 +138,7 @@ def parse(argv=None):
                          "group runs on gloo (RCCL refuses two ranks on one device); the ranks time-share the GPU, so the "
                          "value is NOT a scaling number")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="the default invocation (N = 1, every workload flag at its default) also runs short lines of BASELINE "
+                    help="the --full run of the default workload (N = 1, every workload flag at its default) also runs short lines of BASELINE "
                          "configs[1], [3], [4] and the 4-clips-per-GPU share of configs[2] as sub-processes and reports them "
                          "under other_configs; this switch skips them")
     ap.add_argument("--verify-seconds", type=float, default=2.56,
@@ -142,9 +153,19 @@ def parse(argv=None):
                     help="after the timed steps, write what the last one returned to its caller (target and residual waveforms, "
                          "the noise it drew) as DIR/<name>.npy in float32, at most 64 MB in all (see dump_outputs); the inputs "
                          "are seeded, so two builds run with the same arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else this file measures or checks: rooflines (one instrumented "
+                         "step), cpu_baseline and parity_check against the CPU oracle, hostile_check, the plain 16-bit modes side by "
+                         "side, other_configs, the other scaling mode (N > 1), rerank_breakdown and vision_tower; the --no-* switches "
+                         "trim it.  Without --full none of them runs and their keys of the JSON line are null")
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        if args.verify:
+            ap.error("--verify asks for parity_check, which is part of --full")
+        for extra in EXTRAS:
+            setattr(args, extra, True)
     return args
 
 
@@ -496,7 +517,7 @@ def other_configs(args):
     --oracle-cache and says so); configs[3] and [4] run their own samples (parity_rerank / parity_visual)."""
     import subprocess
     large = args.oracle_cache
-    common = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    common = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
               "--verify", "--no-other-configs", "--no-parity-mode", "--precision", args.precision]
     runs = [
         ("configs[1] small* 8 clips", ["--size", "small*", "--batch", "8"]),
@@ -935,7 +956,7 @@ def run(args):
 
     # ---- configs[3]: what the span predictor and the Judge reranker cost, by difference ---------------------------------
     breakdown = None
-    if rank == 0 and (args.candidates > 1 or args.predict_spans):
+    if rank == 0 and args.full and (args.candidates > 1 or args.predict_spans):
         ranker, predictor = model.text_ranker, model.span_predictor
         b_steps = max(1, min(args.steps - 1, 4))
 
@@ -1017,7 +1038,7 @@ def run(args):
                 "frac": round(ref_fl / (elapsed / args.steps) / 1e12 / PEAK_BF16_TFLOPS, 4)}
 
     # ---- visual prompting: the tower alone, HIP events around the frames of ONE video (250 frames) ---------------
-    if rank == 0 and args.visual:
+    if rank == 0 and args.full and args.visual:
         from sam_audio_amd.vision_tower import tower_flops
         frames = model.vision_encoder.transform(batch.masked_video[0])
         model.vision_encoder.encode(frames)
@@ -1129,7 +1150,7 @@ def run(args):
     if rank == 0:
         line = {
             "metric": "seconds-of-audio separated/sec/node", "value": round(value, 3), "unit": "s-audio/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": bool(args.full),
             "ms_per_step": round(1e3 * elapsed / args.steps, 2), "higher_is_better": True, "scaling": args.scaling,
             "vs_baseline": None,
             "dtype": {"fp16x3": "fp16x3 (fp32 storage as the reference; every big contraction on IEEE-half hi + lo split operands: 3 MFMA "
