@@ -480,6 +480,48 @@ int samaudio_op_layernorm_rows(const float* x, int64_t x_ld, const float* w, con
  * in the library's 16-bit format = [lo | hi | hi] per row, hi = rn16(x) (clamped to the largest finite value), lo = rn16(x - hi) */
 int samaudio_op_split3(const float* x, int64_t x_ld, void* out, int64_t rows, int k, samaudio_stream stream);
 
+/* ---- the kernels a DiT layer launches, one hook each (tests/test_layer_kernels_gpu.py) ------------------- */
+
+/* RMSNorm + modulate operands of one evaluation: for norm n < n_norms (HOST arrays of device pointers / offsets) and time value t,
+ * gs[n][t] = [g | s] (2 * dim floats), g = w[n] * (1 + scale_tab[n] + tvec[t * tvec_ld + scale_off[n] + :]),
+ * s = shift_tab[n] + tvec[t * tvec_ld + shift_off[n] + :] */
+int samaudio_op_mod_tables(const float* const* w, const float* const* shift_tab, const float* const* scale_tab,
+                           const int* shift_off, const int* scale_off, int n_norms, const float* tvec, int64_t tvec_ld,
+                           int n_time, float* gs, int dim, samaudio_stream stream);
+/* out[m, :] = rmsnorm(x[m, :]) * g + s with [g | s] = gs + (m / rows_per_batch) * gs_ld (one norm's slice of the table above;
+ * gs_ld = 0: one time value for every row); dim <= 3072.  form 0: out [rows, dim] in the activation type of `precision`,
+ * 1: in the alt 16-bit format (16-bit precision only), 2: out [rows, 3 * dim] 16-bit = [lo | hi | hi] (fp32 precision only) */
+int samaudio_op_rmsnorm_gs(const float* x, const float* gs, int64_t gs_ld, void* out, int precision, int form, int rows,
+                           int dim, int rows_per_batch, float eps, samaudio_stream stream);
+/* samaudio_op_qkv_prep with head_dim 64 | 128 (rope tables [frames, head_dim / 2]).  form 0: the kernel of `precision`,
+ * 1: the fp32 fast path of the compensated mode (fp32 tensors, head_dim 128 only) */
+int samaudio_op_qkv_prep_hd(const void* qkv, const float* q_w, const float* k_w, const float* rope_cos,
+                            const float* rope_sin, void* q, void* k, void* vt, int precision, int form, int batch,
+                            int frames, int frames_padded, int heads, int head_dim, float eps, samaudio_stream stream);
+/* samaudio_op_self_attention with head_dim 64 | 128; precision 2 = the compensated kernel (fp32 tensors).  form 0: out
+ * [batch * frames, heads * head_dim] in the activation type, 1: the same in the alt 16-bit format (precision 1 only),
+ * 2: out [batch * frames, 3 * heads * head_dim] 16-bit = [lo | hi | hi] (precision 2 only) */
+int samaudio_op_self_attention_hd(const void* q, const void* k, const void* vt, const uint8_t* key_mask, void* out,
+                                  int precision, int form, int batch, int frames, int frames_padded, int heads,
+                                  int head_dim, samaudio_stream stream);
+/* samaudio_op_cross_attention with head_dim 64 | 128 and kv rows of stride kv_ld >= 2 * heads * head_dim elements ((k | v) in
+ * columns [0, 2 D) of the pointer handed in; k is normalised in place first, at that width) */
+int samaudio_op_cross_attention_hd(const void* q, const float* q_w, void* kv, int64_t kv_ld, const float* k_w,
+                                   const uint8_t* mask, void* out, int precision, int batch, int frames, int text_len,
+                                   int heads, int head_dim, float eps, samaudio_stream stream);
+/* folded cross-attention, 16-bit: p[m][h * ltp + j] = softmax probability of token j < ltp (0 for masked tokens and for
+ * j >= text_len; columns >= heads * ltp of the ldp-wide row are not written); q raw (q-norm applied here), k already normalised */
+int samaudio_op_cross_attn_probs(const void* q, const float* q_w, const void* kv, int64_t kv_ld, const uint8_t* mask, void* p,
+                                 int ldp, int batch, int frames, int text_len, int ltp, int heads, float eps,
+                                 samaudio_stream stream);
+/* the same on fp32 tensors as the compensated operand p3 [rows, 3 * kp] 16-bit = [P_lo | P_hi | P_hi] */
+int samaudio_op_cross_attn_probs3(const float* q, const float* q_w, const float* kv, int64_t kv_ld, const uint8_t* mask, void* p3,
+                                  int kp, int batch, int frames, int text_len, int ltp, int heads, float eps,
+                                  samaudio_stream stream);
+/* samaudio_op_cross_attn_fold on fp32 tensors (one layer): ut3 [batch][D][3 * kp] 16-bit = [U_hi | U_lo | U_hi] */
+int samaudio_op_cross_attn_fold3(const float* wo, const float* kv, int64_t kv_ld, void* ut3, int kp, int batch, int text_len,
+                                 int ltp, int heads, samaudio_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

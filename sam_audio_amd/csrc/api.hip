@@ -288,6 +288,113 @@ int samaudio_op_split3(const float* x, int64_t x_ld, void* out, int64_t rows, in
   return hip_ret(sa::launch_split3(x, x_ld, out, rows, k, (hipStream_t)stream), "split3");
 }
 
+// ---- hooks of the kernels a DiT layer launches (tests/test_layer_kernels_gpu.py) ----------------------------
+int samaudio_op_mod_tables(const float* const* w, const float* const* shift_tab, const float* const* scale_tab,
+                           const int* shift_off, const int* scale_off, int n_norms, const float* tvec, int64_t tvec_ld,
+                           int n_time, float* gs, int dim, samaudio_stream stream) {
+  if (!w || !shift_tab || !scale_tab || !shift_off || !scale_off || !tvec || !gs) return bad("mod_tables: null argument");
+  if (n_norms <= 0 || n_norms > sa::kMaxModNorms || n_time <= 0 || dim <= 0) return bad("mod_tables: n_norms / n_time / dim");
+  sa::ModTables mt;
+  for (int n = 0; n < sa::kMaxModNorms; ++n) {
+    const bool on = n < n_norms;
+    mt.w[n] = on ? w[n] : nullptr;
+    mt.shift_tab[n] = on ? shift_tab[n] : nullptr;
+    mt.scale_tab[n] = on ? scale_tab[n] : nullptr;
+    mt.shift_off[n] = on ? shift_off[n] : 0;
+    mt.scale_off[n] = on ? scale_off[n] : 0;
+  }
+  return hip_ret(sa::launch_mod_tables(mt, n_norms, tvec, tvec_ld, n_time, gs, dim, (hipStream_t)stream), "mod_tables");
+}
+
+int samaudio_op_rmsnorm_gs(const float* x, const float* gs, int64_t gs_ld, void* out, int precision, int form, int rows,
+                           int dim, int rows_per_batch, float eps, samaudio_stream stream) {
+  if (dim <= 0 || dim % 4 || dim > 3072) return bad("rmsnorm_gs: dim % 4, dim <= 3072");
+  if (rows <= 0 || rows_per_batch <= 0 || gs_ld % 4) return bad("rmsnorm_gs: rows / rows_per_batch / gs_ld % 4");
+  const bool bf16 = precision == SAMAUDIO_BF16;
+  if (form == 2) {
+    if (bf16) return bad("rmsnorm_gs: the split form belongs to fp32 contexts");
+    return hip_ret(sa::launch_rmsnorm_gs_split3(x, gs, gs_ld, out, rows, dim, rows_per_batch, eps, (hipStream_t)stream),
+                   "rmsnorm_gs_split3");
+  }
+  if (form != 0 && form != 1) return bad("rmsnorm_gs: form");
+  if (form == 1 && !bf16) return bad("rmsnorm_gs: the alt-16 form belongs to 16-bit contexts");
+  return hip_ret(sa::launch_rmsnorm_gs(x, gs, gs_ld, out, bf16, rows, dim, rows_per_batch, eps, (hipStream_t)stream, form == 1),
+                 "rmsnorm_gs");
+}
+
+int samaudio_op_qkv_prep_hd(const void* qkv, const float* q_w, const float* k_w, const float* rope_cos,
+                            const float* rope_sin, void* q, void* k, void* vt, int precision, int form, int batch,
+                            int frames, int frames_padded, int heads, int head_dim, float eps, samaudio_stream stream) {
+  if (frames_padded % 64 || frames_padded < frames || frames <= 0) return bad("qkv_prep_hd: frames_padded");
+  if (head_dim != 64 && head_dim != 128) return bad("qkv_prep_hd: head_dim");
+  if (form == 1) {
+    if (precision != SAMAUDIO_F32 || head_dim != 128) return bad("qkv_prep_hd: the f32x form takes fp32 tensors and head_dim 128");
+    return hip_ret(sa::launch_qkv_prep_f32x((const float*)qkv, q_w, k_w, rope_cos, rope_sin, (float*)q, (float*)k, (float*)vt, batch,
+                                            frames, frames_padded, heads, eps, (hipStream_t)stream), "qkv_prep_f32x");
+  }
+  if (form != 0) return bad("qkv_prep_hd: form");
+  return hip_ret(sa::launch_qkv_prep(qkv, q_w, k_w, rope_cos, rope_sin, q, k, vt, precision == SAMAUDIO_BF16, batch, frames,
+                                     frames_padded, heads, eps, (hipStream_t)stream, head_dim), "qkv_prep");
+}
+
+int samaudio_op_self_attention_hd(const void* q, const void* k, const void* vt, const uint8_t* key_mask, void* out,
+                                  int precision, int form, int batch, int frames, int frames_padded, int heads,
+                                  int head_dim, samaudio_stream stream) {
+  if (frames_padded % 64 || frames_padded < frames || frames <= 0) return bad("self_attention_hd: frames_padded");
+  if (head_dim != 64 && head_dim != 128) return bad("self_attention_hd: head_dim");
+  if (precision < 0 || precision > 2 || form < 0 || form > 2) return bad("self_attention_hd: precision / form");
+  if (form == 1 && precision != SAMAUDIO_BF16) return bad("self_attention_hd: the alt-16 output belongs to the 16-bit kernel");
+  if (form == 2 && precision != 2) return bad("self_attention_hd: the split output belongs to the compensated kernel");
+  if (precision == 2)
+    return hip_ret(sa::launch_self_attention_x3((const float*)q, (const float*)k, (const float*)vt, key_mask,
+                                                form == 2 ? nullptr : (float*)out, batch, frames, frames_padded, heads, head_dim,
+                                                (hipStream_t)stream, form == 2 ? out : nullptr), "self_attention_x3");
+  return hip_ret(sa::launch_self_attention_hd(q, k, vt, key_mask, out, precision == SAMAUDIO_BF16, batch, frames, frames_padded,
+                                              heads, head_dim, (hipStream_t)stream, form == 1), "self_attention_hd");
+}
+
+int samaudio_op_cross_attention_hd(const void* q, const float* q_w, void* kv, int64_t kv_ld, const float* k_w,
+                                   const uint8_t* mask, void* out, int precision, int batch, int frames, int text_len,
+                                   int heads, int head_dim, float eps, samaudio_stream stream) {
+  if (head_dim != 64 && head_dim != 128) return bad("cross_attention_hd: head_dim");
+  if (batch <= 0 || frames <= 0 || text_len <= 0 || heads <= 0 || kv_ld < 2L * heads * head_dim || kv_ld % 8)
+    return bad("cross_attention_hd: shape / kv_ld");
+  const bool bf16 = precision == SAMAUDIO_BF16;
+  hipError_t e = sa::launch_headnorm(kv, k_w, bf16, batch * text_len, kv_ld, 0, heads, eps, (hipStream_t)stream, head_dim);
+  if (e != hipSuccess) return hip_ret(e, "headnorm");
+  return hip_ret(sa::launch_cross_attention(q, q_w, kv, kv_ld, mask, out, bf16, batch, frames, text_len, heads, eps,
+                                            (hipStream_t)stream, head_dim), "cross_attention");
+}
+
+int samaudio_op_cross_attn_probs(const void* q, const float* q_w, const void* kv, int64_t kv_ld, const uint8_t* mask, void* p,
+                                 int ldp, int batch, int frames, int text_len, int ltp, int heads, float eps,
+                                 samaudio_stream stream) {
+  if ((ltp != 8 && ltp != 16) || text_len <= 0 || text_len > ltp || ldp < heads * ltp || ldp % 4 || kv_ld < 2L * heads * 128 || kv_ld % 8)
+    return bad("cross_attn_probs: shape");
+  if (batch <= 0 || frames <= 0 || heads <= 0) return bad("cross_attn_probs: batch / frames / heads");
+  return hip_ret(sa::launch_cross_attn_probs(q, q_w, kv, kv_ld, mask, p, ldp, batch, frames, text_len, ltp, heads, eps,
+                                             (hipStream_t)stream), "cross_attn_probs");
+}
+
+int samaudio_op_cross_attn_probs3(const float* q, const float* q_w, const float* kv, int64_t kv_ld, const uint8_t* mask, void* p3,
+                                  int kp, int batch, int frames, int text_len, int ltp, int heads, float eps,
+                                  samaudio_stream stream) {
+  if ((ltp != 8 && ltp != 16) || text_len <= 0 || text_len > ltp || kp < heads * ltp || kp % 8 || kv_ld < 2L * heads * 128 || kv_ld % 4)
+    return bad("cross_attn_probs3: shape");
+  if (batch <= 0 || frames <= 0 || heads <= 0) return bad("cross_attn_probs3: batch / frames / heads");
+  return hip_ret(sa::launch_cross_attn_probs3(q, q_w, kv, kv_ld, mask, p3, kp, batch, frames, text_len, ltp, heads, eps,
+                                              (hipStream_t)stream), "cross_attn_probs3");
+}
+
+int samaudio_op_cross_attn_fold3(const float* wo, const float* kv, int64_t kv_ld, void* ut3, int kp, int batch, int text_len,
+                                 int ltp, int heads, samaudio_stream stream) {
+  if ((ltp != 8 && ltp != 16) || text_len <= 0 || text_len > ltp || kp % 64 || kp < heads * ltp || kv_ld < 2L * heads * 128 || kv_ld % 4)
+    return bad("cross_attn_fold3: shape");
+  if (batch <= 0 || heads <= 0) return bad("cross_attn_fold3: batch / heads");
+  return hip_ret(sa::launch_cross_attn_fold3_layers(&wo, 1, kv, kv_ld, ut3, kp, batch, text_len, ltp, heads, (hipStream_t)stream),
+                 "cross_attn_fold3");
+}
+
 // ---- Judge reranker ----------------------------------------------------------------------------------
 int samaudio_judge_create(const samaudio_judge_config* cfg, samaudio_judge** out) {
   if (!cfg || !out) return bad("samaudio_judge_create: null argument");

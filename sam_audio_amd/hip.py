@@ -270,6 +270,15 @@ _PROTOS = {
     "samaudio_op_layernorm_rows": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_int,
                                                                                           C.c_float, C.c_void_p]),
     "samaudio_op_split3": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "samaudio_op_mod_tables": (C.c_int, [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_int)] * 2 + [C.c_int, C.c_void_p, C.c_int64,
+                                                                                                 C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "samaudio_op_rmsnorm_gs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "samaudio_op_qkv_prep_hd": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 7 + [C.c_float, C.c_void_p]),
+    "samaudio_op_self_attention_hd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]),
+    "samaudio_op_cross_attention_hd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
+    "samaudio_op_cross_attn_probs": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
+    "samaudio_op_cross_attn_probs3": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
+    "samaudio_op_cross_attn_fold3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "samaudio_judge_create": (C.c_int, [C.POINTER(JudgeConfig), C.POINTER(C.c_void_p)]),
     "samaudio_judge_destroy": (None, [C.c_void_p]),
     "samaudio_judge_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),

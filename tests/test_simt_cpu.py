@@ -113,3 +113,19 @@ def test_operand_sharing_x3_kernel_with_dma_landing_as_late_as_the_isa_allows():
             else:
                 os.environ[k] = v
     assert "3 passed" in out and "failed" not in out
+
+
+def test_layer_kernels_on_the_simulator_plain_and_with_poisoned_lds():
+    """A light subset of tests/test_layer_kernels_gpu.py (the kernels a DiT layer launches, each against float64 through its own hook):
+    the norm family at D = 512 / 3072, all of qkv_prep, cross-attention and the probability kernels (both head widths, 8- and 16-token
+    slots), three fold3 shapes, and the three self-attention kernels at both head widths with T = 1, 65 (64-row workgroups, incl. a
+    first key tile masked whole) and 128 (128-row workgroups) under every mask kind - once plain and once with every LDS array full
+    of NaN patterns before each workgroup: the fully masked tile and T = 1 are where a kernel could consume LDS it never wrote.
+    141 tests; measured 105 s of wall time for the two runs inside the CPU suite on an 8-core host (the whole file by hand: 70 s plain,
+    4.5 min poisoned)."""
+    subset = ["tests/test_layer_kernels_gpu.py", "-k",
+              "(self_attention and (-1- or -65- or -128-)) or (not self_attention and not fold3 and not 2816) or "
+              "(fold3 and (3-8-3-4 or 11-16-3-4 or 16-16-5-2))"]
+    for extra in ({}, {"SAMAUDIO_SIMT_POISON": "1"}):
+        out = _run(subset, 600, **extra)
+        assert "141 passed" in out and "failed" not in out and "skipped" not in out, out
