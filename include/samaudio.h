@@ -420,13 +420,15 @@ int samaudio_profile_begin(samaudio_ctx* ctx);
 /* SAMAUDIO_OPT_SENTINEL: synchronises `stream`, copies out absmax[SAMAUDIO_SENTINEL_SLOTS] / nonfinite[SAMAUDIO_SENTINEL_SLOTS]
  * (counts as doubles) accumulated since the last read, and resets them. */
 int samaudio_sentinel_read(samaudio_ctx* ctx, float* absmax, double* nonfinite, samaudio_stream stream);
-/* Test hook: force the GEMM kernel variant (-1 automatic; 0..2 the 128-row tiles of gemm.hip; 22 = gemm8 256x256 8-phase,
- * 27 = gemm8s 128x128, 25 / 26 / 28 / 29 / 32 / 33 / 34 = the 32x32x16-family tiles, 35 = conv7h; csrc/gemm.hip
- * gemm_variant_name).  A launch the forced kernel does not cover falls back to gemm.hip's tiles - except launches on
- * K-tile-major weights or with the split-form output, which exist in the 8-phase family only: forcing anything but 22 / 27 on
- * them is refused with SAMAUDIO_ERR_ARG and that reason (a model's own launches never leave the family). */
+/* Test hook: force the GEMM kernel variant (-1 automatic; otherwise an id of csrc/kernels.h `enum GemmVariant`, whose numbers are
+ * kept stable: 0..2 the 128-row tiles of gemm.hip; 22 = gemm8 256x256 8-phase, 27 = gemm8s 128x128; 25 / 26 / 28 / 29 / 32 / 33 /
+ * 34 = the 32x32x16-family tiles, 35 = conv7h; csrc/kernels.h kGemmVariantTable has the names).  A launch the forced kernel does
+ * not cover falls back to gemm.hip's tiles - except launches on K-tile-major weights or with the split-form output, which exist in
+ * the 8-phase family only: forcing anything outside that family on them is refused with SAMAUDIO_ERR_ARG and that reason (a
+ * model's own launches never leave the family). */
 void samaudio_debug_force_gemm_variant(int variant);
-/* Test hooks (csrc/kernels.h lists them; 0 = shipped behaviour): 11 = k7 convolutions as implicit GEMMs, 16 = DAC residual
+/* Test hooks (csrc/kernels.h `enum DebugFlag` names and documents every one, sam_audio_amd/hip.py mirrors the names; the numbers
+ * are kept stable; 0 = shipped behaviour): 11 = k7 convolutions as implicit GEMMs, 16 = DAC residual
  * units as two launches, 18 = fuse residual units whatever the launch size, 19 = residual-unit kernel form (1 / 3 = weight-
  * stationary, 2 = ring), 21 = gemm8s always in its plain double-buffered form, 24 = epilogue form of the 8-phase family (1 = the
  * general one for every launch, 2 / 3 = one lean form for every eligible launch), 26 = 1: one workgroup per tile (shipped:

@@ -44,11 +44,7 @@ inline float snake_h(float x, float a) {
 }
 int g_flags[64] = {0};
 int g_force = -1;
-unsigned long long g_epoch = 0;
 }  // namespace
-
-void debug_touch() { ++g_epoch; }
-unsigned long long debug_epoch() { return g_epoch; }
 
 hipError_t launch_poison_lds(hipStream_t) { return hipSuccess; }
 void set_debug_flag(int flag, int value) {
@@ -59,7 +55,7 @@ void gemm_force_variant(int v) { g_force = v; }
 int gemm_variant(const GemmParams&, bool) { return 0; }
 const char* gemm_variant_name(int v, bool) { return v == 0 ? "emu_gemm" : ""; }
 bool gemm2_ok(const GemmParams&) { return false; }
-hipError_t launch_gemm2(const GemmParams&, int, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_gemm2(const GemmParams&, GemmVariant, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_gemm8(const GemmParams&, int, hipStream_t) { return hipErrorNotSupported; }
 int gemm_tail_split(const GemmParams&, bool) { return 0; }
 hipError_t launch_gemm_part(const GemmParams&, bool, int, hipStream_t) { return hipErrorNotSupported; }

@@ -219,13 +219,7 @@ struct GemmParams {
   long c_ld_rel;
   long w_bstride;          // per-batch offset of W in elements (0: one weight matrix for every batch)
   int raster_gm;           // gemm2/gemm3 tile raster: M-tiles per group (0 = default 8)
-  int flags;               // launch switches: bit 0 (set by launch_gemm2) accumulator-layout epilogue; bit 1 (set by the
-                           // caller) never split the launch into whole rounds + tail (gemm.hip gemm_tail_split);
-                           // bits 2-3 / 4-5 (fp32 kernel only): round the A / W operand to bf16 (1) or fp16 (2) first;
-                           // bit 6 (set by the gemm8.hip launchers): linear epilogue (gemm8_linear_epilogue)
-                           // bits 9 / 10: 16-bit output / operands in the alt format (mixed mode)
-                           // bit 11: W is K-TILE-MAJOR, [K/64][N][64] - the 64-element K slab of ALL N rows contiguous, so a
-                           // launch streams W front to back (8-phase family only, plain operands; weights.py ktm_layout)
+  int flags;               // launch switches: the GEMM_FLAG_* constants below the struct
   int tag;                 // 1: DAC-VAE launch - same code under its own kernel symbol (rocprofv3 / roofline attribution)
   // Optional (8-phase family, launches of fewer than 256 workgroups): the workgroups that would otherwise idle touch these bytes
   // once, line by line - the NEXT launch's weights, so that it finds them in the memory-side cache instead of fetching them
@@ -233,6 +227,28 @@ struct GemmParams {
   const void* pf_ptr;
   long pf_bytes;
 };
+// ---- GemmParams.flags: one constant per bit (mirrored in sam_audio_amd/hip.py; tests/test_gemm_names_cpu.py pins the values) ----
+// bit 0: accumulator-layout epilogue (such a launch never takes a lean epilogue of the 8-phase family)
+constexpr int GEMM_FLAG_EPI_ACC = 1;
+// bit 1 (set by the caller): never split the launch into whole rounds + tail (gemm.hip gemm_tail_split)
+constexpr int GEMM_FLAG_NO_TAIL_SPLIT = 2;
+// bits 2-3 / 4-5 (fp32 kernel of gemm.hip only): round the A / W operand to a 16-bit format first (gemm.hip quant16)
+constexpr int GEMM_QUANT_NONE = 0, GEMM_QUANT_BF16 = 1, GEMM_QUANT_FP16 = 2;
+constexpr int GEMM_FLAG_QUANT_A_SHIFT = 2, GEMM_FLAG_QUANT_W_SHIFT = 4, GEMM_FLAG_QUANT_MASK = 3;
+constexpr int gemm_quant_a(int flags) { return (flags >> GEMM_FLAG_QUANT_A_SHIFT) & GEMM_FLAG_QUANT_MASK; }
+constexpr int gemm_quant_w(int flags) { return (flags >> GEMM_FLAG_QUANT_W_SHIFT) & GEMM_FLAG_QUANT_MASK; }
+// bits 6 / 7 (set by the gemm8.hip launchers, gemm8_linear_epilogue): the lean epilogues of the 8-phase family - bit 6 the LINEAR
+// register form (16-bit output straight from the accumulator layout, epilogue8_linear), bit 7 the LDS-staged ROWS form (fp32 output /
+// residual through the wave's LDS area, epilogue8_rows); neither = the general contract
+constexpr int GEMM_FLAG_EPI_LINEAR = 64;
+constexpr int GEMM_FLAG_EPI_ROWS = 128;
+constexpr int GEMM_FLAG_EPI_LEAN = GEMM_FLAG_EPI_LINEAR | GEMM_FLAG_EPI_ROWS;
+// (bit 8 is not used)
+// bits 9 / 10 (mixed mode, 8-phase family only): the 16-bit output is written / the operands are read in the alt format
+constexpr int GEMM_FLAG_OUT_ALT = 512;
+constexpr int GEMM_FLAG_OPND_ALT = 1024;
+// bit 11: W is K-TILE-MAJOR, [K/64][N][64] - the 64-element K slab of ALL N rows contiguous, so a launch streams W front to back
+// (8-phase family only, plain operands; weights.py ktm_layout)
 constexpr int GEMM_FLAG_W_KTM = 2048;
 // flags bit 12 (8-phase family, SwiGLU launches with a 16-bit output only): out_act receives the COMPENSATED-operand form of the
 // result - row stride act_ld = 3 * (N / 2), [lo | hi | hi] with hi = rn16(v), lo = rn16(v - hi) - i.e. the next GEMM's split

@@ -417,7 +417,7 @@ Status Engine::plan_dit(Bump& b, int rows, int T, int Lt, bool assign) {
   const long ltp = Lt <= 8 ? 8 : 16, kp = round_up(H * ltp, 64);
   const bool fold = bf16_ && Lt <= 16 && D / cfg_.n_heads == 128 && !std::getenv("SAMAUDIO_NO_FOLD");
   void* probs = fold ? act(M * kp) : nullptr;
-  // (one slice per layer: the folds of an evaluation run as one launch in front of the layer loop; debug flag 31 - one launch per
+  // (one slice per layer: the folds of an evaluation run as one launch in front of the layer loop; DBG_FOLD_PER_LAYER - one launch per
   // layer - only ever uses the first slice)
   const bool fold_all = cfg_.n_layers <= kMaxFoldLayers;
   void* ut = fold ? act((long)rows * D * kp * (fold_all ? cfg_.n_layers : 1)) : nullptr;
@@ -654,15 +654,16 @@ GemmParams Engine::launch_params(const GemmParams& p_in, int cls, int mode) cons
   const bool f32 = mode == 1;
   GemmParams p = p_in;
   p.tag = prof_cls_[0] == 'c' ? 1 : 0;  // codec launches run under their own kernel symbols
-  // bit 1: no tail split (gemm.hip gemm_tail_split); bit 9 (from the caller): 16-bit output in the alt format; bit 10: operands
-  // in the alt format (SAMAUDIO_OPT_ALT16_CLASSES, mixed mode)
-  // bit 11 (from the caller): W is K-tile-major
-  p.flags = (p_in.flags & (512 | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split_ ? 0 : 2) | (alt16(cls) && !f32 ? 1024 : 0);
+  // from the caller: alt-format output, K-tile-major W, split-form output; from the context: the tail split (gemm.hip gemm_tail_split) and
+  // the classes with operands in the alt format (SAMAUDIO_OPT_ALT16_CLASSES, mixed mode)
+  p.flags = (p_in.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split_ ? 0 : GEMM_FLAG_NO_TAIL_SPLIT) |
+            (alt16(cls) && !f32 ? GEMM_FLAG_OPND_ALT : 0);
   if (p.tag) cls = SAMAUDIO_CLS_CODEC;
   // an x3 launch on K-concatenated split operands: let the 8-phase kernels share the operand tiles the three products have in common
-  // (common.h GEMM_FLAG_X3_SHARE) wherever the launch qualifies; debug flag 38 = 1: the plain walk over K' (A/B, tests)
+  // (common.h GEMM_FLAG_X3_SHARE) wherever the launch qualifies; DBG_X3_PLAIN_WALK = 1: the plain walk over K' (A/B, tests)
   // mode 3 (the convolutions: every Cin-block of K' is its own [hi | lo | hi]) never qualifies
-  if (mode == 2 && debug_flag(38) != 1 && (debug_flag(38) < 2 || (cls & (debug_flag(38) >> 1)))) {   // (flag 38 >= 2: class mask << 1, diagnosis)
+  const int plain_walk = debug_flag(DBG_X3_PLAIN_WALK);   // (>= 2: class mask << 1, diagnosis)
+  if (mode == 2 && plain_walk != 1 && (plain_walk < 2 || (cls & (plain_walk >> 1)))) {
     GemmParams q = p;
     q.flags |= GEMM_FLAG_X3_SHARE;
     if (q.kc == q.K && q.K % 192 == 0 && !gemm_check(q, true)) p = q;
@@ -679,7 +680,7 @@ Status Engine::gemm(const GemmParams& p_in, hipStream_t st, double alg_flops, in
     sentinel_on_ = true;
     if (!s.ok()) return s;
     const int c = prof_cls_[0] == 'c' ? SAMAUDIO_CLS_CODEC : cls;
-    const int fmt = (f32 || !bf16_) ? 0 : ((p_in.flags & 512) ? 2 : 1);
+    const int fmt = (f32 || !bf16_) ? 0 : ((p_in.flags & GEMM_FLAG_OUT_ALT) ? 2 : 1);
     const int n_out = p_in.swiglu ? p_in.N / 2 : p_in.N;
     for (int b = 0; b < p_in.nbatch; ++b) {
       const size_t esz = fmt == 0 ? 4 : 2;
@@ -709,7 +710,7 @@ Status Engine::gemm(const GemmParams& p_in, hipStream_t st, double alg_flops, in
     return op(gemm_variant_name(gemm_variant(p, false), false), gemm_alg_bytes(p, 4), flops, st,
               [&] { return launch_gemm(p, false, st); });
   }
-  if (!is16 && quant_fmt_ && (quant_classes_ & cls)) p.flags |= (quant_fmt_ << 2) | (quant_fmt_ << 4);
+  if (!is16 && quant_fmt_ && (quant_classes_ & cls)) p.flags |= (quant_fmt_ << GEMM_FLAG_QUANT_A_SHIFT) | (quant_fmt_ << GEMM_FLAG_QUANT_W_SHIFT);
   // SAMAUDIO_OPT_X3_CLASSES bit CODEC (fp32 contexts): the convolution multiplies on split operands, split in registers (gemm.hip)
   if (!is16 && p.tag && x3(SAMAUDIO_CLS_CODEC)) {
     p.flags |= GEMM_FLAG_X3_FLY;
@@ -733,8 +734,8 @@ Status Engine::gemm(const GemmParams& p_in, hipStream_t st, double alg_flops, in
     ProfRec r;
     // implicit convolutions (kc < K) run the 8-phase kernels under their own instantiation (gemm8_kernel<true>): own record
     const int variant = gemm_variant(p, is16);
-    const char* conv = (variant == 22 || variant == 27) && p.kc < p.K ? "_conv" : "";
-    r.key = std::string(prof_cls_) + "/" + (part ? "gemm8s_bf16_128x128_tail" : gemm_variant_name(variant, is16)) + conv + (x3m ? "_x3" : "");
+    const char* conv = gemm_is_8phase(variant) && p.kc < p.K ? "_conv" : "";
+    r.key = std::string(prof_cls_) + "/" + (part ? kGemm8sTailName : gemm_variant_name(variant, is16)) + conv + (x3m ? "_x3" : "");
     if (static const bool by_class = std::getenv("SAMAUDIO_PROF_BY_CLASS") != nullptr; by_class) {   // diagnosis: one record per GEMM class
       int bit = 0;
       while (bit < SAMAUDIO_CLS_COUNT && !(cls & (1 << bit))) ++bit;
@@ -836,8 +837,8 @@ Status Engine::res_unit(GemmParams p, GemmParams q, void*& cur, void*& alt, doub
   // fused for all four channel counts: since the residual-unit kernels issue their direct-to-LDS loads as inline assembly
   // (gemm2.hip dma16a) the fused form is the faster one everywhere (profiles/r3_call12/op_bench.log, 8 waveforms, fused vs
   // two launches: C = 64 923 vs 1193 us, C = 96 1697 vs 2269, C = 128 1353 vs 1391, C = 192 2515 vs 2784)
-  const bool fuse = bf16_ && covered && !debug_flag(16) && resunit_ok(fp, fq) &&
-                    ((long)((p.M + 255) / 256) * p.nbatch >= 256 || debug_flag(18));
+  const bool fuse = bf16_ && covered && !debug_flag(DBG_RESUNIT_TWO_LAUNCHES) && resunit_ok(fp, fq) &&
+                    ((long)((p.M + 255) / 256) * p.nbatch >= 256 || debug_flag(DBG_RESUNIT_FUSE_ALWAYS));
   if (!fuse) {
     SA_TRY(gemm(p, st, flops7));
     return gemm(q, st, flops1);
@@ -1190,7 +1191,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
   // the fold on compensated operands as prepare() set it up - unless class CWO was switched off since: then the unfolded path
   const bool fold3 = fold3_ && x3(SAMAUDIO_CLS_CWO);
   const int fold_ltp = fold3_ && !fold3 ? 0 : fold_ltp_;
-  const bool fold_all = fold_ltp && !fold3 && cfg_.n_layers <= kMaxFoldLayers && !debug_flag(31);   // flag 31: one launch per layer (A/B, tests)
+  const bool fold_all = fold_ltp && !fold3 && cfg_.n_layers <= kMaxFoldLayers && !debug_flag(DBG_FOLD_PER_LAYER);   // (one launch per layer: A/B, tests)
   if (fold3) {   // x3 context: U = Wo V of every layer on split operands, [L][rows][D][3 kp] = [U_hi | U_lo | U_hi]
     const float* wos[kMaxFoldLayers];
     for (int l = 0; l < cfg_.n_layers; ++l) wos[l] = (const float*)layers_[l].c_wo;
@@ -1270,7 +1271,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       with_res(p, d_.h, D);
       out_f32(p, d_.h, D);
       out_act(p, d_.hbf, D);
-      if (alt16(SAMAUDIO_CLS_CWQ)) p.flags |= 512;   // hbf is c_wq's operand
+      if (alt16(SAMAUDIO_CLS_CWQ)) p.flags |= GEMM_FLAG_OUT_ALT;   // hbf is c_wq's operand
       ktm(p, w, 1);
       prefetch(p, w.c_wq, (double)D * D);
       if (x3(SAMAUDIO_CLS_WO)) {   // (fp32 outputs only: c_wq then reads h itself)
@@ -1356,7 +1357,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       GemmParams p = lin(d_.xn, D, w.w13, M, 2 * F, D);
       p.swiglu = 1;
       out_act(p, d_.u, F);
-      if (alt16(SAMAUDIO_CLS_W2)) p.flags |= 512;    // u is w2's operand
+      if (alt16(SAMAUDIO_CLS_W2)) p.flags |= GEMM_FLAG_OUT_ALT;    // u is w2's operand
       ktm(p, w, 3);
       prefetch(p, w.w2, (double)D * F);
       if (x3(SAMAUDIO_CLS_W13)) {

@@ -46,17 +46,17 @@ template <> struct Mma<float> {
   }
 };
 
-// fp32 kernel only (GemmParams.flags bits 2-3: A operand, 4-5: W operand): round an operand to a 16-bit format before the
-// multiply - 1 = bfloat16, 2 = IEEE fp16, both round-to-nearest-even as the 16-bit kernels' stores do.  Products of two
+// fp32 kernel only (common.h gemm_quant_a / gemm_quant_w of GemmParams.flags): round an operand to a 16-bit format before the
+// multiply - GEMM_QUANT_BF16 = bfloat16, GEMM_QUANT_FP16 = IEEE fp16, both round-to-nearest-even as the 16-bit kernels' stores do.  Products of two
 // such values are exact in fp32, so the launch computes what the 16-bit MFMA would, operand class by operand class
 // (SAMAUDIO_OPT_QUANT_CLASSES: the error budget of DESIGN.md section 4).
 __device__ __forceinline__ float quant16(float x, int fmt) {
-  if (fmt == 1) {
+  if (fmt == GEMM_QUANT_BF16) {
     unsigned u = __float_as_uint(x);
     u += 0x7fffu + ((u >> 16) & 1u);
     return __uint_as_float(u & 0xffff0000u);
   }
-  if (fmt == 2) return (float)(_Float16)x;
+  if (fmt == GEMM_QUANT_FP16) return (float)(_Float16)x;
   return x;
 }
 __device__ __forceinline__ f32x4_t quant16x4(f32x4_t v, int fmt) {
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256, (FLY ? 2 : 1)) void gemm_kernel(const GemmPara
 
   const int nslab = p.K / BK;
   const int lr = lane & 15, lg = lane >> 4;
-  const int qa = (p.flags >> 2) & 3, qw = (p.flags >> 4) & 3;  // operand rounding (fp32 kernel only, see quant16)
+  const int qa = gemm_quant_a(p.flags), qw = gemm_quant_w(p.flags);  // operand rounding (fp32 kernel only, see quant16)
   const bool x3fly = FLY || (sizeof(T) == 4 && (p.flags & GEMM_FLAG_X3_FLY) != 0);   // (uniform)
   const bool wfly = FLY || (p.flags & GEMM_FLAG_W_FLY16) != 0;                         // (uniform) W arrives split: common.h
   // one 32-k slab of an X3_FLY launch (stage image sA | sB)
@@ -421,28 +421,33 @@ static hipError_t launch_cfg(const GemmParams& p, hipStream_t st) {
 }
 
 static int g_force = -1;
-void gemm_force_variant(int v) { g_force = v; debug_touch(); }
+void gemm_force_variant(int v) { g_force = v; }
 
-// tile variant of gemm.hip: 0 = 128x128, 1 = 128x64, 2 = 128x32.  Narrow outputs (codec stages with 1 / 64 /
+const char* gemm_variant_name(int v, bool is_bf16) {   // from kernels.h kGemmVariantTable
+  const GemmVariantRow* r = gemm_variant_row(v);
+  return !r ? "" : is_bf16 ? r->name16 : r->name32;
+}
+
+// tile variant of gemm.hip: 128x128, 128x64 or 128x32.  Narrow outputs (codec stages with 1 / 64 /
 // 96 / 192 channels) use narrower N tiles.
-static int gemm1_variant(const GemmParams& p) {
+static GemmVariant gemm1_variant(const GemmParams& p) {
   const int N = p.N;
-  if (p.swiglu) return 0;
-  if (N <= 32 || N == 96) return 2;
-  if (N <= 64 || (N % 128 != 0 && N % 64 == 0 && N <= 448)) return 1;
+  if (p.swiglu) return GV_GEMM_128x128;
+  if (N <= 32 || N == 96) return GV_GEMM_128x32;
+  if (N <= 64 || (N % 128 != 0 && N % 64 == 0 && N <= 448)) return GV_GEMM_128x64;
   // Few tiles (the fp32 classes of a 16-bit context: D -> 256 output projection at 8000 rows = 126 tiles of 128x128; one
   // time row; 256 text rows): narrower tiles until every CU has one.  Every tile of this file accumulates an output
   // element over k in the same order, so the choice may depend on M without breaking batch-sharding invariance.
   const long t128 = (long)((p.M + 127) / 128) * ((N + 127) / 128) * p.nbatch;
-  if (t128 < 192) return 2 * t128 < 192 ? 2 : 1;
-  return 0;
+  if (t128 < 192) return 2 * t128 < 192 ? GV_GEMM_128x32 : GV_GEMM_128x64;
+  return GV_GEMM_128x128;
 }
-// Which kernel launch_gemm runs: 0..2 = gemm.hip tiles, 3 + v = gemm2.hip / gemm8.hip variant v (16-bit operands only).  The
+// Which kernel launch_gemm runs (GemmVariant, kernels.h; the gemm2.hip / gemm8.hip families take 16-bit operands only).  The
 // choice depends on (N, K, epilogue) and - only INSIDE one accumulation-order family - on the number of rows, so that
 // sharding the batch cannot change the accumulation order of any output element:
-//   16x16x32 family: 22 = gemm8 (256x256, 8-phase K loop), 27 = gemm8s (128x128) - every N >= 256;
-//   32x32x16 family: 25 / 26 (128x128, 64x128 BK 64), 28 (256x64), 29 / 32 / 33 / 34 (BK 32 multi-workgroup tiles),
-//                    35 = conv7h - the DAC-VAE stages with 64 .. 192 channels.
+//   16x16x32 family: gemm8 (256x256, 8-phase K loop), gemm8s (128x128) - every N >= 256;
+//   32x32x16 family: 128x128 / 64x128 BK 64, 256x64, the BK 32 multi-workgroup tiles, conv7h - the DAC-VAE stages with
+//                    64 .. 192 channels.
 // How each entry was chosen (one-box A/B per step, round 2): DESIGN.md sections 3.1 and 3.4, profiles/r2_call*/.
 // GEMM_FLAG_X3_FLY | GEMM_FLAG_W_FLY16 launches (the DAC-VAE stages with < 256 channels in an fp32 context): 4 x 1 waves, each 32
 // rows x the whole tile width.  In the K loop a wave then splits only ITS OWN two activation fragments (2 x 28 vector-ALU
@@ -450,38 +455,37 @@ static int gemm1_variant(const GemmParams& p) {
 // 128 x 32 tile of gemm1_variant had 12 MFMAs behind the split of two activation AND two weight fragments, three times per row block
 // (one workgroup per 32 columns).  128 x 96 for N = 96 / 192, 128 x 128 for N = 128, 128 x 64 / 128 x 32 below.  Same k order per
 // output element as every tile of this file.
-static int fly_variant(const GemmParams& p) {
-  if (p.N <= 32) return 39;
-  if (p.N <= 64) return 38;
-  if (p.N % 96 == 0 || p.N <= 96) return 36;
-  return 37;
+static GemmVariant fly_variant(const GemmParams& p) {
+  if (p.N <= 32) return GV_FLY_128x32;
+  if (p.N <= 64) return GV_FLY_128x64;
+  if (p.N % 96 == 0 || p.N <= 96) return GV_FLY_128x96;
+  return GV_FLY_128x128;
 }
 int gemm_variant(const GemmParams& p, bool is_bf16) {
   const bool g2 = is_bf16 && gemm2_ok(p);
-  if (!is_bf16 && g_force < 0 && (p.flags & GEMM_FLAG_W_FLY16) && debug_flag(36) != 1) return fly_variant(p);   // flag 36 = 1 (A/B): the old tiles
-  // (K-tile-major weights / the split-form output exist in the 8-phase family only: a FORCED variant other than 22 / 27 on such a
+  if (!is_bf16 && g_force < 0 && (p.flags & GEMM_FLAG_W_FLY16) && debug_flag(DBG_FLY_OLD_TILES) != 1) return fly_variant(p);   // (A/B: the old tiles)
+  // (K-tile-major weights / the split-form output exist in the 8-phase family only: a FORCED variant outside the family on such a
   // launch is refused by gemm_check with that reason - tests/test_gemm2_gpu.py::test_ktm_weights_are_refused_outside_the_8phase_family;
   // the policy itself never leaves the family for them, and every side operand the engine registers is 16-byte aligned by
   // samaudio_set_tensor, so gemm2_ok cannot fail for a model's launches)
-  if (g_force >= 3) {
-    const bool known = g_force == 22 || (g_force >= 25 && g_force <= 29) || (g_force >= 32 && g_force < kGemmVariants);
-    if (g_force == 35 && !(g2 && conv7h_ok(p))) return gemm1_variant(p);   // conv7h computes convolutions only
-    return g2 && known ? g_force : gemm1_variant(p);
+  if (g_force > GV_GEMM_128x32) {
+    if (g_force == GV_CONV7H && !(g2 && conv7h_ok(p))) return gemm1_variant(p);   // conv7h computes convolutions only
+    return g2 && gemm_variant_row(g_force) ? g_force : gemm1_variant(p);   // (an id without a kernel: the automatic tile)
   }
   if (g_force >= 0 || !g2) return gemm1_variant(p);
   const long rows256 = (long)((p.M + 255) / 256) * p.nbatch, rows128 = (long)((p.M + 127) / 128) * p.nbatch;
   // k7 'same' convolutions of the DAC stages with <= 96 channels: halo tile resident in LDS (C = 64 485 vs 567 us, C = 96
-  // 1149 vs 1307 us for the implicit GEMM; C = 128 / 192 measured slower and stay implicit GEMMs).  Flag 11 = off (tests).
-  if (!debug_flag(11) && p.N <= 96 && conv7h_ok(p) && rows256 >= 256) return 35;
+  // 1149 vs 1307 us for the implicit GEMM; C = 128 / 192 measured slower and stay implicit GEMMs).  DBG_NO_CONV7H = off (tests).
+  if (!debug_flag(DBG_NO_CONV7H) && p.N <= 96 && conv7h_ok(p) && rows256 >= 256) return GV_CONV7H;
   // 64-channel outputs (first DAC encoder stage): one 64-wide tile of the DMA-fed family.  The small-launch fallback stays
   // in the SAME MFMA family: how many waveforms one codec pass holds depends on the caller's workspace, and a family
   // switch at a row-count threshold made two identical calls differ in the last bits (round 2, GPU call 14).
-  if (p.N >= 64 && p.N < 96 && p.K >= 64) return rows256 >= 256 ? 28 : 32;
+  if (p.N >= 64 && p.N < 96 && p.K >= 64) return rows256 >= 256 ? GV_GEMM2_256x64_S2 : GV_GEMM2_128x64_K32;
   // 96 - 192 channels with very many rows: a K-tile of such a tile is ~0.4 us of MFMA work behind ~2 us of L2 latency, so
   // what pays is MORE TILES IN FLIGHT per CU: BK 32, 36 - 60 KiB per workgroup, 2 - 4 workgroups per CU.
   if (p.N >= 96 && p.N <= 192 && p.K >= 64 && rows128 >= 1024) {
-    if (p.N <= 128) return p.K <= 256 ? 33 : 29;   // 64x128 k32 s3 (k1) | 128x128 k32 s3 (k7)
-    return p.K <= 256 ? 29 : 34;                   // 128x128 k32 s3 (k1) | 128x192 k32 s3 (k7)
+    if (p.N <= 128) return p.K <= 256 ? GV_GEMM2_64x128_K32 : GV_GEMM2_128x128_K32;   // 64x128 k32 s3 (k1) | 128x128 k32 s3 (k7)
+    return p.K <= 256 ? GV_GEMM2_128x128_K32 : GV_GEMM2_128x192_K32;                  // 128x128 k32 s3 (k1) | 128x192 k32 s3 (k7)
   }
   if (p.N >= 96 && p.K >= 128) {
     if (p.N >= 256) {
@@ -491,47 +495,21 @@ int gemm_variant(const GemmParams& p, bool is_bf16) {
       // 256x192 tile delivers 20 % fewer flops per CU-second, and the CUs a 352-tile launch leaves idle are not idle in the
       // timed configuration - the other row group's HBM-bound kernels run on them.  profiles/r3_call2/.)
       const long t256 = rows256 * ((p.N + 255) / 256);
-      if (p.N < 1024 && p.N % 256) return 27;
-      const long min256 = debug_flag(30) > 0 ? debug_flag(30) : 128;   // flag 30 (A/B): the tile count from which gemm8 is used
-      return t256 >= min256 ? 22 : 27;
+      if (p.N < 1024 && p.N % 256) return GV_GEMM8S_128x128;
+      const long min256 = debug_flag(DBG_GEMM8_MIN_TILES) > 0 ? debug_flag(DBG_GEMM8_MIN_TILES) : 128;   // (A/B): the tile count from which gemm8 is used
+      return t256 >= min256 ? GV_GEMM8_256x256 : GV_GEMM8S_128x128;
     }
     // 96 <= N < 256 with few rows: 128- / 64-row tiles of the 32x32x16 family
-    return rows128 * ((p.N + 127) / 128) >= 192 ? 25 : 26;
+    return rows128 * ((p.N + 127) / 128) >= 192 ? GV_GEMM2_128x128_S2 : GV_GEMM2_64x128_S3;
   }
   return gemm1_variant(p);
-}
-const char* gemm_variant_name(int v, bool is_bf16) {
-  if (v < 0 || v >= kGemmVariants) return "";
-  if (v >= 36) {
-    static const char* fly[4] = {"gemm_f32x3_128x96", "gemm_f32x3_128x128", "gemm_f32x3_128x64", "gemm_f32x3_128x32"};
-    return is_bf16 ? "" : fly[v - 36];
-  }
-  if (v < 3) {
-    static const char* base[2][3] = {{"gemm_f32_128x128", "gemm_f32_128x64", "gemm_f32_128x32"},
-                                     {"gemm_bf16_128x128", "gemm_bf16_128x64", "gemm_bf16_128x32"}};
-    return base[is_bf16 ? 1 : 0][v];
-  }
-  if (!is_bf16) return "";
-  switch (v) {
-    case 22: return "gemm8_bf16_256x256_8phase";
-    case 25: return "gemm2_bf16_128x128_s2";
-    case 26: return "gemm2_bf16_64x128_s3";
-    case 27: return "gemm8s_bf16_128x128";
-    case 28: return "gemm2_bf16_256x64_s2";
-    case 29: return "gemm2_bf16_128x128_k32_s3";
-    case 32: return "gemm2_bf16_128x64_k32_s2";
-    case 33: return "gemm2_bf16_64x128_k32_s3";
-    case 34: return "gemm2_bf16_128x192_k32_s3";
-    case 35: return "conv7h_bf16";
-    default: return "";
-  }
 }
 
 template <typename T>
 static hipError_t launch_t(const GemmParams& p, int variant, hipStream_t st) {
   switch (variant) {
-    case 2: return launch_cfg<T, 128, 32, 4, 1>(p, st);
-    case 1: return launch_cfg<T, 128, 64, 2, 2>(p, st);
+    case GV_GEMM_128x32: return launch_cfg<T, 128, 32, 4, 1>(p, st);
+    case GV_GEMM_128x64: return launch_cfg<T, 128, 64, 2, 2>(p, st);
     default: return launch_cfg<T, 128, 128, 2, 2>(p, st);
   }
 }
@@ -540,7 +518,7 @@ static hipError_t launch_t(const GemmParams& p, int variant, hipStream_t st) {
 // returns the number of tiles the main launch keeps, 0 = one launch.  Only when the policy (not a forced variant) chose
 // the kernel; the tail must be worth a launch (>= 16 tiles) and the last round must be at most half full.
 int gemm_tail_split(const GemmParams& p, bool is_bf16) {
-  if (g_force >= 0 || (p.flags & 2) || gemm_variant(p, is_bf16) != 22) return 0;
+  if (g_force >= 0 || (p.flags & GEMM_FLAG_NO_TAIL_SPLIT) || gemm_variant(p, is_bf16) != GV_GEMM8_256x256) return 0;
   const long tiles = (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.nbatch;
   const long full = tiles / 256 * 256, rem = tiles - full;
   // ... and only for launches of a few rounds: with many rounds the idle part of the last one is a small share of the
@@ -550,8 +528,8 @@ int gemm_tail_split(const GemmParams& p, bool is_bf16) {
   // + 176: 249 us in one launch, 268 split; qkv, 528 = 2 x 256 + 16: 179 vs 160 split; profiles/r4_call5/gemm_bench_f3.log)
   // (round 5: the floor of the tail went from 16 to 8 tiles - qkv at 8 clips per GPU, the 4-GPU share of the 32-clip batch, is 264
   //  tiles = one round + 8, i.e. a second round of 8 tiles as long as the first: 164.8 / 165.3 -> 170.0 s-audio/s at 8 clips, nothing
-  //  at 4 clips or small* (profiles/r5_call12/); flag 33 = another floor for the A/B)
-  const long min_tail = debug_flag(33) > 0 ? debug_flag(33) : 8;
+  //  at 4 clips or small* (profiles/r5_call12/); DBG_TAIL_SPLIT_MIN = another floor for the A/B)
+  const long min_tail = debug_flag(DBG_TAIL_SPLIT_MIN) > 0 ? debug_flag(DBG_TAIL_SPLIT_MIN) : 8;
   return full >= 256 && full <= 1024 && rem >= min_tail && rem <= 128 ? (int)full : 0;
 }
 hipError_t launch_gemm_part(const GemmParams& p, bool is_bf16, int part, hipStream_t st) {
@@ -565,23 +543,28 @@ hipError_t launch_gemm(const GemmParams& p, bool is_bf16, hipStream_t st) {
     return e != hipSuccess ? e : launch_gemm8_split(p, full, 1, st);
   }
   const int v = gemm_variant(p, is_bf16);
-  if (v >= 36) {   // fly_variant (fp32 operands, weights already split)
+  if (v >= GV_FLY_128x96) {   // fly_variant (fp32 operands, weights already split)
     const auto go = [&](auto kern, int bm, int bn) {
       const long tiles = (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * p.nbatch;
       hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), 0, st, p);
       return hipGetLastError();
     };
     switch (v) {
-      case 36: return go(gemm_kernel<float, 128, 96, 4, 1, true>, 128, 96);
-      case 37: return go(gemm_kernel<float, 128, 128, 4, 1, true>, 128, 128);
-      case 38: return go(gemm_kernel<float, 128, 64, 4, 1, true>, 128, 64);
+      case GV_FLY_128x96: return go(gemm_kernel<float, 128, 96, 4, 1, true>, 128, 96);
+      case GV_FLY_128x128: return go(gemm_kernel<float, 128, 128, 4, 1, true>, 128, 128);
+      case GV_FLY_128x64: return go(gemm_kernel<float, 128, 64, 4, 1, true>, 128, 64);
       default: return go(gemm_kernel<float, 128, 32, 4, 1, true>, 128, 32);
     }
   }
-  if (v >= 3) return launch_gemm2(p, v - 3, st);
+  if (v > GV_GEMM_128x32) return launch_gemm2(p, (GemmVariant)v, st);
   return is_bf16 ? launch_t<bf16_t>(p, v, st) : launch_t<float>(p, v, st);
 }
 
+static const char* need_8phase(const GemmParams& p, bool is_bf16, bool (*eligible)(const GemmParams&), const char* not_eligible,
+                               const char* not_chosen) {
+  if (!is_bf16 || !gemm2_ok(p) || !eligible(p)) return not_eligible;
+  return gemm_is_8phase(gemm_variant(p, is_bf16)) ? nullptr : not_chosen;
+}
 const char* gemm_check(const GemmParams& p, bool is_bf16) {
   const int bk = is_bf16 ? 64 : 32, ch = is_bf16 ? 8 : 4;
   if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.nbatch <= 0) return "gemm: empty problem";
@@ -593,26 +576,20 @@ const char* gemm_check(const GemmParams& p, bool is_bf16) {
   if (p.gate && p.rows_per_gate <= 0) return "gemm: rows_per_gate";
   if ((p.flags & GEMM_FLAG_W_FLY16) && (is_bf16 || !(p.flags & GEMM_FLAG_X3_FLY)))
     return "gemm: split-weight layout (flags bit 14): fp32 launches with operands split on the fly (bit 13) only";
-  if (p.flags & (512 | 1024)) {   // mixed mode: alt-format output / operands exist in the 8-phase family only
-    if (!is_bf16 || !gemm2_ok(p) || !gemm8_alt_ok(p)) return "gemm: alt 16-bit format: plain 16-bit launches with a lean epilogue only";
-    const int v = gemm_variant(p, is_bf16);
-    if (v != 22 && v != 27) return "gemm: alt 16-bit format: the tile policy did not pick the 8-phase family for this launch";
-  }
-  if (p.flags & GEMM_FLAG_OUT_SPLIT3) {   // compensated-operand output: the register epilogue of the 8-phase family, SwiGLU launches
-    if (!is_bf16 || !gemm2_ok(p) || !gemm8_split3_ok(p)) return "gemm: split3 output: 16-bit SwiGLU launches with a lean epilogue only";
-    const int v = gemm_variant(p, is_bf16);
-    if (v != 22 && v != 27) return "gemm: split3 output: the tile policy did not pick the 8-phase family for this launch";
-  }
-  if (p.flags & GEMM_FLAG_X3_SHARE) {   // operand-sharing walk of K-concatenated split operands: the 8-phase family, plain launches
-    if (!is_bf16 || !gemm2_ok(p) || !gemm8_share_ok(p)) return "gemm: shared split operands (flags bit 15): plain 16-bit launches with K' = 3K, K % 64 == 0";
-    const int v = gemm_variant(p, is_bf16);
-    if (v != 22 && v != 27) return "gemm: shared split operands: the tile policy did not pick the 8-phase family for this launch";
-  }
-  if (p.flags & GEMM_FLAG_W_KTM) {   // K-tile-major weights: only the 8-phase family addresses them
-    if (!is_bf16 || !gemm2_ok(p) || p.w_bstride) return "gemm: K-tile-major W: plain 16-bit launches with one weight matrix only";
-    const int v = gemm_variant(p, is_bf16);
-    if (v != 22 && v != 27) return "gemm: K-tile-major W: the tile policy did not pick the 8-phase family for this launch";
-  }
+  // flags only the 8-phase family implements: the launch must be eligible, and the tile policy must have chosen the family
+  if (p.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_OPND_ALT))   // mixed mode: alt-format output / operands
+    if (const char* e = need_8phase(p, is_bf16, gemm8_alt_ok, "gemm: alt 16-bit format: plain 16-bit launches with a lean epilogue only",
+                                    "gemm: alt 16-bit format: the tile policy did not pick the 8-phase family for this launch")) return e;
+  if (p.flags & GEMM_FLAG_OUT_SPLIT3)   // compensated-operand output: the register epilogue, SwiGLU launches
+    if (const char* e = need_8phase(p, is_bf16, gemm8_split3_ok, "gemm: split3 output: 16-bit SwiGLU launches with a lean epilogue only",
+                                    "gemm: split3 output: the tile policy did not pick the 8-phase family for this launch")) return e;
+  if (p.flags & GEMM_FLAG_X3_SHARE)   // operand-sharing walk of K-concatenated split operands: plain launches
+    if (const char* e = need_8phase(p, is_bf16, gemm8_share_ok, "gemm: shared split operands (flags bit 15): plain 16-bit launches with K' = 3K, K % 64 == 0",
+                                    "gemm: shared split operands: the tile policy did not pick the 8-phase family for this launch")) return e;
+  if (p.flags & GEMM_FLAG_W_KTM)   // K-tile-major weights: one weight matrix
+    if (const char* e = need_8phase(p, is_bf16, [](const GemmParams& q) { return q.w_bstride == 0; },
+                                    "gemm: K-tile-major W: plain 16-bit launches with one weight matrix only",
+                                    "gemm: K-tile-major W: the tile policy did not pick the 8-phase family for this launch")) return e;
   return nullptr;
 }
 

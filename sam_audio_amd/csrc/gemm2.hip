@@ -883,7 +883,7 @@ static hipError_t launch_ru(const GemmParams& p, const GemmParams& q, hipStream_
 
 template <int C>
 static hipError_t launch_ws(const GemmParams& p, const GemmParams& q, long tiles, hipStream_t st) {
-  const long cap = debug_flag(19) == 3 ? 3 : 256;                // one workgroup per CU, walking tiles
+  const long cap = debug_flag(DBG_RESUNIT_WS) == DBG_WS_ALWAYS_GRID3 ? 3 : 256;                // one workgroup per CU, walking tiles
   const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
   if (p.tag == 1)
     hipLaunchKernelGGL((resws_kernel<C, 1>), dim3(grid), dim3(C / 32 * 64), 0, st, p, q);
@@ -892,12 +892,12 @@ static hipError_t launch_ws(const GemmParams& p, const GemmParams& q, long tiles
   return hipGetLastError();
 }
 
-// 96-channel launches of >= 1024 tiles of 128 rows (four sweeps of the chip) run the weight-stationary kernel; flag 19 = whatever
-// the launch size (its tests; 3 = the same on a grid of 3 workgroups, so that small cases walk several tiles), 2 = never
+// 96-channel launches of >= 1024 tiles of 128 rows (four sweeps of the chip) run the weight-stationary kernel; DBG_RESUNIT_WS = whatever
+// the launch size (its tests; DBG_WS_ALWAYS_GRID3 = on a grid of 3 workgroups, so that small cases walk several tiles) or never
 static bool resunit_ws(const GemmParams& p, const GemmParams& q) {
-  if (!(p.N == 64 || p.N == 96) || debug_flag(19) == 2) return false;
+  if (!(p.N == 64 || p.N == 96) || debug_flag(DBG_RESUNIT_WS) == DBG_WS_NEVER) return false;
   if (q.act != ACT_SNAKE && q.act != ACT_NONE) return false;
-  if (debug_flag(19) == 1 || debug_flag(19) == 3) return true;
+  if (debug_flag(DBG_RESUNIT_WS) == DBG_WS_ALWAYS || debug_flag(DBG_RESUNIT_WS) == DBG_WS_ALWAYS_GRID3) return true;
   // 96 channels: 1 697 vs 1 939 us for 8 waveforms (ring kernel), profiles/r3_call12/op_bench.log.  64 channels would run
   // two waves per CU - too few to cover its LDS / VALU latencies: 1 564 vs 923 us - and stays on the ring kernel.
   return p.N == 96 && (long)((p.M + 127) / 128) * p.nbatch >= 1024;
@@ -912,7 +912,7 @@ hipError_t launch_resunit(const GemmParams& p, const GemmParams& q, hipStream_t 
     case 64: return launch_ru<64, 256, 8, 1, 3>(p, q, st);
     // 96 channels: 128-row tiles on 4 waves and a 2-stage ring = 72 KiB, two workgroups per CU, so that one workgroup's
     // memory-bound phase-2 epilogue overlaps the other's MFMA-bound phase 1 (2023 vs 2102 us for 8 waveforms, two launches
-    // 2204; profiles/r2_call21/).  Flag 20 = the 8-wave 256-row shape.
+    // 2204; profiles/r2_call21/).
     case 96: return launch_ru<96, 128, 4, 1, 2>(p, q, st);   // 72 KiB: two workgroups per CU (2 023 vs 2 127 us on 256 rows / 8 waves)
     case 128: return launch_ru<128, 256, 4, 2, 3>(p, q, st);
     case 192: return launch_ru<192, 128, 4, 2, 3>(p, q, st);
@@ -950,26 +950,21 @@ bool gemm2_ok(const GemmParams& p) {
   return true;
 }
 
-// variants: 0 = 256x128 3-stage ring, 1 = 256x128 2-stage ring, 2 = 256x256 2-stage ring (8 waves, BK 64, one
-// workgroup per CU); 3 = 256x192 2-stage ring; 6 = 256x256 role-split (half-slab phases, 2 stages).
-// Measured and dropped (profiles/r1_gemm_variants_*.log): 4-wave BK-32 tiles with two workgroups per CU (3-5),
-// 256x128 role-split with 3 stages (7, 8), 256x256 with one 512-register wave per SIMD (12), hand-pipelined asm
-// fragment reads (13, 14) - all within +-3 % of the kept kernels or slower.  Ablation builds (9-11: no DMA / no MFMA /
-// no LDS reads; wrong results, timing only) compile with -DSAMAUDIO_GEMM_ABLATIONS.
-// variant = gemm_variant()'s number - 3 (gemm.hip): only the tiles the policy selects are built
-hipError_t launch_gemm2(const GemmParams& p, int variant, hipStream_t st) {
+// Only the tiles the policy (gemm.hip gemm_variant) selects are built; the variants measured and dropped since round 1 are
+// recorded in profiles/DESIGN_rounds1-4.md.
+hipError_t launch_gemm2(const GemmParams& p, GemmVariant variant, hipStream_t st) {
   switch (variant) {
-    case 19: return launch_gemm8(p, st);   // gemm8.hip: 256x256 tile, the guide's 8-phase K loop, 16x16x32 MFMA
-    case 24: return launch_gemm8s(p, st);  // gemm8.hip: 128x128 tile of the same arithmetic (few rows; split tails)
+    case GV_GEMM8_256x256: return launch_gemm8(p, st);    // gemm8.hip: 256x256 tile, the guide's 8-phase K loop, 16x16x32 MFMA
+    case GV_GEMM8S_128x128: return launch_gemm8s(p, st);  // gemm8.hip: 128x128 tile of the same arithmetic (few rows; split tails)
     // 32x32x16 family (DAC-VAE stages with 64 - 192 channels): M-aware tiles, bitwise equal among themselves
-    case 22: return launch2<128, 128, 2, 2, 2, 64>(p, st);  // few rows: 4 waves, 64 KiB => two workgroups per CU
-    case 23: return launch2<64, 128, 1, 4, 3, 64>(p, st);   // fewer rows: 4 waves, 72 KiB => two workgroups per CU
-    case 25: return launch2<256, 64, 8, 1, 2, 64, true>(p, st);  // N = 64 outputs (first DAC encoder stage) in one 64-wide tile
-    case 26: return launch2<128, 128, 2, 2, 3, 32>(p, st);  // BK 32: 48 KiB => three workgroups per CU, 3 stages each
-    case 29: return launch2<128, 64, 2, 2, 2, 32>(p, st);   // N <= 64: 24 KiB => six workgroups per CU
-    case 30: return launch2<64, 128, 1, 4, 3, 32>(p, st);   // 36 KiB => four workgroups per CU
-    case 31: return launch2<128, 192, 2, 2, 3, 32>(p, st);  // N = 192 in one tile, 60 KiB => two workgroups per CU
-    case 32: return launch_conv7h(p, st);  // k7 convolution with the halo tile resident in LDS (conv7h_ok launches only)
+    case GV_GEMM2_128x128_S2: return launch2<128, 128, 2, 2, 2, 64>(p, st);  // few rows: 4 waves, 64 KiB => two workgroups per CU
+    case GV_GEMM2_64x128_S3: return launch2<64, 128, 1, 4, 3, 64>(p, st);   // fewer rows: 4 waves, 72 KiB => two workgroups per CU
+    case GV_GEMM2_256x64_S2: return launch2<256, 64, 8, 1, 2, 64, true>(p, st);  // N = 64 outputs (first DAC encoder stage) in one 64-wide tile
+    case GV_GEMM2_128x128_K32: return launch2<128, 128, 2, 2, 3, 32>(p, st);  // BK 32: 48 KiB => three workgroups per CU, 3 stages each
+    case GV_GEMM2_128x64_K32: return launch2<128, 64, 2, 2, 2, 32>(p, st);   // N <= 64: 24 KiB => six workgroups per CU
+    case GV_GEMM2_64x128_K32: return launch2<64, 128, 1, 4, 3, 32>(p, st);   // 36 KiB => four workgroups per CU
+    case GV_GEMM2_128x192_K32: return launch2<128, 192, 2, 2, 3, 32>(p, st);  // N = 192 in one tile, 60 KiB => two workgroups per CU
+    case GV_CONV7H: return launch_conv7h(p, st);  // k7 convolution with the halo tile resident in LDS (conv7h_ok launches only)
     default: return hipErrorInvalidValue;
   }
 }

@@ -37,11 +37,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 namespace {
 
-__device__ __forceinline__ void dma16_8(const void* gsrc, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-// The same DMA with the source as (wave-uniform base, per-lane 32-bit byte offset) and issued as inline assembly
+// The direct-to-LDS load with the source as (wave-uniform base, per-lane 32-bit byte offset) and issued as inline assembly
 // (gemm8_kernel, gemm8s_kernel).  Two reasons: the scalar-base form needs no 64-bit address arithmetic per issue and half the address
 // registers; and hipcc treats a global_load_lds it can see as a "flat" access pending on BOTH counters - while one is in
 // flight every LDS fragment read is waited for with lgkmcnt(0) (and every ordinary load with vmcnt(0)), whatever the order
@@ -189,7 +185,7 @@ __device__ __forceinline__ void epilogue8(const GemmParams& p, f32x4_t (&acc)[NH
   }
 }
 
-// The LINEAR epilogue (p.flags bit 6, set by gemm8_linear_epilogue() on the host): what every Linear of the DiT needs -
+// The LINEAR epilogue (GEMM_FLAG_EPI_LINEAR, set by gemm8_linear_epilogue() on the host): what every Linear of the DiT needs -
 // bias, adaLN gate, alpha, residual, fp32 and / or 16-bit output, SwiGLU - and nothing else (no activation, no per-channel
 // period, no window mask, N a multiple of 64), straight from the accumulator layout.  Round 4, GPU call 1
 // (profiles/r4_call1/ksweep.log): one 256 x 256 tile of the general epilogue above costs 24 us (plain 16-bit output) to 32 us
@@ -207,7 +203,7 @@ __device__ __forceinline__ void epilogue8_linear(const GemmParams& p, f32x4_t (&
 #pragma clang fp contract(off)
   constexpr int NI = NH * 4;
   const int lr = lane & 15, lg = lane >> 4;
-  const bool out_alt = (p.flags & 512) != 0;   // mixed mode: the 16-bit output feeds a GEMM on alt-format operands
+  const bool out_alt = (p.flags & GEMM_FLAG_OUT_ALT) != 0;   // mixed mode: the 16-bit output feeds a GEMM on alt-format operands
   auto pack = [&](float x, float y) { return out_alt ? pack_alt16x2(x, y) : pack_h16x2(x, y); };
   if (n_wave0 >= p.N) return;   // N % 64 == 0: a wave's 64 columns are all inside or all outside
   const long bM = (long)b * p.M;
@@ -335,7 +331,7 @@ __device__ __forceinline__ void epilogue8_rows(const GemmParams& p, f32x4_t (&ac
                                                const int m_wave0, const int n_wave0, const int lane) {
 #pragma clang fp contract(off)
   const int lr = lane & 15, lg = lane >> 4;
-  const bool out_alt = (p.flags & 512) != 0;
+  const bool out_alt = (p.flags & GEMM_FLAG_OUT_ALT) != 0;
   const long bM = (long)b * p.M;
   const bool has_bias = p.bias != nullptr, has_gate = p.gate != nullptr, has_tab = p.gate_tab != nullptr,
              has_res = p.res != nullptr, has_f32 = p.out_f32 != nullptr, has_act = p.out_act != nullptr;
@@ -423,25 +419,14 @@ __device__ __forceinline__ void tile_of(const GemmParams& p, const int BM, const
   tm = first_m + in_grp % gsz;
   tn = in_grp / gsz;
 }
-// blockIdx.x -> position in a run of `total` units dealt to the 8 XCDs as contiguous sub-runs
-__device__ __forceinline__ int xcd_run_pos(const int total) {
-  const int bid = blockIdx.x;
+// workgroup (or virtual workgroup of a persistent launch) `bid` -> position in a run of `total` units dealt to the 8 XCDs as contiguous sub-runs
+__device__ __forceinline__ int xcd_run_pos(const int bid, const int total) {
   const int q = total >> 3, r = total & 7;
   const int xcd = bid & 7, idx = bid >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
-__device__ __forceinline__ int xcd_run_pos_of(const int total, const int bid) {
-  const int q = total >> 3, r = total & 7;
-  const int xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-__device__ __forceinline__ void tile_raster8(const GemmParams& p, const int BM, const int BN, int& b, int& tm, int& tn) {
-  const int total = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.nbatch;
-  tile_of(p, BM, BN, xcd_run_pos(total), b, tm, tn);
-}
 
-
-// W addressing (GemmParams.flags bit 11): row-major [N][K] - rows K elements apart, a K-tile 128 bytes further along the row -
+// W addressing (GEMM_FLAG_W_KTM): row-major [N][K] - rows K elements apart, a K-tile 128 bytes further along the row -
 // or K-TILE-MAJOR [K/64][N][64] - rows 64 elements apart inside a slab, a K-tile N * 128 bytes further.  Row-major, a launch of
 // few rows fetches each K-tile of its cold weights as one 128-byte piece out of every one of N DRAM rows 2 K bytes apart, all
 // workgroups at the same K offset at the same time (round 4, profiles/r4_call13 .. 17: that order of requests, not issue time or
@@ -476,241 +461,8 @@ __device__ __forceinline__ void prefetch_lines(const GemmParams& p, const int wg
 
 }  // namespace
 
-#ifdef SAMAUDIO_GEMM8_ABL
-// gemm8o: the round-2 / round-3 form of the 8-phase loop (DMA through the builtin, buffer-major LDS layout), kept for the
-// ablation build only (tools/build_abl.sh, tools/gemm8_ablate.py): its ablations are what located the read side as the
-// longer leg (profiles/r4_call4/ablate.log).  The shipped kernel is gemm8_kernel below.
-// The two wave groups run one barrier apart and every MFMA cluster runs under s_setprio 1 (round-2 A/B builds of the
-// template on one box: without the stagger -11 %, without the priority -9 %; profiles/r2_call3/).
-// CONV: A's k axis is split into taps (implicit convolutions: kc < K); plain GEMMs compile the per-K-tile tap walk - a
-// per-lane loop under an exec mask, twice per K-tile - out of the K loop.
-// (Round 3, GPU call 3: issuing the second staging instruction of every phase from inside the wave's own MFMA cluster -
-// to shorten the read sections, which carry 2 global_load_lds at 100 - 185 issue cycles each - measured 4 - 7 % SLOWER on
-// every DiT shape than this loop (profiles/r3_call3/gemm_bench_r3.log); removed.  Compiling the tap walk out of plain
-// GEMMs measured 3 - 5 % faster and is what CONV = false is.  GPU call 10: issuing a phase's staging instructions BEFORE its
-// ds_reads, and merging the four phases into two super-phases (32-MFMA clusters, 4 barriers per K-tile instead of 8), both
-// measured within +-1 % of this loop on every shape (profiles/r3_call10/): neither the barrier count nor the order inside
-// a read section is what bounds it.)
-// ABL (only instantiated with -DSAMAUDIO_GEMM8_ABL, tools/build_abl.sh; timing experiments, wrong results): 1 = no DMA inside the K
-// loop, 2 = no LDS fragment reads inside the K loop, 3 = no MFMA, 4 = no barriers, 5 = no s_setprio, 9 = correct results +
-// s_memtime stamps of (entry, prologue done, K loop done, epilogue done) written per tile to p.act_alpha
-template <bool CONV, int ABL = 0>
-__global__ __launch_bounds__(512) void gemm8o_kernel(const GemmParams p, const int tile_count) {
-  unsigned long long ts0 = 0, ts1 = 0, ts2 = 0;
-  if constexpr (ABL == 9) ts0 = __builtin_readcyclecounter();
-  constexpr bool STAGGER = true, PRIO = ABL != 5;
-  constexpr int BM = 256, BN = 256, BK = 64, HT = 128 * 128;  // HT: bytes of one half-tile
-  __shared__ __attribute__((aligned(16))) char smem[2 * 4 * HT];  // [K-tile buffer][HA0, HA1, HB0, HB1]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;  // waves w and w+4 share a SIMD: one of each group per SIMD
-  const int lr = lane & 15, lg = lane >> 4;
-
-  // tile_count > 0: this launch covers only the first tile_count tiles of the raster order (the full rounds of the chip);
-  // the rest runs as 128x128 tiles of gemm8s_kernel (launch_gemm8_split below)
-  int b, tm, tn;
-  if (tile_count > 0) tile_of(p, BM, BN, xcd_run_pos(tile_count), b, tm, tn);
-  else tile_raster8(p, BM, BN, b, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-
-  // ---- staging bookkeeping ---------------------------------------------------------------------------------
-  // A half-tile = 128 rows; wave w stages rows 16w .. 16w+15 as two wave-instructions of 8 rows (1 KiB each):
-  // lane -> row 16w + 8q + (lane>>3), 16-byte slot lane&7, which must hold source chunk slot ^ ((row>>1)&7).
-  const int r8 = lane >> 3;
-  const bf16_t* a_row[2][2];  // [half][q] activation row pointers (row clamped to M-1), without the k offset
-  const bf16_t* w_row[2][2];  // [half][q] weight row pointers incl. the lane's chunk
-  int chunk[2];
-  {
-    const bf16_t* A = (const bf16_t*)p.A + p.a_off + (long)b * p.a_bstride;
-    const bf16_t* W = (const bf16_t*)p.W + (long)b * p.w_bstride;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int row = wave * 16 + q * 8 + r8;  // row inside a half-tile
-      chunk[q] = (lane & 7) ^ ((row >> 1) & 7);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        int m = m0 + h * 128 + row;
-        m = m < p.M ? m : p.M - 1;
-        a_row[h][q] = A + (long)m * p.lda;
-        int n = n0 + h * 128 + row;
-        n = n < p.N ? n : p.N - 1;
-        w_row[h][q] = W + (long)n * p.K + chunk[q] * 8;
-      }
-    }
-  }
-  // position of the lane's chunk in the (tap, offset) structure of A's k axis, per q, for the K-tile being staged.
-  // HA0 and HA1 of a K-tile are staged in consecutive phases and share it; it advances once both are out.
-  int a_in[2];
-  long a_tap[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    a_in[q] = chunk[q] * 8;
-    a_tap[q] = 0;
-    if constexpr (CONV)
-      while (a_in[q] >= p.kc) { a_in[q] -= p.kc; a_tap[q] += p.tap_stride; }
-  }
-  const int nt = p.K / BK;
-  auto stage_a = [&](int h, int buf) {  // HA_h of the K-tile the a_in / a_tap state points at
-    char* dst = smem + buf * (4 * HT) + h * HT + wave * 2048;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) dma16_8(a_row[h][q] + a_tap[q] + a_in[q], dst + q * 1024);
-  };
-  auto advance_a = [&]() {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      a_in[q] += BK;
-      if constexpr (CONV)
-        while (a_in[q] >= p.kc) { a_in[q] -= p.kc; a_tap[q] += p.tap_stride; }
-    }
-  };
-  auto stage_w = [&](int h, int buf, int kt) {  // HB_h of K-tile kt
-    char* dst = smem + buf * (4 * HT) + (2 + h) * HT + wave * 2048;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) dma16_8(w_row[h][q] + (long)kt * BK, dst + q * 1024);
-  };
-
-  // ---- fragments --------------------------------------------------------------------------------------------
-  f32x4_t acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  bf16x8_t af[4][2];      // activation fragments of the current 64-row half: [m-fragment][k-step]
-  bf16x8_t wf[2][2][2];   // weight fragments: [32-column half][n-fragment][k-step]
-
-  auto frag = [&](const char* half_base, int row, int ks) -> bf16x8_t {
-    return *(const bf16x8_t*)(half_base + row * 128 + ((((ks << 2) + lg) ^ ((row >> 1) & 7)) << 4));
-  };
-  auto read_a = [&](int buf, int sub) {  // rows 64*sub .. +63 of the wave's half-tile HA_wr
-    const char* base = smem + buf * (4 * HT) + wr * HT;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) af[i][ks] = frag(base, sub * 64 + i * 16 + lr, ks);
-  };
-  // weight rows (output columns) 64*(wc&1) + 32*SUB .. +31 of HB_(wc>>1); SUB compile-time (static register index)
-#define SA_GEMM8_READ_W(BUF, SUB)                                                                                 \
-  do {                                                                                                            \
-    const char* base_ = smem + (BUF) * (4 * HT) + (2 + (wc >> 1)) * HT;                                           \
-    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                 \
-      _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                            \
-        wf[SUB][j][ks] = frag(base_, (wc & 1) * 64 + (SUB) * 32 + j * 16 + lr, ks);                               \
-  } while (0)
-  // one C quadrant x K = 64: 16 MFMAs.  ASUB / WSUB are compile-time so that acc[][] is indexed statically and stays in
-  // registers (a run-time quadrant index sends the whole accumulator to scratch).
-#define SA_GEMM8_MMA(ASUB, WSUB)                                                                                  \
-  do {                                                                                                            \
-    if constexpr (ABL == 3) {                                                                                     \
-      _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                          \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(wf[WSUB][j][ks]));                    \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(af[i][ks]));                          \
-      }                                                                                                           \
-      break;                                                                                                      \
-    }                                                                                                             \
-    if (PRIO) __builtin_amdgcn_s_setprio(1);                                                                      \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                              \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                               \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                             \
-          acc[(ASUB) * 4 + i][(WSUB) * 2 + j] = SA_MFMA_16x16x32(                          \
-              wf[WSUB][j][ks], af[i][ks], acc[(ASUB) * 4 + i][(WSUB) * 2 + j]);                          \
-    if (PRIO) __builtin_amdgcn_s_setprio(0);                                                                      \
-  } while (0)
-
-#define SA_BAR()                                   \
-  do {                                             \
-    if constexpr (ABL != 4) __builtin_amdgcn_s_barrier(); \
-  } while (0)
-  // ---- prologue: K-tile 0 complete, HB0 / HB1 of K-tile 1 in flight (what the steady state expects) ----------
-  stage_w(0, 0, 0);
-  stage_w(1, 0, 0);
-  stage_a(0, 0);
-  stage_a(1, 0);
-  advance_a();
-  if (nt > 1) {
-    stage_w(0, 1, 1);
-    stage_w(1, 1, 1);
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __builtin_amdgcn_s_barrier();
-  if (STAGGER && wr == 1) __builtin_amdgcn_s_barrier();  // group 1 runs one barrier behind group 0
-
-  if constexpr (ABL == 2) {
-    SA_GEMM8_READ_W(0, 0);
-    SA_GEMM8_READ_W(0, 1);
-    read_a(0, 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-  if constexpr (ABL == 9) ts1 = __builtin_readcyclecounter();
-  for (int t = 0; t < nt; ++t) {
-    const int cb = t & 1, nb = cb ^ 1;
-    const bool s1 = t + 1 < nt, s2 = t + 2 < nt;
-    // P1
-    if constexpr (ABL != 2) SA_GEMM8_READ_W(cb, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (ABL != 2) read_a(cb, 0);
-    if (ABL != 1 && s1) stage_a(0, nb);
-    SA_BAR();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    SA_GEMM8_MMA(0, 0);
-    SA_BAR();
-    // P2
-    if constexpr (ABL != 2) SA_GEMM8_READ_W(cb, 1);
-    if (ABL != 1 && s1) { stage_a(1, nb); advance_a(); }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // HB(t) is restaged in the next phase: its reads end here
-    SA_BAR();
-    SA_GEMM8_MMA(0, 1);
-    SA_BAR();
-    // P3
-    if constexpr (ABL != 2) read_a(cb, 1);
-    if (ABL != 1 && s2) stage_w(0, cb, t + 2);
-    SA_BAR();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    SA_GEMM8_MMA(1, 1);
-    SA_BAR();
-    // P4
-    if (ABL == 1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (s2) {
-      stage_w(1, cb, t + 2);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // HB0 / HB1 of t+2 stay in flight; K-tile t+1 has landed
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    SA_BAR();
-    SA_GEMM8_MMA(1, 0);
-    SA_BAR();
-  }
-  if (STAGGER && wr == 0) __builtin_amdgcn_s_barrier();  // every wave passes the same number of barriers
-#undef SA_GEMM8_MMA
-#undef SA_GEMM8_READ_W
-#undef SA_BAR
-  if constexpr (ABL == 9) ts2 = __builtin_readcyclecounter();
-
-  // ---- epilogue (contract of GemmParams, common.h): shared with gemm8s_kernel below ----------------------------
-  if (p.flags & 64) {   // the linear epilogue needs no LDS: no barrier either
-    epilogue8_linear<2>(p, acc, b, m0 + wr * 128, n0 + wc * 64, lane);
-  } else {
-    __syncthreads();
-    if (p.flags & 128) epilogue8_rows<2>(p, acc, smem + wave * 16384, b, m0 + wr * 128, n0 + wc * 64, lane);
-    else epilogue8<2>(p, acc, smem + wave * 16384, b, m0 + wr * 128, n0 + wc * 64, lane);
-  }
-  if constexpr (ABL == 9) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stores have left the wave
-    const unsigned long long ts3 = __builtin_readcyclecounter();
-    if (lane == 0) {
-      unsigned long long* o = (unsigned long long*)p.act_alpha + ((size_t)blockIdx.x * 8 + wave) * 4;
-      o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = ts3;
-    }
-  }
-}
-
-#endif  // SAMAUDIO_GEMM8_ABL
-
-// gemm8_kernel (round 4): the 8-phase loop above with the DMA issued as inline assembly.  GPU call 4
+// gemm8_kernel (round 4): the 8-phase loop of the header with the DMA issued as inline assembly (rounds 2 - 3 issued it through the
+// builtin, into a buffer-major LDS layout: the git history; its ablations are profiles/r4_call4/).  GPU call 4
 // (profiles/r4_call4/ablate.log): a K-tile of the round-3 loop took 2 533 cycles for 2 048 cycles of MFMA work; without its
 // DMA instructions 2 105, without its LDS fragment reads 2 006, without barriers / priorities no less - the read side of the
 // heavy phases was the longer leg, and the ISA showed why: hipcc treats a global_load_lds it can see as a "flat" access
@@ -726,7 +478,11 @@ __global__ __launch_bounds__(512) void gemm8o_kernel(const GemmParams p, const i
 // end to end 234.5 -> 240.7 s-audio/s.  Also measured there and dropped: reading the next K-tile's first W fragments in P4
 // (8 / 4 / 8 / 4 reads per phase instead of 12 / 4 / 8 / 0; +-0.5 %), and in call 1 a deeper staging pipeline (five
 // half-tiles in flight instead of two: 1 - 3 % slower - load latency was never the limiter).
-// Same tile, MFMA order and epilogues as gemm8o / gemm8s: the same bits.
+// Same tile, MFMA order and epilogues as the round-3 loop and as gemm8s: the same bits.
+// The two wave groups run one barrier apart and every MFMA cluster runs under s_setprio 1 (round-2 A/B builds of the template on one
+// box: without the stagger -11 %, without the priority -9 %; profiles/r2_call3/).
+// CONV: A's k axis is split into taps (implicit convolutions: kc < K); plain GEMMs compile the per-K-tile tap walk - a per-lane loop
+// under an exec mask, twice per K-tile - out of the K loop (3 - 5 % faster, round 3).
 // ALT: the operands are in the alt 16-bit format (mixed mode: bf16 inside the fp16 build) - the MFMA opcode is the only difference
 template <bool CONV, bool ALT = false>
 __global__ __launch_bounds__(512) void gemm8_kernel(const GemmParams p, const int tile_count) {
@@ -754,7 +510,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmParams p, const in
   }
   for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
   int b, tm, tn;
-  tile_of(p, BM, BN, xcd_run_pos_of(total, vb), b, tm, tn);
+  tile_of(p, BM, BN, xcd_run_pos(vb, total), b, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
 
   // ---- staging: plain GEMMs address a row as (uniform base advancing 128 bytes per K-tile) + (per-lane 32-bit byte offset)
@@ -952,18 +708,18 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmParams p, const in
 #undef SA_G8P_READ_W
 #undef SA_G8P_READ_A
 
-  if (p.flags & 64) {
+  if (p.flags & GEMM_FLAG_EPI_LINEAR) {
     epilogue8_linear<2>(p, acc, b, m0 + wr * 128, n0 + wc * 64, lane);
   } else {
     __syncthreads();
-    if (p.flags & 128) epilogue8_rows<2>(p, acc, smem + wave * 16384, b, m0 + wr * 128, n0 + wc * 64, lane);
+    if (p.flags & GEMM_FLAG_EPI_ROWS) epilogue8_rows<2>(p, acc, smem + wave * 16384, b, m0 + wr * 128, n0 + wc * 64, lane);
     else epilogue8<2>(p, acc, smem + wave * 16384, b, m0 + wr * 128, n0 + wc * 64, lane);
     if (vb + (int)gridDim.x < total) __syncthreads();   // the staging area is the next tile's K-tile buffers
   }
   }   // tiles of this workgroup
 }
 
-// gemm8x_kernel (round 6): gemm8_kernel for the K-CONCATENATED operands of the compensated mode (GemmParams.flags bit 15,
+// gemm8x_kernel (round 6): gemm8_kernel for the K-CONCATENATED operands of the compensated mode (GEMM_FLAG_X3_SHARE,
 // GEMM_FLAG_X3_SHARE: A rows [x_lo | x_hi | x_hi], W rows [W_hi | W_lo | W_hi], K' = 3K - common.h), aware that a third of what the plain
 // kernel stages is a copy.  Per 64 original k the plain kernel walks three K-tiles far apart in K' - (x_lo, W_hi), (x_hi, W_lo),
 // (x_hi, W_hi) - and stages six operand tiles; here the three products of one original k-tile run back to back in the order
@@ -1003,7 +759,7 @@ __global__ __launch_bounds__(512) void gemm8x_kernel(const GemmParams p, const i
   const int T3 = p.K / 192;   // original K-tiles: K' = 3K, 64 k each
   for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
   int b, tm, tn;
-  tile_of(p, BM, BN, xcd_run_pos_of(total, vb), b, tm, tn);
+  tile_of(p, BM, BN, xcd_run_pos(vb, total), b, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   const int r8 = lane >> 3;
   unsigned a_off[2][2], w_off[2][2];
@@ -1180,11 +936,11 @@ __global__ __launch_bounds__(512) void gemm8x_kernel(const GemmParams p, const i
 #undef SA_G8X_READ_W
 #undef SA_G8X_READ_A
 
-  if (p.flags & 64) {
+  if (p.flags & GEMM_FLAG_EPI_LINEAR) {
     epilogue8_linear<2>(p, acc, b, m0 + wr * 128, n0 + wc * 64, lane);
   } else {
     __syncthreads();
-    if (p.flags & 128) epilogue8_rows<2>(p, acc, smem + wave * 16384, b, m0 + wr * 128, n0 + wc * 64, lane);
+    if (p.flags & GEMM_FLAG_EPI_ROWS) epilogue8_rows<2>(p, acc, smem + wave * 16384, b, m0 + wr * 128, n0 + wc * 64, lane);
     else epilogue8<2>(p, acc, smem + wave * 16384, b, m0 + wr * 128, n0 + wc * 64, lane);
     if (vb + (int)gridDim.x < total) __syncthreads();
   }
@@ -1252,7 +1008,7 @@ __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const Gem
   int b, tm, tn, m0, n0;
   if (skip256 >= 0) {
     const int total256 = ((p.M + 255) / 256) * ((p.N + 255) / 256) * p.nbatch;
-    const int pos = xcd_run_pos((total256 - skip256) * 4);
+    const int pos = xcd_run_pos(blockIdx.x, (total256 - skip256) * 4);
     tile_of(p, 256, 256, skip256 + (pos >> 2), b, tm, tn);
     m0 = tm * 256 + ((pos >> 1) & 1) * 128;
     n0 = tn * 256 + (pos & 1) * 128;
@@ -1263,7 +1019,7 @@ __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const Gem
       if (p.pf_ptr) prefetch_lines(p, (int)blockIdx.x - total, (int)gridDim.x - total, (int)blockDim.x);
       return;
     }
-    tile_of(p, BM, BN, xcd_run_pos(total), b, tm, tn);
+    tile_of(p, BM, BN, xcd_run_pos(blockIdx.x, total), b, tm, tn);
     m0 = tm * BM;
     n0 = tn * BN;
   }
@@ -1362,7 +1118,7 @@ __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const Gem
         else wait_vm_lit<0>();
         __builtin_amdgcn_s_barrier();
       }
-      if (!(p.flags & 64)) __syncthreads();   // the multiplying waves' barrier in front of the LDS-staged epilogues
+      if (!(p.flags & GEMM_FLAG_EPI_LINEAR)) __syncthreads();   // the multiplying waves' barrier in front of the LDS-staged epilogues
       return;
     }
   }
@@ -1445,12 +1201,12 @@ __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const Gem
     } else {
       step(t, I0{}, std::false_type{});
     }
-    if (p.flags & 64) {
+    if (p.flags & GEMM_FLAG_EPI_LINEAR) {
       epilogue8_linear<1>(p, acc, b, m0 + wr * 64, n0 + wc * 64, lane);
       return;
     }
     __syncthreads();
-    if (p.flags & 128) epilogue8_rows<1>(p, acc, smem + wave * 16384, b, m0 + wr * 64, n0 + wc * 64, lane);
+    if (p.flags & GEMM_FLAG_EPI_ROWS) epilogue8_rows<1>(p, acc, smem + wave * 16384, b, m0 + wr * 64, n0 + wc * 64, lane);
     else epilogue8<1>(p, acc, smem + wave * 16384, b, m0 + wr * 64, n0 + wc * 64, lane);
     return;
   }
@@ -1484,12 +1240,12 @@ __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const Gem
         for (int i = 0; i < 4; ++i)
           acc[i][j] = ALT ? SA_MFMA_16x16x32_ALT(wf[j][ks], af[i][ks], acc[i][j]) : SA_MFMA_16x16x32(wf[j][ks], af[i][ks], acc[i][j]);
   }
-  if (p.flags & 64) {
+  if (p.flags & GEMM_FLAG_EPI_LINEAR) {
     epilogue8_linear<1>(p, acc, b, m0 + wr * 64, n0 + wc * 64, lane);
     return;
   }
   __syncthreads();
-  if (p.flags & 128) epilogue8_rows<1>(p, acc, smem + wave * 16384, b, m0 + wr * 64, n0 + wc * 64, lane);
+  if (p.flags & GEMM_FLAG_EPI_ROWS) epilogue8_rows<1>(p, acc, smem + wave * 16384, b, m0 + wr * 64, n0 + wc * 64, lane);
   else epilogue8<1>(p, acc, smem + wave * 16384, b, m0 + wr * 64, n0 + wc * 64, lane);
 }
 
@@ -1498,17 +1254,17 @@ __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const Gem
 static bool gemm8_wide(const GemmParams& p) {
   return p.kc < p.K || (long)p.M * p.lda * 2 >= (1L << 32) || (long)p.N * p.K * 2 >= (1L << 32);
 }
-// The launches whose epilogue is "linear" (every Linear of the DiT / the towers): bit 6 = epilogue8_linear (16-bit output
-// only: straight from the accumulator layout), bit 7 = epilogue8_rows (fp32 output / residual: through the wave's LDS area).
-// Debug flag 24: 1 = the general epilogue for everything (the bitwise-equality tests), 2 / 3 = the register / LDS form for
-// every eligible launch (A/B).
+// The launches whose epilogue is "linear" (every Linear of the DiT / the towers): GEMM_FLAG_EPI_LINEAR = epilogue8_linear (16-bit
+// output only: straight from the accumulator layout), GEMM_FLAG_EPI_ROWS = epilogue8_rows (fp32 output / residual: through the wave's
+// LDS area), 0 = the general epilogue.  DBG_GEMM8_EPILOGUE: the general epilogue for everything (the bitwise-equality tests), or the
+// register / LDS form for every eligible launch (A/B).
 static int gemm8_linear_epilogue(const GemmParams& p) {
-  const int mode = debug_flag(24);
-  if (mode == 1) return 0;
-  if (p.act != ACT_NONE || p.chan_mod || p.c_ld_rel || (p.flags & 1) || p.N % 64 || p.alpha != 1.f) return 0;
+  const int mode = debug_flag(DBG_GEMM8_EPILOGUE);
+  if (mode == DBG_EPI_GENERAL) return 0;
+  if (p.act != ACT_NONE || p.chan_mod || p.c_ld_rel || (p.flags & GEMM_FLAG_EPI_ACC) || p.N % 64 || p.alpha != 1.f) return 0;
   if (!p.out_act && !p.out_f32) return 0;
   if (p.swiglu && (!p.out_act || p.out_f32 || p.bias || p.gate || p.res)) return 0;
-  if ((p.flags & GEMM_FLAG_OUT_SPLIT3) && (!p.swiglu || (p.flags & 512) || (p.N / 2) % 8)) return 0;   // (gemm8_split3_ok)
+  if ((p.flags & GEMM_FLAG_OUT_SPLIT3) && (!p.swiglu || (p.flags & GEMM_FLAG_OUT_ALT) || (p.N / 2) % 8)) return 0;   // (gemm8_split3_ok)
   if (p.bias && (p.gate || p.gate_tab)) return 0;
   if (p.gate_tab && !p.gate) return 0;
   auto al = [](long v, long a) { return v % a == 0; };
@@ -1516,14 +1272,14 @@ static int gemm8_linear_epilogue(const GemmParams& p) {
     return 0;
   if (p.gate && (p.rows_per_gate <= 0 || (long)p.M * p.nbatch >= (1L << 31))) return 0;
   // 16-byte alignment of the fp32 operands: gemm2_ok(), checked by the policy for every launch of this file
-  if (p.swiglu || mode == 2) return 64;
-  if (mode == 3) return 128;
-  return p.out_f32 || p.res ? 128 : 64;
+  if (p.swiglu || mode == DBG_EPI_LINEAR) return GEMM_FLAG_EPI_LINEAR;
+  if (mode == DBG_EPI_ROWS) return GEMM_FLAG_EPI_ROWS;
+  return p.out_f32 || p.res ? GEMM_FLAG_EPI_ROWS : GEMM_FLAG_EPI_LINEAR;
 }
 static GemmParams with_epilogue_choice(const GemmParams& p) {
   GemmParams q = p;
-  q.flags = (q.flags & ~192) | gemm8_linear_epilogue(p);
-  if (!q.raster_gm && debug_flag(35) > 0) q.raster_gm = debug_flag(35);   // (A/B) M-tiles per raster group of the 8-phase family
+  q.flags = (q.flags & ~GEMM_FLAG_EPI_LEAN) | gemm8_linear_epilogue(p);
+  if (!q.raster_gm && debug_flag(DBG_RASTER_GM) > 0) q.raster_gm = debug_flag(DBG_RASTER_GM);   // (A/B) M-tiles per raster group of the 8-phase family
   return q;
 }
 
@@ -1532,52 +1288,47 @@ static GemmParams with_epilogue_choice(const GemmParams& p) {
 // identical - ran exactly as fast: c_wq 36.0 vs 35.3 us, 4 clips 114.8 vs 115.1 s-audio/s, small* 423 vs 424.  With few
 // rows a launch lasts nt x ~0.8 us whatever its workgroup count: it is bound by the depth of the K-tile prefetch (two K-tiles
 // of L2 latency in flight), not by how many CUs hold a tile.  Removed; profiles/r3_call8/.)
-// alt-format operands (flags bit 10, mixed mode) exist for plain GEMMs only - the DiT's Linears - gemm8_alt_ok()
-#define SA_GEMM8S_ROLES_DEFAULT 2   // the shipped form of the pipelined kernel: -1 no roles, 0 / 2 = PROD
+// alt-format operands (GEMM_FLAG_OPND_ALT, mixed mode) exist for plain GEMMs only - the DiT's Linears - gemm8_alt_ok()
+// the run-time (conv, alt) of a launch -> gemm8s_kernel<PIPE, CONV, ALT, PROD>; PROD >= 0: 8 waves.  conv launches never carry
+// alt-format operands (gemm8_alt_ok), so 3 operand forms x (plain | pipelined x 3 role settings) = 12 instantiations exist
+template <bool PIPE, int PROD>
+static void launch_gemm8s_as(const GemmParams& p, bool conv, dim3 grid, int skip256, hipStream_t st) {
+  const dim3 block(PROD >= 0 ? 512 : 256);
+  if (conv) hipLaunchKernelGGL((gemm8s_kernel<PIPE, true, false, PROD>), grid, block, 0, st, p, skip256);
+  else if (p.flags & GEMM_FLAG_OPND_ALT) hipLaunchKernelGGL((gemm8s_kernel<PIPE, false, true, PROD>), grid, block, 0, st, p, skip256);
+  else hipLaunchKernelGGL((gemm8s_kernel<PIPE, false, false, PROD>), grid, block, 0, st, p, skip256);
+}
 static void launch_gemm8s_grid(const GemmParams& p, bool pipe, bool conv, dim3 grid, int skip256, hipStream_t st) {
-  const dim3 block(256);
-  const bool alt = (p.flags & 1024) != 0;
-  // wave roles of the pipelined form (see the kernel): debug flag 27 = 1 the form without roles (round 3), 2 / 3 force PROD = 0 / 2
-  const int roles = !pipe || debug_flag(27) == 1 ? -1 : debug_flag(27) == 3 ? 2 : debug_flag(27) == 2 ? 0 : SA_GEMM8S_ROLES_DEFAULT;
-  if (roles >= 0) {
-    const dim3 block8(512);
-    if (conv && roles == 0) hipLaunchKernelGGL((gemm8s_kernel<true, true, false, 0>), grid, block8, 0, st, p, skip256);
-    else if (conv) hipLaunchKernelGGL((gemm8s_kernel<true, true, false, 2>), grid, block8, 0, st, p, skip256);
-    else if (alt && roles == 0) hipLaunchKernelGGL((gemm8s_kernel<true, false, true, 0>), grid, block8, 0, st, p, skip256);
-    else if (alt) hipLaunchKernelGGL((gemm8s_kernel<true, false, true, 2>), grid, block8, 0, st, p, skip256);
-    else if (roles == 0) hipLaunchKernelGGL((gemm8s_kernel<true, false, false, 0>), grid, block8, 0, st, p, skip256);
-    else hipLaunchKernelGGL((gemm8s_kernel<true, false, false, 2>), grid, block8, 0, st, p, skip256);
-    return;
+  if (!pipe) return launch_gemm8s_as<false, -1>(p, conv, grid, skip256, st);
+  // wave roles of the pipelined form (see the kernel; PROD of the shipped form: 2)
+  switch (debug_flag(DBG_GEMM8S_ROLES)) {
+    case DBG_ROLES_NONE: return launch_gemm8s_as<true, -1>(p, conv, grid, skip256, st);
+    case DBG_ROLES_PROD0: return launch_gemm8s_as<true, 0>(p, conv, grid, skip256, st);
+    default: return launch_gemm8s_as<true, 2>(p, conv, grid, skip256, st);   // (DBG_ROLES_PROD2 = the shipped form)
   }
-  if (pipe && conv) hipLaunchKernelGGL((gemm8s_kernel<true, true>), grid, block, 0, st, p, skip256);
-  else if (pipe && alt) hipLaunchKernelGGL((gemm8s_kernel<true, false, true>), grid, block, 0, st, p, skip256);
-  else if (pipe) hipLaunchKernelGGL((gemm8s_kernel<true, false>), grid, block, 0, st, p, skip256);
-  else if (conv) hipLaunchKernelGGL((gemm8s_kernel<false, true>), grid, block, 0, st, p, skip256);
-  else if (alt) hipLaunchKernelGGL((gemm8s_kernel<false, false, true>), grid, block, 0, st, p, skip256);
-  else hipLaunchKernelGGL((gemm8s_kernel<false, false>), grid, block, 0, st, p, skip256);
 }
-// flags bit 12 is well-formed: only the register epilogue of a SwiGLU launch writes the split form
+// GEMM_FLAG_OUT_SPLIT3 is well-formed: only the register epilogue of a SwiGLU launch writes the split form
 bool gemm8_split3_ok(const GemmParams& p) {
-  return !(p.flags & GEMM_FLAG_OUT_SPLIT3) || (p.swiglu && p.out_act && gemm8_linear_epilogue(p) == 64);
+  return !(p.flags & GEMM_FLAG_OUT_SPLIT3) || (p.swiglu && p.out_act && gemm8_linear_epilogue(p) == GEMM_FLAG_EPI_LINEAR);
 }
-// flags bit 15 is well-formed: plain operands within 32-bit offsets (no implicit convolution), K' = 3K with K a multiple of 64, the
+// GEMM_FLAG_X3_SHARE is well-formed: plain operands within 32-bit offsets (no implicit convolution), K' = 3K with K a multiple of 64, the
 // library's own operand format
 bool gemm8_share_ok(const GemmParams& p) {
-  return !(p.flags & GEMM_FLAG_X3_SHARE) || (!gemm8_wide(p) && !(p.flags & 1024) && p.K % 192 == 0 && p.kc == p.K);
+  return !(p.flags & GEMM_FLAG_X3_SHARE) || (!gemm8_wide(p) && !(p.flags & GEMM_FLAG_OPND_ALT) && p.K % 192 == 0 && p.kc == p.K);
 }
-// flags bits 9 / 10 are well-formed for this launch: plain operands within 32-bit offsets, a lean epilogue for an alt-format output
+// GEMM_FLAG_OUT_ALT / GEMM_FLAG_OPND_ALT are well-formed for this launch: plain operands within 32-bit offsets, a lean epilogue for an alt-format output
 bool gemm8_alt_ok(const GemmParams& p) {
-  if (!(p.flags & (512 | 1024))) return true;
-  if ((p.flags & 1024) && gemm8_wide(p)) return false;
-  if ((p.flags & 512) && (!p.out_act || gemm8_linear_epilogue(p) == 0)) return false;
+  if (!(p.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_OPND_ALT))) return true;
+  if ((p.flags & GEMM_FLAG_OPND_ALT) && gemm8_wide(p)) return false;
+  if ((p.flags & GEMM_FLAG_OUT_ALT) && (!p.out_act || gemm8_linear_epilogue(p) == 0)) return false;
   return true;
 }
 
 hipError_t launch_gemm8s(const GemmParams& p_in, hipStream_t st) {
   const GemmParams p = with_epilogue_choice(p_in);
   const long tiles = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.nbatch;
-  // flag 21 (A/B): the plain double-buffered form for every launch, as before GPU call 25 of round 2
-  const bool pipe = tiles <= 256 && !debug_flag(21), conv = gemm8_wide(p);
+  // DBG_GEMM8S_PLAIN (A/B): the plain double-buffered form for every launch, as before GPU call 25 of round 2
+  const bool pipe = tiles <= 256 && !debug_flag(DBG_GEMM8S_PLAIN), conv = gemm8_wide(p);
   // pf_ptr: the pipelined form holds one workgroup per CU - a launch of fewer than 256 tiles is padded with workgroups that
   // touch the next launch's weights on the CUs it leaves idle (prefetch_lines)
   const dim3 grid((unsigned)(p.pf_ptr && p.pf_bytes > 0 && pipe && tiles < 256 ? 256 : tiles));
@@ -1587,28 +1338,16 @@ hipError_t launch_gemm8s(const GemmParams& p_in, hipStream_t st) {
 
 static void launch_gemm8_tiles(const GemmParams& p, dim3 grid, int tile_count, hipStream_t st) {
   const dim3 block(512);
-#ifdef SAMAUDIO_GEMM8_ABL   // timing experiments (tools/build_abl.sh): debug flag 25 selects an ablation of the round-3 loop
-  if (!(p.kc < p.K)) switch (debug_flag(25)) {
-    case 1: hipLaunchKernelGGL((gemm8o_kernel<false, 1>), grid, block, 0, st, p, tile_count); return;
-    case 2: hipLaunchKernelGGL((gemm8o_kernel<false, 2>), grid, block, 0, st, p, tile_count); return;
-    case 3: hipLaunchKernelGGL((gemm8o_kernel<false, 3>), grid, block, 0, st, p, tile_count); return;
-    case 4: hipLaunchKernelGGL((gemm8o_kernel<false, 4>), grid, block, 0, st, p, tile_count); return;
-    case 5: hipLaunchKernelGGL((gemm8o_kernel<false, 5>), grid, block, 0, st, p, tile_count); return;
-    case 8: hipLaunchKernelGGL((gemm8o_kernel<false, 0>), grid, block, 0, st, p, tile_count); return;
-    case 9: hipLaunchKernelGGL((gemm8o_kernel<false, 9>), grid, block, 0, st, p, tile_count); return;
-    default: break;
-  }
-#endif
-  // Persistent above one round of the chip: at most one workgroup per CU, each walking its XCD's run of tiles (debug flag 26 =
+  // Persistent above one round of the chip: at most one workgroup per CU, each walking its XCD's run of tiles (DBG_GEMM8_NOT_PERSISTENT =
   // 1: one workgroup per tile, as in round 3).  Per launch the walk is worth 1 - 4 % (w13 at 4 000 rows 259 -> 254 us: the
   // epilogue stores drain under the next prologue); end to end, with two row groups on two streams, 223.5 -> 234.2 s-audio/s
   // (+4.7 %, profiles/r4_call7/): a launch now keeps its CUs for its whole duration instead of re-competing for them with
   // the other group's launch after every tile.
-  if (debug_flag(26) != 1 && grid.x > 256) grid.x = 256;
+  if (debug_flag(DBG_GEMM8_NOT_PERSISTENT) != 1 && grid.x > 256) grid.x = 256;
   if (p.pf_ptr && p.pf_bytes > 0 && tile_count == 0 && grid.x < 256) grid.x = 256;   // idle CUs warm the next launch's weights
-  if ((p.flags & GEMM_FLAG_X3_SHARE) && !gemm8_wide(p) && !(p.flags & 1024)) hipLaunchKernelGGL(gemm8x_kernel, grid, block, 0, st, p, tile_count);
+  if ((p.flags & GEMM_FLAG_X3_SHARE) && !gemm8_wide(p) && !(p.flags & GEMM_FLAG_OPND_ALT)) hipLaunchKernelGGL(gemm8x_kernel, grid, block, 0, st, p, tile_count);
   else if (gemm8_wide(p)) hipLaunchKernelGGL((gemm8_kernel<true>), grid, block, 0, st, p, tile_count);
-  else if (p.flags & 1024) hipLaunchKernelGGL((gemm8_kernel<false, true>), grid, block, 0, st, p, tile_count);   // alt-format operands
+  else if (p.flags & GEMM_FLAG_OPND_ALT) hipLaunchKernelGGL((gemm8_kernel<false, true>), grid, block, 0, st, p, tile_count);   // alt-format operands
   else hipLaunchKernelGGL((gemm8_kernel<false>), grid, block, 0, st, p, tile_count);
 }
 
@@ -1630,7 +1369,7 @@ hipError_t launch_gemm8_split(const GemmParams& p_in, int full, int part, hipStr
   if (full <= 0 || full >= tiles) return hipErrorInvalidValue;
   if (part == 0) launch_gemm8_tiles(p, dim3((unsigned)full), full, st);
   else {
-    const bool pipe = (tiles - full) * 4 <= 256 && !debug_flag(21);   // a tail that cannot give a CU two workgroups
+    const bool pipe = (tiles - full) * 4 <= 256 && !debug_flag(DBG_GEMM8S_PLAIN);   // a tail that cannot give a CU two workgroups
     const bool conv = gemm8_wide(p);
     const dim3 grid((unsigned)((tiles - full) * 4));
     launch_gemm8s_grid(p, pipe, conv, grid, full, st);

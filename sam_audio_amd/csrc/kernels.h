@@ -8,30 +8,55 @@ namespace sa {
 // test aid: fill the LDS of every CU with NaN bit patterns (LDS persists between kernels)
 hipError_t launch_poison_lds(hipStream_t st);
 
-// test / tuning switches (samaudio_debug_set_flag); 0 = shipped path.  Round 3 removed the A/B generations that had lost
-// their measurements (the logs are under profiles/, the code in the git history); what is left are hooks the tests use:
-//   flag 11: k7 convolutions as implicit GEMMs (no conv7h kernel) - the bitwise-equality tests of conv7h
-//   flag 16: DAC residual units as two launches (k7 + k1) instead of the fused resunit kernel - its bitwise-equality tests
-//   flag 18: fuse residual units whatever the launch size (tests: small launches otherwise stay two launches)
-//   flag 19: 1 = residual units on the weight-stationary kernel whatever the launch size (its tests; otherwise >= 1024
-//            tiles), 3 = the same on 3 workgroups (small cases then walk several tiles each), 2 = never (ring kernel: A/B)
-//   flag 21: gemm8s always in its plain double-buffered form (launches of <= 256 workgroups use the pipelined form)
-//   flag 24: epilogue of the 8-phase family: 0 = shipped choice (register form for 16-bit-only outputs, LDS-staged lean form
-//            for fp32 output / residual, general contract for everything else), 1 = the general epilogue for every launch
-//            (bitwise-equality tests of the lean forms), 2 / 3 = the register / LDS form for every eligible launch (A/B)
-//   flag 26: 1 = the 8-phase kernel launches one workgroup per tile (shipped: persistent above 256 tiles) - its bitwise test
-//   flag 29: 1 = qkv_prep with its 16-bit rounding written out (the form before round 4: reproducer of the run-to-run difference its
-//            SDWA instruction sequence showed beside another kernel's waves - kernels.hip, tools/stress_qkv_prep.py)
-//   flag 27: wave roles of gemm8s' pipelined form (gemm8.hip): 0 = shipped choice, 1 = none (4 waves request and multiply, round 3),
-//            2 = 4 requesting waves beside 4 multiplying ones, 3 = the same with the multiplying waves issuing 2 of their 8 loads
-//   flag 33: (A/B) smallest last round, in 256x256 tiles, that is split off as a 128x128-tile tail launch (0 = shipped: 8)
-//   flag 31: 1 = the folded cross-attention operand U = Wo V of every layer in its own launch (shipped: all layers of an evaluation in
-//            one launch in front of the layer loop) - its bitwise test
-//   flag 35: (A/B) M-tiles per raster group of the 8-phase family (0 = shipped: 8; GemmParams.raster_gm)
-//   flag 36: 1 = (A/B, tests) split-weight launches of the fp32 kernel (GEMM_FLAG_W_FLY16) on the tiles of gemm1_variant instead of fly_variant's
-//   flag 38: 1 = x3 launches walk K' = 3K as a plain GEMM (shipped: the operand-sharing order of GEMM_FLAG_X3_SHARE) - A/B, bitwise tests
-//   flag 30: (A/B) number of 256x256 tiles from which the policy uses gemm8 instead of gemm8s (0 = shipped: 128)
-//   flag 25: only in the ablation build (tools/build_abl.sh): selects an ablation of the round-3 8-phase loop
+// test / tuning switches (samaudio_debug_set_flag, SAMAUDIO_DEBUG_FLAGS=N=V); 0 = shipped path.  The numbers are a debugging ABI (the
+// tests, the tools and the logs under profiles/ use them; sam_audio_amd/hip.py mirrors the names, tests/test_gemm_names_cpu.py pins
+// both).  Round 3 removed the A/B generations that had lost their measurements (the logs are under profiles/, the code in the git
+// history); what is left are hooks the tests use and one-line policy thresholds.
+enum DebugFlag : int {
+  // 1 = k7 convolutions as implicit GEMMs, no conv7h kernel (the bitwise-equality tests of conv7h: test_gemm2_gpu.py)
+  DBG_NO_CONV7H = 11,
+  // 1 = DAC residual units as two launches (k7 + k1) instead of the fused resunit kernel (test_path_gpu.py)
+  DBG_RESUNIT_TWO_LAUNCHES = 16,
+  // 1 = fuse residual units whatever the launch size; small launches otherwise stay two launches (test_path_gpu.py)
+  DBG_RESUNIT_FUSE_ALWAYS = 18,
+  // residual units on the weight-stationary kernel: DBG_WS_* below (test_gemm2_gpu.py, test_path_gpu.py, tools/op_bench.py)
+  DBG_RESUNIT_WS = 19,
+  // 1 = gemm8s always in its plain double-buffered form; launches of <= 256 workgroups otherwise use the pipelined form (test_gemm2_gpu.py)
+  DBG_GEMM8S_PLAIN = 21,
+  // epilogue of the 8-phase family: DBG_EPI_* below (the bitwise-equality tests of the lean forms: test_gemm2_gpu.py)
+  DBG_GEMM8_EPILOGUE = 24,
+  // 1 = the 8-phase kernel launches one workgroup per tile; shipped: persistent above 256 tiles (its bitwise test: test_gemm2_gpu.py)
+  DBG_GEMM8_NOT_PERSISTENT = 26,
+  // wave roles of gemm8s' pipelined form (gemm8.hip): DBG_ROLES_* below (test_gemm2_gpu.py, test_fp16_gpu.py)
+  DBG_GEMM8S_ROLES = 27,
+  // 1 = qkv_prep with its 16-bit rounding written out: the form before round 4, reproducer of the run-to-run difference its SDWA
+  // instruction sequence showed beside another kernel's waves (kernels.hip; test_isa_cpu.py needs the form, tools/stress_qkv_prep.py)
+  DBG_QKV_PREP_SWROUND = 29,
+  // (A/B, no test) number of 256x256 tiles from which the policy uses gemm8 instead of gemm8s (0 = shipped: 128)
+  DBG_GEMM8_MIN_TILES = 30,
+  // 1 = the folded cross-attention operand U = Wo V of every layer in its own launch; shipped: all layers of an evaluation in one launch
+  // in front of the layer loop (its bitwise test: test_path_gpu.py)
+  DBG_FOLD_PER_LAYER = 31,
+  // (A/B, no test) smallest last round, in 256x256 tiles, that is split off as a 128x128-tile tail launch (0 = shipped: 8)
+  DBG_TAIL_SPLIT_MIN = 33,
+  // (A/B, no test) M-tiles per raster group of the 8-phase family (0 = shipped: 8; GemmParams.raster_gm)
+  DBG_RASTER_GM = 35,
+  // 1 = split-weight launches of the fp32 kernel (GEMM_FLAG_W_FLY16) on the tiles of gemm1_variant instead of fly_variant's
+  // (test_x3_gpu.py, tools/fly_probe.py)
+  DBG_FLY_OLD_TILES = 36,
+  // 1 = x3 launches walk K' = 3K as a plain GEMM; shipped: the operand-sharing order of GEMM_FLAG_X3_SHARE.  >= 2: a class mask << 1 that
+  // keeps the sharing order for those classes only (diagnosis).  (A/B through SAMAUDIO_DEBUG_FLAGS; test_x3_gpu.py compares the two walks)
+  DBG_X3_PLAIN_WALK = 38,
+};
+// values of DBG_RESUNIT_WS: whatever the launch size (its tests; otherwise >= 1024 tiles) | never (ring kernel: A/B) | as ALWAYS on a
+// grid of 3 workgroups (small cases then walk several tiles each)
+enum : int { DBG_WS_ALWAYS = 1, DBG_WS_NEVER = 2, DBG_WS_ALWAYS_GRID3 = 3 };
+// values of DBG_GEMM8_EPILOGUE: 0 = shipped choice (register form for 16-bit-only outputs, LDS-staged form for fp32 output / residual,
+// general contract for everything else) | the general epilogue for every launch | the register / LDS form for every eligible launch (A/B)
+enum : int { DBG_EPI_GENERAL = 1, DBG_EPI_LINEAR = 2, DBG_EPI_ROWS = 3 };
+// values of DBG_GEMM8S_ROLES: 0 = shipped choice | none (4 waves request and multiply, round 3) | 4 requesting waves beside 4 multiplying
+// ones | the same with the multiplying waves issuing 2 of their 8 loads
+enum : int { DBG_ROLES_NONE = 1, DBG_ROLES_PROD0 = 2, DBG_ROLES_PROD2 = 3 };
 void set_debug_flag(int flag, int value);
 // SAMAUDIO_TRACE_HASH debugging aid (engine.hip): per-item checksums of a buffer; the only device allocation of the library
 hipError_t launch_hash_items(const unsigned* x, size_t words_per_item, int items, unsigned long long* out, hipStream_t st);
@@ -41,28 +66,85 @@ hipError_t launch_sentinel(const void* x, int fmt, long rows, int cols, long ld,
 void* debug_device_alloc(size_t bytes);
 void debug_device_free(void* p);
 int debug_flag(int flag);
-void debug_touch();   // a process-wide debugging switch changed
-unsigned long long debug_epoch();
 
 hipError_t launch_gemm(const GemmParams& p, bool is_bf16, hipStream_t st);
 const char* gemm_check(const GemmParams& p, bool is_bf16);
-int gemm_variant(const GemmParams& p, bool is_bf16);       // which kernel / tile shape launch_gemm picks
-const char* gemm_variant_name(int variant, bool is_bf16);
-constexpr int kGemmVariants = 40;  // 36 .. 39 = the fp32 kernel's 4 x 1-wave tiles of split-weight launches (gemm.hip fly_variant);  // 35 = conv7h (k7 convolution, halo tile resident in LDS; conv7h_ok launches only)  // 0..2 gemm.hip tiles, 3.. = 3 + gemm2.hip variant; 25 / 26 = 128x128 / 64x128 tiles for small M
-                                   // (32x32x16 family); 27 = gemm8s, the 128x128 tile of the 16x16x32 (8-phase) family;
-                                   // 28 = 256x64 tile of the 32x32x16 family for 64-channel convolutions
-// gemm2.hip: 256-row-tile bf16 kernels (variants 3.. in gemm_variant's numbering are gemm2 variants 0..)
+// Which kernel / tile shape a launch runs on.  The numbers are a debugging ABI (samaudio_debug_force_gemm_variant, the tests, the tools
+// and the logs under profiles/ use them); kGemmVariantTable below has one row per id: family and profile names.
+enum GemmVariant : int {
+  // gemm.hip tiles (16-bit and fp32 operands)
+  GV_GEMM_128x128 = 0,
+  GV_GEMM_128x64 = 1,
+  GV_GEMM_128x32 = 2,
+  // the 16x16x32 "8-phase" family (gemm8.hip): bitwise equal between themselves
+  GV_GEMM8_256x256 = 22,     // gemm8
+  GV_GEMM8S_128x128 = 27,    // gemm8s: few rows; the tail of a split launch
+  // the 32x32x16 family (gemm2.hip), 16-bit operands only: bitwise equal among themselves
+  GV_GEMM2_128x128_S2 = 25,  // 25 / 26: 128x128 / 64x128 tiles for small M
+  GV_GEMM2_64x128_S3 = 26,
+  GV_GEMM2_256x64_S2 = 28,   // 64-channel convolutions
+  GV_GEMM2_128x128_K32 = 29,
+  GV_GEMM2_128x64_K32 = 32,
+  GV_GEMM2_64x128_K32 = 33,
+  GV_GEMM2_128x192_K32 = 34,
+  GV_CONV7H = 35,            // k7 convolution, halo tile resident in LDS; conv7h_ok launches only
+  // the fp32 kernel's 4 x 1-wave tiles of split-weight launches (gemm.hip fly_variant)
+  GV_FLY_128x96 = 36,
+  GV_FLY_128x128 = 37,
+  GV_FLY_128x64 = 38,
+  GV_FLY_128x32 = 39,
+};
+constexpr int kGemmVariants = 40;   // ids are < kGemmVariants
+// One row per GemmVariant: the family whose accumulation order the tile shares, and its profile names for 16-bit and fp32 operands
+// ("" = no such kernel).  The names are keys of the profile records and of bench.py's attribution.  (In this header, not in gemm.hip:
+// engine.hip reads it too, and the CPU emulation of the launchers - oracle/emu - links engine.hip without gemm.hip.)
+enum GemmFamily : int { FAM_TILES, FAM_32x32x16, FAM_8PHASE, FAM_FLY };   // gemm.hip tiles | gemm2.hip | gemm8.hip | gemm.hip fly_variant
+struct GemmVariantRow {
+  GemmVariant id;
+  GemmFamily family;
+  const char* name16;
+  const char* name32;
+};
+inline constexpr GemmVariantRow kGemmVariantTable[] = {
+    {GV_GEMM_128x128, FAM_TILES, "gemm_bf16_128x128", "gemm_f32_128x128"},
+    {GV_GEMM_128x64, FAM_TILES, "gemm_bf16_128x64", "gemm_f32_128x64"},
+    {GV_GEMM_128x32, FAM_TILES, "gemm_bf16_128x32", "gemm_f32_128x32"},
+    {GV_GEMM8_256x256, FAM_8PHASE, "gemm8_bf16_256x256_8phase", ""},
+    {GV_GEMM2_128x128_S2, FAM_32x32x16, "gemm2_bf16_128x128_s2", ""},
+    {GV_GEMM2_64x128_S3, FAM_32x32x16, "gemm2_bf16_64x128_s3", ""},
+    {GV_GEMM8S_128x128, FAM_8PHASE, "gemm8s_bf16_128x128", ""},
+    {GV_GEMM2_256x64_S2, FAM_32x32x16, "gemm2_bf16_256x64_s2", ""},
+    {GV_GEMM2_128x128_K32, FAM_32x32x16, "gemm2_bf16_128x128_k32_s3", ""},
+    {GV_GEMM2_128x64_K32, FAM_32x32x16, "gemm2_bf16_128x64_k32_s2", ""},
+    {GV_GEMM2_64x128_K32, FAM_32x32x16, "gemm2_bf16_64x128_k32_s3", ""},
+    {GV_GEMM2_128x192_K32, FAM_32x32x16, "gemm2_bf16_128x192_k32_s3", ""},
+    {GV_CONV7H, FAM_32x32x16, "conv7h_bf16", ""},
+    {GV_FLY_128x96, FAM_FLY, "", "gemm_f32x3_128x96"},
+    {GV_FLY_128x128, FAM_FLY, "", "gemm_f32x3_128x128"},
+    {GV_FLY_128x64, FAM_FLY, "", "gemm_f32x3_128x64"},
+    {GV_FLY_128x32, FAM_FLY, "", "gemm_f32x3_128x32"},
+};
+constexpr const GemmVariantRow* gemm_variant_row(int v) {   // nullptr: not an id
+  for (const GemmVariantRow& r : kGemmVariantTable)
+    if (r.id == v) return &r;
+  return nullptr;
+}
+constexpr bool gemm_is_8phase(int v) { return gemm_variant_row(v) && gemm_variant_row(v)->family == FAM_8PHASE; }
+constexpr const char* kGemm8sTailName = "gemm8s_bf16_128x128_tail";   // profile name of gemm8s as the tail of a split 8-phase GEMM
+int gemm_variant(const GemmParams& p, bool is_bf16);        // the GemmVariant launch_gemm picks
+const char* gemm_variant_name(int variant, bool is_bf16);   // "" for an id without a kernel of that operand type
+// gemm2.hip: the 32x32x16 family's tiles; dispatches the 8-phase family and conv7h to their launchers
 bool gemm2_ok(const GemmParams& p);
-hipError_t launch_gemm2(const GemmParams& p, int variant, hipStream_t st);
-// gemm8.hip: 256x256 8-phase kernel (variant 22); needs gemm2_ok(p)
+hipError_t launch_gemm2(const GemmParams& p, GemmVariant variant, hipStream_t st);
+// gemm8.hip: 256x256 8-phase kernel (GV_GEMM8_256x256); needs gemm2_ok(p)
 hipError_t launch_gemm8(const GemmParams& p, hipStream_t st);
-bool gemm8_share_ok(const GemmParams& p);   // GemmParams.flags bit 15 is well-formed for this launch (gemm8.hip)
+bool gemm8_share_ok(const GemmParams& p);   // GEMM_FLAG_X3_SHARE is well-formed for this launch (gemm8.hip)
 // gemm8.hip: 128x128 tile with gemm8's arithmetic (bitwise identical results), two workgroups per CU; needs gemm2_ok(p)
 hipError_t launch_gemm8s(const GemmParams& p, hipStream_t st);
-// gemm8.hip: GemmParams.flags bits 9 / 10 (mixed mode: out_act written / operands read in the alt 16-bit format) are well-formed;
-// only the 8-phase family (variants 22 / 27) implements them
+// gemm8.hip: GEMM_FLAG_OUT_ALT / GEMM_FLAG_OPND_ALT (mixed mode: out_act written / operands read in the alt 16-bit format) are
+// well-formed; only the 8-phase family implements them
 bool gemm8_alt_ok(const GemmParams& p);
-// gemm8.hip: GemmParams.flags bit 12 (out_act in the compensated-operand form [lo | hi | hi]) is well-formed: SwiGLU launches of the
+// gemm8.hip: GEMM_FLAG_OUT_SPLIT3 (out_act in the compensated-operand form [lo | hi | hi]) is well-formed: SwiGLU launches of the
 // 8-phase family with a 16-bit output only
 bool gemm8_split3_ok(const GemmParams& p);
 // gemm2.hip: dilated k = 7 'same' convolution C -> C (C = 64 / 96 / 128 / 192) with the activation halo tile resident in
@@ -78,7 +160,7 @@ hipError_t launch_gemm8_split(const GemmParams& p, int full, int part, hipStream
 int gemm_tail_split(const GemmParams& p, bool is_bf16);
 hipError_t launch_gemm_part(const GemmParams& p, bool is_bf16, int part, hipStream_t st);
 // test / tuning hook: force a variant for every eligible bf16 GEMM (-1 = automatic, 0..2 = gemm.hip tiles only,
-// 3.. = gemm2 variant when gemm2_ok)
+// a GemmVariant of the 16-bit families when gemm2_ok)
 void gemm_force_variant(int v);
 
 // out[m,:] = AT( rmsnorm(x[m,:]) * w * (1 + scale) + shift ),  shift = shift_tab + tvec[b, shift_off:],

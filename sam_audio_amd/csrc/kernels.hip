@@ -6,12 +6,8 @@
 namespace sa {
 
 static int g_debug_flags[64] = {0};
-static unsigned long long g_debug_epoch = 0;   // counts changes of the process-wide debugging switches (captured solves check it)
-void debug_touch() { ++g_debug_epoch; }
-unsigned long long debug_epoch() { return g_debug_epoch; }
 void set_debug_flag(int flag, int value) {
   if (flag >= 0 && flag < 64) g_debug_flags[flag] = value;
-  debug_touch();
 }
 int debug_flag(int flag) { return flag >= 0 && flag < 64 ? g_debug_flags[flag] : 0; }
 
@@ -57,9 +53,9 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_kernel(const float* __restric
   }
 }
 
-// Candidate replacement (debug flag 2, never on by default - not yet timed): the row stays in registers between the
-// statistics pass and the output pass (MAXV float4 per lane, D <= 256 * MAXV), so x is read from memory once instead of
-// twice.  Same arithmetic order per lane as the kernel above, so results are bit-identical.
+// The shipped form for rows of D <= 256 * MAXV (launch_rmsnorm_mod): the row stays in registers between the statistics pass
+// and the output pass (MAXV float4 per lane), so x is read from memory once instead of twice.  Same arithmetic order per
+// lane as the kernel above, so results are bit-identical.
 template <typename TO, int MAXV>
 __global__ __launch_bounds__(256) void rmsnorm_mod_reg_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                               const float* __restrict__ shift_tab,
@@ -432,7 +428,7 @@ __global__ __launch_bounds__(256) void qkv_prep_kernel(const TA* __restrict__ qk
 // bf16 fast path: 16 lanes x 16 bytes per 128-wide head row (4 rows per wave-instruction), so every global access
 // is a 16-byte load / store; the V tile is transposed through LDS as 16-bit words and leaves as 16-byte rows of V^T.
 // SWROUND = false (shipped): the 16-bit rounding of Q / K is the hardware conversion (pack_h16x2: v_cvt_pk_bf16_f32 / v_cvt_f16_f32).
-// SWROUND = true (debug flag 29 = 1) is the form this kernel had until round 4, kept as the reproducer of what it did: written out
+// SWROUND = true (DBG_QKV_PREP_SWROUND = 1) is the form this kernel had until round 4, kept as the reproducer of what it did: written out
 // (f2bf: integer add of 0x7fff + lsb), hipcc turns the bf16 rounding into SDWA word-select instructions (v_and_b32_sdwa ...
 // src0_sel:WORD_1) directly behind the packed-fp32 rotation (v_pk_fma_f32) that produces their operand - and when another kernel's waves
 // share the SIMD, the high half of one dword of Q (element 5 of a lane's 8) comes out wrong in ~0.5 % of the launches: 208 of 40 000
@@ -626,7 +622,7 @@ hipError_t launch_qkv_prep(const void* qkv, const float* qw, const float* kw, co
     return hipGetLastError();
   }
   if (head_dim != 128) return hipErrorInvalidValue;
-  if (bf16 && debug_flag(29) == 1)   // the pre-round-4 rounding: reproducer only (see the kernel)
+  if (bf16 && debug_flag(DBG_QKV_PREP_SWROUND) == 1)   // the pre-round-4 rounding: reproducer only (see the kernel)
     hipLaunchKernelGGL(qkv_prep_bf16_kernel<true>, grid, block, 0, st, (const bf16_t*)qkv, qw, kw, rope_cos, rope_sin, (bf16_t*)Q,
                        (bf16_t*)K, (bf16_t*)Vt, T, Tp, H, eps);
   else if (bf16)

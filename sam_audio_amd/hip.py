@@ -121,6 +121,28 @@ def class_mask(classes) -> int:
 
 ACT_NONE, ACT_SNAKE, ACT_TANH, ACT_SILU, ACT_GELU, ACT_QUICK_GELU, ACT_RELU, ACT_GELU_TANH = 0, 1, 2, 3, 4, 5, 6, 7
 
+# Mirrors of csrc/common.h (GemmParams.flags) and csrc/kernels.h (GemmVariant, DebugFlag and its values): the comments are there;
+# tests/test_gemm_names_cpu.py holds the two sides together.
+GEMM_FLAG_EPI_ACC, GEMM_FLAG_NO_TAIL_SPLIT = 1, 2
+GEMM_QUANT_NONE, GEMM_QUANT_BF16, GEMM_QUANT_FP16 = 0, 1, 2
+GEMM_FLAG_QUANT_A_SHIFT, GEMM_FLAG_QUANT_W_SHIFT, GEMM_FLAG_QUANT_MASK = 2, 4, 3
+GEMM_FLAG_EPI_LINEAR, GEMM_FLAG_EPI_ROWS, GEMM_FLAG_EPI_LEAN = 64, 128, 192
+GEMM_FLAG_OUT_ALT, GEMM_FLAG_OPND_ALT, GEMM_FLAG_W_KTM, GEMM_FLAG_OUT_SPLIT3 = 512, 1024, 2048, 4096
+GEMM_FLAG_X3_FLY, GEMM_FLAG_W_FLY16, GEMM_FLAG_X3_SHARE = 8192, 16384, 32768
+
+GV_GEMM_128x128, GV_GEMM_128x64, GV_GEMM_128x32 = 0, 1, 2
+GV_GEMM8_256x256, GV_GEMM8S_128x128 = 22, 27
+GV_GEMM2_128x128_S2, GV_GEMM2_64x128_S3, GV_GEMM2_256x64_S2, GV_GEMM2_128x128_K32 = 25, 26, 28, 29
+GV_GEMM2_128x64_K32, GV_GEMM2_64x128_K32, GV_GEMM2_128x192_K32, GV_CONV7H = 32, 33, 34, 35
+GV_FLY_128x96, GV_FLY_128x128, GV_FLY_128x64, GV_FLY_128x32 = 36, 37, 38, 39
+
+DBG_NO_CONV7H, DBG_RESUNIT_TWO_LAUNCHES, DBG_RESUNIT_FUSE_ALWAYS, DBG_RESUNIT_WS, DBG_GEMM8S_PLAIN = 11, 16, 18, 19, 21
+DBG_GEMM8_EPILOGUE, DBG_GEMM8_NOT_PERSISTENT, DBG_GEMM8S_ROLES, DBG_QKV_PREP_SWROUND, DBG_GEMM8_MIN_TILES = 24, 26, 27, 29, 30
+DBG_FOLD_PER_LAYER, DBG_TAIL_SPLIT_MIN, DBG_RASTER_GM, DBG_FLY_OLD_TILES, DBG_X3_PLAIN_WALK = 31, 33, 35, 36, 38
+DBG_WS_ALWAYS, DBG_WS_NEVER, DBG_WS_ALWAYS_GRID3 = 1, 2, 3
+DBG_EPI_GENERAL, DBG_EPI_LINEAR, DBG_EPI_ROWS = 1, 2, 3
+DBG_ROLES_NONE, DBG_ROLES_PROD0, DBG_ROLES_PROD2 = 1, 2, 3
+
 ERR_ARG, ERR_WEIGHT, ERR_WORKSPACE, ERR_HIP, ERR_STATE = -1, -2, -3, -4, -5
 
 

@@ -30,7 +30,7 @@ def _mk(shape, seed, scale=1.0):
 def _restore_variant():
     yield
     hip.lib("fp16").samaudio_debug_force_gemm_variant(-1)
-    hip.lib("fp16").samaudio_debug_set_flag(27, 0)
+    hip.lib("fp16").samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, 0)
 
 
 @pytest.mark.parametrize("variant", [-1, 1, 22, 25, 26, 27])
@@ -90,7 +90,7 @@ def test_mixed_mode_gemm_reads_and_writes_bfloat16_inside_the_fp16_library(gpu, 
     import ctypes as C
     lib = hip.lib("fp16")
     lib.samaudio_debug_force_gemm_variant(variant)
-    lib.samaudio_debug_set_flag(27, roles)   # gemm8s' pipelined form: without / with requesting waves (gemm8.hip)
+    lib.samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, roles)   # gemm8s' pipelined form: without / with requesting waves (gemm8.hip)
     M, N, K = 333, 512, 320
     A, W = _mk((M, K), 31), _mk((N, K), 32, 1 / math.sqrt(K))
     Ab, Wb = A.to(torch.bfloat16).to(gpu), W.to(torch.bfloat16).to(gpu)
@@ -112,7 +112,7 @@ def test_mixed_mode_gemm_reads_and_writes_bfloat16_inside_the_fp16_library(gpu, 
                       f32_geom=(0, N, 0))
             want = prod * (tab.cpu()[None] + gate.cpu()) + res.cpu()
         p = util.gemm_params(Ab, Wb, M, N, K, **kw)
-        p.flags = 1024 | (512 if out_alt else 0)
+        p.flags = hip.GEMM_FLAG_OPND_ALT | (hip.GEMM_FLAG_OUT_ALT if out_alt else 0)
         hip.check(lib.samaudio_op_gemm(C.byref(p), C.sizeof(p), util.PREC["fp16"], util.stream()))
         tol16 = want.abs().max().item() * (2.0 ** -8 if out_alt else 2.0 ** -11) * 1.02   # half an ulp of the output format
         util.report(f"mixed gemm v{variant} {kind} out_alt={out_alt} 16-bit", o16, want, tol16)

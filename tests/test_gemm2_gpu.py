@@ -31,7 +31,7 @@ def _mk(shape, seed, scale=1.0):
 def _restore_variant():
     yield
     hip.lib().samaudio_debug_force_gemm_variant(-1)
-    hip.lib().samaudio_debug_set_flag(27, 0)
+    hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, 0)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -203,16 +203,16 @@ def test_gemm8s_pipelined_form_is_bitwise_identical(gpu, M, N, K):
         for name, variant, flag, roles in (("pipelined", 27, 0, 0), ("no roles", 27, 0, 1), ("roles 0", 27, 0, 2),
                                            ("roles 2", 27, 0, 3), ("plain", 27, 1, 0), ("8phase", 22, 0, 0)):
             hip.lib().samaudio_debug_force_gemm_variant(variant)
-            hip.lib().samaudio_debug_set_flag(21, flag)
-            hip.lib().samaudio_debug_set_flag(27, roles)
+            hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_PLAIN, flag)
+            hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, roles)
             out = torch.full((M, N), float("nan"), device=gpu)
             out_act = torch.zeros(M, N, device=gpu, dtype=torch.bfloat16)
             util.gemm("bf16", keep[0], keep[1], M, N, K, gate_tab=keep[2], gate=keep[3], gate_ld=N, rows_per_gate=M,
                       res=keep[4], res_geom=(0, N, 0), out_f32=out, f32_geom=(0, N, 0), out_act=out_act, act_geom=(0, N, 0))
             outs[name] = (out.cpu(), out_act.cpu())
     finally:
-        hip.lib().samaudio_debug_set_flag(21, 0)
-        hip.lib().samaudio_debug_set_flag(27, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_PLAIN, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, 0)
         hip.lib().samaudio_debug_force_gemm_variant(-1)
     want = (util.rounded(A, "bf16") @ util.rounded(W, "bf16").T) * (tab[None] + gate) + res
     util.report(f"gemm8s pipelined {M}x{N}x{K}", outs["pipelined"][0], want, 5e-4)
@@ -244,11 +244,11 @@ def test_ktm_weights_and_prefetch_workgroups_are_bitwise_invisible(gpu, M, N, K,
             for layout in ("rows", "ktm"):
                 for pf in (False, True):
                     hip.lib().samaudio_debug_force_gemm_variant(variant)
-                    hip.lib().samaudio_debug_set_flag(21, flag21)
-                    hip.lib().samaudio_debug_set_flag(27, roles)
+                    hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_PLAIN, flag21)
+                    hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, roles)
                     out = torch.full((M, n_out), float("nan"), device=gpu)
                     out_act = torch.zeros(M, n_out, device=gpu, dtype=torch.bfloat16)
-                    kw = dict(out_act=out_act, act_geom=(0, n_out, 0), flags=2048 if layout == "ktm" else 0,
+                    kw = dict(out_act=out_act, act_geom=(0, n_out, 0), flags=hip.GEMM_FLAG_W_KTM if layout == "ktm" else 0,
                               prefetch=nxt if pf else None)
                     if kind == "swiglu":
                         kw.update(swiglu=1)
@@ -258,8 +258,8 @@ def test_ktm_weights_and_prefetch_workgroups_are_bitwise_invisible(gpu, M, N, K,
                     util.gemm("bf16", keep[0], Wk if layout == "ktm" else Wb, M, N, K, **kw)
                     outs[(variant, flag21, roles, layout, pf)] = (out.cpu(), out_act.cpu())
     finally:
-        hip.lib().samaudio_debug_set_flag(21, 0)
-        hip.lib().samaudio_debug_set_flag(27, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_PLAIN, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, 0)
         hip.lib().samaudio_debug_force_gemm_variant(-1)
     first = outs[(22, 0, 0, "rows", False)]
     if kind == "gated":
@@ -279,9 +279,9 @@ def test_ktm_weights_are_refused_outside_the_8phase_family(gpu):
     M, N, K = 300, 512, 192
     A, W = util.as_act(_mk((M, K), 97), "bf16", gpu), ktm_layout(util.as_act(_mk((N, K), 98), "bf16", gpu))
     out = torch.zeros(M, N, device=gpu)
-    hip.lib().samaudio_debug_force_gemm_variant(25)
+    hip.lib().samaudio_debug_force_gemm_variant(hip.GV_GEMM2_128x128_S2)
     with pytest.raises(AssertionError, match="K-tile-major"):
-        util.gemm("bf16", A, W, M, N, K, out_f32=out, f32_geom=(0, N, 0), flags=2048)
+        util.gemm("bf16", A, W, M, N, K, out_f32=out, f32_geom=(0, N, 0), flags=hip.GEMM_FLAG_W_KTM)
 
 
 @pytest.mark.parametrize("kind", ["conv", "plain16", "swiglu"])
@@ -292,7 +292,7 @@ def test_gemm8s_wave_roles_are_bitwise_invisible(gpu, kind):
     the epilogue barrier) and SwiGLU."""
     outs = {}
     try:
-        hip.lib().samaudio_debug_force_gemm_variant(27)
+        hip.lib().samaudio_debug_force_gemm_variant(hip.GV_GEMM8S_128x128)
         if kind == "conv":
             items, T, C, dil, halo = 2, 300, 256, 3, 40
             x, w = _mk((items, C, T), 81), _mk((C, C, 7), 82, 1 / math.sqrt(7 * C))
@@ -305,7 +305,7 @@ def test_gemm8s_wave_roles_are_bitwise_invisible(gpu, kind):
             A, W = _mk((M, K), 85), _mk((N, K), 86, 1 / math.sqrt(K))
             keep = [util.as_act(A, "bf16", gpu), util.as_act(W, "bf16", gpu)]
         for roles in (1, 2, 3):
-            hip.lib().samaudio_debug_set_flag(27, roles)
+            hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, roles)
             if kind == "conv":
                 out = torch.zeros(items, T + 2 * halo, C, device=gpu, dtype=torch.bfloat16)
                 util.gemm("bf16", keep[0], keep[1], T, C, 7 * C, nbatch=items, a_off=(halo - 3 * dil) * C,
@@ -317,7 +317,7 @@ def test_gemm8s_wave_roles_are_bitwise_invisible(gpu, kind):
                 util.gemm("bf16", keep[0], keep[1], M, N, K, out_act=out, act_geom=(0, n_out, 0), swiglu=int(kind == "swiglu"))
             outs[roles] = out.cpu()
     finally:
-        hip.lib().samaudio_debug_set_flag(27, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8S_ROLES, 0)
         hip.lib().samaudio_debug_force_gemm_variant(-1)
     assert torch.isfinite(outs[1].float()).all() and float(outs[1].float().abs().max()) > 0
     for roles in (2, 3):
@@ -463,7 +463,7 @@ def test_fused_residual_unit_is_bitwise_the_two_launches(gpu, C, dil, T, items):
     forms = [(False, 2), (True, 2)] + ([(True, 1), (True, 3)] if C <= 96 else [])   # (fused, debug flag 19)
     try:
         for fused, ws in forms:
-            hip.lib().samaudio_debug_set_flag(19, ws)
+            hip.lib().samaudio_debug_set_flag(hip.DBG_RESUNIT_WS, ws)
             mid = torch.zeros(items, T + 2 * halo, C, device=gpu, dtype=torch.bfloat16)
             out = torch.zeros(items, T + 2 * halo, C, device=gpu, dtype=torch.bfloat16)
             raw = raw0.to(gpu)
@@ -476,7 +476,7 @@ def test_fused_residual_unit_is_bitwise_the_two_launches(gpu, C, dil, T, items):
                     hip.check(hip.lib().samaudio_op_gemm(CT.byref(p), CT.sizeof(p), hip.BF16, util.stream()))
             res[(fused, ws)] = (raw.cpu(), out.cpu())
     finally:
-        hip.lib().samaudio_debug_set_flag(19, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_RESUNIT_WS, 0)
     assert torch.equal(xin.cpu().view(torch.int16), util.as_act(xb, "bf16", "cpu").view(torch.int16))
     for form in forms[1:]:
         assert torch.equal(res[form][0].view(torch.int32), res[(False, 2)][0].view(torch.int32)), form
@@ -514,7 +514,7 @@ def test_linear_epilogue_is_bitwise_the_general_one(gpu, variant, kind):
     try:
         for flag in (1, 0, 2, 3):
             hip.lib().samaudio_debug_force_gemm_variant(variant)
-            hip.lib().samaudio_debug_set_flag(24, flag)
+            hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8_EPILOGUE, flag)
             o32 = torch.full((nb, M, N), float("nan"), device=gpu)
             o16 = torch.zeros(nb, M, n_out, device=gpu, dtype=torch.bfloat16)
             if kind == "act":
@@ -536,7 +536,7 @@ def test_linear_epilogue_is_bitwise_the_general_one(gpu, variant, kind):
             util.gemm("bf16", keep["A"], keep["W"], M, N, K, **kw)
             outs[flag] = (o32.cpu(), o16.cpu())
     finally:
-        hip.lib().samaudio_debug_set_flag(24, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8_EPILOGUE, 0)
         hip.lib().samaudio_debug_force_gemm_variant(-1)
     uses32, uses16 = "out_f32" in kw, "out_act" in kw
     for flag in (0, 2, 3):
@@ -565,8 +565,8 @@ def test_persistent_tile_walk_is_bitwise_invisible(gpu, kind):
     outs = {}
     try:
         for flag in (0, 1):
-            hip.lib().samaudio_debug_force_gemm_variant(22)
-            hip.lib().samaudio_debug_set_flag(26, flag)
+            hip.lib().samaudio_debug_force_gemm_variant(hip.GV_GEMM8_256x256)
+            hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8_NOT_PERSISTENT, flag)
             o32 = torch.full((M, N), float("nan"), device=gpu)
             o16 = torch.zeros(M, N, device=gpu, dtype=torch.bfloat16)
             kw = dict(out_act=o16, act_geom=(0, N, 0))
@@ -576,7 +576,7 @@ def test_persistent_tile_walk_is_bitwise_invisible(gpu, kind):
             util.gemm("bf16", keep["A"], keep["W"], M, N, K, **kw)
             outs[flag] = (o32.cpu(), o16.cpu())
     finally:
-        hip.lib().samaudio_debug_set_flag(26, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_GEMM8_NOT_PERSISTENT, 0)
         hip.lib().samaudio_debug_force_gemm_variant(-1)
     assert torch.equal(outs[0][1].view(torch.int16), outs[1][1].view(torch.int16))
     if kind == "gated":

@@ -105,9 +105,11 @@ def test_codec_fused_residual_units_equal_the_two_launch_form(gpu):
     lat = torch.randn(4, 3, 128, generator=torch.Generator().manual_seed(2))
     model = _model(cfg, sd, "bf16", gpu)
     from sam_audio_amd import hip
+    TWO, FUSE, WS = hip.DBG_RESUNIT_TWO_LAUNCHES, hip.DBG_RESUNIT_FUSE_ALWAYS, hip.DBG_RESUNIT_WS
     outs = {}
     try:
-        for name, flags in (("two", {16: 1, 18: 0, 19: 0}), ("fused", {16: 0, 18: 1, 19: 2}), ("ws", {16: 0, 18: 1, 19: 3})):
+        for name, flags in (("two", {TWO: 1, FUSE: 0, WS: 0}), ("fused", {TWO: 0, FUSE: 1, WS: hip.DBG_WS_NEVER}),
+                            ("ws", {TWO: 0, FUSE: 1, WS: hip.DBG_WS_ALWAYS_GRID3})):
             for k, v in flags.items():
                 hip.lib().samaudio_debug_set_flag(k, v)
             if gpu.type == "cuda":     # the per-kernel records say which form ran (hipEvents: hardware only)
@@ -117,7 +119,7 @@ def test_codec_fused_residual_units_equal_the_two_launch_form(gpu):
                 ran = [r["name"] for r in model.profile_end()]
                 assert any("resunit" in r for r in ran) == (name != "two"), ran
     finally:
-        for k in (16, 18, 19):
+        for k in (TWO, FUSE, WS):
             hip.lib().samaudio_debug_set_flag(k, 0)
     for name in ("fused", "ws"):
         assert torch.equal(outs["two"][0], outs[name][0]) and torch.equal(outs["two"][1], outs[name][1]), name
@@ -383,9 +385,9 @@ def test_fold_of_all_layers_in_one_launch_is_bitwise_the_per_layer_launches(gpu)
     lat = {}
     try:
         for flag in (0, 1):
-            hip.lib().samaudio_debug_set_flag(31, flag)
+            hip.lib().samaudio_debug_set_flag(hip.DBG_FOLD_PER_LAYER, flag)
             model._prepare(feats, text, tmask, None, None, None, None)
             lat[flag] = model.solve(noise, opt).clone()
     finally:
-        hip.lib().samaudio_debug_set_flag(31, 0)
+        hip.lib().samaudio_debug_set_flag(hip.DBG_FOLD_PER_LAYER, 0)
     assert torch.isfinite(lat[0]).all() and torch.equal(lat[0], lat[1])

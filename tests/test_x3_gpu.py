@@ -75,7 +75,7 @@ def test_x3_gemm_is_the_fp32_product(gpu, prec, shape):
         if ktm:
             assert torch.equal(ktm_to_rows(w3.cpu()), x3_weight(w, half, ktm=False))
         out = torch.full((M, N), float("nan"), device=gpu)
-        util.gemm(PLAIN[prec], a3, w3, M, N, 3 * K, out_f32=out, f32_geom=(0, N, 0), flags=2048 if ktm else 0)
+        util.gemm(PLAIN[prec], a3, w3, M, N, 3 * K, out_f32=out, f32_geom=(0, N, 0), flags=hip.GEMM_FLAG_W_KTM if ktm else 0)
         errs[ktm] = (out.cpu() - ref).abs().max().item()
     e_plain = (plain - ref).abs().max().item()
     print(f"x3 GEMM {prec} {shape}: max-abs err rows {errs[False]:.3e} / ktm {errs[True]:.3e}; plain 16-bit operands {e_plain:.3e}; "
@@ -107,18 +107,19 @@ def test_fp32_gemm_with_operands_split_on_the_fly(gpu, prec, shape):
     assert torch.equal(fly16_to_f32(wfly.cpu()), w.to(HALF[prec]).float() + (w - w.to(HALF[prec]).float()).to(HALF[prec]).float())
     # (flags, debug flag 36): exact fp32 | both operands split in registers | the split weight on the 4 x 1-wave tiles (shipped) | on the
     # tiles of the plain policy
-    cases = {"exact": (0, 0), "fly": (8192, 0), "twin": (8192 | 16384, 0), "twin_old_tiles": (8192 | 16384, 1)}
+    cases = {"exact": (0, 0), "fly": (hip.GEMM_FLAG_X3_FLY, 0), "twin": (hip.GEMM_FLAG_X3_FLY | hip.GEMM_FLAG_W_FLY16, 0),
+             "twin_old_tiles": (hip.GEMM_FLAG_X3_FLY | hip.GEMM_FLAG_W_FLY16, 1)}
     for name, (flags, dbg) in cases.items():
         o32, oact = torch.full((M, N), float("nan"), device=gpu), torch.full((M, N), float("nan"), device=gpu)
-        xd, wd, bd, ad = x.to(gpu).contiguous(), (wfly if flags & 16384 else w.to(gpu).contiguous()), bias.to(gpu), alpha.to(gpu)
+        xd, wd, bd, ad = x.to(gpu).contiguous(), (wfly if flags & hip.GEMM_FLAG_W_FLY16 else w.to(gpu).contiguous()), bias.to(gpu), alpha.to(gpu)
         prm = util.gemm_params(xd, wd, M, N, K, a_off=a_off, lda=kc, kc=kc, tap_stride=dil * kc, bias=bd, out_f32=o32, f32_geom=(0, N, 0),
                                out_act=oact, act_geom=(0, N, 0), act=hip.ACT_SNAKE, act_alpha=ad, flags=flags)
-        lib.samaudio_debug_set_flag(36, dbg)
+        lib.samaudio_debug_set_flag(hip.DBG_FLY_OLD_TILES, dbg)
         try:
             hip.check(lib.samaudio_op_gemm(C.byref(prm), C.sizeof(prm), hip.F32, util.stream()))
             outs[name] = (o32.cpu(), oact.cpu())
         finally:
-            lib.samaudio_debug_set_flag(36, 0)
+            lib.samaudio_debug_set_flag(hip.DBG_FLY_OLD_TILES, 0)
     for name in cases:
         if name.startswith("twin"):
             assert torch.equal(outs[name][0], outs["fly"][0]) and torch.equal(outs[name][1], outs["fly"][1]), f"{name}: same bits as the register split"
@@ -328,16 +329,16 @@ def test_x3_gemm_sharing_the_operand_tiles(gpu, prec, shape):
     try:
         for ktm in (False, True):
             w3 = x3_weight(w, half, ktm=ktm).to(gpu)
-            for variant in (22, 27):
-                for share in (0, 32768):
+            for variant in (hip.GV_GEMM8_256x256, hip.GV_GEMM8S_128x128):
+                for share in (0, hip.GEMM_FLAG_X3_SHARE):
                     lib.samaudio_debug_force_gemm_variant(variant)
                     out = torch.full((M, N), float("nan"), device=gpu)
-                    util.gemm(PLAIN[prec], a3, w3, M, N, 3 * K, out_f32=out, f32_geom=(0, N, 0), flags=(2048 if ktm else 0) | share)
+                    util.gemm(PLAIN[prec], a3, w3, M, N, 3 * K, out_f32=out, f32_geom=(0, N, 0), flags=(hip.GEMM_FLAG_W_KTM if ktm else 0) | share)
                     outs[(ktm, variant, share)] = out.cpu()
     finally:
         lib.samaudio_debug_force_gemm_variant(-1)
-    plain = outs[(False, 22, 0)]
-    shared = outs[(False, 22, 32768)]
+    plain = outs[(False, hip.GV_GEMM8_256x256, 0)]
+    shared = outs[(False, hip.GV_GEMM8_256x256, hip.GEMM_FLAG_X3_SHARE)]
     e_plain, e_shared = (plain - ref).abs().max().item(), (shared - ref).abs().max().item()
     print(f"x3 GEMM {prec} {shape}: max-abs err plain walk {e_plain:.3e}, shared operand tiles {e_shared:.3e}; |ref| <= {ref.abs().max():.2f}")
     for key, o in outs.items():

@@ -28,7 +28,7 @@ SIZE = os.environ.get("SAMAUDIO_SHAPES_SIZE", "small*")
 PREC = os.environ.get("SAMAUDIO_SHAPES_PRECISION", "fp16x3")
 SIM = os.environ.get("SAMAUDIO_EMU_DRYRUN", "") != ""
 # The 8-candidate test carries ~3 minutes of CPU oracle time (8 x 10 s rows + the Judge oracle on 16 waveforms): it runs when
-# SAMAUDIO_SLOW_TESTS=1 (tools/r6_final.sh sets it: profiles/r6_final2/gpu_tests.log, shapes_large.log), so that the default
+# SAMAUDIO_SLOW_TESTS=1 (profiles/r6_final4/run.sh sets it: profiles/r6_final2/gpu_tests.log, shapes_large.log), so that the default
 # `pytest -m gpu` stays near the duration of the earlier rounds' suites; the visual test (45 s) always runs.
 SLOW = os.environ.get("SAMAUDIO_SLOW_TESTS", "") not in ("", "0")
 

@@ -49,7 +49,7 @@ def gemm_params(A, W, M, N, K, *, nbatch=1, a_off=0, a_bstride=0, lda=None, kc=N
     p.act_alpha = 0 if act_alpha is None else act_alpha.data_ptr()
     p.c_lo, p.c_hi, p.c_ld_rel = c_lo, c_hi, c_ld_rel
     p.w_bstride, p.raster_gm = w_bstride, raster_gm
-    p.flags = flags   # e.g. 2048: W is K-tile-major (common.h GEMM_FLAG_W_KTM)
+    p.flags = flags   # hip.GEMM_FLAG_* (csrc/common.h), e.g. GEMM_FLAG_W_KTM: W is K-tile-major
     if prefetch is not None:   # bytes the launch's idle workgroups touch (the next launch's weights)
         p.pf_ptr, p.pf_bytes = prefetch.data_ptr(), prefetch.numel() * prefetch.element_size()
     return p

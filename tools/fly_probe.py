@@ -22,7 +22,8 @@ lib = hip.lib("fp16")
 SHAPES = [("k7 96ch d1", 96, 672, 96, 1), ("k7 96ch d9", 96, 672, 96, 9), ("k1 96ch", 96, 96, 96, 1), ("k7 192ch d3", 192, 1344, 192, 3),
           ("k1 192ch", 192, 192, 192, 1), ("up 192->2x96", 192, 384, 384, 1), ("k7 128ch d1", 128, 896, 128, 1), ("k7 64ch d1", 64, 448, 64, 1),
           ("k7 96->1", 1, 672, 96, 1)]
-FORMS = [("fly", 8192, 0), ("twin old tiles", 8192 | 16384, 1), ("twin 4x1", 8192 | 16384, 0)]
+FORMS = [("fly", hip.GEMM_FLAG_X3_FLY, 0), ("twin old tiles", hip.GEMM_FLAG_X3_FLY | hip.GEMM_FLAG_W_FLY16, 1),
+         ("twin 4x1", hip.GEMM_FLAG_X3_FLY | hip.GEMM_FLAG_W_FLY16, 0)]
 for name, N, K, kc, dil in SHAPES:
     rows = M // 2 if N == 192 and kc == 192 else M    # the 192-channel stage runs at half the sample rate
     taps, halo = K // kc, 32
@@ -34,9 +35,9 @@ for name, N, K, kc, dil in SHAPES:
     a_off = (halo - (taps // 2) * dil) * kc
     line = []
     for form, flags, dbg in FORMS:
-        prm = util.gemm_params(x, wf if flags & 16384 else wd, rows, N, K, a_off=a_off, lda=kc, kc=kc, tap_stride=dil * kc if taps > 1 else 0,
+        prm = util.gemm_params(x, wf if flags & hip.GEMM_FLAG_W_FLY16 else wd, rows, N, K, a_off=a_off, lda=kc, kc=kc, tap_stride=dil * kc if taps > 1 else 0,
                                bias=bias, out_f32=out, f32_geom=(0, out.shape[1], 0), flags=flags)
-        lib.samaudio_debug_set_flag(36, dbg)
+        lib.samaudio_debug_set_flag(hip.DBG_FLY_OLD_TILES, dbg)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         for it in range(3):
             if it == 1:
@@ -44,7 +45,7 @@ for name, N, K, kc, dil in SHAPES:
             hip.check(lib.samaudio_op_gemm(C.byref(prm), C.sizeof(prm), hip.F32, util.stream()))
         ev[1].record()
         torch.cuda.synchronize()
-        lib.samaudio_debug_set_flag(36, 0)
+        lib.samaudio_debug_set_flag(hip.DBG_FLY_OLD_TILES, 0)
         ms = ev[0].elapsed_time(ev[1]) / 2
         line.append(f"{form} {ms:7.3f} ms {2.0 * rows * N * K / ms / 1e9:6.1f} TF/s")
     print(f"{name:14s} rows {rows}: " + " | ".join(line) + f" | fp32 in+out {rows * (kc + N) * 4 / 1e9:.2f} GB", flush=True)

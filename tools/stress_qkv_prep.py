@@ -64,7 +64,7 @@ def main():
         return torch.stack([a * c - b_ * s_, a * s_ + b_ * c], -1).reshape(B, H, T, 128)
 
     for variant in args.variants:
-        lib.samaudio_debug_set_flag(29, variant)
+        lib.samaudio_debug_set_flag(hip.DBG_QKV_PREP_SWROUND, variant)
         print(f"--- variant {variant} (debug flag 29), {args.operands} library")
         refs = []
         for x in inputs:
@@ -131,7 +131,7 @@ def main():
         err = max(float((refs[w_][0][:, :, :T].float() - want_q(inputs[w_])).abs().max()) for w_ in range(2))
         print(f"first launches against torch fp32 on the device: max |Q - want| {err:.3g} (half a 16-bit ulp of values up to ~4 is "
               f"{'0.016' if args.operands == 'bf16' else '0.002'})")
-    lib.samaudio_debug_set_flag(29, 0)
+    lib.samaudio_debug_set_flag(hip.DBG_QKV_PREP_SWROUND, 0)
     return 0
 
 

@@ -28,7 +28,7 @@ for M in [int(r) for r in os.environ.get("PROBE_ROWS", "4000,500").split(",")]:
         out = torch.empty(m, n, device=dev, dtype=torch.float32)
         line = f"M={m} {name} N={n} K'={k3}:"
         keep = {}
-        for flags in (0, 32768):
+        for flags in (0, hip.GEMM_FLAG_X3_SHARE):
             if k % 64:
                 continue
             for _ in range(2):
@@ -44,20 +44,20 @@ for M in [int(r) for r in os.environ.get("PROBE_ROWS", "4000,500").split(",")]:
             keep[flags] = out.clone()
             line += f"  {'shared' if flags else 'plain'} {us:8.1f} us {2.0 * m * n * k3 / us / 1e6:7.1f} TF/s(mfma)"
         if len(keep) == 2:   # another order of the same sum: fp32 rounding apart (a race or a missed wait shows as O(1))
-            line += f"  |shared - plain| <= {(keep[0] - keep[32768]).abs().max().item():.2e} (|out| <= {keep[0].abs().max().item():.1f})"
-        if 32768 in keep:   # the full-size race check: ten more launches and the 128 x 128 kernel's walk of the same order, bit for bit
+            line += f"  |shared - plain| <= {(keep[0] - keep[hip.GEMM_FLAG_X3_SHARE]).abs().max().item():.2e} (|out| <= {keep[0].abs().max().item():.1f})"
+        if hip.GEMM_FLAG_X3_SHARE in keep:   # the full-size race check: ten more launches and the 128 x 128 kernel's walk of the same order, bit for bit
             lib = hip.lib(hip.operands_for("fp16"))
             same = True
             for _ in range(10):
-                util.gemm("fp16", A, W, m, n, k3, out_f32=out, f32_geom=(0, n, 0), flags=32768)
-                same &= torch.equal(out, keep[32768])
-            lib.samaudio_debug_force_gemm_variant(27)
+                util.gemm("fp16", A, W, m, n, k3, out_f32=out, f32_geom=(0, n, 0), flags=hip.GEMM_FLAG_X3_SHARE)
+                same &= torch.equal(out, keep[hip.GEMM_FLAG_X3_SHARE])
+            lib.samaudio_debug_force_gemm_variant(hip.GV_GEMM8S_128x128)
             try:
                 out.fill_(float("nan"))
-                util.gemm("fp16", A, W, m, n, k3, out_f32=out, f32_geom=(0, n, 0), flags=32768)
+                util.gemm("fp16", A, W, m, n, k3, out_f32=out, f32_geom=(0, n, 0), flags=hip.GEMM_FLAG_X3_SHARE)
             finally:
                 lib.samaudio_debug_force_gemm_variant(-1)
-            line += f"  repeatable {same}, gemm8s bitwise {torch.equal(out, keep[32768])}"
+            line += f"  repeatable {same}, gemm8s bitwise {torch.equal(out, keep[hip.GEMM_FLAG_X3_SHARE])}"
         print(line, flush=True)
         if SUSTAIN > 0 and name in os.environ.get("PROBE_SUSTAIN_SHAPES", "w13").split(","):
             import time
@@ -65,7 +65,7 @@ for M in [int(r) for r in os.environ.get("PROBE_ROWS", "4000,500").split(",")]:
             n_l = 0
             while time.time() - t0 < SUSTAIN:
                 for _ in range(200):
-                    util.gemm("fp16", A, W, m, n, k3, out_f32=out, f32_geom=(0, n, 0), flags=32768)
+                    util.gemm("fp16", A, W, m, n, k3, out_f32=out, f32_geom=(0, n, 0), flags=hip.GEMM_FLAG_X3_SHARE)
                 torch.cuda.synchronize()
                 n_l += 200
             dt = time.time() - t0
