@@ -86,56 +86,76 @@ class Engine {
   ~Engine();
 
  private:
-  struct DitBuffers;
-  struct DitW;
-  struct CodecW;
   // one field evaluation; out = res + alpha * v(noisy, t) (res may be null)
   Status eval_field(const float* noisy, const float* time, int n_time, float* out, const float* res, float alpha,
                     hipStream_t st);
   Status plan_dit(Bump& b, int rows, int frames, int text_len, bool assign);
+  // the folded cross-attention for a text memory of Lt tokens, decided once (plan_dit sizes by it, prepare sets it up): tokens per head
+  // slot, padded K, the 16-bit fold, the fold on compensated operands, one operand slice per layer
+  struct FoldPlan { int ltp, kp; bool fold16, fold3, all_layers; };
+  FoldPlan fold_plan(int Lt) const;
+  // The DAC-VAE workspace, described once: carves every buffer a pass over `n` waveforms uses into `out` (null: sizing only) and returns
+  // the bytes the linear model allots to n items (engine.hip kCodecFixed); codec_bytes and codec_chunk size by it, a pass checks b.fits()
+  struct CodecBufs;
+  size_t plan_codec(Bump& b, bool decode, int n, int64_t samples, CodecBufs* out) const;
+  size_t codec_per_item(int64_t samples) const;   // the larger direction's plan_codec of one item
   size_t codec_bytes(int items, int64_t samples) const;
-  // alg_flops < 0: 2*M*N*K*nbatch (exact unless K carries zero padding, then the caller passes the true count).
-  // cls: SAMAUDIO_CLS_* bit of the launch (0: codec launches are classed by prof_cls_); f32: exact-fp32 operands inside a
-  // 16-bit context (SAMAUDIO_OPT_F32_CLASSES - the caller hands fp32 A / W / out_act pointers)
-  // mode 2: a SAMAUDIO_OPT_X3_CLASSES launch inside an fp32 context (16-bit A / W over K' = 3K, fp32 outputs; gemm_x3 builds it), both operands split over the
-  // whole K (A rows [lo | hi | hi], W rows [W_hi | W_lo | W_hi]: the launch may share operand tiles, common.h GEMM_FLAG_X3_SHARE); mode 3: the same
-  // with K' split per input block (the convolutions of gemm_codec_x3 / the patcher: [block][3 Cin]) - a plain walk over K' only
-  Status gemm(const GemmParams& p, hipStream_t st, double alg_flops = -1.0, int cls = 0, int mode = 0);
-  GemmParams launch_params(const GemmParams& p_in, int cls, int mode) const;   // the tag / flags gemm() launches p_in with
+  int codec_chunk(int items, int64_t samples, bool pairs) const;   // items per pass in this workspace (whole pairs); 0: not even one
+  Status codec_carve(bool decode, int n, int64_t samples, CodecBufs& cb);   // one pass's buffers out of the workspace
+  // The kind of a GEMM launch.  F32: exact fp32 inside a 16-bit context (SAMAUDIO_OPT_F32_CLASSES - the caller hands fp32 A / W / out_act
+  // pointers).  X3: a SAMAUDIO_OPT_X3_CLASSES launch inside an fp32 context (16-bit A / W over K' = 3K, fp32 outputs; gemm_x3 builds it),
+  // both operands split over the whole K (A rows [lo | hi | hi], W rows [W_hi | W_lo | W_hi]: the launch may share operand tiles,
+  // common.h GEMM_FLAG_X3_SHARE).  X3Block: the same with K' split per input block (the convolutions of gemm_codec_x3 / the patcher:
+  // [block][3 Cin]) - a plain walk over K' only
+  enum class GemmKind { Native, F32, X3, X3Block };
+  static GemmKind f32_if(bool f) { return f ? GemmKind::F32 : GemmKind::Native; }
+  enum class Phase { Prep, Dit, Codec } phase_ = Phase::Dit;   // the profile label; Codec: launches run under the codec's kernel symbols
+  const char* phase_name() const { return phase_ == Phase::Prep ? "prep" : phase_ == Phase::Dit ? "dit" : "codec"; }
+  // gemm = launch_params + launch + the sentinel scan of the 16-bit output.  cls: SAMAUDIO_CLS_* bit; alg_flops < 0: 2*M*N*K*nbatch
+  // (exact unless K carries zero padding, then the caller passes the true count).  The codec's convolutions go through codec_gemm.
+  Status gemm(const GemmParams& p, hipStream_t st, double alg_flops, int cls, GemmKind kind = GemmKind::Native);
+  GemmParams launch_params(const GemmParams& p_in, int cls, GemmKind kind) const;   // the tag / flags p_in launches with
+  Status launch(GemmParams p, hipStream_t st, double alg_flops, int cls, GemmKind kind);   // one launch, profiled
+  Status scan_out(const GemmParams& p, int cls, GemmKind kind, hipStream_t st);
   // SAMAUDIO_OPT_X3_CLASSES: `p` = the fp32 context's plain launch (fp32 A rows, fp32-typed outputs) of a class that is switched
   // on; `w3` = its "<name>.x3" weight.  Splits A into the scratch operand [lo | hi | hi] and runs ONE 16-bit GEMM over K' = 3K.
-  // `presplit`: the activation operand is already in its split form at that address (written by the kernel that produced it)
   // `presplit`: A already split; otherwise gemm_x3 splits it into x3a, or into x3u when `ffn_wide` (w2's F-wide operand)
   Status gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, int cls, const void* presplit = nullptr, bool ffn_wide = false);
   static void x3_operands(GemmParams& p, const void* a3, const void* w3, bool ktm);
   // the launch gemm_x3 would make of `p` with GEMM_FLAG_OUT_SPLIT3 passes gemm_check (the 8-phase family takes it)
   bool x3_split3_out_ok(GemmParams p, const void* w3, bool ktm, void* out3) const;
   bool x3(int cls) const { return !bf16_ && (x3_classes_ & cls) != 0; }
-  // SAMAUDIO_OPT_X3_CLASSES bit CODEC, convolutions with >= 256 output channels whose weight has a registered "<name>.x3" twin
-  // ([N, K / Cin, 3 Cin]: every Cin-block of a weight row as [W_hi | W_lo | W_hi]): the fp32 activation buffer is split row by row
-  // into a scratch operand and the launch runs on the 8-phase 16-bit kernels over K' = 3K; the activation is applied to the raw fp32
-  // result by an elementwise kernel.  Everything else of the codec multiplies on operands split in registers (GEMM_FLAG_X3_FLY).
+  // A convolution of the DAC-VAE.  SAMAUDIO_OPT_X3_CLASSES bit CODEC: one with >= 256 output channels whose weight has a registered
+  // "<name>.x3" twin ([N, K / Cin, 3 Cin]: every Cin-block of a weight row as [W_hi | W_lo | W_hi]) runs through gemm_codec_x3 - the fp32
+  // activation buffer is split row by row into a scratch operand, the launch runs on the 8-phase 16-bit kernels over K' = 3K and an
+  // elementwise kernel applies the activation to the raw fp32 result.  Everything else of the codec multiplies on operands split in
+  // registers (GEMM_FLAG_X3_FLY), on the weight's "<name>.fly" twin where there is one (GEMM_FLAG_W_FLY16).
+  Status codec_gemm(const GemmParams& p, hipStream_t st, double alg_flops = -1.0);
   struct X3CodecW { const void* w; int cin; };
   std::map<const void*, X3CodecW> x3_codec_;
-  std::map<const void*, const void*> fly_codec_;   // fp32 codec weight -> its "<name>.fly" twin (GEMM_FLAG_W_FLY16)
-  void* x3_codec_scratch_ = nullptr;
+  std::map<const void*, const void*> fly_codec_;   // fp32 codec weight -> its "<name>.fly" twin
+  void* x3_codec_scratch_ = nullptr;               // the running pass's split scratch (plan_codec)
   size_t x3_codec_scratch_bytes_ = 0;
-  size_t codec_x3_per_item(int64_t samples) const;
+  const X3CodecW* codec_x3_twin(const GemmParams& p) const;   // the twin `p` can run on, or null
   Status gemm_codec_x3(const GemmParams& p, const X3CodecW& w, hipStream_t st, double alg_flops);
   Status check_x3_weights(int classes) const;
   bool f32c(int cls) const { return bf16_ && (f32_classes_ & cls) != 0; }
   bool alt16(int cls) const { return bf16_ && (alt_classes_ & cls) != 0; }   // SAMAUDIO_OPT_ALT16_CLASSES (mixed mode)
   const void* opt(const std::string& name, std::vector<int64_t> shape) const;  // optional fp32 tensor, null if absent / mis-shaped
+  // optional 16-bit twin: [N, K] row-major, or [K/64, N, 64] K-tile-major (then sets `bit` of *ktm); null if absent / mis-shaped
+  const void* twin16(const std::string& name, int64_t N, int64_t K, int* ktm, int bit) const;
   struct ProfRec {
     std::string key;
     double flops, bytes;
     hipEvent_t e0, e1;
   };
-  const char* prof_cls_ = "dit";
   // non-GEMM launch, event-bracketed while profiling
   template <class F>
   Status op(const char* name, double alg_bytes, double alg_flops, hipStream_t st, F&& launch);
   Status res_unit(GemmParams p, GemmParams q, void*& cur, void*& alt, double flops7, double flops1, hipStream_t st);
+  struct SBuf;
+  struct StageW;   // the three residual units of one codec stage on `sb`; `next_alpha`: the Snake after the last unit
+  Status res_units(const StageW& sw, SBuf& sb, int n, const float* next_alpha, hipStream_t st);
   void* hash_ = nullptr;   // SAMAUDIO_TRACE_HASH recorder (engine.hip HashTrace; debugging aid)
   bool prof_on_ = false;
   std::vector<ProfRec> prof_;

@@ -2,11 +2,11 @@
 // Host code only - every arithmetic step is a kernel from gemm.hip / kernels.hip / attention.hip.
 #include "engine.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <tuple>
 
 namespace sa {
 
@@ -179,6 +179,13 @@ Status Engine::need_w5(const std::string& name, int N, int K, const void** out, 
   return need(name, at_dtype_, {N, K}, out);
 }
 
+const void* Engine::twin16(const std::string& name, int64_t N, int64_t K, int* ktm, int bit) const {
+  const TensorRef* t = find(name);
+  if (!t || t->dtype != SAMAUDIO_DT_BF16) return nullptr;
+  if (t->shape == std::vector<int64_t>{K / 64, N, 64}) { *ktm |= 1 << bit; return t->p; }
+  return t->shape == std::vector<int64_t>{N, K} ? t->p : nullptr;
+}
+
 static int kpad(int k, bool bf16) { return (int)round_up(k, bf16 ? 64 : 32); }
 
 Status Engine::finalize(int what) {
@@ -214,14 +221,7 @@ Status Engine::finalize(int what) {
         const struct { const char* leaf; int N, K; const void** out; } x3w[6] = {
             {"wqkv", 3 * D, D, &w.wqkv3}, {"wo", D, D, &w.wo3}, {"c_wq", D, D, &w.c_wq3},
             {"c_wo", D, D, &w.c_wo3},     {"w13", 2 * F, D, &w.w13_3}, {"w2", D, F, &w.w2_3}};
-        for (int j = 0; j < 6; ++j) {
-          const TensorRef* t = find(P + x3w[j].leaf + ".x3");
-          *x3w[j].out = nullptr;
-          if (!t || t->dtype != SAMAUDIO_DT_BF16) continue;
-          const int64_t N = x3w[j].N, K3 = 3L * x3w[j].K;
-          if (t->shape == std::vector<int64_t>{K3 / 64, N, 64}) { *x3w[j].out = t->p; w.ktm3 |= 1 << j; }
-          else if (t->shape == std::vector<int64_t>{N, K3}) *x3w[j].out = t->p;
-        }
+        for (int j = 0; j < 6; ++j) *x3w[j].out = twin16(P + x3w[j].leaf + ".x3", x3w[j].N, 3L * x3w[j].K, &w.ktm3, j);
       }
     }
     NEEDF(g_.final_table, "final_table", 2, D);
@@ -281,12 +281,7 @@ Status Engine::finalize(int what) {
       std::memset(&g3_, 0, sizeof(g3_));
       const struct { const char* name; int64_t N, K3; const void** out; } x3g[3] = {
           {"patch1.w.x3", D, 9L * D, &g3_.pw1}, {"patch2.w.x3", D, 9L * D, &g3_.pw2}, {"c_wkv_all.x3", (int64_t)L * 2 * D, 3L * D, &g3_.c_wkv_all}};
-      for (int j = 0; j < 3; ++j) {
-        const TensorRef* t = find(x3g[j].name);
-        if (!t || t->dtype != SAMAUDIO_DT_BF16) continue;
-        if (t->shape == std::vector<int64_t>{x3g[j].K3 / 64, x3g[j].N, 64}) { *x3g[j].out = t->p; g3_.ktm |= 1 << j; }
-        else if (t->shape == std::vector<int64_t>{x3g[j].N, x3g[j].K3}) *x3g[j].out = t->p;
-      }
+      for (int j = 0; j < 3; ++j) *x3g[j].out = twin16(x3g[j].name, x3g[j].N, x3g[j].K3, &g3_.ktm, j);
     }
     dit_ready_ = true;   // (check_x3_weights looks at the resolved layers)
     if (const Status s3 = check_x3_weights(x3_classes_); !s3.ok()) { dit_ready_ = false; return s3; }
@@ -327,32 +322,28 @@ Status Engine::finalize(int what) {
     NEEDW(enc_.proj_w, "enc.proj.w", CD, CL);
     NEEDF(enc_.proj_b, "enc.proj.b", CD);
     enc_ready_ = true;
-    // SAMAUDIO_OPT_X3_CLASSES bit CODEC: "<name>.x3" twins of registered codec weights, keyed by the weight's own pointer
+    // SAMAUDIO_OPT_X3_CLASSES bit CODEC: twins of registered codec weights, keyed by the weight's own pointer.  "<name>.x3": every
+    // Cin-block of a row as [W_hi | W_lo | W_hi] (the wide convolutions, gemm_codec_x3); "<name>.fly" (weights.py convert_codec_fly16): the
+    // narrow convolutions' weights already split, in the layout the fp32 kernel's on-the-fly multiply reads (common.h GEMM_FLAG_W_FLY16)
     x3_codec_.clear();
-    if (!bf16_)
-      for (const auto& kv : tensors_) {
-        const std::string& name = kv.first;
-        if (name.size() < 4 || name.compare(name.size() - 3, 3, ".x3") != 0 || (name.rfind("enc.", 0) != 0 && name.rfind("dec.", 0) != 0)) continue;
-        const TensorRef* base = find(name.substr(0, name.size() - 3));
-        const TensorRef& t = kv.second;
-        if (!base || base->shape.size() != 2 || t.dtype != SAMAUDIO_DT_BF16 || t.shape.size() != 3 || t.shape[2] % 3) continue;
-        const int64_t cin = t.shape[2] / 3;
-        if (t.shape[0] != base->shape[0] || t.shape[1] * cin != base->shape[1] || cin % 8) continue;
-        x3_codec_[base->p] = X3CodecW{t.p, (int)cin};
-      }
-    // ... and "<name>.fly" twins (weights.py convert_codec_fly16): the narrow convolutions' weights already split, in the layout the
-    // fp32 kernel's on-the-fly multiply reads (common.h GEMM_FLAG_W_FLY16)
     fly_codec_.clear();
-    if (!bf16_)
-      for (const auto& kv : tensors_) {
-        const std::string& name = kv.first;
-        if (name.size() < 5 || name.compare(name.size() - 4, 4, ".fly") != 0 || (name.rfind("enc.", 0) != 0 && name.rfind("dec.", 0) != 0)) continue;
-        const TensorRef* base = find(name.substr(0, name.size() - 4));
-        const TensorRef& t = kv.second;
-        if (!base || base->shape.size() != 2 || t.dtype != SAMAUDIO_DT_BF16 || t.shape.size() != 2) continue;
-        if (t.shape[0] != base->shape[0] || t.shape[1] != 2 * base->shape[1] || base->shape[1] % 32) continue;
-        fly_codec_[base->p] = t.p;
+    for (const auto& kv : tensors_) {
+      const std::string& name = kv.first;
+      const size_t dot = name.rfind('.');
+      const std::string ext = dot == std::string::npos ? "" : name.substr(dot);
+      const bool x3t = ext == ".x3";
+      if (bf16_ || (!x3t && ext != ".fly") || (name.rfind("enc.", 0) != 0 && name.rfind("dec.", 0) != 0)) continue;
+      const TensorRef* base = find(name.substr(0, dot));
+      const TensorRef& t = kv.second;
+      if (!base || base->shape.size() != 2 || t.dtype != SAMAUDIO_DT_BF16) continue;
+      const int64_t N = base->shape[0], K = base->shape[1];
+      if (!x3t) {
+        if (t.shape == std::vector<int64_t>{N, 2 * K} && K % 32 == 0) fly_codec_[base->p] = t.p;
+      } else if (t.shape.size() == 3 && t.shape[2] % 3 == 0) {
+        const int64_t cin = t.shape[2] / 3;
+        if (t.shape[0] == N && t.shape[1] * cin == K && cin % 8 == 0) x3_codec_[base->p] = X3CodecW{t.p, (int)cin};
       }
+    }
     if (what == 2) return Status{};  // encoder only: the Judge's DACVAEEncoder (reference codec.py:42-78)
     // decoder
     NEEDW(dec_.proj_w, "dec.proj.w", CL, CD);
@@ -384,71 +375,68 @@ Status Engine::finalize(int what) {
 // ---------------------------------------------------------------------------------------------------
 // workspace
 // ---------------------------------------------------------------------------------------------------
+// The folds run for a short text memory on 128-wide heads unless switched off (SAMAUDIO_NO_FOLD): in a 16-bit context the 16-bit fold; in
+// an fp32 context whose class CWO (beside any other DiT class) runs on compensated operands, and few enough layers, the fold on those.
+Engine::FoldPlan Engine::fold_plan(int Lt) const {
+  const int ltp = Lt <= 8 ? 8 : 16;
+  const bool all_layers = cfg_.n_layers <= kMaxFoldLayers;
+  const bool can = Lt <= 16 && cfg_.dim / cfg_.n_heads == 128 && !std::getenv("SAMAUDIO_NO_FOLD");
+  return FoldPlan{ltp, (int)round_up((long)cfg_.n_heads * ltp, 64), can && bf16_, can && x3(SAMAUDIO_CLS_CWO) && all_layers, all_layers};
+}
+
 Status Engine::plan_dit(Bump& b, int rows, int T, int Lt, bool assign) {
-  const long D = cfg_.dim, F = cfg_.ffn_hidden, C2 = cfg_.latent_channels, H = cfg_.n_heads;
+  const long D = cfg_.dim, F = cfg_.ffn_hidden, C2 = cfg_.latent_channels;
   const long M = (long)rows * T, Mt = (long)rows * Lt, Tp = round_up(T, 64);
   const long nt = rows;  // worst case: one time value per row
   auto f32 = [&](long n) { return (float*)b.take((size_t)n * 4); };
   auto act = [&](long n) { return b.take((size_t)n * esz_); };
-  auto& d = d_;
-  float* ymid = f32(M * C2); float* aligned = f32(M * D); float* cond = f32(M * D); float* h = f32(M * D);
+  decltype(d_) d{};   // every buffer, in the order the plan carves them
+  d.ymid = f32(M * C2); d.aligned = f32(M * D); d.cond = f32(M * D); d.h = f32(M * D);
   // (hp1 also stages the per-clip text projection of a prepare with candidates: B * Lt <= rows * Lt rows of it)
-  float* hp1 = f32((M > Mt ? M : Mt) * D); float* text_proj = f32(Mt * D); float* t_emb = f32(nt * D); float* t0 = f32(nt * 6 * D);
-  float* tsin = f32(nt * D); float* vtmp = f32(M * D); float* times = f32(4096);
-  float* modgs = f32(2L * cfg_.n_layers * nt * 2 * D);   // pre-combined RMSNorm + modulate operands of an evaluation
-  void* ybf = act(M * C2); void* xn = act(M * D); void* qkv = act(M * 3 * D);
-  void* Q = act((long)rows * Tp * D); void* K = act((long)rows * Tp * D);   // [rows, H, Tp, head_dim]
-  void* Vt = act((long)rows * D * Tp);
-  void* attn = act(M * D); void* hbf = act(M * D); void* qc = act(M * D); void* ca = act(M * D); void* u = act(M * F);
-  void* gnbuf = act((long)rows * (T + 2) * D); void* mem = act(Mt * D); void* yu = act(Mt * D); void* yemb = act(Mt * D);
-  void* kvc = act(Mt * 2 * D * cfg_.n_layers); void* temb = act(nt * cfg_.freq_dim); void* tu = act(nt * D); void* tsilu = act(nt * D);
-  void* feats = act(M * C2); void* text = act(Mt * cfg_.text_dim); void* video = act(M * cfg_.video_dim);
-  void* anch = act(M * cfg_.anchor_dim);
+  d.hp1 = f32((M > Mt ? M : Mt) * D); d.text_proj = f32(Mt * D); d.t_emb = f32(nt * D); d.t0 = f32(nt * 6 * D);
+  d.tsin = f32(nt * D); d.vtmp = f32(M * D); d.times = f32(4096);
+  d.modgs = f32(2L * cfg_.n_layers * nt * 2 * D);   // pre-combined RMSNorm + modulate operands of an evaluation
+  d.ybf = act(M * C2); d.xn = act(M * D); d.qkv = act(M * 3 * D);
+  d.Q = act((long)rows * Tp * D); d.K = act((long)rows * Tp * D);   // [rows, H, Tp, head_dim]
+  d.Vt = act((long)rows * D * Tp);
+  d.attn = act(M * D); d.hbf = act(M * D); d.qc = act(M * D); d.ca = act(M * D); d.u = act(M * F);
+  d.gnbuf = act((long)rows * (T + 2) * D); d.mem = act(Mt * D); d.yu = act(Mt * D); d.yemb = act(Mt * D);
+  d.kvc = act(Mt * 2 * D * cfg_.n_layers); d.temb = act(nt * cfg_.freq_dim); d.tu = act(nt * D); d.tsilu = act(nt * D);
+  d.feats = act(M * C2); d.text = act(Mt * cfg_.text_dim); d.video = act(M * cfg_.video_dim);
+  d.anch = act(M * cfg_.anchor_dim);
   // fp32 operands of the classes SAMAUDIO_OPT_F32_CLASSES may switch to exact fp32 (16-bit contexts only)
-  float *temb32 = nullptr, *tu32 = nullptr, *tsilu32 = nullptr, *xn32 = nullptr, *prep32 = nullptr, *mem32 = nullptr,
-        *yu32 = nullptr, *yemb32 = nullptr;
   if (bf16_) {
-    temb32 = f32(nt * cfg_.freq_dim); tu32 = f32(nt * D); tsilu32 = f32(nt * D); xn32 = f32(M * D);
-    prep32 = f32(M * (cfg_.video_dim > cfg_.anchor_dim ? cfg_.video_dim : cfg_.anchor_dim));
-    mem32 = f32(Mt * D); yu32 = f32(Mt * D); yemb32 = f32(Mt * D);
+    d.temb32 = f32(nt * cfg_.freq_dim); d.tu32 = f32(nt * D); d.tsilu32 = f32(nt * D); d.xn32 = f32(M * D);
+    d.prep32 = f32(M * (cfg_.video_dim > cfg_.anchor_dim ? cfg_.video_dim : cfg_.anchor_dim));
+    d.mem32 = f32(Mt * D); d.yu32 = f32(Mt * D); d.yemb32 = f32(Mt * D);
   }
-  // folded cross-attention (bf16, Lt <= 16): probabilities [M, KP] and the per-batch operand U^T [rows][D][KP]
-  // (the condition prepare() folds under: 16-bit context, short memory, 128-wide heads, not switched off)
-  const long ltp = Lt <= 8 ? 8 : 16, kp = round_up(H * ltp, 64);
-  const bool fold = bf16_ && Lt <= 16 && D / cfg_.n_heads == 128 && !std::getenv("SAMAUDIO_NO_FOLD");
-  void* probs = fold ? act(M * kp) : nullptr;
+  // folded cross-attention (fold_plan): probabilities [M, KP] and the per-batch operand U^T [rows][D][KP]
+  const FoldPlan fp = fold_plan(Lt);
+  const long kp = fp.kp;
+  d.probs = fp.fold16 ? act(M * kp) : nullptr;
   // (one slice per layer: the folds of an evaluation run as one launch in front of the layer loop; DBG_FOLD_PER_LAYER - one launch per
   // layer - only ever uses the first slice)
-  const bool fold_all = cfg_.n_layers <= kMaxFoldLayers;
-  void* ut = fold ? act((long)rows * D * kp * (fold_all ? cfg_.n_layers : 1)) : nullptr;
+  d.ut = fp.fold16 ? act((long)rows * D * kp * (fp.all_layers ? cfg_.n_layers : 1)) : nullptr;
   // SAMAUDIO_OPT_X3_CLASSES: the split activation operand [lo | hi | hi] of the widest GEMM input (16-bit, 3 K elements per row)
   // (x3a: D-wide operands - the M frame rows, the Mt text rows of class CKV - and the patcher's halo-padded rows; x3u: the SwiGLU
   // hidden, written by the w13 launch while it reads x3a)
   const bool x3g = !bf16_ && (x3_classes_ & ~(SAMAUDIO_X3_ATTENTION | SAMAUDIO_CLS_CODEC));
   const long x3a_rows = (long)rows * (T + 2) > Mt ? (long)rows * (T + 2) : Mt;
-  const size_t x3a_bytes = x3g ? (size_t)x3a_rows * 3 * (size_t)D * 2 : 0;
-  void* x3a = x3g ? b.take(x3a_bytes) : nullptr;
-  const size_t x3u_bytes = x3g ? (size_t)M * 3 * (size_t)F * 2 : 0;
-  void* x3u = x3g ? b.take(x3u_bytes) : nullptr;
-  // folded cross-attention on compensated operands (class CWO of an x3 context, short memory, 128-wide heads): probabilities
-  // [M][3 kp] and the per-batch operands of all layers [L][rows][D][3 kp]
-  const bool fold3 = x3g && (x3_classes_ & SAMAUDIO_CLS_CWO) && Lt <= 16 && D / cfg_.n_heads == 128 && cfg_.n_layers <= kMaxFoldLayers &&
-                     !std::getenv("SAMAUDIO_NO_FOLD");
-  void* x3p = fold3 ? b.take((size_t)M * 3 * kp * 2) : nullptr;
-  void* ut3 = fold3 ? b.take((size_t)rows * D * 3 * kp * 2 * cfg_.n_layers) : nullptr;
-  unsigned char* pad_mask = (unsigned char*)b.take((size_t)M);
-  unsigned char* text_mask = (unsigned char*)b.take((size_t)Mt);
-  double* gn_part = (double*)b.take((size_t)rows * 64 * 2 * 8);
-  if (assign) {
-    d.ymid = ymid; d.aligned = aligned; d.cond = cond; d.h = h; d.hp1 = hp1; d.text_proj = text_proj; d.t_emb = t_emb;
-    d.t0 = t0; d.modgs = modgs; d.tsin = tsin; d.vtmp = vtmp; d.times = times; d.ybf = ybf; d.xn = xn; d.qkv = qkv; d.Q = Q; d.K = K;
-    d.Vt = Vt; d.attn = attn; d.hbf = hbf; d.qc = qc; d.ca = ca; d.u = u; d.gnbuf = gnbuf; d.mem = mem; d.yu = yu;
-    d.yemb = yemb; d.kvc = kvc; d.temb = temb; d.tu = tu; d.tsilu = tsilu; d.feats = feats; d.text = text;
-    d.video = video; d.anch = anch; d.temb32 = temb32; d.tu32 = tu32; d.tsilu32 = tsilu32; d.xn32 = xn32; d.prep32 = prep32;
-    d.mem32 = mem32; d.yu32 = yu32; d.yemb32 = yemb32; d.probs = probs; d.ut = ut; d.x3a = x3a; d.x3a_bytes = x3a_bytes; d.x3u = x3u; d.x3u_bytes = x3u_bytes; d.x3p = x3p; d.ut3 = ut3; d.pad_mask = pad_mask; d.text_mask = text_mask; d.gn_part = gn_part;
-  }
+  d.x3a_bytes = x3g ? (size_t)x3a_rows * 3 * (size_t)D * 2 : 0;
+  d.x3a = x3g ? b.take(d.x3a_bytes) : nullptr;
+  d.x3u_bytes = x3g ? (size_t)M * 3 * (size_t)F * 2 : 0;
+  d.x3u = x3g ? b.take(d.x3u_bytes) : nullptr;
+  // folded cross-attention on compensated operands: probabilities [M][3 kp] and the per-batch operands of all layers [L][rows][D][3 kp]
+  d.x3p = fp.fold3 ? b.take((size_t)M * 3 * kp * 2) : nullptr;
+  d.ut3 = fp.fold3 ? b.take((size_t)rows * D * 3 * kp * 2 * cfg_.n_layers) : nullptr;
+  d.pad_mask = (unsigned char*)b.take((size_t)M);
+  d.text_mask = (unsigned char*)b.take((size_t)Mt);
+  d.gn_part = (double*)b.take((size_t)rows * 64 * 2 * 8);
+  if (assign) d_ = d;
   return Status{};
 }
+
+static long codec_hop(const samaudio_config& c) { return (long)c.enc_rates[0] * c.enc_rates[1] * c.enc_rates[2] * c.enc_rates[3]; }
 
 // per-item element counts of the codec stage buffers (see codec_encode / codec_decode)
 static void codec_stage_dims(const samaudio_config& c, int64_t samples, long encT[5], int encC[5], long decT[5],
@@ -459,9 +447,7 @@ static void codec_stage_dims(const samaudio_config& c, int64_t samples, long enc
     encT[i] = T; encC[i] = C;
     if (i < 4) { T /= c.enc_rates[i]; C *= 2; }
   }
-  long hop = 1;
-  for (int i = 0; i < 4; ++i) hop *= c.enc_rates[i];
-  T = samples / hop;
+  T = samples / codec_hop(c);
   C = c.dec_dim;
   for (int i = 0; i < 5; ++i) {
     decT[i] = T; decC[i] = C;
@@ -469,36 +455,72 @@ static void codec_stage_dims(const samaudio_config& c, int64_t samples, long enc
   }
 }
 
-size_t Engine::codec_bytes(int items, int64_t samples) const {
-  if (items <= 0) return 0;
+struct Engine::SBuf {   // one codec stage: raw fp32 stream, activated copy, a second halo-zeroed buffer of the same shape
+  float* raw; void* act; void* tmp;
+  long T; int C;
+};
+struct Engine::CodecBufs {
+  void *in8, *eout;   // encode: the waveform as [HALO + S + HALO][8], the latent in front of the projection
+  void *lat, *p0;     // decode: the latent, its projection
+  SBuf sb[5];
+  void* x3; size_t x3_bytes;   // split scratch of gemm_codec_x3 (null: no twin can run)
+};
+
+// The linear model the codec workspace is sized by: kCodecFixed + n * per_item, per_item = the bytes of one item's buffers plus, per
+// stage and for the split scratch, slack for Bump's 256-byte alignment of the takes (the fixed part covers the remaining ones).
+constexpr size_t kCodecFixed = 1 << 16, kCodecStageSlack = 1024, kCodecX3Slack = 256;
+
+size_t Engine::plan_codec(Bump& b, bool decode, int n, int64_t S, CodecBufs* out) const {
   long encT[5], decT[5];
   int encC[5], decC[5];
-  codec_stage_dims(cfg_, samples, encT, encC, decT, decC);
-  const size_t per_elem = 4 + 2 * esz_;  // raw f32 + act + tmp
-  size_t enc = (size_t)(samples + 2 * HALO) * 8 * esz_, dec = 0;
-  for (int i = 0; i < 5; ++i) enc += (size_t)(encT[i] + 2 * HALO) * encC[i] * per_elem + 1024;
-  enc += (size_t)(encT[4] + 2 * HALO) * cfg_.codec_latent * esz_;
-  dec += (size_t)(decT[0] + 2 * HALO) * (cfg_.codec_dim + cfg_.codec_latent) * esz_;
-  for (int i = 0; i < 5; ++i) dec += (size_t)(decT[i] + 2 * HALO) * decC[i] * per_elem + 1024;
-  return (size_t)items * ((enc > dec ? enc : dec) + codec_x3_per_item(samples)) + (1 << 16);
+  codec_stage_dims(cfg_, S, encT, encC, decT, decC);
+  const long* T = decode ? decT : encT;
+  const int* C = decode ? decC : encC;
+  size_t model = 0;
+  auto take = [&](size_t item_bytes) { model += (size_t)n * item_bytes; return b.take((size_t)n * item_bytes); };
+  auto halo = [](long t, int c) { return (size_t)(t + 2 * HALO) * c; };   // elements of one item's halo-padded [t][c]
+  CodecBufs cb{};
+  if (decode) { cb.lat = take(halo(T[0], cfg_.codec_dim) * esz_); cb.p0 = take(halo(T[0], cfg_.codec_latent) * esz_); }
+  else cb.in8 = take(halo(S, 8) * esz_);
+  for (int i = 0; i < 5; ++i) {
+    const size_t e = halo(T[i], C[i]);
+    cb.sb[i] = SBuf{(float*)take(e * 4), take(e * esz_), take(e * esz_), T[i], C[i]};
+    model += (size_t)n * kCodecStageSlack;
+  }
+  if (!decode) cb.eout = take(halo(T[4], cfg_.codec_latent) * esz_);
+  // the split activation operand of the widest launch - of either direction - that can run as a compensated 16-bit launch
+  // (gemm_codec_x3): the whole halo buffer it reads, 3 x 16 bits per element; nothing unless the option and the twins are there
+  size_t x3_item = 0;
+  if (x3(SAMAUDIO_CLS_CODEC) && !x3_codec_.empty()) {
+    auto see = [&](long t, int c) { x3_item = std::max(x3_item, halo(t, c) * 6 + kCodecX3Slack); };
+    for (int i = 0; i < 5; ++i) {
+      if (2 * encC[i] >= 256) see(encT[i], encC[i]);   // (the strided convolution out of stage i has 2 C outputs)
+      if (decC[i] >= 256) see(decT[i], decC[i]);
+    }
+    see(decT[0], cfg_.codec_dim);
+    see(decT[0], cfg_.codec_latent);
+    cb.x3_bytes = (size_t)n * x3_item;
+    cb.x3 = take(x3_item);
+  }
+  if (out) *out = cb;
+  return model;
 }
 
-// bytes per waveform of the split activation operand of the widest codec launch that can run as a compensated 16-bit launch
-// (gemm_codec_x3): the whole halo buffer a launch reads, 3 x 16 bits per element; 0 unless the option and the twins are there
-size_t Engine::codec_x3_per_item(int64_t samples) const {
-  if (!x3(SAMAUDIO_CLS_CODEC) || x3_codec_.empty()) return 0;
-  long encT[5], decT[5];
-  int encC[5], decC[5];
-  codec_stage_dims(cfg_, samples, encT, encC, decT, decC);
-  size_t m = 0;
-  auto see = [&](long T, int C) { const size_t v = (size_t)(T + 2 * HALO) * C * 6 + 256; if (v > m) m = v; };
-  for (int i = 0; i < 5; ++i) {
-    if (2 * encC[i] >= 256) see(encT[i], encC[i]);   // (the strided convolution out of stage i has 2 C outputs)
-    if (decC[i] >= 256) see(decT[i], decC[i]);
-  }
-  see(decT[0], cfg_.codec_dim);
-  see(decT[0], cfg_.codec_latent);
-  return m;
+size_t Engine::codec_per_item(int64_t samples) const {
+  Bump enc, dec;
+  return std::max(plan_codec(enc, false, 1, samples, nullptr), plan_codec(dec, true, 1, samples, nullptr));
+}
+
+size_t Engine::codec_bytes(int items, int64_t samples) const { return items <= 0 ? 0 : (size_t)items * codec_per_item(samples) + kCodecFixed; }
+
+// A workspace holds (bytes - kCodecFixed) / per_item waveforms per pass: dividing by codec_bytes(1) would turn a workspace sized for
+// exactly n of them into passes of n - 1 and 1 (and the stray single-waveform pass runs at a fraction of the rate)
+int Engine::codec_chunk(int items, int64_t samples, bool pairs) const {
+  const size_t per_item = codec_per_item(samples);
+  int chunk = ws_ && ws_bytes_ > kCodecFixed ? (int)((ws_bytes_ - kCodecFixed) / (per_item ? per_item : 1)) : 0;
+  if (chunk > items) chunk = items;
+  if (pairs && chunk > 1) chunk &= ~1;   // a pass holds whole (target, residual) pairs
+  return pairs && chunk < 2 ? 0 : chunk;
 }
 
 size_t Engine::workspace_bytes(int rows, int frames, int text_len, int codec_items, int64_t samples) {
@@ -641,29 +663,25 @@ Status Engine::sentinel_read(float* absmax, double* nonfinite, hipStream_t st) {
   return Status{};
 }
 
-// the 16-bit output of a GEMM launch, scanned into its class's slot (outputs with a window mask - transposed convolutions - have
-// rows the launch does not write: skipped)
-static int cls_slot(int cls) {
+static int cls_slot(int cls) {   // the sentinel slot of a class
   int bit = 0;
   while (bit < SAMAUDIO_CLS_COUNT - 1 && !(cls & (1 << bit))) ++bit;
   return bit;
 }
 
 // the tag and flags a launch of gemm() runs with (x3_split3_out_ok dry-runs gemm_check on them)
-GemmParams Engine::launch_params(const GemmParams& p_in, int cls, int mode) const {
-  const bool f32 = mode == 1;
+GemmParams Engine::launch_params(const GemmParams& p_in, int cls, GemmKind kind) const {
   GemmParams p = p_in;
-  p.tag = prof_cls_[0] == 'c' ? 1 : 0;  // codec launches run under their own kernel symbols
+  p.tag = phase_ == Phase::Codec ? 1 : 0;  // codec launches run under their own kernel symbols
   // from the caller: alt-format output, K-tile-major W, split-form output; from the context: the tail split (gemm.hip gemm_tail_split) and
   // the classes with operands in the alt format (SAMAUDIO_OPT_ALT16_CLASSES, mixed mode)
   p.flags = (p_in.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split_ ? 0 : GEMM_FLAG_NO_TAIL_SPLIT) |
-            (alt16(cls) && !f32 ? GEMM_FLAG_OPND_ALT : 0);
-  if (p.tag) cls = SAMAUDIO_CLS_CODEC;
+            (alt16(cls) && kind != GemmKind::F32 ? GEMM_FLAG_OPND_ALT : 0);
   // an x3 launch on K-concatenated split operands: let the 8-phase kernels share the operand tiles the three products have in common
   // (common.h GEMM_FLAG_X3_SHARE) wherever the launch qualifies; DBG_X3_PLAIN_WALK = 1: the plain walk over K' (A/B, tests)
-  // mode 3 (the convolutions: every Cin-block of K' is its own [hi | lo | hi]) never qualifies
+  // X3Block (the convolutions: every Cin-block of K' is its own [hi | lo | hi]) never qualifies
   const int plain_walk = debug_flag(DBG_X3_PLAIN_WALK);   // (>= 2: class mask << 1, diagnosis)
-  if (mode == 2 && plain_walk != 1 && (plain_walk < 2 || (cls & (plain_walk >> 1)))) {
+  if (kind == GemmKind::X3 && plain_walk != 1 && (plain_walk < 2 || (cls & (plain_walk >> 1)))) {
     GemmParams q = p;
     q.flags |= GEMM_FLAG_X3_SHARE;
     if (q.kc == q.K && q.K % 192 == 0 && !gemm_check(q, true)) p = q;
@@ -671,60 +689,69 @@ GemmParams Engine::launch_params(const GemmParams& p_in, int cls, int mode) cons
   return p;
 }
 
-Status Engine::gemm(const GemmParams& p_in, hipStream_t st, double alg_flops, int cls, int mode) {
-  const bool f32 = mode == 1, x3m = mode == 2 || mode == 3;   // mode 3: an x3 launch whose K' is split per input block, not as a whole
-  const bool is16 = bf16_ || x3m;   // the launch's operand format (an X3 launch: 16-bit operands inside an fp32 context)
-  if (sentinel_on_ && p_in.out_act && !p_in.c_ld_rel && !x3m) {
-    sentinel_on_ = false;   // (the launch itself, without recursion)
-    const Status s = gemm(p_in, st, alg_flops, cls, mode);
-    sentinel_on_ = true;
-    if (!s.ok()) return s;
-    const int c = prof_cls_[0] == 'c' ? SAMAUDIO_CLS_CODEC : cls;
-    const int fmt = (f32 || !bf16_) ? 0 : ((p_in.flags & GEMM_FLAG_OUT_ALT) ? 2 : 1);
-    const int n_out = p_in.swiglu ? p_in.N / 2 : p_in.N;
-    for (int b = 0; b < p_in.nbatch; ++b) {
-      const size_t esz = fmt == 0 ? 4 : 2;
-      const char* base = (const char*)p_in.out_act + ((size_t)p_in.act_off + (size_t)b * p_in.act_bstride) * esz;
-      SA_TRY(sentinel(cls_slot(c), base, fmt, p_in.M, n_out, p_in.act_ld, st));
-    }
-    return Status{};
+Status Engine::gemm(const GemmParams& p, hipStream_t st, double alg_flops, int cls, GemmKind kind) {
+  SA_TRY(launch(launch_params(p, cls, kind), st, alg_flops, cls, kind));
+  return scan_out(p, cls, kind, st);
+}
+
+// the 16-bit output of a GEMM launch, scanned into its class's slot (outputs with a window mask - transposed convolutions - have
+// rows the launch does not write, x3 launches fp32 outputs: skipped)
+Status Engine::scan_out(const GemmParams& p, int cls, GemmKind kind, hipStream_t st) {
+  if (!sentinel_on_ || !p.out_act || p.c_ld_rel || kind == GemmKind::X3 || kind == GemmKind::X3Block) return Status{};
+  const int fmt = (kind == GemmKind::F32 || !bf16_) ? 0 : ((p.flags & GEMM_FLAG_OUT_ALT) ? 2 : 1);
+  const int n_out = p.swiglu ? p.N / 2 : p.N;
+  for (int b = 0; b < p.nbatch; ++b) {
+    const size_t esz = fmt == 0 ? 4 : 2;
+    const char* base = (const char*)p.out_act + ((size_t)p.act_off + (size_t)b * p.act_bstride) * esz;
+    SA_TRY(sentinel(cls_slot(cls), base, fmt, p.M, n_out, p.act_ld, st));
   }
-  if (mode == 0 && !bf16_ && prof_cls_[0] == 'c' && p_in.N >= 256 && x3_codec_scratch_ && x3(SAMAUDIO_CLS_CODEC)) {
-    const auto it = x3_codec_.find(p_in.W);
-    if (it != x3_codec_.end()) {
-      const int c = it->second.cin;
-      const bool both = p_in.out_f32 && p_in.out_act;
-      const bool flat = !p_in.c_ld_rel ? (p_in.out_f32 ? p_in.f32_ld == p_in.N : p_in.act_ld == p_in.N) : true;
-      if (p_in.a_bstride > 0 && !p_in.w_bstride && !p_in.swiglu && !p_in.gate && !(p_in.kc % c) && !(p_in.lda % c) && !(p_in.a_off % c) &&
-          !(p_in.a_bstride % c) && !(p_in.tap_stride % c) && !(p_in.K % c) && !((3L * p_in.K) % 64) && flat && (!both || !p_in.f32_act) &&
-          (size_t)p_in.nbatch * (p_in.a_bstride / c) * 3 * c * 2 <= x3_codec_scratch_bytes_)
-        return gemm_codec_x3(p_in, it->second, st, alg_flops);
+  return Status{};
+}
+
+const Engine::X3CodecW* Engine::codec_x3_twin(const GemmParams& p) const {
+  if (p.N < 256 || !x3_codec_scratch_ || !x3(SAMAUDIO_CLS_CODEC)) return nullptr;
+  const auto it = x3_codec_.find(p.W);
+  if (it == x3_codec_.end()) return nullptr;
+  const int c = it->second.cin;
+  const bool both = p.out_f32 && p.out_act;
+  const bool flat = !p.c_ld_rel ? (p.out_f32 ? p.f32_ld == p.N : p.act_ld == p.N) : true;
+  const bool ok = p.a_bstride > 0 && !p.w_bstride && !p.swiglu && !p.gate && !(p.kc % c) && !(p.lda % c) && !(p.a_off % c) &&
+                  !(p.a_bstride % c) && !(p.tap_stride % c) && !(p.K % c) && !((3L * p.K) % 64) && flat && (!both || !p.f32_act) &&
+                  (size_t)p.nbatch * (p.a_bstride / c) * 3 * c * 2 <= x3_codec_scratch_bytes_;
+  return ok ? &it->second : nullptr;
+}
+
+Status Engine::codec_gemm(const GemmParams& p_in, hipStream_t st, double alg_flops) {
+  if (const X3CodecW* w3 = codec_x3_twin(p_in)) {
+    SA_TRY(gemm_codec_x3(p_in, *w3, st, alg_flops));
+  } else {
+    GemmParams p = launch_params(p_in, SAMAUDIO_CLS_CODEC, GemmKind::Native);
+    if (x3(SAMAUDIO_CLS_CODEC)) {   // (fp32 contexts): the convolution multiplies on split operands, split in registers (gemm.hip)
+      p.flags |= GEMM_FLAG_X3_FLY;
+      const auto it = p.w_bstride ? fly_codec_.end() : fly_codec_.find(p.W);
+      if (it != fly_codec_.end()) { p.W = it->second; p.flags |= GEMM_FLAG_W_FLY16; }
     }
+    SA_TRY(launch(p, st, alg_flops, SAMAUDIO_CLS_CODEC, GemmKind::Native));
   }
-  GemmParams p = launch_params(p_in, cls, mode);
-  if (p.tag) cls = SAMAUDIO_CLS_CODEC;
-  if (f32) {  // a class of SAMAUDIO_OPT_F32_CLASSES: exact-fp32 kernel inside a 16-bit context
+  return scan_out(p_in, SAMAUDIO_CLS_CODEC, GemmKind::Native, st);
+}
+
+Status Engine::launch(GemmParams p, hipStream_t st, double alg_flops, int cls, GemmKind kind) {
+  const bool x3m = kind == GemmKind::X3 || kind == GemmKind::X3Block;
+  const bool is16 = bf16_ || x3m;   // the launch's operand format (an x3 launch: 16-bit operands inside an fp32 context)
+  const double flops = alg_flops >= 0 ? alg_flops : 2.0 * p.M * (double)p.N * p.K * p.nbatch;
+  if (kind == GemmKind::F32) {  // a class of SAMAUDIO_OPT_F32_CLASSES: exact-fp32 kernel inside a 16-bit context
     if (!p.W) return fail(SAMAUDIO_ERR_WEIGHT, "SAMAUDIO_OPT_F32_CLASSES: the class's \"<name>.f32\" weight copy is not registered");
     if (const char* why = gemm_check(p, false)) return fail(SAMAUDIO_ERR_ARG, why);
-    const double flops = alg_flops >= 0 ? alg_flops : 2.0 * p.M * (double)p.N * p.K * p.nbatch;
     return op(gemm_variant_name(gemm_variant(p, false), false), gemm_alg_bytes(p, 4), flops, st,
               [&] { return launch_gemm(p, false, st); });
   }
   if (!is16 && quant_fmt_ && (quant_classes_ & cls)) p.flags |= (quant_fmt_ << GEMM_FLAG_QUANT_A_SHIFT) | (quant_fmt_ << GEMM_FLAG_QUANT_W_SHIFT);
-  // SAMAUDIO_OPT_X3_CLASSES bit CODEC (fp32 contexts): the convolution multiplies on split operands, split in registers (gemm.hip)
-  if (!is16 && p.tag && x3(SAMAUDIO_CLS_CODEC)) {
-    p.flags |= GEMM_FLAG_X3_FLY;
-    if (!p.w_bstride && !fly_codec_.empty()) {
-      const auto it = fly_codec_.find(p.W);
-      if (it != fly_codec_.end()) { p.W = it->second; p.flags |= GEMM_FLAG_W_FLY16; }
-    }
-  }
   if (const char* why = gemm_check(p, is16)) return fail(SAMAUDIO_ERR_ARG, why);
   if (!prof_on_) {
     SA_HIP(launch_gemm(p, is16, st));
     return Status{};
   }
-  const double flops = alg_flops >= 0 ? alg_flops : 2.0 * p.M * (double)p.N * p.K * p.nbatch;
   const double bytes = gemm_alg_bytes(p, is16 ? 2 : 4);
   const int full = gemm_tail_split(p, is16);
   const long tiles = (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.nbatch;
@@ -735,7 +762,7 @@ Status Engine::gemm(const GemmParams& p_in, hipStream_t st, double alg_flops, in
     // implicit convolutions (kc < K) run the 8-phase kernels under their own instantiation (gemm8_kernel<true>): own record
     const int variant = gemm_variant(p, is16);
     const char* conv = gemm_is_8phase(variant) && p.kc < p.K ? "_conv" : "";
-    r.key = std::string(prof_cls_) + "/" + (part ? kGemm8sTailName : gemm_variant_name(variant, is16)) + conv + (x3m ? "_x3" : "");
+    r.key = std::string(phase_name()) + "/" + (part ? kGemm8sTailName : gemm_variant_name(variant, is16)) + conv + (x3m ? "_x3" : "");
     if (static const bool by_class = std::getenv("SAMAUDIO_PROF_BY_CLASS") != nullptr; by_class) {   // diagnosis: one record per GEMM class
       int bit = 0;
       while (bit < SAMAUDIO_CLS_COUNT && !(cls & (1 << bit))) ++bit;
@@ -768,7 +795,7 @@ Status Engine::gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, i
     presplit = dst;
   }
   x3_operands(p, presplit, w3, ktm);
-  return gemm(p, st, 2.0 * p.M * (double)p.N * K, cls, 2);   // flops as the reference counts them: one product over K
+  return gemm(p, st, 2.0 * p.M * (double)p.N * K, cls, GemmKind::X3);   // flops as the reference counts them: one product over K
 }
 
 // the 16-bit launch over K' = 3K that an x3 class makes of its fp32 GemmParams: A = the split operand, W = the split weight
@@ -791,7 +818,7 @@ bool Engine::x3_split3_out_ok(GemmParams p, const void* w3, bool ktm, void* out3
   p.out_act = out3;
   p.flags |= GEMM_FLAG_OUT_SPLIT3;
   x3_operands(p, d_.x3a, w3, ktm);
-  return gemm_check(launch_params(p, SAMAUDIO_CLS_W13, 2), true) == nullptr;   // the parameters gemm() would launch
+  return gemm_check(launch_params(p, SAMAUDIO_CLS_W13, GemmKind::X3), true) == nullptr;   // the parameters gemm() would launch
 }
 
 Status Engine::gemm_codec_x3(const GemmParams& p_in, const X3CodecW& w, hipStream_t st, double alg_flops) {
@@ -809,7 +836,8 @@ Status Engine::gemm_codec_x3(const GemmParams& p_in, const X3CodecW& w, hipStrea
   if (!p_in.out_f32) { p.out_f32 = raw; p.f32_ld = p_in.act_ld; p.f32_bstride = p_in.act_bstride; p.f32_off = p_in.act_off; }
   p.out_act = nullptr; p.act_ld = p.act_bstride = p.act_off = 0; p.act = ACT_NONE; p.f32_act = 0;
   const double flops = alg_flops >= 0 ? alg_flops : 2.0 * p_in.M * (double)p_in.N * p_in.K * p_in.nbatch;
-  SA_TRY(gemm(p, st, flops, SAMAUDIO_CLS_CODEC, p_in.K == c && p_in.kc == c ? 2 : 3));   // one block: [lo | hi | hi] x [W_hi | W_lo | W_hi] over the whole K'
+  // one block: [lo | hi | hi] x [W_hi | W_lo | W_hi] over the whole K'
+  SA_TRY(gemm(p, st, flops, SAMAUDIO_CLS_CODEC, p_in.K == c && p_in.kc == c ? GemmKind::X3 : GemmKind::X3Block));
   if (!p_in.out_act || (act == ACT_NONE && !p_in.out_f32)) return Status{};
   // region the launch wrote, per item: [c_lo, c_hi) of the windowed (transposed) convolutions, else M rows of N
   const long start = p_in.c_ld_rel ? p_in.c_lo : 0, count = p_in.c_ld_rel ? p_in.c_hi - p_in.c_lo : (long)p_in.M * p_in.N;
@@ -832,7 +860,7 @@ Status Engine::res_unit(GemmParams p, GemmParams q, void*& cur, void*& alt, doub
   q.out_act = cur;
   GemmParams fp = p, fq = q;
   fq.out_act = alt;
-  fp.tag = fq.tag = prof_cls_[0] == 'c' ? 1 : 0;
+  fp.tag = fq.tag = phase_ == Phase::Codec ? 1 : 0;
   const bool covered = p.N == 64 || p.N == 96 || p.N == 128 || p.N == 192;
   // fused for all four channel counts: since the residual-unit kernels issue their direct-to-LDS loads as inline assembly
   // (gemm2.hip dma16a) the fused form is the faster one everywhere (profiles/r3_call12/op_bench.log, 8 waveforms, fused vs
@@ -840,18 +868,15 @@ Status Engine::res_unit(GemmParams p, GemmParams q, void*& cur, void*& alt, doub
   const bool fuse = bf16_ && covered && !debug_flag(DBG_RESUNIT_TWO_LAUNCHES) && resunit_ok(fp, fq) &&
                     ((long)((p.M + 255) / 256) * p.nbatch >= 256 || debug_flag(DBG_RESUNIT_FUSE_ALWAYS));
   if (!fuse) {
-    SA_TRY(gemm(p, st, flops7));
-    return gemm(q, st, flops1);
+    SA_TRY(codec_gemm(p, st, flops7));
+    return codec_gemm(q, st, flops1);
   }
   if (const char* why = gemm_check(fp, bf16_)) return fail(SAMAUDIO_ERR_ARG, why);
   if (const char* why = gemm_check(fq, bf16_)) return fail(SAMAUDIO_ERR_ARG, why);
   const double inter = (double)p.M * p.N * p.nbatch * esz_;   // the intermediate: neither written nor read
   SA_TRY(op("resunit_bf16", gemm_alg_bytes(fp, esz_) + gemm_alg_bytes(fq, esz_) - 2 * inter, flops7 + flops1, st,
             [&] { return launch_resunit(fp, fq, st); }));
-  if (sentinel_on_)   // the fused unit's 16-bit output (halo layout: the rows the launch writes)
-    for (int b = 0; b < fq.nbatch; ++b)
-      SA_TRY(sentinel(cls_slot(SAMAUDIO_CLS_CODEC), (const char*)fq.out_act + ((size_t)fq.act_off + (size_t)b * fq.act_bstride) * esz_,
-                      bf16_ ? 1 : 0, fq.M, fq.N, fq.act_ld, st));
+  SA_TRY(scan_out(fq, SAMAUDIO_CLS_CODEC, GemmKind::Native, st));   // the fused unit's 16-bit output (halo layout: the rows the launch writes)
   std::swap(cur, alt);
   return Status{};
 }
@@ -863,7 +888,7 @@ Status Engine::op(const char* name, double alg_bytes, double alg_flops, hipStrea
     return Status{};
   }
   ProfRec r;
-  r.key = std::string(prof_cls_) + "/" + name;
+  r.key = std::string(phase_name()) + "/" + name;
   r.flops = alg_flops;
   r.bytes = alg_bytes;
   SA_TRY(prof_event(&r.e0));
@@ -951,7 +976,7 @@ Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float*
   if (text && Lt <= 0) return fail(SAMAUDIO_ERR_ARG, "prepare: text_len must be positive");
   if (!text) Lt = 1;
   if (anchor_ids && (!anchor_alignment || n_ids <= 0)) return fail(SAMAUDIO_ERR_ARG, "prepare: anchors incomplete");
-  prof_cls_ = "prep";
+  phase_ = Phase::Prep;
   Bump b(ws_, ws_bytes_);
   plan_dit(b, rows, T, Lt, true);
   if (!ws_ || !b.fits())
@@ -979,6 +1004,7 @@ Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float*
   // SAMAUDIO_CLS_PREP in exact fp32 (16-bit contexts): the caller's fp32 tensors are the operands themselves
   const bool pf = f32c(SAMAUDIO_CLS_PREP);
   const int PREP = SAMAUDIO_CLS_PREP;
+  const GemmKind pk = f32_if(pf);
   // cond = proj_b + audio_features @ Wf^T                           (model.py:116-125, columns 512..767)
   // latent_feats: audio_features = (z | z) of the codec latent z [Mb, C2 / 2] (model.py:182-184): the K axis of this GEMM is two
   // taps of C2 / 2 channels that read the SAME row (tap stride 0) - the same products in the same order as on the concatenation
@@ -989,7 +1015,7 @@ Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float*
     if (latent_feats) { p.kc = fw; p.tap_stride = 0; }
     p.bias = g_.proj_b;
     out_f32(p, cond_b, D);
-    SA_TRY(gemm(p, st, -1.0, PREP, pf));
+    SA_TRY(gemm(p, st, -1.0, PREP, pk));
   }
   // cond += tanh(g_v) * LayerNorm(conv1x1(video))                   (align.py:41-50; zeros if no video: Q8)
   const void* vid_op = d_.video;
@@ -1001,24 +1027,21 @@ Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float*
     GemmParams p = lin(vid_op, cfg_.video_dim, pf ? (const void*)g32_.vid_w : g_.vid_w, Mb, D, cfg_.video_dim);
     p.bias = g_.vid_b;
     out_f32(p, d_.vtmp, D);
-    SA_TRY(gemm(p, st, -1.0, PREP, pf));
+    SA_TRY(gemm(p, st, -1.0, PREP, pk));
     SA_HIP(launch_layernorm_accum(d_.vtmp, g_.vid_ln_w, g_.vid_ln_b, g_.vid_gate, cond_b, (int)Mb, D, 1e-5f, st));
   }
   // cond += tanh(g_a) * proj(Emb[ids.gather(alignment)])            (model.py:54-65; tanh folded into anc_w)
   // folded cross-attention output projection: zero the probability buffer once (its K padding columns stay zero)
-  fold_ltp_ = fold_kp_ = 0;
-  if (bf16_ && Lt <= 16 && D / cfg_.n_heads == 128 && !std::getenv("SAMAUDIO_NO_FOLD")) {
-    fold_ltp_ = Lt <= 8 ? 8 : 16;
-    fold_kp_ = (int)round_up((long)cfg_.n_heads * fold_ltp_, 64);
+  const FoldPlan fp = fold_plan(Lt);   // (as plan_dit sized it above)
+  fold3_ = fp.fold3;
+  fold_ltp_ = fp.fold16 || fp.fold3 ? fp.ltp : 0;
+  fold_kp_ = fold_ltp_ ? fp.kp : 0;
+  if (fp.fold16) {
     SA_HIP(hipMemsetAsync(d_.probs, 0, (size_t)M * fold_kp_ * esz_, st));
     // 0 * (K padding of U) must stay 0
-    SA_HIP(hipMemsetAsync(d_.ut, 0, (size_t)rows * D * fold_kp_ * esz_ * (cfg_.n_layers <= kMaxFoldLayers ? cfg_.n_layers : 1), st));
+    SA_HIP(hipMemsetAsync(d_.ut, 0, (size_t)rows * D * fold_kp_ * esz_ * (fp.all_layers ? cfg_.n_layers : 1), st));
   }
-  fold3_ = false;
-  if (d_.ut3 && d_.x3p) {   // x3 context: the fold on compensated operands (zero K padding of P and U, once per prepare)
-    fold3_ = true;
-    fold_ltp_ = Lt <= 8 ? 8 : 16;
-    fold_kp_ = (int)round_up((long)cfg_.n_heads * fold_ltp_, 64);
+  if (fp.fold3) {   // x3 context: the fold on compensated operands (zero K padding of P and U, once per prepare)
     SA_HIP(hipMemsetAsync(d_.x3p, 0, (size_t)M * 3 * fold_kp_ * 2, st));
     SA_HIP(hipMemsetAsync(d_.ut3, 0, (size_t)rows * D * 3 * fold_kp_ * 2 * cfg_.n_layers, st));
   }
@@ -1031,7 +1054,7 @@ Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float*
                       : lin(d_.anch, cfg_.anchor_dim, g_.anc_w, Mb, D, cfg_.anchor_dim);
     with_res(p, cond_b, D);
     out_f32(p, cond_b, D);
-    SA_TRY(gemm(p, st, -1.0, PREP, pf));
+    SA_TRY(gemm(p, st, -1.0, PREP, pk));
   }
   // text_proj = memory_proj(text)                                   (model.py:171)
   if (text) {
@@ -1040,7 +1063,7 @@ Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float*
                       : lin(d_.text, cfg_.text_dim, g_.mem_w, Mtb, D, cfg_.text_dim);
     p.bias = g_.mem_b;
     out_f32(p, textp_b, D);
-    SA_TRY(gemm(p, st, -1.0, PREP, pf));
+    SA_TRY(gemm(p, st, -1.0, PREP, pk));
   } else {
     SA_HIP(hipMemsetAsync(textp_b, 0, (size_t)Mtb * D * 4, st));
   }
@@ -1065,7 +1088,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
   const float eps = cfg_.norm_eps;
   const int hd = D / H;   // 128 | 64 (finalize)
   const long t6 = nt == 1 ? 0 : 6L * D, t1 = nt == 1 ? 0 : (long)D;
-  prof_cls_ = "dit";
+  phase_ = Phase::Dit;
   const double MD = (double)M * D;
   if (hash_on() && !hash_) hash_ = new HashTrace();
   const HashScope hash_scope(hash_on() ? (HashTrace*)hash_ : nullptr, rows);
@@ -1078,7 +1101,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     GemmParams p = f ? lin(noisy, C2, g32_.proj_wy, M, D, C2) : lin(d_.ybf, C2, g_.proj_wy, M, D, C2);
     with_res(p, d_.cond, D);
     out_f32(p, d_.aligned, D);
-    SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_IN, f));
+    SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_IN, f32_if(f)));
   }
   // patcher: (GroupNorm(1) -> SiLU -> conv k3) x 2 + skip           (patcher.py:138-141)
   auto patch_conv = [&](const void* W, const void* W3, bool ktm3, const float* bias, const float* skip, float* dst) -> Status {
@@ -1096,7 +1119,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     SA_TRY(op("split3", (double)prow * D * (4 + 6), 0, st, [&] { return launch_split3((const float*)d_.gnbuf, D, d_.x3a, prow, D, st); }));
     p.A = d_.x3a; p.W = W3; p.lda = 3L * D; p.kc = 3 * D; p.tap_stride = 3L * D; p.a_bstride = (long)(T + 2) * 3 * D; p.K = 9 * D;
     if (ktm3) p.flags |= GEMM_FLAG_W_KTM;
-    return gemm(p, st, 2.0 * T * (double)D * 3 * D * rows, SAMAUDIO_CLS_PATCH, 3);
+    return gemm(p, st, 2.0 * T * (double)D * 3 * D * rows, SAMAUDIO_CLS_PATCH, GemmKind::X3Block);
   };
   trace("cond", d_.cond, (size_t)M * D, false, st);
   trace("aligned", d_.aligned, (size_t)M * D, false, st);
@@ -1120,15 +1143,15 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     GemmParams p = lin(temb, cfg_.freq_dim, f ? (const void*)g32_.t_w13 : g_.t_w13, nt, 2 * D, cfg_.freq_dim);
     p.swiglu = 1;
     out_act(p, tu, D);
-    SA_TRY(gemm(p, st, -1.0, TIME, f));
+    SA_TRY(gemm(p, st, -1.0, TIME, f32_if(f)));
     p = lin(tu, D, f ? (const void*)g32_.t_w2 : g_.t_w2, nt, D, D);
     out_f32(p, d_.t_emb, D);
     out_act(p, tsilu, D, ACT_SILU);
-    SA_TRY(gemm(p, st, -1.0, TIME, f));
+    SA_TRY(gemm(p, st, -1.0, TIME, f32_if(f)));
     p = lin(tsilu, D, f ? (const void*)g32_.tb_w : g_.tb_w, nt, 6 * D, D);
     p.bias = g_.tb_b;
     out_f32(p, d_.t0, 6L * D);
-    SA_TRY(gemm(p, st, -1.0, TIME, f));
+    SA_TRY(gemm(p, st, -1.0, TIME, f32_if(f)));
   }
   // RMSNorm + modulate operands of this evaluation, pre-combined for every layer's two norms (kernels.hip mod_tables)
   const bool mod_gs = 2 * cfg_.n_layers <= kMaxModNorms && cfg_.n_layers > 0 && D <= 256 * 12;
@@ -1163,11 +1186,11 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     GemmParams p = lin(mem, D, f ? (const void*)g32_.y_w13 : g_.y_w13, Mt, 2 * D, D);
     p.swiglu = 1;
     out_act(p, yu, D);
-    SA_TRY(gemm(p, st, -1.0, YEMB, f));
+    SA_TRY(gemm(p, st, -1.0, YEMB, f32_if(f)));
     p = lin(yu, D, f ? (const void*)g32_.y_w2 : g_.y_w2, Mt, D, D);
     if (f) {  // the K | V projections read the 16-bit copy
       out_f32(p, d_.yemb32, D);
-      SA_TRY(gemm(p, st, -1.0, YEMB, true));
+      SA_TRY(gemm(p, st, -1.0, YEMB, GemmKind::F32));
       SA_HIP(launch_to_act(d_.yemb32, 0, D, 0, d_.yemb, 0, true, 1, Mt, D, D, 0, st));
     } else {
       out_act(p, d_.yemb, D);
@@ -1216,6 +1239,29 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     if (pf_on && w_next) { p.pf_ptr = w_next; p.pf_bytes = (long)(elems * esz_); }
   };
   auto ktm = [](GemmParams& p, const LayerW& w, int bit) { if (w.ktm & (1 << bit)) p.flags |= GEMM_FLAG_W_KTM; };
+  // the modulated RMSNorm in front of class `cls` of layer l (k = 0: the attention norm, QKV; k = 1: the FFN norm, W13) and the scan of
+  // its output; `pre`: it writes the class's split operand [lo | hi | hi] itself
+  auto norm_for = [&](int l, int k, int cls, bool pre) -> Status {
+    const LayerW& w = layers_[l];
+    const float* tab = w.mod_table + 3 * k * D;
+    const float* gs = d_.modgs + (2L * l + k) * nt * 2 * D;
+    SA_TRY(op("rmsnorm_mod", MD * (4 + (pre ? 6 : esz_)), 0, st, [&] {
+      if (pre) return launch_rmsnorm_gs_split3(d_.h, gs, gs_ld, d_.x3a, (int)M, D, T, eps, st);
+      if (mod_gs) return launch_rmsnorm_gs(d_.h, gs, gs_ld, d_.xn, bf16_, (int)M, D, T, eps, st, alt16(cls));
+      return launch_rmsnorm_mod(d_.h, k ? w.ffn_norm : w.attn_norm, tab, tab + D, d_.t0, t6, 3 * k * D, (3 * k + 1) * D, d_.xn, bf16_,
+                                (int)M, D, T, eps, st);
+    }));
+    return sentinel(14, d_.xn, !bf16_ ? 0 : (alt16(cls) ? 2 : 1), M, D, D, st);
+  };
+  // h += P . U of one layer, the batched GEMM of either fold: P [rows][T][K] probabilities, U [rows][D][K] = Wo V per batch item
+  auto fold_gemm = [&](const void* P, const void* U, int K) {
+    GemmParams p = lin(P, K, U, T, D, K);
+    p.nbatch = rows; p.a_bstride = (long)T * K; p.w_bstride = (long)D * K;
+    with_res(p, d_.h, D);
+    out_f32(p, d_.h, D);
+    p.res_bstride = p.f32_bstride = (long)T * D;
+    return p;
+  };
   for (int l = 0; l < cfg_.n_layers; ++l) {  // DiTBlock.forward, transformer.py:354-391
     const LayerW& w = layers_[l];
     const float* tab = w.mod_table;
@@ -1224,16 +1270,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     const bool qkv_pre = x3(SAMAUDIO_CLS_QKV) && mod_gs, w13_pre = x3(SAMAUDIO_CLS_W13) && mod_gs;
     const bool wo_pre = x3(SAMAUDIO_CLS_WO) && x3(SAMAUDIO_X3_ATTENTION);
     bool w2_pre = false;   // (decided with the w13 launch below)
-    SA_TRY(op("rmsnorm_mod", MD * (4 + (qkv_pre ? 6 : esz_)), 0, st, [&] {
-      if (qkv_pre)
-        return launch_rmsnorm_gs_split3(d_.h, d_.modgs + (2L * l) * nt * 2 * D, gs_ld, d_.x3a, (int)M, D, T, eps, st);
-      if (mod_gs)
-        return launch_rmsnorm_gs(d_.h, d_.modgs + (2L * l) * nt * 2 * D, gs_ld, d_.xn, bf16_, (int)M, D, T, eps, st,
-                                 alt16(SAMAUDIO_CLS_QKV));
-      return launch_rmsnorm_mod(d_.h, w.attn_norm, tab + 0 * D, tab + 1 * D, d_.t0, t6, 0 * D, 1 * D, d_.xn, bf16_, (int)M, D,
-                                T, eps, st);
-    }));
-    SA_TRY(sentinel(14, d_.xn, !bf16_ ? 0 : (alt16(SAMAUDIO_CLS_QKV) ? 2 : 1), M, D, D, st));
+    SA_TRY(norm_for(l, 0, SAMAUDIO_CLS_QKV, qkv_pre));
     {
       GemmParams p = lin(d_.xn, D, w.wqkv, M, 3 * D, D);
       ktm(p, w, 0);
@@ -1299,15 +1336,8 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
                                         fold_ltp_, H, eps, st);
       }));
       const int K3 = 3 * fold_kp_;
-      GemmParams p = lin(d_.x3p, K3, (const char*)d_.ut3 + (size_t)l * rows * D * K3 * 2, T, D, K3);
-      p.nbatch = rows;
-      p.a_bstride = (long)T * K3;
-      p.w_bstride = (long)D * K3;
-      with_res(p, d_.h, D);
-      p.res_bstride = (long)T * D;
-      out_f32(p, d_.h, D);
-      p.f32_bstride = (long)T * D;
-      SA_TRY(gemm(p, st, 2.0 * M * (double)D * H * Lt, SAMAUDIO_CLS_CWO, 2));
+      const GemmParams p = fold_gemm(d_.x3p, (const char*)d_.ut3 + (size_t)l * rows * D * K3 * 2, K3);
+      SA_TRY(gemm(p, st, 2.0 * M * (double)D * H * Lt, SAMAUDIO_CLS_CWO, GemmKind::X3));
     } else if (fold_ltp) {
       // h += P . U with U = Wo V folded per (batch, head, token): K = H*Lt instead of D (see attention.hip)
       SA_TRY(op("cross_attn_probs", (MD + (double)M * fold_kp_ + (double)Mt * 2 * D) * esz_, 0, st, [&] {
@@ -1319,14 +1349,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
         SA_TRY(op("cross_attn_fold", ((double)D * D + (double)rows * D * fold_kp_ + (double)Mt * D) * esz_, 0, st, [&] {
           return launch_cross_attn_fold(w.c_wo, kv_l, kv_ld, d_.ut, fold_kp_, rows, Lt, fold_ltp_, H, st);
         }));
-      GemmParams p = lin(d_.probs, fold_kp_, ut_l, T, D, fold_kp_);
-      p.nbatch = rows;
-      p.a_bstride = (long)T * fold_kp_;
-      p.w_bstride = (long)D * fold_kp_;
-      with_res(p, d_.h, D);
-      p.res_bstride = (long)T * D;
-      out_f32(p, d_.h, D);
-      p.f32_bstride = (long)T * D;
+      const GemmParams p = fold_gemm(d_.probs, ut_l, fold_kp_);
       trace("  probs", d_.probs, (size_t)M * fold_kp_, bf16_, st);
       trace("  ut", ut_l, (size_t)rows * D * fold_kp_, bf16_, st);
       SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_CWO));
@@ -1343,16 +1366,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     trace("  qc", d_.qc, (size_t)M * D, bf16_, st);
     trace("  h after cross", d_.h, (size_t)M * D, false, st);
     // feed-forward branch
-    SA_TRY(op("rmsnorm_mod", MD * (4 + (w13_pre ? 6 : esz_)), 0, st, [&] {
-      if (w13_pre)
-        return launch_rmsnorm_gs_split3(d_.h, d_.modgs + (2L * l + 1) * nt * 2 * D, gs_ld, d_.x3a, (int)M, D, T, eps, st);
-      if (mod_gs)
-        return launch_rmsnorm_gs(d_.h, d_.modgs + (2L * l + 1) * nt * 2 * D, gs_ld, d_.xn, bf16_, (int)M, D, T, eps, st,
-                                 alt16(SAMAUDIO_CLS_W13));
-      return launch_rmsnorm_mod(d_.h, w.ffn_norm, tab + 3 * D, tab + 4 * D, d_.t0, t6, 3 * D, 4 * D, d_.xn, bf16_, (int)M, D,
-                                T, eps, st);
-    }));
-    SA_TRY(sentinel(14, d_.xn, !bf16_ ? 0 : (alt16(SAMAUDIO_CLS_W13) ? 2 : 1), M, D, D, st));
+    SA_TRY(norm_for(l, 1, SAMAUDIO_CLS_W13, w13_pre));
     {
       GemmParams p = lin(d_.xn, D, w.w13, M, 2 * F, D);
       p.swiglu = 1;
@@ -1392,7 +1406,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     p.alpha = alpha;
     if (res) with_res(p, res, C2);
     out_f32(p, out, C2);
-    SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_OUT, f));
+    SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_OUT, f32_if(f)));
   }
   hash_stage("field out", out, (size_t)M * C2 * 4, st);
   return Status{};
@@ -1525,13 +1539,6 @@ Status Engine::solve_launches(float* y, int method, const float* grid, int n_gri
 // halo-padded activations; Snake is fused into the producer's epilogue (raw f32 stream for residuals,
 // activated copy as the next convolution's operand).
 // ---------------------------------------------------------------------------------------------------
-namespace {
-struct SBuf {
-  float* raw; void* act; void* tmp;
-  long T; int C;
-};
-}  // namespace
-
 static GemmParams conv_same(const void* x, long T, int Cin, int taps, int dil, const void* W, int Kp, int Cout,
                             int items) {
   GemmParams p = lin(x, Cin, W, T, Cout, Kp);
@@ -1549,85 +1556,84 @@ static void halo_out(GemmParams& p, float* raw, void* act, long T, int C, int ac
   p.act_alpha = alpha;
 }
 
+// the buffers of one pass over n waveforms, carved from the workspace (plan_codec)
+Status Engine::codec_carve(bool decode, int n, int64_t S, CodecBufs& cb) {
+  Bump b(ws_, ws_bytes_);
+  plan_codec(b, decode, n, S, &cb);
+  if (!b.fits()) return fail(SAMAUDIO_ERR_WORKSPACE, "codec: workspace too small");
+  x3_codec_scratch_ = cb.x3;
+  x3_codec_scratch_bytes_ = cb.x3_bytes;
+  return Status{};
+}
+
+Status Engine::res_units(const StageW& sw, SBuf& sb, int n, const float* next_alpha, hipStream_t st) {
+  const long T = sb.T;
+  const int C = sb.C, dil[3] = {1, 3, 9};
+  for (int j = 0; j < 3; ++j) {
+    const ResUnitW& r = sw.r[j];
+    GemmParams p = conv_same(sb.act, T, C, 7, dil[j], r.w1, r.k1pad, C, n);
+    p.bias = r.b1;
+    halo_out(p, nullptr, sb.tmp, T, C, ACT_SNAKE, r.a2);
+    GemmParams q = conv_same(sb.tmp, T, C, 1, 1, r.w2, r.k2pad, C, n);
+    q.bias = r.b2;
+    q.res = sb.raw; q.res_bstride = (T + 2L * HALO) * C; q.res_ld = C; q.res_off = (long)HALO * C;
+    halo_out(q, sb.raw, sb.act, T, C, ACT_SNAKE, j < 2 ? sw.r[j + 1].a1 : next_alpha);
+    SA_TRY(res_unit(p, q, sb.act, sb.tmp, 2.0 * T * C * 7 * C * n, 2.0 * T * C * C * n, st));
+  }
+  return Status{};
+}
+
 Status Engine::codec_encode(const float* wav, int items, int64_t S, float* latent, hipStream_t st) {
   if (!enc_ready_) return fail(SAMAUDIO_ERR_STATE, "codec_encode: codec weights not finalized");
-  long hop = 1;
-  for (int i = 0; i < 4; ++i) hop *= cfg_.enc_rates[i];
+  const long hop = codec_hop(cfg_);
   if (!wav || !latent || items <= 0 || S <= 0 || S % hop) return fail(SAMAUDIO_ERR_ARG, "codec_encode: samples % hop != 0");
-  // codec_bytes(n) = n * per_item + a fixed 64 KiB: dividing the workspace by codec_bytes(1) would turn a workspace sized
-  // for exactly n waveforms into passes of n - 1 and 1 (and the stray single-waveform pass runs at a fraction of the rate)
-  const size_t fixed = (size_t)1 << 16;
-  const size_t per_item = codec_bytes(1, S) - fixed;
-  int chunk = ws_bytes_ > fixed ? (int)((ws_bytes_ - fixed) / (per_item ? per_item : 1)) : 0;
-  if (!ws_ || chunk < 1) return fail(SAMAUDIO_ERR_WORKSPACE, "codec_encode: workspace too small");
-  if (chunk > items) chunk = items;
+  const int chunk = codec_chunk(items, S, false);
+  if (chunk < 1) return fail(SAMAUDIO_ERR_WORKSPACE, "codec_encode: workspace too small");
   prepared_ = false;  // the codec scratch aliases the DiT scratch
-  prof_cls_ = "codec";
-  long encT[5], decT[5];
-  int encC[5], decC[5];
-  codec_stage_dims(cfg_, S, encT, encC, decT, decC);
+  phase_ = Phase::Codec;
   const int CL = cfg_.codec_latent, CD = cfg_.codec_dim;
   for (int i0 = 0; i0 < items; i0 += chunk) {
     const int n = items - i0 < chunk ? items - i0 : chunk;
-    Bump b(ws_, ws_bytes_);
-    void* in8 = b.take((size_t)n * (S + 2 * HALO) * 8 * esz_);
-    SBuf sb[5];
-    for (int i = 0; i < 5; ++i) {
-      const size_t e = (size_t)n * (encT[i] + 2 * HALO) * encC[i];
-      sb[i] = SBuf{(float*)b.take(e * 4), b.take(e * esz_), b.take(e * esz_), encT[i], encC[i]};
-    }
-    void* eout = b.take((size_t)n * (encT[4] + 2 * HALO) * CL * esz_);
-    x3_codec_scratch_bytes_ = (size_t)n * codec_x3_per_item(S);
-    x3_codec_scratch_ = x3_codec_scratch_bytes_ ? b.take(x3_codec_scratch_bytes_) : nullptr;
-    if (!b.fits()) return fail(SAMAUDIO_ERR_WORKSPACE, "codec_encode: workspace too small");
+    CodecBufs cb;
+    SA_TRY(codec_carve(false, n, S, cb));
+    SBuf* const sb = cb.sb;
     // waveform -> [n][HALO + S + HALO][8] (channel 0), zero halos
-    SA_HIP(hipMemsetAsync(in8, 0, (size_t)n * (S + 2 * HALO) * 8 * esz_, st));
-    SA_HIP(launch_to_act(wav + (long)i0 * S, S, 1, 0, in8, 0, bf16_, n, S, 1, 8, HALO, st));
+    SA_HIP(hipMemsetAsync(cb.in8, 0, (size_t)n * (S + 2 * HALO) * 8 * esz_, st));
+    SA_HIP(launch_to_act(wav + (long)i0 * S, S, 1, 0, cb.in8, 0, bf16_, n, S, 1, 8, HALO, st));
     for (int i = 0; i < 5; ++i) {
       SA_HIP(launch_zero_halo(sb[i].act, bf16_, n, sb[i].T, sb[i].C, HALO, st));
       SA_HIP(launch_zero_halo(sb[i].tmp, bf16_, n, sb[i].T, sb[i].C, HALO, st));
     }
-    SA_HIP(launch_zero_halo(eout, bf16_, n, encT[4], CL, HALO, st));
+    SA_HIP(launch_zero_halo(cb.eout, bf16_, n, sb[4].T, CL, HALO, st));
     {  // conv k7 (1 -> 64): window of 8 samples x 8 padded channels = one 64-wide row
-      GemmParams p = lin(in8, 8, enc_.in_w, S, encC[0], 64);
+      GemmParams p = lin(cb.in8, 8, enc_.in_w, S, sb[0].C, 64);
       p.a_off = (long)(HALO - 3) * 8; p.a_bstride = (S + 2L * HALO) * 8; p.nbatch = n; p.bias = enc_.in_b;
-      halo_out(p, sb[0].raw, sb[0].act, S, encC[0], ACT_SNAKE, enc_.s[0].r[0].a1);
-      SA_TRY(gemm(p, st, 2.0 * S * encC[0] * 7 * n));
+      halo_out(p, sb[0].raw, sb[0].act, S, sb[0].C, ACT_SNAKE, enc_.s[0].r[0].a1);
+      SA_TRY(codec_gemm(p, st, 2.0 * S * sb[0].C * 7 * n));
     }
     for (int i = 0; i < 4; ++i) {
       const StageW& sw = enc_.s[i];
       const long T = sb[i].T;
       const int C = sb[i].C, s = cfg_.enc_rates[i];
-      const int dil[3] = {1, 3, 9};
-      for (int j = 0; j < 3; ++j) {
-        const ResUnitW& r = sw.r[j];
-        GemmParams p = conv_same(sb[i].act, T, C, 7, dil[j], r.w1, r.k1pad, C, n);
-        p.bias = r.b1;
-        halo_out(p, nullptr, sb[i].tmp, T, C, ACT_SNAKE, r.a2);
-        GemmParams q = conv_same(sb[i].tmp, T, C, 1, 1, r.w2, r.k2pad, C, n);
-        q.bias = r.b2;
-        q.res = sb[i].raw; q.res_bstride = (T + 2L * HALO) * C; q.res_ld = C; q.res_off = (long)HALO * C;
-        halo_out(q, sb[i].raw, sb[i].act, T, C, ACT_SNAKE, j < 2 ? sw.r[j + 1].a1 : sw.a);
-        SA_TRY(res_unit(p, q, sb[i].act, sb[i].tmp, 2.0 * T * C * 7 * C * n, 2.0 * T * C * C * n, st));
-      }
+      SA_TRY(res_units(sw, sb[i], n, sw.a, st));
       // strided conv k = 2s, stride s, pad s/2: the 2s input rows of one output are contiguous
       const int pad = (s + 1) / 2;
       GemmParams p = lin(sb[i].act, (long)s * C, sw.w, T / s, 2 * C, 2 * s * C);
       p.a_off = (long)(HALO - pad) * C; p.a_bstride = (T + 2L * HALO) * C; p.nbatch = n; p.bias = sw.b;
       halo_out(p, sb[i + 1].raw, sb[i + 1].act, T / s, 2 * C, ACT_SNAKE, i < 3 ? enc_.s[i + 1].r[0].a1 : enc_.out_a);
-      SA_TRY(gemm(p, st));
+      SA_TRY(codec_gemm(p, st));
     }
     {
       const long T = sb[4].T;
       const int C = sb[4].C;
       GemmParams p = conv_same(sb[4].act, T, C, 3, 1, enc_.out_w, 3 * C, CL, n);
       p.bias = enc_.out_b;
-      halo_out(p, nullptr, eout, T, CL, ACT_NONE, nullptr);
-      SA_TRY(gemm(p, st));
-      p = conv_same(eout, T, CL, 1, 1, enc_.proj_w, CL, CD, n);  // quantizer.in_proj, mean half only
+      halo_out(p, nullptr, cb.eout, T, CL, ACT_NONE, nullptr);
+      SA_TRY(codec_gemm(p, st));
+      p = conv_same(cb.eout, T, CL, 1, 1, enc_.proj_w, CL, CD, n);  // quantizer.in_proj, mean half only
       p.bias = enc_.proj_b;
       p.out_f32 = latent + (long)i0 * T * CD; p.f32_bstride = T * CD; p.f32_ld = CD; p.f32_off = 0;
-      SA_TRY(gemm(p, st));
+      SA_TRY(codec_gemm(p, st));
     }
   }
   return Status{};
@@ -1637,37 +1643,19 @@ Status Engine::codec_decode(const float* latent, int items, int T0, float* wav, 
   if (!codec_ready_) return fail(SAMAUDIO_ERR_STATE, "codec_decode: codec weights not finalized");
   if (!latent || !wav || items <= 0 || T0 <= 0) return fail(SAMAUDIO_ERR_ARG, "codec_decode: bad argument");
   if (pairs && items % 2) return fail(SAMAUDIO_ERR_ARG, "codec_decode: the state layout holds (target, residual) pairs");
-  long hop = 1;
-  for (int i = 0; i < 4; ++i) hop *= cfg_.enc_rates[i];
-  const int64_t S = (int64_t)T0 * hop;
-  // codec_bytes(n) = n * per_item + a fixed 64 KiB: dividing the workspace by codec_bytes(1) would turn a workspace sized
-  // for exactly n waveforms into passes of n - 1 and 1 (and the stray single-waveform pass runs at a fraction of the rate)
-  const size_t fixed = (size_t)1 << 16;
-  const size_t per_item = codec_bytes(1, S) - fixed;
-  int chunk = ws_bytes_ > fixed ? (int)((ws_bytes_ - fixed) / (per_item ? per_item : 1)) : 0;
-  if (!ws_ || chunk < 1) return fail(SAMAUDIO_ERR_WORKSPACE, "codec_decode: workspace too small");
-  if (chunk > items) chunk = items;
-  if (pairs && chunk > 1) chunk &= ~1;   // a pass holds whole pairs
-  if (pairs && chunk < 2) return fail(SAMAUDIO_ERR_WORKSPACE, "codec_decode: workspace too small for one (target, residual) pair");
+  const int64_t S = (int64_t)T0 * codec_hop(cfg_);
+  const int chunk = codec_chunk(items, S, pairs);
+  if (chunk < 1)
+    return fail(SAMAUDIO_ERR_WORKSPACE, pairs ? "codec_decode: workspace too small for one (target, residual) pair" : "codec_decode: workspace too small");
   prepared_ = false;
-  prof_cls_ = "codec";
-  long encT[5], decT[5];
-  int encC[5], decC[5];
-  codec_stage_dims(cfg_, S, encT, encC, decT, decC);
+  phase_ = Phase::Codec;
   const int CL = cfg_.codec_latent, CD = cfg_.codec_dim;
   for (int i0 = 0; i0 < items; i0 += chunk) {
     const int n = items - i0 < chunk ? items - i0 : chunk;
-    Bump b(ws_, ws_bytes_);
-    void* lat = b.take((size_t)n * (T0 + 2 * HALO) * CD * esz_);
-    void* p0 = b.take((size_t)n * (T0 + 2 * HALO) * CL * esz_);
-    SBuf sb[5];
-    for (int i = 0; i < 5; ++i) {
-      const size_t e = (size_t)n * (decT[i] + 2 * HALO) * decC[i];
-      sb[i] = SBuf{(float*)b.take(e * 4), b.take(e * esz_), b.take(e * esz_), decT[i], decC[i]};
-    }
-    x3_codec_scratch_bytes_ = (size_t)n * codec_x3_per_item(S);
-    x3_codec_scratch_ = x3_codec_scratch_bytes_ ? b.take(x3_codec_scratch_bytes_) : nullptr;
-    if (!b.fits()) return fail(SAMAUDIO_ERR_WORKSPACE, "codec_decode: workspace too small");
+    CodecBufs cb;
+    SA_TRY(codec_carve(true, n, S, cb));
+    SBuf* const sb = cb.sb;
+    void *const lat = cb.lat, *const p0 = cb.p0;
     SA_HIP(launch_zero_halo(lat, bf16_, n, T0, CD, HALO, st));
     SA_HIP(launch_zero_halo(p0, bf16_, n, T0, CL, HALO, st));
     for (int i = 0; i < 5; ++i) {
@@ -1685,11 +1673,11 @@ Status Engine::codec_decode(const float* latent, int items, int T0, float* wav, 
       GemmParams p = conv_same(lat, T0, CD, 1, 1, dec_.proj_w, CD, CL, n);  // quantizer.out_proj
       p.bias = dec_.proj_b;
       halo_out(p, nullptr, p0, T0, CL, ACT_NONE, nullptr);
-      SA_TRY(gemm(p, st));
-      p = conv_same(p0, T0, CL, 7, 1, dec_.in_w, 7 * CL, decC[0], n);
+      SA_TRY(codec_gemm(p, st));
+      p = conv_same(p0, T0, CL, 7, 1, dec_.in_w, 7 * CL, sb[0].C, n);
       p.bias = dec_.in_b;
-      halo_out(p, nullptr, sb[0].act, T0, decC[0], ACT_SNAKE, dec_.s[0].a);
-      SA_TRY(gemm(p, st));
+      halo_out(p, nullptr, sb[0].act, T0, sb[0].C, ACT_SNAKE, dec_.s[0].a);
+      SA_TRY(codec_gemm(p, st));
     }
     for (int i = 0; i < 4; ++i) {
       const StageW& sw = dec_.s[i];
@@ -1704,21 +1692,9 @@ Status Engine::codec_decode(const float* latent, int items, int T0, float* wav, 
         p.f32_ld = p.act_ld = (long)s * C;
         p.f32_off = p.act_off = (long)(HALO - pad) * C;
         p.c_ld_rel = (long)s * C; p.c_lo = (long)pad * C; p.c_hi = (Tout + pad) * (long)C;
-        SA_TRY(gemm(p, st, 2.0 * Tout * C * 2 * Cin * n));
+        SA_TRY(codec_gemm(p, st, 2.0 * Tout * C * 2 * Cin * n));
       }
-      const int dil[3] = {1, 3, 9};
-      for (int j = 0; j < 3; ++j) {
-        const ResUnitW& r = sw.r[j];
-        GemmParams p = conv_same(sb[i + 1].act, Tout, C, 7, dil[j], r.w1, r.k1pad, C, n);
-        p.bias = r.b1;
-        halo_out(p, nullptr, sb[i + 1].tmp, Tout, C, ACT_SNAKE, r.a2);
-        GemmParams q = conv_same(sb[i + 1].tmp, Tout, C, 1, 1, r.w2, r.k2pad, C, n);
-        q.bias = r.b2;
-        q.res = sb[i + 1].raw; q.res_bstride = (Tout + 2L * HALO) * C; q.res_ld = C; q.res_off = (long)HALO * C;
-        const float* next_alpha = j < 2 ? sw.r[j + 1].a1 : (i < 3 ? dec_.s[i + 1].a : dec_.out_a);
-        halo_out(q, sb[i + 1].raw, sb[i + 1].act, Tout, C, ACT_SNAKE, next_alpha);
-        SA_TRY(res_unit(p, q, sb[i + 1].act, sb[i + 1].tmp, 2.0 * Tout * C * 7 * C * n, 2.0 * Tout * C * C * n, st));
-      }
+      SA_TRY(res_units(sw, sb[i + 1], n, i < 3 ? dec_.s[i + 1].a : dec_.out_a, st));
     }
     {  // conv k7 (C -> 1) + tanh
       const long T = sb[4].T;
@@ -1727,7 +1703,7 @@ Status Engine::codec_decode(const float* latent, int items, int T0, float* wav, 
       p.bias = dec_.out_b;
       p.act = ACT_TANH; p.f32_act = 1;
       p.out_f32 = wav + (long)i0 * T; p.f32_bstride = T; p.f32_ld = 1; p.f32_off = 0;
-      SA_TRY(gemm(p, st, 2.0 * T * 7 * C * n));
+      SA_TRY(codec_gemm(p, st, 2.0 * T * 7 * C * n));
     }
   }
   return Status{};
