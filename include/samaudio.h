@@ -178,6 +178,9 @@ int samaudio_set_workspace(samaudio_ctx* ctx, void* workspace, size_t bytes);
 #define SAMAUDIO_CLS_X3_CAPABLE \
   (SAMAUDIO_CLS_QKV | SAMAUDIO_CLS_WO | SAMAUDIO_CLS_CWQ | SAMAUDIO_CLS_CWO | SAMAUDIO_CLS_W13 | SAMAUDIO_CLS_W2 | SAMAUDIO_CLS_PATCH | \
    SAMAUDIO_CLS_CKV | SAMAUDIO_CLS_CODEC | SAMAUDIO_X3_ATTENTION)
+/* the bits samaudio_judge_set_option / samaudio_frame_set_option accept (the PE-AV towers, see there) */
+#define SAMAUDIO_CLS_X3_TOWER \
+  (SAMAUDIO_CLS_QKV | SAMAUDIO_CLS_WO | SAMAUDIO_CLS_W13 | SAMAUDIO_CLS_W2 | SAMAUDIO_CLS_PATCH | SAMAUDIO_X3_ATTENTION)
 #define SAMAUDIO_CLS_F32_CAPABLE (SAMAUDIO_CLS_TIME | SAMAUDIO_CLS_OUT | SAMAUDIO_CLS_IN | SAMAUDIO_CLS_PREP | SAMAUDIO_CLS_YEMB)
 int samaudio_set_option(samaudio_ctx* ctx, int option, int value);
 
@@ -265,6 +268,20 @@ void samaudio_judge_destroy(samaudio_judge* j);
 /* engine names: sam_audio_amd/judge.py documents the mapping from the reference state_dict keys */
 int samaudio_judge_set_tensor(samaudio_judge* j, const char* name, const void* data, int dtype, int ndim,
                               const int64_t* shape);
+/* SAMAUDIO_OPT_X3_CLASSES for the PE-AV towers (fp32 contexts only; set it BEFORE samaudio_judge_finalize, which resolves the twins;
+ * query the workspace after it): value = mask of SAMAUDIO_CLS_X3_TOWER bits, 0 (default) = the exact-fp32 launches.  Per transformer:
+ *   QKV / WO / W13 / W2   the four GEMMs of every layer as 16-bit launches over K' = 3K on "<prefix>L<i>.<name>.x3"
+ *                         ([N, 3K] = [W_hi | W_lo | W_hi], or K-tile-major [3K/64, N, 64]); QKV / W13 also need the norm in front
+ *                         as a constant table "<prefix>L<i>.attn_norm.gs" / ".ffn_norm.gs" [2, dim] f32 = [gain | zeros];
+ *                         WO also switches the output projection ("<prefix>out.w.x3", "<prefix>norm.gs") and, in a Judge, both halves of
+ *                         cat_audio_proj ("cat.wh.x3", "cat.wi.x3": K = dim over every frame)
+ *   PATCH                 the two k3 convolutions of the ResNet block on "<prefix>conv<n>.w.x3" [dim, 3 taps x 3 dim] (each tap's
+ *                         columns split on their own, like patch1.w.x3)
+ *   SAMAUDIO_X3_ATTENTION the self-attention's two contractions on split operands
+ * The input projections, the Judge's text branch and proj_audio_and_text, the span predictor's heads (K <= 256, or one row per
+ * pair) stay exact fp32.  Any other bit, or a 16-bit context: SAMAUDIO_ERR_ARG.  A twin that is missing: SAMAUDIO_ERR_WEIGHT from
+ * finalize, naming it. */
+int samaudio_judge_set_option(samaudio_judge* j, int option, int value);
 int samaudio_judge_finalize(samaudio_judge* j);
 size_t samaudio_judge_workspace_bytes(samaudio_judge* j, int inputs, int candidates, int frames);
 int samaudio_judge_set_workspace(samaudio_judge* j, void* workspace, size_t bytes);
@@ -298,6 +315,7 @@ int samaudio_frame_create(const samaudio_frame_config* cfg, samaudio_frame** out
 void samaudio_frame_destroy(samaudio_frame* f);
 int samaudio_frame_set_tensor(samaudio_frame* f, const char* name, const void* data, int dtype, int ndim,
                               const int64_t* shape);
+int samaudio_frame_set_option(samaudio_frame* f, int option, int value);   /* as samaudio_judge_set_option (prefix "a.") */
 int samaudio_frame_finalize(samaudio_frame* f);
 size_t samaudio_frame_workspace_bytes(samaudio_frame* f, int rows, int frames);
 int samaudio_frame_set_workspace(samaudio_frame* f, void* workspace, size_t bytes);
@@ -476,6 +494,11 @@ int samaudio_op_layernorm_accum(const float* x, const float* w, const float* b, 
 int samaudio_op_masked_groupnorm_silu(const float* x, const float* w, const float* b, const uint8_t* mask,
                                       void* partials_f64, void* out, int precision, int batch, int frames,
                                       int channels, int halo, float eps, samaudio_stream stream);
+/* the same with the output as a compensated GEMM operand (SAMAUDIO_OPT_X3_CLASSES): out3 [batch][halo + frames + halo][3 channels] in
+ * the library's 16-bit format, a valid frame = [lo | hi | hi] of the fp32 kernel's value, a masked frame zeros, halo rows untouched */
+int samaudio_op_masked_groupnorm_silu_split3(const float* x, const float* w, const float* b, const uint8_t* mask,
+                                             void* partials_f64, void* out3, int batch, int frames, int channels, int halo,
+                                             float eps, samaudio_stream stream);
 int samaudio_op_layernorm_rows(const float* x, int64_t x_ld, const float* w, const float* b, float* out_f32,
                                void* out_act, int precision, int64_t rows, int dim, float eps, samaudio_stream stream);
 /* SAMAUDIO_OPT_X3_CLASSES: the activation operand of a compensated GEMM - x [rows, k] f32 (row stride x_ld) -> out [rows, 3k]

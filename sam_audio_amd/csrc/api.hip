@@ -276,6 +276,17 @@ int samaudio_op_masked_groupnorm_silu(const float* x, const float* w, const floa
                  "masked_groupnorm_silu");
 }
 
+int samaudio_op_masked_groupnorm_silu_split3(const float* x, const float* w, const float* b, const uint8_t* mask,
+                                             void* partials_f64, void* out3, int batch, int frames, int channels, int halo,
+                                             float eps, samaudio_stream stream) {
+  if (channels % 4 || !mask || !x || !w || !b || !out3 || !partials_f64 || batch <= 0 || frames <= 0 || halo < 0)
+    return bad("masked_groupnorm_split3: channels % 4 / null argument");
+  if (!sa::launch_masked_groupnorm_silu_split3) return bad("masked_groupnorm_split3: not in this build of the library");
+  return hip_ret(sa::launch_masked_groupnorm_silu_split3(x, w, b, mask, (double*)partials_f64, out3, batch, frames, channels, halo,
+                                                         eps, (hipStream_t)stream),
+                 "masked_groupnorm_silu_split3");
+}
+
 int samaudio_op_layernorm_rows(const float* x, int64_t x_ld, const float* w, const float* b, float* out_f32,
                                void* out_act, int precision, int64_t rows, int dim, float eps, samaudio_stream stream) {
   if (dim % 4 || x_ld % 4) return bad("layernorm_rows: dim % 4");
@@ -417,6 +428,11 @@ int samaudio_judge_set_tensor(samaudio_judge* j, const char* name, const void* d
   return ret(j->judge->set_tensor(name, data, dtype, ndim, shape));
 }
 
+int samaudio_judge_set_option(samaudio_judge* j, int option, int value) {
+  if (!j) return bad("null judge");
+  return ret(j->judge->set_option(option, value));
+}
+
 int samaudio_judge_finalize(samaudio_judge* j) {
   if (!j) return bad("null judge");
   return ret(j->judge->finalize());
@@ -466,6 +482,11 @@ int samaudio_frame_set_tensor(samaudio_frame* f, const char* name, const void* d
                               const int64_t* shape) {
   if (!f) return bad("null frame predictor");
   return ret(f->frame->set_tensor(name, data, dtype, ndim, shape));
+}
+
+int samaudio_frame_set_option(samaudio_frame* f, int option, int value) {
+  if (!f) return bad("null frame predictor");
+  return ret(f->frame->set_option(option, value));
 }
 
 int samaudio_frame_finalize(samaudio_frame* f) {

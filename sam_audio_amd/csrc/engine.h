@@ -23,6 +23,35 @@ struct Status {
 
 void set_last_error(const std::string& msg);  // api.hip: the thread-local string behind samaudio_last_error()
 
+// SAMAUDIO_OPT_X3_CLASSES, shared by the DiT engine and the PE-AV towers (peav.hip).
+// The 16-bit launch over K' = 3K that an x3 class makes of its fp32 GemmParams: A = the split operand [lo | hi | hi] (row stride 3K),
+// W = the split weight [W_hi | W_lo | W_hi] (K-tile-major when `ktm`)
+inline void x3_operands(GemmParams& p, const void* a3, const void* w3, bool ktm) {
+  const int K = p.K;
+  p.A = a3; p.lda = 3L * K; p.K = 3 * K; p.kc = 3 * K; p.W = w3;
+  if (p.out_act) {   // an fp32 context's "activation" outputs are fp32 tensors: the 16-bit kernel writes them as its fp32 output
+    p.out_f32 = (float*)p.out_act; p.f32_ld = p.act_ld; p.f32_bstride = p.act_bstride; p.f32_off = p.act_off;
+    p.f32_act = p.act != ACT_NONE;
+    p.out_act = nullptr; p.act_ld = p.act_bstride = p.act_off = 0;
+  }
+  if (ktm) p.flags |= GEMM_FLAG_W_KTM;
+  if ((p.flags & GEMM_FLAG_OUT_SPLIT3) && p.out_f32) {   // the result leaves as the next GEMM's split operand (16-bit, 3 x n_out per row)
+    p.out_act = p.out_f32; p.act_ld = 3L * (p.swiglu ? p.N / 2 : p.N); p.act_bstride = p.act_off = 0;
+    p.out_f32 = nullptr; p.f32_ld = p.f32_bstride = p.f32_off = 0; p.f32_act = 0;
+  }
+}
+// An x3 launch on K-concatenated split operands: let the 8-phase kernels share the operand tiles the three products have in common
+// (common.h GEMM_FLAG_X3_SHARE) wherever the launch qualifies; DBG_X3_PLAIN_WALK = 1: the plain walk over K' (A/B, tests), >= 2: a class
+// mask << 1 that keeps the sharing order for those classes only (diagnosis).  Launches with K' split per input block (the
+// convolutions) never come here.
+inline GemmParams x3_share(const GemmParams& p, int cls) {
+  const int plain_walk = debug_flag(DBG_X3_PLAIN_WALK);
+  if (plain_walk == 1 || (plain_walk >= 2 && !(cls & (plain_walk >> 1)))) return p;
+  GemmParams q = p;
+  q.flags |= GEMM_FLAG_X3_SHARE;
+  return q.kc == q.K && q.K % 192 == 0 && !gemm_check(q, true) ? q : p;
+}
+
 constexpr int HALO = 40;  // zero rows either side of codec activations (>= 4 * max dilation 9)
 
 class Bump {  // workspace carving (also used dry to size the workspace)
@@ -121,7 +150,6 @@ class Engine {
   // on; `w3` = its "<name>.x3" weight.  Splits A into the scratch operand [lo | hi | hi] and runs ONE 16-bit GEMM over K' = 3K.
   // `presplit`: A already split; otherwise gemm_x3 splits it into x3a, or into x3u when `ffn_wide` (w2's F-wide operand)
   Status gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, int cls, const void* presplit = nullptr, bool ffn_wide = false);
-  static void x3_operands(GemmParams& p, const void* a3, const void* w3, bool ktm);
   // the launch gemm_x3 would make of `p` with GEMM_FLAG_OUT_SPLIT3 passes gemm_check (the 8-phase family takes it)
   bool x3_split3_out_ok(GemmParams p, const void* w3, bool ktm, void* out3) const;
   bool x3(int cls) const { return !bf16_ && (x3_classes_ & cls) != 0; }

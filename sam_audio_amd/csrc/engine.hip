@@ -677,15 +677,9 @@ GemmParams Engine::launch_params(const GemmParams& p_in, int cls, GemmKind kind)
   // the classes with operands in the alt format (SAMAUDIO_OPT_ALT16_CLASSES, mixed mode)
   p.flags = (p_in.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split_ ? 0 : GEMM_FLAG_NO_TAIL_SPLIT) |
             (alt16(cls) && kind != GemmKind::F32 ? GEMM_FLAG_OPND_ALT : 0);
-  // an x3 launch on K-concatenated split operands: let the 8-phase kernels share the operand tiles the three products have in common
-  // (common.h GEMM_FLAG_X3_SHARE) wherever the launch qualifies; DBG_X3_PLAIN_WALK = 1: the plain walk over K' (A/B, tests)
-  // X3Block (the convolutions: every Cin-block of K' is its own [hi | lo | hi]) never qualifies
-  const int plain_walk = debug_flag(DBG_X3_PLAIN_WALK);   // (>= 2: class mask << 1, diagnosis)
-  if (kind == GemmKind::X3 && plain_walk != 1 && (plain_walk < 2 || (cls & (plain_walk >> 1)))) {
-    GemmParams q = p;
-    q.flags |= GEMM_FLAG_X3_SHARE;
-    if (q.kc == q.K && q.K % 192 == 0 && !gemm_check(q, true)) p = q;
-  }
+  // an x3 launch on K-concatenated split operands shares operand tiles wherever it qualifies (engine.h x3_share); X3Block (the
+  // convolutions: every Cin-block of K' is its own [hi | lo | hi]) never does
+  if (kind == GemmKind::X3) p = x3_share(p, cls);
   return p;
 }
 
@@ -796,22 +790,6 @@ Status Engine::gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, i
   }
   x3_operands(p, presplit, w3, ktm);
   return gemm(p, st, 2.0 * p.M * (double)p.N * K, cls, GemmKind::X3);   // flops as the reference counts them: one product over K
-}
-
-// the 16-bit launch over K' = 3K that an x3 class makes of its fp32 GemmParams: A = the split operand, W = the split weight
-void Engine::x3_operands(GemmParams& p, const void* a3, const void* w3, bool ktm) {
-  const int K = p.K;
-  p.A = a3; p.lda = 3L * K; p.K = 3 * K; p.kc = 3 * K; p.W = w3;
-  if (p.out_act) {   // an fp32 context's "activation" outputs are fp32 tensors: the 16-bit kernel writes them as its fp32 output
-    p.out_f32 = (float*)p.out_act; p.f32_ld = p.act_ld; p.f32_bstride = p.act_bstride; p.f32_off = p.act_off;
-    p.f32_act = p.act != ACT_NONE;
-    p.out_act = nullptr; p.act_ld = p.act_bstride = p.act_off = 0;
-  }
-  if (ktm) p.flags |= GEMM_FLAG_W_KTM;
-  if ((p.flags & GEMM_FLAG_OUT_SPLIT3) && p.out_f32) {   // the result leaves as the next GEMM's split operand (16-bit, 3 x n_out per row)
-    p.out_act = p.out_f32; p.act_ld = 3L * (p.swiglu ? p.N / 2 : p.N); p.act_bstride = p.act_off = 0;
-    p.out_f32 = nullptr; p.f32_ld = p.f32_bstride = p.f32_off = 0; p.f32_act = 0;
-  }
 }
 
 bool Engine::x3_split3_out_ok(GemmParams p, const void* w3, bool ktm, void* out3) const {

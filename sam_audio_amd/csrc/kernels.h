@@ -310,6 +310,12 @@ hipError_t launch_repeat_items_f32(const float* src, float* dst, int items, int 
 hipError_t launch_masked_groupnorm_silu(const float* x, const float* w, const float* b, const unsigned char* mask,
                                         double* partials, void* out, bool bf16, int B, int S, int C, int halo,
                                         float eps, hipStream_t st);
+// the same with the result as a compensated GEMM operand (SAMAUDIO_OPT_X3_CLASSES): out3 [B][S + 2 halo][3C] 16-bit, valid frames
+// [lo | hi | hi] of the fp32 kernel's value, masked frames zeros, halo rows untouched.  weak: the CPU emulation of the launchers
+// (oracle/emu) does not define it - the x3 towers then write the fp32 buffer and split it with launch_split3 (peav.hip)
+__attribute__((weak)) hipError_t launch_masked_groupnorm_silu_split3(const float* x, const float* w, const float* b,
+                                                                     const unsigned char* mask, double* partials, void* out3, int B,
+                                                                     int S, int C, int halo, float eps, hipStream_t st);
 // out[m,:] = LayerNorm(x[m,:]) * w + b; either output may be null
 hipError_t launch_layernorm_rows(const float* x, long x_ld, const float* w, const float* b, float* out_f32,
                                  void* out_act, bool bf16, long M, int D, float eps, hipStream_t st);

@@ -16,6 +16,9 @@ class Registry {  // name -> borrowed weight tensor
   Status set(const char* name, const void* p, int dtype, int ndim, const int64_t* shape);
   Status need(const std::string& name, int dtype, std::vector<int64_t> shape, const void** out) const;
   bool has(const std::string& name) const { return tensors_.count(name) != 0; }
+  // SAMAUDIO_OPT_X3_CLASSES: the 16-bit split twin "<name>" of a weight, [N, K3] row-major or K-tile-major [K3 / 64, N, 64] (*ktm set);
+  // SAMAUDIO_ERR_WEIGHT names a twin that is not registered in either shape
+  Status need_twin(const std::string& name, int64_t N, int64_t K3, const void** out, bool* ktm) const;
 
  private:
   std::map<std::string, TensorRef> tensors_;
@@ -26,14 +29,23 @@ class Registry {  // name -> borrowed weight tensor
 class PeavEncoder {
  public:
   PeavEncoder(const samaudio_peav_dims& d, bool bf16, std::string prefix);
+  // SAMAUDIO_OPT_X3_CLASSES of an fp32 context (mask of SAMAUDIO_CLS_X3_TOWER bits; before finalize): the switched classes multiply
+  // compensated 16-bit operands - QKV / WO / W13 / W2 the four GEMMs of every layer, WO also the output projection out.w, PATCH the two
+  // k3 convolutions of the ResNet block (per-tap split, plain walk), SAMAUDIO_X3_ATTENTION the self-attention.  0 = the fp32 path.
+  void set_x3(int mask) { x3_ = bf16_ ? 0 : mask; ready_ = false; }
+  bool x3(int cls) const { return (x3_ & cls) != 0; }
   Status finalize(const Registry& reg);
   void plan(Bump& b, int rows, int frames, bool assign);
   // x_act [rows, frames, in_dim] GEMM-operand dtype; pad_mask [rows, frames] u8 (1 = valid) or null.
   Status forward(const void* x_act, const unsigned char* pad_mask, int rows, int frames, hipStream_t st);
   // results of the last forward: [rows][frames + 1][dim], row 0 of each item = class token (pooler_output)
   const float* out_f32() const { return w_.out; }
-  const void* out_act() const { return w_.out_act; }
+  const void* out_act() const { return x3(SAMAUDIO_CLS_WO) ? (const void*)w_.out : w_.out_act; }   // (x3 out.w: one fp32 output)
   const unsigned char* seq_mask() const { return w_.mask_s; }  // [rows][frames + 1]
+  // x3 contexts: the D-wide split scratch [rows * (frames + 1), 3 dim] 16-bit - free between two forwards (the Judge splits the
+  // hidden states into it for cat_audio_proj)
+  void* x3_scratch() const { return w_.x3a; }
+  size_t x3_scratch_bytes() const { return w_.x3a_bytes; }
   int dim() const { return d_.dim; }
   int in_dim() const { return d_.in_dim; }
 
@@ -43,20 +55,35 @@ class PeavEncoder {
   size_t esz_;
   std::string prefix_;
   bool ready_ = false;
+  int x3_ = 0;
+  // one launch of an x3 class: `p` = the fp32 launch; A is `presplit` (already [lo | hi | hi], 3K per row) or split here into `scratch`
+  Status gemm_x3(GemmParams p, const void* w3, bool ktm, int cls, const void* presplit, void* scratch, size_t scratch_bytes,
+                 hipStream_t st) const;
   struct LayerW {
     const float *attn_norm, *ffn_norm, *q_norm, *k_norm, *bqkv, *bo;
     const void *wqkv, *wo, *w13, *w2;
+    // x3: "<name>.x3" twins and the constant [gain | shift 0] tables "<norm>.gs" [2, D] of launch_rmsnorm_gs_split3
+    const void *wqkv3, *wo3, *w13_3, *w2_3;
+    bool ktm_qkv, ktm_wo, ktm_w13, ktm_w2;
+    const float *attn_gs, *ffn_gs;
   };
   std::vector<LayerW> layers_;
   struct {
     const void *in_w, *conv1_w, *conv2_w, *out_w;
     const float *in_b, *cls, *gn1_w, *gn1_b, *gn2_w, *gn2_b, *conv1_b, *conv2_b, *norm, *rope_cos, *rope_sin;
+    const void *conv1_w3, *conv2_w3, *out_w3;   // x3 twins: the convolutions per tap [D, 3 taps x 3D], out.w [D, 3D]
+    bool ktm_conv1, ktm_conv2, ktm_out;
+    const float* norm_gs;
   } g_{};
   struct {
     float *h0, *r1, *h, *out;
     void *out_act, *xn, *qkv, *Q, *K, *Vt, *attn, *u, *gnbuf;
     unsigned char* mask_s;
     double* gn_part;
+    // x3 split scratch (16-bit; null / 0 unless a class that needs it is on): D-wide rows, the SwiGLU hidden, the 3x-wide halo buffer
+    // of the convolutions, the attention's split output
+    void *x3a, *x3u, *gn3, *attn3;
+    size_t x3a_bytes, x3u_bytes, gn3_bytes, attn3_bytes;
   } w_{};
 };
 
@@ -65,6 +92,7 @@ class Judge {
   explicit Judge(const samaudio_judge_config& c);
   Status set_tensor(const char* name, const void* p, int dtype, int ndim, const int64_t* shape);
   Status finalize();
+  Status set_option(int option, int value);   // SAMAUDIO_OPT_X3_CLASSES (fp32 contexts, before finalize)
   size_t workspace_bytes(int inputs, int candidates, int frames);
   Status set_workspace(void* p, size_t bytes);
   // reference judge.py:90-132 with the mixture branch evaluated once per clip instead of once per candidate
@@ -86,11 +114,14 @@ class Judge {
   int at_dtype_;
   Registry reg_;
   PeavEncoder enc_, fin_;
+  int x3_ = 0;
   bool ready_ = false;
   char* ws_ = nullptr;
   size_t ws_bytes_ = 0;
   struct {
     const void *cat_wh, *cat_wi, *tp1_w, *tp2_w, *pat_wa, *pat_wt;
+    const void *cat_wh3, *cat_wi3;   // x3 (class WO): "cat.wh.x3" / "cat.wi.x3" [Bn, 3D]
+    bool ktm_wh, ktm_wi;
     const float *cat_b, *tp2_b, *ln_w, *ln_b, *pat_b, *head_w, *mean, *std_;
   } g_{};
   struct {
@@ -105,6 +136,7 @@ class FramePredictor {  // PE-A-Frame span predictor: per-frame audio-text logit
   explicit FramePredictor(const samaudio_frame_config& c);
   Status set_tensor(const char* name, const void* p, int dtype, int ndim, const int64_t* shape);
   Status finalize();
+  Status set_option(int option, int value);   // SAMAUDIO_OPT_X3_CLASSES (fp32 contexts, before finalize)
   size_t workspace_bytes(int rows, int frames);
   Status set_workspace(void* p, size_t bytes);
   // codec_features [rows, frames, codec_dim] f32, text_pooled [rows, embed_dim] f32, pad_mask [rows, frames] u8 or
@@ -120,6 +152,7 @@ class FramePredictor {  // PE-A-Frame span predictor: per-frame audio-text logit
   int at_dtype_;
   Registry reg_;
   PeavEncoder enc_;
+  int x3_ = 0;
   bool ready_ = false;
   char* ws_ = nullptr;
   size_t ws_bytes_ = 0;

@@ -75,6 +75,18 @@ Status Registry::need(const std::string& name, int dtype, std::vector<int64_t> s
   return Status{};
 }
 
+Status Registry::need_twin(const std::string& name, int64_t N, int64_t K3, const void** out, bool* ktm) const {
+  auto it = tensors_.find(name);
+  if (it != tensors_.end() && it->second.dtype == SAMAUDIO_DT_BF16) {
+    const TensorRef& t = it->second;
+    if (t.shape == std::vector<int64_t>{K3 / 64, N, 64} && K3 % 64 == 0) { *out = t.p; *ktm = true; return Status{}; }
+    if (t.shape == std::vector<int64_t>{N, K3}) { *out = t.p; *ktm = false; return Status{}; }
+  }
+  return fail(SAMAUDIO_ERR_WEIGHT, "SAMAUDIO_OPT_X3_CLASSES: the split weight '" + name + "' (16-bit, [" + std::to_string(N) + ", " +
+                                       std::to_string(K3) + "] or [" + std::to_string(K3 / 64) + ", " + std::to_string(N) +
+                                       ", 64]) of a class that is switched on is not registered");
+}
+
 // ---------------------------------------------------------------------------------------------------
 // PE-AV transformer
 // ---------------------------------------------------------------------------------------------------
@@ -120,9 +132,29 @@ Status PeavEncoder::finalize(const Registry& reg) {
       NEEDF(w.bqkv, L + "bqkv", 3 * D);
       NEEDF(w.bo, L + "bo", D);
     }
+    // SAMAUDIO_OPT_X3_CLASSES: the twins of the classes that are switched on, and the [gain | 0] tables of the norms in front of them
+    if (x3(SAMAUDIO_CLS_QKV)) {
+      SA_TRY(reg.need_twin(L + "wqkv.x3", 3 * D, 3L * D, &w.wqkv3, &w.ktm_qkv));
+      NEEDF(w.attn_gs, L + "attn_norm.gs", 2, D);
+    }
+    if (x3(SAMAUDIO_CLS_WO)) SA_TRY(reg.need_twin(L + "wo.x3", D, 3L * D, &w.wo3, &w.ktm_wo));
+    if (x3(SAMAUDIO_CLS_W13)) {
+      SA_TRY(reg.need_twin(L + "w13.x3", 2 * F, 3L * D, &w.w13_3, &w.ktm_w13));
+      NEEDF(w.ffn_gs, L + "ffn_norm.gs", 2, D);
+    }
+    if (x3(SAMAUDIO_CLS_W2)) SA_TRY(reg.need_twin(L + "w2.x3", D, 3L * F, &w.w2_3, &w.ktm_w2));
+  }
+  if (x3(SAMAUDIO_CLS_PATCH)) {
+    SA_TRY(reg.need_twin(P + "conv1.w.x3", D, 9L * D, &g_.conv1_w3, &g_.ktm_conv1));
+    SA_TRY(reg.need_twin(P + "conv2.w.x3", D, 9L * D, &g_.conv2_w3, &g_.ktm_conv2));
+  }
+  if (x3(SAMAUDIO_CLS_WO)) {
+    SA_TRY(reg.need_twin(P + "out.w.x3", D, 3L * D, &g_.out_w3, &g_.ktm_out));
+    NEEDF(g_.norm_gs, P + "norm.gs", 2, D);
   }
 #undef NEEDF
 #undef NEEDW
+  if (x3_ && D > 256 * 12) return fail(SAMAUDIO_ERR_ARG, P + ": SAMAUDIO_OPT_X3_CLASSES needs dim <= 3072 (launch_rmsnorm_gs_split3)");
   ready_ = true;
   return Status{};
 }
@@ -139,10 +171,37 @@ void PeavEncoder::plan(Bump& b, int rows, int frames, bool assign) {
   void* attn = act(M * D); void* u = act(M * F); void* gnbuf = act((long)rows * (S + 2) * D);
   unsigned char* mask_s = (unsigned char*)b.take((size_t)M);
   double* gn_part = (double*)b.take((size_t)rows * 64 * 3 * 8);
+  // SAMAUDIO_OPT_X3_CLASSES: the split operands, 3 x 16 bits per element, only those a switched class reads
+  const bool gemms = x3(SAMAUDIO_CLS_QKV | SAMAUDIO_CLS_WO | SAMAUDIO_CLS_W13 | SAMAUDIO_CLS_W2);
+  const size_t x3a_bytes = gemms ? (size_t)M * 3 * D * 2 : 0, x3u_bytes = x3(SAMAUDIO_CLS_W2) ? (size_t)M * 3 * F * 2 : 0;
+  const size_t gn3_bytes = x3(SAMAUDIO_CLS_PATCH) ? (size_t)rows * (S + 2) * 3 * D * 2 : 0;
+  const size_t attn3_bytes = x3(SAMAUDIO_CLS_WO) && x3(SAMAUDIO_X3_ATTENTION) ? (size_t)M * 3 * D * 2 : 0;
+  void* x3a = x3a_bytes ? b.take(x3a_bytes) : nullptr; void* x3u = x3u_bytes ? b.take(x3u_bytes) : nullptr;
+  void* gn3 = gn3_bytes ? b.take(gn3_bytes) : nullptr; void* attn3 = attn3_bytes ? b.take(attn3_bytes) : nullptr;
   if (assign) {
+    w_.x3a = x3a; w_.x3u = x3u; w_.gn3 = gn3; w_.attn3 = attn3;
+    w_.x3a_bytes = x3a_bytes; w_.x3u_bytes = x3u_bytes; w_.gn3_bytes = gn3_bytes; w_.attn3_bytes = attn3_bytes;
     w_.h0 = h0; w_.r1 = r1; w_.h = h; w_.out = out; w_.out_act = out_act; w_.xn = xn; w_.qkv = qkv; w_.Q = Q; w_.K = K;
     w_.Vt = Vt; w_.attn = attn; w_.u = u; w_.gnbuf = gnbuf; w_.mask_s = mask_s; w_.gn_part = gn_part;
   }
+}
+
+Status PeavEncoder::gemm_x3(GemmParams p, const void* w3, bool ktm, int cls, const void* presplit, void* scratch, size_t scratch_bytes,
+                            hipStream_t st) const {
+  if (!w3) return fail(SAMAUDIO_ERR_STATE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: split weight missing (set the option before finalize)");
+  if (p.kc != p.K || p.tap_stride || (p.out_act && p.out_f32))
+    return fail(SAMAUDIO_ERR_ARG, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: plain launches with one output only");
+  const int K = p.K;
+  if (!presplit) {   // split the fp32 rows here (an operand no kernel wrote in split form)
+    if (p.nbatch != 1 || p.a_off) return fail(SAMAUDIO_ERR_ARG, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: a batched operand must arrive split");
+    if (!scratch || (size_t)p.M * 3 * K * 2 > scratch_bytes)
+      return fail(SAMAUDIO_ERR_WORKSPACE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: the split operand does not fit the scratch the workspace plan holds");
+    SA_HIP(launch_split3((const float*)p.A, p.lda, scratch, p.M, K, st));
+    presplit = scratch;
+  }
+  x3_operands(p, presplit, w3, ktm);
+  p.a_off *= 3; p.a_bstride *= 3;   // (a batched launch: offsets into the split copy of the same tensor)
+  return run_gemm(x3_share(p, cls), true, st);
 }
 
 Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, int rows, int T, hipStream_t st) {
@@ -164,59 +223,121 @@ Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, in
   // class token + sequence mask                                                    (hf:273-285)
   SA_HIP(launch_peav_cls_mask(w_.h0, g_.cls, pad_mask, w_.mask_s, rows, T, D, st));
   // ResNet block: h = h0 + conv(silu(mgn(conv(silu(mgn(h0))))))                     (hf:224-263)
-  SA_HIP(hipMemsetAsync(w_.gnbuf, 0, (size_t)rows * (S + 2) * D * esz_, st));  // zero halo rows = 'same' padding
-  auto conv3 = [&](const void* W, const float* bias, const float* skip, float* dst) -> Status {
+  const bool patch3 = x3(SAMAUDIO_CLS_PATCH);
+  // (weak launcher: absent in a library linked against the CPU emulation of the launchers - fp32 buffer + launch_split3 then)
+  const bool gn_direct = patch3 && launch_masked_groupnorm_silu_split3 != nullptr;
+  if (patch3 && (!w_.gn3 || (size_t)rows * (S + 2) * 3 * D * 2 > w_.gn3_bytes))
+    return fail(SAMAUDIO_ERR_WORKSPACE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: the split halo buffer does not fit the workspace plan");
+  // zero halo rows = 'same' padding (the split form of a zero row is a zero row)
+  if (gn_direct) SA_HIP(hipMemsetAsync(w_.gn3, 0, (size_t)rows * (S + 2) * 3 * D * 2, st));
+  else SA_HIP(hipMemsetAsync(w_.gnbuf, 0, (size_t)rows * (S + 2) * D * esz_, st));
+  auto gn_silu = [&](const float* x, const float* gw, const float* gb) -> Status {
+    if (gn_direct) {
+      SA_HIP(launch_masked_groupnorm_silu_split3(x, gw, gb, w_.mask_s, w_.gn_part, w_.gn3, rows, S, D, 1, 1e-5f, st));
+      return Status{};
+    }
+    SA_HIP(launch_masked_groupnorm_silu(x, gw, gb, w_.mask_s, w_.gn_part, w_.gnbuf, bf16_, rows, S, D, 1, 1e-5f, st));
+    if (patch3) SA_HIP(launch_split3((const float*)w_.gnbuf, D, w_.gn3, (long)rows * (S + 2), D, st));
+    return Status{};
+  };
+  auto conv3 = [&](const void* W, const void* W3, bool ktm3, const float* bias, const float* skip, float* dst) -> Status {
     GemmParams p = lin(w_.gnbuf, D, W, S, D, 3 * D);
     p.kc = D; p.tap_stride = D; p.a_bstride = (long)(S + 2) * D; p.nbatch = rows; p.bias = bias;
     if (skip) { p.res = skip; p.res_ld = D; p.res_bstride = (long)S * D; }
     p.out_f32 = dst; p.f32_ld = D; p.f32_bstride = (long)S * D;
-    return run_gemm(p, bf16_, st);
+    if (!patch3) return run_gemm(p, bf16_, st);
+    // compensated operands: a tap of the convolution is 3 D contiguous elements [lo | hi | hi] of a halo-buffer row against that
+    // tap's [W_hi | W_lo | W_hi]: K' split per tap, a plain walk (no operand sharing)
+    p.A = w_.gn3; p.W = W3; p.lda = 3L * D; p.kc = 3 * D; p.tap_stride = 3L * D; p.a_bstride = (long)(S + 2) * 3 * D; p.K = 9 * D;
+    if (ktm3) p.flags |= GEMM_FLAG_W_KTM;
+    return run_gemm(p, true, st);
   };
-  SA_HIP(launch_masked_groupnorm_silu(w_.h0, g_.gn1_w, g_.gn1_b, w_.mask_s, w_.gn_part, w_.gnbuf, bf16_, rows, S, D, 1,
-                                      1e-5f, st));
-  SA_TRY(conv3(g_.conv1_w, g_.conv1_b, nullptr, w_.r1));
-  SA_HIP(launch_masked_groupnorm_silu(w_.r1, g_.gn2_w, g_.gn2_b, w_.mask_s, w_.gn_part, w_.gnbuf, bf16_, rows, S, D, 1,
-                                      1e-5f, st));
-  SA_TRY(conv3(g_.conv2_w, g_.conv2_b, w_.h0, w_.h));
+  SA_TRY(gn_silu(w_.h0, g_.gn1_w, g_.gn1_b));
+  SA_TRY(conv3(g_.conv1_w, g_.conv1_w3, g_.ktm_conv1, g_.conv1_b, nullptr, w_.r1));
+  SA_TRY(gn_silu(w_.r1, g_.gn2_w, g_.gn2_b));
+  SA_TRY(conv3(g_.conv2_w, g_.conv2_w3, g_.ktm_conv2, g_.conv2_b, w_.h0, w_.h));
 
+  // RMSNorm in front of a GEMM: fp32 rows into xn, or - the GEMM's class on compensated operands - the split rows into x3a
+  auto norm = [&](const float* w, const float* gs, bool split) -> Status {
+    if (!split) {
+      SA_HIP(launch_rmsnorm_mod(w_.h, w, nullptr, nullptr, nullptr, 0, 0, 0, w_.xn, bf16_, (int)M, D, S, eps, st));
+      return Status{};
+    }
+    if (!w_.x3a || (size_t)M * 3 * D * 2 > w_.x3a_bytes)
+      return fail(SAMAUDIO_ERR_WORKSPACE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: the split operand does not fit the workspace plan");
+    SA_HIP(launch_rmsnorm_gs_split3(w_.h, gs, 0, w_.x3a, (int)M, D, S, eps, st));
+    return Status{};
+  };
+  const bool qkv3 = x3(SAMAUDIO_CLS_QKV), wo3 = x3(SAMAUDIO_CLS_WO), w13_3 = x3(SAMAUDIO_CLS_W13), w2_3 = x3(SAMAUDIO_CLS_W2),
+             att3 = x3(SAMAUDIO_X3_ATTENTION);
   for (int l = 0; l < d_.n_layers; ++l) {  // hf:457-490
     const LayerW& w = layers_[l];
-    SA_HIP(launch_rmsnorm_mod(w_.h, w.attn_norm, nullptr, nullptr, nullptr, 0, 0, 0, w_.xn, bf16_, (int)M, D, S, eps, st));
+    SA_TRY(norm(w.attn_norm, w.attn_gs, qkv3));
     {
       GemmParams p = lin(w_.xn, D, w.wqkv, M, 3 * D, D);
       p.bias = w.bqkv;
       p.out_act = w_.qkv; p.act_ld = 3L * D;
-      SA_TRY(run_gemm(p, bf16_, st));
+      if (qkv3) SA_TRY(gemm_x3(p, w.wqkv3, w.ktm_qkv, SAMAUDIO_CLS_QKV, w_.x3a, nullptr, 0, st));
+      else SA_TRY(run_gemm(p, bf16_, st));
     }
-    SA_HIP(launch_qkv_prep(w_.qkv, w.q_norm, w.k_norm, g_.rope_cos, g_.rope_sin, w_.Q, w_.K, w_.Vt, bf16_, rows, S, Sp, H,
-                           eps, st));
-    SA_HIP(launch_self_attention(w_.Q, w_.K, w_.Vt, w_.mask_s, w_.attn, bf16_, rows, S, Sp, H, st));
+    const void* attn_split = nullptr;   // the context rows in split form, when the attention wrote them for wo
+    if (att3) {   // fp32 tensors, both contractions on hi/lo-split operands (head width 128, Sp % 64 == 0)
+      if (wo3 && (!w_.attn3 || (size_t)M * 3 * D * 2 > w_.attn3_bytes))
+        return fail(SAMAUDIO_ERR_WORKSPACE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: the attention's split output does not fit the workspace plan");
+      SA_HIP(launch_qkv_prep_f32x((const float*)w_.qkv, w.q_norm, w.k_norm, g_.rope_cos, g_.rope_sin, (float*)w_.Q, (float*)w_.K,
+                                  (float*)w_.Vt, rows, S, Sp, H, eps, st));
+      SA_HIP(launch_self_attention_x3((const float*)w_.Q, (const float*)w_.K, (const float*)w_.Vt, w_.mask_s, (float*)w_.attn, rows, S,
+                                      Sp, H, 128, st, wo3 ? w_.attn3 : nullptr));
+      if (wo3) attn_split = w_.attn3;
+    } else {
+      SA_HIP(launch_qkv_prep(w_.qkv, w.q_norm, w.k_norm, g_.rope_cos, g_.rope_sin, w_.Q, w_.K, w_.Vt, bf16_, rows, S, Sp, H,
+                             eps, st));
+      SA_HIP(launch_self_attention(w_.Q, w_.K, w_.Vt, w_.mask_s, w_.attn, bf16_, rows, S, Sp, H, st));
+    }
     {
       GemmParams p = lin(w_.attn, D, w.wo, M, D, D);  // h = h + o_proj(attn)
       p.bias = w.bo;
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
-      SA_TRY(run_gemm(p, bf16_, st));
+      if (wo3) SA_TRY(gemm_x3(p, w.wo3, w.ktm_wo, SAMAUDIO_CLS_WO, attn_split, w_.x3a, w_.x3a_bytes, st));
+      else SA_TRY(run_gemm(p, bf16_, st));
     }
-    SA_HIP(launch_rmsnorm_mod(w_.h, w.ffn_norm, nullptr, nullptr, nullptr, 0, 0, 0, w_.xn, bf16_, (int)M, D, S, eps, st));
+    SA_TRY(norm(w.ffn_norm, w.ffn_gs, w13_3));
     {
       GemmParams p = lin(w_.xn, D, w.w13, M, 2 * F, D);
       p.swiglu = 1;
       p.out_act = w_.u; p.act_ld = F;
-      SA_TRY(run_gemm(p, bf16_, st));
+      bool w2_pre = false;   // w13 writes w2's operand in split form where the launch it would make passes gemm_check
+      if (w13_3) {
+        if (w2_3 && w_.x3u && (size_t)M * 3 * F * 2 <= w_.x3u_bytes) {
+          GemmParams q = p;
+          q.out_act = w_.x3u; q.flags |= GEMM_FLAG_OUT_SPLIT3;
+          x3_operands(q, w_.x3a, w.w13_3, w.ktm_w13);
+          w2_pre = gemm_check(x3_share(q, SAMAUDIO_CLS_W13), true) == nullptr;
+        }
+        if (w2_pre) { p.out_act = w_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
+        SA_TRY(gemm_x3(p, w.w13_3, w.ktm_w13, SAMAUDIO_CLS_W13, w_.x3a, nullptr, 0, st));
+      } else {
+        SA_TRY(run_gemm(p, bf16_, st));
+      }
       p = lin(w_.u, F, w.w2, M, D, F);  // h = h + down_proj(...)
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
-      SA_TRY(run_gemm(p, bf16_, st));
+      if (w2_3) SA_TRY(gemm_x3(p, w.w2_3, w.ktm_w2, SAMAUDIO_CLS_W2, w2_pre ? w_.x3u : nullptr, w_.x3u, w_.x3u_bytes, st));
+      else SA_TRY(run_gemm(p, bf16_, st));
     }
   }
   // final norm + output projection                                                  (hf:672-673)
-  SA_HIP(launch_rmsnorm_mod(w_.h, g_.norm, nullptr, nullptr, nullptr, 0, 0, 0, w_.xn, bf16_, (int)M, D, S, eps, st));
+  SA_TRY(norm(g_.norm, g_.norm_gs, wo3));
   {
     GemmParams p = lin(w_.xn, D, g_.out_w, M, D, D);
     p.out_f32 = w_.out; p.f32_ld = D;
-    p.out_act = w_.out_act; p.act_ld = D;
-    SA_TRY(run_gemm(p, bf16_, st));
+    if (wo3) {   // (one output: the 16-bit operand copy of an fp32 context is the same fp32 tensor - out_act() below)
+      SA_TRY(gemm_x3(p, g_.out_w3, g_.ktm_out, SAMAUDIO_CLS_WO, w_.x3a, nullptr, 0, st));
+    } else {
+      p.out_act = w_.out_act; p.act_ld = D;
+      SA_TRY(run_gemm(p, bf16_, st));
+    }
   }
   return Status{};
 }
@@ -238,6 +359,25 @@ Judge::Judge(const samaudio_judge_config& c)
 Status Judge::set_tensor(const char* name, const void* p, int dtype, int ndim, const int64_t* shape) {
   ready_ = false;
   return reg_.set(name, p, dtype, ndim, shape);
+}
+
+// SAMAUDIO_OPT_X3_CLASSES of a tower context (Judge / FramePredictor): fp32 contexts, tower bits only
+static Status check_x3_option(int option, int value, bool bf16, const char* who) {
+  if (option != SAMAUDIO_OPT_X3_CLASSES) return fail(SAMAUDIO_ERR_ARG, std::string(who) + ": unknown option");
+  if (value && bf16)
+    return fail(SAMAUDIO_ERR_ARG, std::string(who) + ": SAMAUDIO_OPT_X3_CLASSES applies to fp32 contexts (compensated 16-bit operands under fp32 storage)");
+  if (value & ~SAMAUDIO_CLS_X3_TOWER)
+    return fail(SAMAUDIO_ERR_ARG, std::string(who) + ": SAMAUDIO_OPT_X3_CLASSES: only qkv, wo, w13, w2, patch and SAMAUDIO_X3_ATTENTION");
+  return Status{};
+}
+
+Status Judge::set_option(int option, int value) {
+  SA_TRY(check_x3_option(option, value, bf16_, "samaudio_judge_set_option"));
+  x3_ = value;
+  enc_.set_x3(value);
+  fin_.set_x3(value);
+  ready_ = false;   // finalize resolves the twins of the switched classes
+  return Status{};
 }
 
 Status Judge::finalize() {
@@ -266,6 +406,10 @@ Status Judge::finalize() {
   NEEDF(g_.std_, "std", 4);
 #undef NEEDF
 #undef NEEDW
+  if (x3_ & SAMAUDIO_CLS_WO) {   // cat_audio_proj reads the transformer's output rows: K = D over all frames, with out.w's class
+    SA_TRY(reg_.need_twin("cat.wh.x3", Bn, 3L * D, &g_.cat_wh3, &g_.ktm_wh));
+    SA_TRY(reg_.need_twin("cat.wi.x3", Bn, 3L * D, &g_.cat_wi3, &g_.ktm_wi));
+  }
   if (D2 > 4096) return fail(SAMAUDIO_ERR_ARG, "judge: finetune_transformer.dim > 4096");
   ready_ = true;
   return Status{};
@@ -337,17 +481,31 @@ Status Judge::score(const float* in_lat, const float* sep_lat, int Bi, int cand,
   SA_TRY(enc_.forward(w_.xa, mask1, N1, T, st));
   const void* hid = enc_.out_act();  // [N1][S][D]; last_hidden_state = rows 1..T of each item
   // audio_features = cat_audio_proj(cat[hyp, inp])                                      (judge.py:112-115)
+  const bool cat3 = (x3_ & SAMAUDIO_CLS_WO) != 0;
+  const void* hid3 = nullptr;
+  if (cat3) {   // the hidden states once in split form, into the encoder's D-wide scratch (free until the next forward)
+    if (!enc_.x3_scratch() || (size_t)N1 * S * 3 * D * 2 > enc_.x3_scratch_bytes())
+      return fail(SAMAUDIO_ERR_WORKSPACE, "judge_score: SAMAUDIO_OPT_X3_CLASSES: the split operand does not fit the workspace plan");
+    SA_HIP(launch_split3(enc_.out_f32(), D, enc_.x3_scratch(), (long)N1 * S, D, st));
+    hid3 = enc_.x3_scratch();
+  }
+  auto cat_gemm = [&](GemmParams p, const void* w3, bool ktm) -> Status {
+    if (!cat3) return run_gemm(p, bf16_, st);
+    x3_operands(p, hid3, w3, ktm);
+    p.a_off *= 3; p.a_bstride *= 3;
+    return run_gemm(x3_share(p, SAMAUDIO_CLS_WO), true, st);
+  };
   {
     GemmParams p = lin(hid, D, g_.cat_wi, T, Bn, D);  // mixture half, once per clip, with the bias
     p.nbatch = Bi; p.a_off = D; p.a_bstride = (long)S * D; p.bias = g_.cat_b;
     p.out_f32 = w_.inp_part; p.f32_ld = Bn; p.f32_bstride = (long)T * Bn;
-    SA_TRY(run_gemm(p, bf16_, st));
+    SA_TRY(cat_gemm(p, g_.cat_wi3, g_.ktm_wi));
     for (int c = 0; c < cand; ++c) {  // hypothesis half of candidate c of every clip + the clip's mixture half
       GemmParams q = lin(hid, D, g_.cat_wh, T, Bn, D);
       q.nbatch = Bi; q.a_off = ((long)(Bi + c) * S + 1) * D; q.a_bstride = (long)cand * S * D;
       q.res = w_.inp_part; q.res_ld = Bn; q.res_bstride = (long)T * Bn;
       q.out_act = w_.audio; q.act_ld = Bn; q.act_off = (long)c * T * Bn; q.act_bstride = (long)cand * T * Bn;
-      SA_TRY(run_gemm(q, bf16_, st));
+      SA_TRY(cat_gemm(q, g_.cat_wh3, g_.ktm_wh));
     }
   }
   // text branch: layer_norm(text_proj2(text_proj1(pooled)))                            (judge.py:98-100,116-120)
@@ -409,6 +567,14 @@ FramePredictor::FramePredictor(const samaudio_frame_config& c)
 Status FramePredictor::set_tensor(const char* name, const void* p, int dtype, int ndim, const int64_t* shape) {
   ready_ = false;
   return reg_.set(name, p, dtype, ndim, shape);
+}
+
+Status FramePredictor::set_option(int option, int value) {
+  SA_TRY(check_x3_option(option, value, bf16_, "samaudio_frame_set_option"));
+  x3_ = value;
+  enc_.set_x3(value);
+  ready_ = false;
+  return Status{};
 }
 
 Status FramePredictor::finalize() {

@@ -157,6 +157,67 @@ hipError_t launch_masked_groupnorm_silu(const float* x, const float* w, const fl
   return hipGetLastError();
 }
 
+// The apply pass with the result in the compensated-operand form (SAMAUDIO_OPT_X3_CLASSES, kernels.hip split3_kernel): row
+// halo + t of out3 [B][S + 2 halo][3C] 16-bit = [lo | hi | hi] of silu(...), hi = rn16(v) clamped to the format's largest finite
+// value, lo = rn16(v - hi); both roundings are the hardware conversion (pack_h16x2).  Same statistics (mgn_partial_kernel) and the
+// same fp32 expression as mgn_apply_kernel<float>, so hi + lo is that kernel's output to the split's 2^-22.  Masked frames are
+// written as zeros in all three thirds; halo rows are not touched (the caller zeroes them once, as for the fp32 buffer).
+// 6 bytes written per element instead of the 4 + 4 + 6 of an fp32 write followed by split3.
+__global__ __launch_bounds__(256) void mgn_apply_split3_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                               const float* __restrict__ bias,
+                                                               const unsigned char* __restrict__ mask,
+                                                               const double* __restrict__ partials, bf16_t* __restrict__ out,
+                                                               int S, int C, int halo, float eps) {
+  const int b = blockIdx.y;
+  double s = 0.0, q = 0.0, rows = 0.0;
+  for (int c = 0; c < MGN_CHUNKS; ++c) {
+    const double* p = partials + ((long)b * MGN_CHUNKS + c) * 3;
+    s += p[0];
+    q += p[1];
+    rows += p[2];
+  }
+  double n = rows * (double)C;
+  if (n < 1.0) n = 1.0;
+  const double mean_d = s / n;
+  double var_d = q / n - mean_d * mean_d;
+  if (var_d < 0.0) var_d = 0.0;
+  const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var_d + (double)eps));
+  const int n4 = C >> 2;
+  const long total4 = (long)S * n4;
+  const float4* xs = (const float4*)(x + (long)b * S * C);
+  bf16_t* ob = out + ((long)b * (S + 2 * halo) + halo) * 3L * C;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
+    const int t = (int)(i / n4), c4 = (int)(i - (long)t * n4);
+    uint2 hi = make_uint2(0u, 0u), lo = make_uint2(0u, 0u);
+    if (mask[(long)b * S + t]) {
+      const float4 v = xs[i], ww = ((const float4*)w)[c4], bb = ((const float4*)bias)[c4];
+      const float o0 = silu_f((v.x - mean) * rstd * ww.x + bb.x), o1 = silu_f((v.y - mean) * rstd * ww.y + bb.y),
+                  o2 = silu_f((v.z - mean) * rstd * ww.z + bb.z), o3 = silu_f((v.w - mean) * rstd * ww.w + bb.w);
+      hi.x = pack_h16x2(fminf(fmaxf(o0, -kH16Max), kH16Max), fminf(fmaxf(o1, -kH16Max), kH16Max));
+      hi.y = pack_h16x2(fminf(fmaxf(o2, -kH16Max), kH16Max), fminf(fmaxf(o3, -kH16Max), kH16Max));
+      lo.x = pack_h16x2(o0 - h16_lo(hi.x), o1 - h16_hi(hi.x));
+      lo.y = pack_h16x2(o2 - h16_lo(hi.y), o3 - h16_hi(hi.y));
+    }
+    bf16_t* dst = ob + (long)t * 3 * C + 4 * c4;
+    *(uint2*)dst = lo;
+    *(uint2*)(dst + C) = hi;
+    *(uint2*)(dst + 2L * C) = hi;
+  }
+}
+
+hipError_t launch_masked_groupnorm_silu_split3(const float* x, const float* w, const float* b, const unsigned char* mask,
+                                               double* partials, void* out3, int B, int S, int C, int halo, float eps,
+                                               hipStream_t st) {
+  if (C % 4 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)b & 15) || ((uintptr_t)out3 & 7)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mgn_partial_kernel, dim3(MGN_CHUNKS, B), dim3(256), 0, st, x, mask, partials, S, C);
+  long total4 = (long)S * (C / 4);
+  int gx = (int)((total4 + 255) / 256);
+  if (gx > 512) gx = 512;
+  hipLaunchKernelGGL(mgn_apply_split3_kernel, dim3(gx, B), dim3(256), 0, st, x, w, b, mask, partials, (bf16_t*)out3, S, C, halo,
+                     eps);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // out[m,:] = LayerNorm(x[m,:]) * w + b  (reference judge.py:117: torch.nn.LayerNorm(bottleneck_dim), eps 1e-5;
 // hf:184-195 contrastive heads, eps 1e-6).  fp32 in; writes the fp32 result and/or the GEMM-operand copy.

@@ -41,8 +41,10 @@ def storage_precision(precision: str) -> str:
 
 
 def tower_precision(precision: str) -> str:
-    """The towers beside the DiT (Judge, span predictor, vision tower) have no compensated mode: beside an x3 DiT they run on the
-    library's plain 16-bit operands, as they do beside a plain 16-bit one."""
+    """The DEFAULT precision of the towers beside the DiT (Judge, span predictor, vision tower): beside an x3 DiT they run on the
+    library's plain 16-bit operands, as they do beside a plain 16-bit one.  The Judge and the span predictor do have a compensated
+    mode (precision="fp16x3" / "bf16x3" of their classes); it is opt-in through `tower_precision=` of SAMAudio.from_pretrained /
+    attach_rankers / create_ranker."""
     return {"fp16x3": "fp16", "bf16x3": "bf16"}.get(precision, precision)
 
 
@@ -101,6 +103,10 @@ X3_ATTENTION = 1 << 14   # samaudio.h SAMAUDIO_X3_ATTENTION: the self-attention'
 CLS_X3_GEMMS = CLS["qkv"] | CLS["wo"] | CLS["cwq"] | CLS["cwo"] | CLS["w13"] | CLS["w2"]
 CLS_X3_DEFAULT = CLS_X3_GEMMS | CLS["patch"] | CLS["ckv"] | CLS["codec"] | X3_ATTENTION
 X3_WEIGHTS = {"wqkv": "qkv", "wo": "wo", "c_wq": "cwq", "c_wo": "cwo", "w13": "w13", "w2": "w2"}
+# the PE-AV towers (Judge, span predictor; samaudio.h SAMAUDIO_CLS_X3_TOWER): what samaudio_judge_set_option / samaudio_frame_set_option
+# accept, and what precision="fp16x3" / "bf16x3" towers switch on
+CLS_X3_TOWER = CLS["qkv"] | CLS["wo"] | CLS["w13"] | CLS["w2"] | CLS["patch"] | X3_ATTENTION
+X3_TOWER_WEIGHTS = {"wqkv": "qkv", "wo": "wo", "w13": "w13", "w2": "w2"}
 QUANT_FORMATS = {"bf16": 1, "fp16": 2}
 SENTINEL_NAMES = CLASSES + ("norm", "attn")
 
@@ -289,6 +295,7 @@ _PROTOS = {
     "samaudio_op_cross_attn_fold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "samaudio_op_layernorm_accum": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "samaudio_op_masked_groupnorm_silu": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "samaudio_op_masked_groupnorm_silu_split3": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "samaudio_op_layernorm_rows": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_int,
                                                                                           C.c_float, C.c_void_p]),
     "samaudio_op_split3": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
@@ -304,6 +311,7 @@ _PROTOS = {
     "samaudio_judge_create": (C.c_int, [C.POINTER(JudgeConfig), C.POINTER(C.c_void_p)]),
     "samaudio_judge_destroy": (None, [C.c_void_p]),
     "samaudio_judge_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "samaudio_judge_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "samaudio_judge_finalize": (C.c_int, [C.c_void_p]),
     "samaudio_judge_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "samaudio_judge_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -314,6 +322,7 @@ _PROTOS = {
     "samaudio_frame_create": (C.c_int, [C.POINTER(FrameConfig), C.POINTER(C.c_void_p)]),
     "samaudio_frame_destroy": (None, [C.c_void_p]),
     "samaudio_frame_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "samaudio_frame_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "samaudio_frame_finalize": (C.c_int, [C.c_void_p]),
     "samaudio_frame_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "samaudio_frame_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

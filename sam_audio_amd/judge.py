@@ -29,7 +29,7 @@ import torch
 from . import hip
 from .config import PEAudioFrameConfig, PEAVTransformerConfig, SAMAudioJudgeConfig
 from .judge_util import ensure_ws as _ensure_ws, register as _register
-from .weights import _interleave16, convert_codec
+from .weights import _interleave16, convert_codec, convert_codec_fly16, convert_codec_x3, convert_peav_x3, x3_tower_weight
 
 
 @dataclass
@@ -133,6 +133,17 @@ def convert_judge(sd: Dict[str, torch.Tensor], cfg: SAMAudioJudgeConfig, act_dty
     return out
 
 
+def convert_judge_x3(tensors: Dict[str, torch.Tensor], cfg: SAMAudioJudgeConfig, half: torch.dtype,
+                     classes: int = hip.CLS_X3_TOWER) -> Dict[str, torch.Tensor]:
+    """The split twins / norm tables a Judge context with SAMAUDIO_OPT_X3_CLASSES = `classes` needs beside convert_judge's fp32
+    tensors: both transformers (weights.convert_peav_x3) and, with class `wo`, the two halves of cat_audio_proj."""
+    out = convert_peav_x3(tensors, "t.", cfg.transformer.num_hidden_layers, half, classes)
+    out.update(convert_peav_x3(tensors, "ft.", cfg.finetune_transformer.num_hidden_layers, half, classes))
+    if classes & hip.CLS["wo"]:
+        out["cat.wh.x3"], out["cat.wi.x3"] = x3_tower_weight(tensors["cat.wh"], half), x3_tower_weight(tensors["cat.wi"], half)
+    return out
+
+
 class _CodecEncoder:
     """Codec-only engine context: the DACVAEEncoder of reference codec.py:42-78 on the separate() path's kernels."""
 
@@ -149,6 +160,8 @@ class _CodecEncoder:
         hip.check(self._lib.samaudio_create(C.byref(hc), C.byref(self._ctx)))
         self._tensors: Dict[str, torch.Tensor] = {}
         self._workspace: Optional[torch.Tensor] = None
+        self._x3 = hip.is_x3(precision)
+        self._half = hip.half_dtype(precision)
 
     def __del__(self):
         if getattr(self, "_ctx", None):
@@ -156,6 +169,12 @@ class _CodecEncoder:
             self._ctx = None
 
     def load(self, tensors: Dict[str, torch.Tensor]) -> None:
+        if self._x3:   # the codec's x3 class with its twins, exactly as SAMAudio sets them up for an x3 precision
+            tensors = dict(tensors)
+            codec = {k: v for k, v in tensors.items() if k.startswith(("enc.", "dec."))}
+            tensors.update(convert_codec_x3(codec, self._half))
+            tensors.update(convert_codec_fly16(codec, self._half))
+            hip.check(self._lib.samaudio_set_option(self._ctx, hip.OPT_X3_CLASSES, hip.CLS["codec"]))
         for name, t in tensors.items():
             dt = hip.dtype_code(t.dtype)
             if t.data_ptr() % 16:
@@ -225,7 +244,7 @@ class SAMAudioJudgeModel:
     def __init__(self, config: SAMAudioJudgeConfig, precision: str = "bf16", device: Optional[str] = None,
                  text_model=None):
         config.check_supported()
-        hip.check_precision(precision)
+        hip.check_precision(precision, x3_ok=True)
         self.config = config
         self.precision = precision
         self.device = torch.device(device) if device is not None else None
@@ -244,6 +263,8 @@ class SAMAudioJudgeModel:
             codec_dim=config.audio_codec.codebook_dim, text_hidden=config.text_hidden,
             bottleneck_dim=config.bottleneck_dim)
         hip.check(self._lib.samaudio_judge_create(C.byref(jc), C.byref(self._h)))
+        if hip.is_x3(precision):   # fp32 storage, the towers' big contractions on compensated 16-bit operands
+            hip.check(self._lib.samaudio_judge_set_option(self._h, hip.OPT_X3_CLASSES, hip.CLS_X3_TOWER))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -317,8 +338,10 @@ class SAMAudioJudgeModel:
         self.text_model = self._text.module
         with torch.cuda.device(self.device):
             if not any(k for k in missing if not k.startswith(("audio_codec.", "text_model."))):
-                _register(self._lib.samaudio_judge_set_tensor, self._h, self._tensors,
-                          convert_judge(state_dict, self.config, self.act_dtype, self.device))
+                tensors = convert_judge(state_dict, self.config, self.act_dtype, self.device)
+                if hip.is_x3(self.precision):
+                    tensors.update(convert_judge_x3(tensors, self.config, hip.half_dtype(self.precision)))
+                _register(self._lib.samaudio_judge_set_tensor, self._h, self._tensors, tensors)
                 hip.check(self._lib.samaudio_judge_finalize(self._h))
                 self._loaded = True
             if not any(k for k in missing if k.startswith("audio_codec.")):
@@ -454,6 +477,7 @@ class PEAudioFrame:
     def __init__(self, config: PEAudioFrameConfig, precision: str = "bf16", device: Optional[str] = None,
                  text_model=None, hop_length: int = 1920, sample_rate: int = 48_000):
         config.check_supported()
+        hip.check_precision(precision, x3_ok=True)
         self.config, self.precision = config, precision
         self.device = torch.device(device) if device is not None else None
         self.hop_length, self.sample_rate = hop_length, sample_rate
@@ -468,6 +492,8 @@ class PEAudioFrame:
                              audio=peav_dims(config.audio, config.codebook_dim), codec_dim=config.codebook_dim,
                              embed_dim=config.text_hidden)
         hip.check(self._lib.samaudio_frame_create(C.byref(fc), C.byref(self._h)))
+        if hip.is_x3(precision):
+            hip.check(self._lib.samaudio_frame_set_option(self._h, hip.OPT_X3_CLASSES, hip.CLS_X3_TOWER))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -488,8 +514,11 @@ class PEAudioFrame:
         self._text.place(self.device)
         self.text_model = self._text.module
         with torch.cuda.device(self.device):
-            _register(self._lib.samaudio_frame_set_tensor, self._h, self._tensors,
-                      convert_frame(state_dict, self.config, self.act_dtype, self.device))
+            tensors = convert_frame(state_dict, self.config, self.act_dtype, self.device)
+            if hip.is_x3(self.precision):
+                tensors.update(convert_peav_x3(tensors, "a.", self.config.audio.num_hidden_layers,
+                                               hip.half_dtype(self.precision), hip.CLS_X3_TOWER))
+            _register(self._lib.samaudio_frame_set_tensor, self._h, self._tensors, tensors)
             hip.check(self._lib.samaudio_frame_finalize(self._h))
         self._loaded = True
 

@@ -279,9 +279,15 @@ class SAMAudio:
 
     @classmethod
     def from_pretrained(cls, model_id: str, map_location: str = "cpu", strict: bool = True,
-                        precision: str = "fp16x3", device: Optional[str] = None, **model_kwargs):
+                        precision: str = "fp16x3", device: Optional[str] = None, tower_precision: Optional[str] = None,
+                        **model_kwargs):
         """Local directory with the reference's `config.json` + `checkpoint.pt`
-        (reference base.py:17-62; hub download needs network access this build does not have)."""
+        (reference base.py:17-62; hub download needs network access this build does not have).
+
+        `tower_precision`: the precision of the rankers built here.  None (default) = hip.tower_precision(precision): plain 16-bit
+        operands beside an x3 DiT.  "fp16x3" / "bf16x3" opt the Judge into its compensated mode (fp32 storage, the big contractions
+        on hi/lo-split 16-bit operands).  The PE-Core vision tower has no compensated mode: it keeps the
+        plain mapping whatever is passed here."""
         if not os.path.isdir(model_id):
             raise FileNotFoundError(f"{model_id}: only local checkpoint directories are supported offline")
         with open(os.path.join(model_id, "config.json")) as fin:
@@ -300,7 +306,7 @@ class SAMAudio:
         except FileNotFoundError as exc:
             warnings.warn(f"text encoder not attached ({exc}); pass text_features / text_mask to the processor or set "
                           "model.text_encoder")
-        model.attach_rankers(precision=hip.tower_precision(precision))
+        model.attach_rankers(precision=hip.tower_precision(precision), tower_precision=tower_precision)
         return model
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
@@ -882,10 +888,14 @@ class SAMAudio:
         batch.process_anchors(anchors)
         return batch
 
-    def attach_rankers(self, **kwargs) -> None:
+    def attach_rankers(self, tower_precision: Optional[str] = None, **kwargs) -> None:
         """Build the rankers named in the config (reference model.py:94-95) when they point at LOCAL checkpoint
-        directories; hub ids cannot be resolved offline and are left unattached (a warning says so)."""
+        directories; hub ids cannot be resolved offline and are left unattached (a warning says so).
+        `tower_precision` (None = whatever `precision=` says): see from_pretrained."""
         from .ranking import create_ranker
+        if tower_precision is not None:
+            hip.check_precision(tower_precision, x3_ok=True)
+            kwargs["precision"] = tower_precision
         for name in ("visual_ranker", "text_ranker"):
             rc = getattr(self.cfg, name)
             if rc is None or getattr(self, name) is not None:

@@ -44,8 +44,11 @@ class JudgeRanker(Ranker):
     The reference expands the mixture to one copy per candidate before the processor (ranking/judge.py:31-33) and the
     Judge encodes every copy; here the mixture is handed over once per clip (`score_candidates`), same scores."""
 
-    def __init__(self, config: Optional[JudgeRankerConfig] = None, model=None, processor=None, **model_kwargs):
+    def __init__(self, config: Optional[JudgeRankerConfig] = None, model=None, processor=None,
+                 tower_precision: Optional[str] = None, **model_kwargs):
         self.config = config
+        if tower_precision is not None:   # the Judge's precision by its SAMAudio-side name ("fp16x3": the compensated towers)
+            model_kwargs["precision"] = tower_precision
         if model is None or processor is None:
             from .judge import SAMAudioJudgeModel
             from .processor import SAMAudioJudgeProcessor

@@ -81,6 +81,46 @@ def x3_weight(w: torch.Tensor, half: torch.dtype, ktm: bool = True) -> torch.Ten
     return ktm_layout(w3) if ktm else w3
 
 
+def x3_tower_weight(w: torch.Tensor, half: torch.dtype) -> torch.Tensor:
+    """x3_weight for a PE-AV tower GEMM: K-tile-major where the 8-phase family takes the launch (N >= 256 - the only family that
+    reads the layout, gemm.hip gemm_variant), row-major otherwise (the narrow bottleneck projections)."""
+    return x3_weight(w, half, ktm=w.shape[0] >= 256)
+
+
+def convert_peav_x3(tensors: Dict[str, torch.Tensor], prefix: str, n_layers: int, half: torch.dtype,
+                    classes: int) -> Dict[str, torch.Tensor]:
+    """What SAMAUDIO_OPT_X3_CLASSES of a PE-AV tower context needs beside the fp32 engine tensors `tensors` (judge.convert_peav's
+    output for act_dtype float32) of the transformer under `prefix`: the "<name>.x3" twins of the classes in the mask `classes`
+    (hip.CLS_X3_TOWER bits), the convolutions per tap as convert_dit_x3 does for the patcher, and the constant [gain | 0] tables
+    "<norm>.gs" [2, D] the split-form RMSNorm reads (samaudio.h samaudio_judge_set_option)."""
+    from . import hip
+    out: Dict[str, torch.Tensor] = {}
+
+    def gs(name):
+        g = tensors[prefix + name]
+        out[prefix + name + ".gs"] = torch.stack([g, torch.zeros_like(g)]).contiguous()
+
+    for i in range(n_layers):
+        L = f"{prefix}L{i}."
+        for leaf, cls in hip.X3_TOWER_WEIGHTS.items():
+            if classes & hip.CLS[cls]:
+                out[L + leaf + ".x3"] = x3_tower_weight(tensors[L + leaf], half)
+        if classes & hip.CLS["qkv"]:
+            gs(f"L{i}.attn_norm")
+        if classes & hip.CLS["w13"]:
+            gs(f"L{i}.ffn_norm")
+    if classes & hip.CLS["wo"]:
+        out[prefix + "out.w.x3"] = x3_tower_weight(tensors[prefix + "out.w"], half)
+        gs("norm")
+    if classes & hip.CLS["patch"]:   # [D, 3 taps x D] -> each tap's D columns split: [D, 3 taps x 3D]
+        for n in (1, 2):
+            cw = tensors[f"{prefix}conv{n}.w"]
+            d = cw.shape[0]
+            w3 = torch.cat([x3_weight(cw[:, j * d:(j + 1) * d], half, ktm=False) for j in range(3)], dim=1).contiguous()
+            out[f"{prefix}conv{n}.w.x3"] = ktm_layout(w3) if d >= 256 else w3
+    return out
+
+
 def _pad_k(w: torch.Tensor, slab: int) -> torch.Tensor:
     n, k = w.shape
     kp = (k + slab - 1) // slab * slab
