@@ -24,7 +24,7 @@ FLAGS="-x c++ -std=c++17 -O2 -fPIC -fopenmp $POISON $SAN -I stub -Wno-unused-val
 pids=()
 for f in gemm gemm2 gemm8 kernels attention peav_kernels vit_kernels t5_kernels engine peav vit t5 mbert api; do
   src=$SRC/$f.hip
-  if [ ! -f $OUT/$f.o ] || [ $src -nt $OUT/$f.o ] || [ stub/hip/hip_runtime.h -nt $OUT/$f.o ] || [ $SRC/common.h -nt $OUT/$f.o ] || [ $SRC/kernels.h -nt $OUT/$f.o ] || [ $SRC/engine.h -nt $OUT/$f.o ] || [ $SRC/peav.h -nt $OUT/$f.o ] || [ $SRC/vit.h -nt $OUT/$f.o ] || [ $SRC/t5.h -nt $OUT/$f.o ] || [ $SRC/mbert.h -nt $OUT/$f.o ]; then
+  if [ ! -f $OUT/$f.o ] || [ $src -nt $OUT/$f.o ] || [ stub/hip/hip_runtime.h -nt $OUT/$f.o ] || [ $SRC/common.h -nt $OUT/$f.o ] || [ $SRC/kernels.h -nt $OUT/$f.o ] || [ $SRC/host.h -nt $OUT/$f.o ] || [ $SRC/engine.h -nt $OUT/$f.o ] || [ $SRC/peav.h -nt $OUT/$f.o ] || [ $SRC/vit.h -nt $OUT/$f.o ] || [ $SRC/t5.h -nt $OUT/$f.o ] || [ $SRC/mbert.h -nt $OUT/$f.o ]; then
     EXTRA=""
     if [ $f = gemm2 ]; then
       EXTRA="-O1 -I $SRC"   # the fully unrolled epilogues are slow to optimise on the host

@@ -1,40 +1,32 @@
 // Host-side orchestration of the separate() hot path: owns no device memory, sequences the kernels.
 #pragma once
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../../include/samaudio.h"
-#include "kernels.h"
+#include "host.h"
 
 namespace sa {
 
-struct TensorRef {
-  const void* p = nullptr;
-  int dtype = 0;
-  std::vector<int64_t> shape;
-};
-
-struct Status {
-  int code = 0;
-  std::string msg;
-  bool ok() const { return code == 0; }
-};
-
-void set_last_error(const std::string& msg);  // api.hip: the thread-local string behind samaudio_last_error()
-
 // SAMAUDIO_OPT_X3_CLASSES, shared by the DiT engine and the PE-AV towers (peav.hip).
-// The 16-bit launch over K' = 3K that an x3 class makes of its fp32 GemmParams: A = the split operand [lo | hi | hi] (row stride 3K),
-// W = the split weight [W_hi | W_lo | W_hi] (K-tile-major when `ktm`)
-inline void x3_operands(GemmParams& p, const void* a3, const void* w3, bool ktm) {
-  const int K = p.K;
-  p.A = a3; p.lda = 3L * K; p.K = 3 * K; p.kc = 3 * K; p.W = w3;
+// A launch stated on an fp32 tensor, restated on that tensor's split copy (every element of the K axis became three): the one place
+// offsets, strides and extents along K are scaled.  It does not say how K' is laid out - the two functions below do, and the caller
+// picks one (a helper that infers it was the bug)
+inline void x3_scale_k(GemmParams& p) { p.a_off *= 3; p.a_bstride *= 3; p.lda *= 3; p.tap_stride *= 3; p.kc *= 3; p.K *= 3; }
+// K' split per input block (the k3 convolutions: a tap is [lo | hi | hi] of a row against that tap's [W_hi | W_lo | W_hi]; the codec's
+// wide convolutions: per Cin-block): the geometry of `p` on the split buffer `a3`.  A plain walk over K' - never x3_share
+inline void x3_block_operands(GemmParams& p, const void* a3, const void* w3, bool ktm3) {
+  p.A = a3; p.W = w3;
+  x3_scale_k(p);
+  if (ktm3) p.flags |= GEMM_FLAG_W_KTM;
+}
+// K' split over the whole K: the 16-bit launch over K' = 3K that an x3 class makes of its fp32 GemmParams (kc == K, no taps).
+// A = the split operand [lo | hi | hi] (dense rows of 3K; a batched launch keeps its offsets, into the split copy of the same tensor),
+// W = the split weight [W_hi | W_lo | W_hi]
+inline void x3_operands(GemmParams& p, const void* a3, const LinW& w) {
+  p.lda = p.K;
+  x3_block_operands(p, a3, w.w3, w.ktm3);
   if (p.out_act) {   // an fp32 context's "activation" outputs are fp32 tensors: the 16-bit kernel writes them as its fp32 output
     p.out_f32 = (float*)p.out_act; p.f32_ld = p.act_ld; p.f32_bstride = p.act_bstride; p.f32_off = p.act_off;
     p.f32_act = p.act != ACT_NONE;
     p.out_act = nullptr; p.act_ld = p.act_bstride = p.act_off = 0;
   }
-  if (ktm) p.flags |= GEMM_FLAG_W_KTM;
   if ((p.flags & GEMM_FLAG_OUT_SPLIT3) && p.out_f32) {   // the result leaves as the next GEMM's split operand (16-bit, 3 x n_out per row)
     p.out_act = p.out_f32; p.act_ld = 3L * (p.swiglu ? p.N / 2 : p.N); p.act_bstride = p.act_off = 0;
     p.out_f32 = nullptr; p.f32_ld = p.f32_bstride = p.f32_off = 0; p.f32_act = 0;
@@ -50,6 +42,20 @@ inline GemmParams x3_share(const GemmParams& p, int cls) {
   GemmParams q = p;
   q.flags |= GEMM_FLAG_X3_SHARE;
   return q.kc == q.K && q.K % 192 == 0 && !gemm_check(q, true) ? q : p;
+}
+
+// The launch of `p` (an x3 class's fp32 launch on the split operand a3) that writes its result as the NEXT GEMM's split operand into
+// `out3`: the caller finishes it the way it launches (launch_params / x3_share) and asks gemm_check whether the 8-phase family takes it
+inline GemmParams x3_split3_out(GemmParams p, const void* a3, const LinW& w, void* out3) {
+  p.out_act = out3;
+  p.flags |= GEMM_FLAG_OUT_SPLIT3;
+  x3_operands(p, a3, w);
+  return p;
+}
+// `rows` split rows of 3 k 16-bit elements fit the scratch `buf` of `cap` bytes; x3_fits: ... or `who` + `what`, the context's message
+inline bool x3_room(const void* buf, size_t cap, long rows, long k) { return buf && (size_t)rows * 3 * k * 2 <= cap; }
+inline Status x3_fits(const void* buf, size_t cap, long rows, long k, const std::string& who, const char* what) {
+  return x3_room(buf, cap, rows, k) ? Status{} : Status{SAMAUDIO_ERR_WORKSPACE, who + "SAMAUDIO_OPT_X3_CLASSES: " + what};
 }
 
 constexpr int HALO = 40;  // zero rows either side of codec activations (>= 4 * max dilation 9)
@@ -132,7 +138,7 @@ class Engine {
   int codec_chunk(int items, int64_t samples, bool pairs) const;   // items per pass in this workspace (whole pairs); 0: not even one
   Status codec_carve(bool decode, int n, int64_t samples, CodecBufs& cb);   // one pass's buffers out of the workspace
   // The kind of a GEMM launch.  F32: exact fp32 inside a 16-bit context (SAMAUDIO_OPT_F32_CLASSES - the caller hands fp32 A / W / out_act
-  // pointers).  X3: a SAMAUDIO_OPT_X3_CLASSES launch inside an fp32 context (16-bit A / W over K' = 3K, fp32 outputs; gemm_x3 builds it),
+  // pointers).  X3: a SAMAUDIO_OPT_X3_CLASSES launch inside an fp32 context (16-bit A / W over K' = 3K, fp32 outputs; linear builds it),
   // both operands split over the whole K (A rows [lo | hi | hi], W rows [W_hi | W_lo | W_hi]: the launch may share operand tiles,
   // common.h GEMM_FLAG_X3_SHARE).  X3Block: the same with K' split per input block (the convolutions of gemm_codec_x3 / the patcher:
   // [block][3 Cin]) - a plain walk over K' only
@@ -146,12 +152,11 @@ class Engine {
   GemmParams launch_params(const GemmParams& p_in, int cls, GemmKind kind) const;   // the tag / flags p_in launches with
   Status launch(GemmParams p, hipStream_t st, double alg_flops, int cls, GemmKind kind);   // one launch, profiled
   Status scan_out(const GemmParams& p, int cls, GemmKind kind, hipStream_t st);
-  // SAMAUDIO_OPT_X3_CLASSES: `p` = the fp32 context's plain launch (fp32 A rows, fp32-typed outputs) of a class that is switched
-  // on; `w3` = its "<name>.x3" weight.  Splits A into the scratch operand [lo | hi | hi] and runs ONE 16-bit GEMM over K' = 3K.
-  // `presplit`: A already split; otherwise gemm_x3 splits it into x3a, or into x3u when `ffn_wide` (w2's F-wide operand)
-  Status gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, int cls, const void* presplit = nullptr, bool ffn_wide = false);
-  // the launch gemm_x3 would make of `p` with GEMM_FLAG_OUT_SPLIT3 passes gemm_check (the 8-phase family takes it)
-  bool x3_split3_out_ok(GemmParams p, const void* w3, bool ktm, void* out3) const;
+  // One GEMM of class `cls` on the weight `w`: gemm() on w.w, or - SAMAUDIO_OPT_X3_CLASSES switched on for the class - ONE 16-bit GEMM
+  // over K' = 3K on w.w3 and the split operand [lo | hi | hi] of A.  `p` = the context's plain launch (fp32 A rows, fp32-typed
+  // outputs in an fp32 context).  `presplit`: A already split; otherwise split here into x3a, or into x3u when `ffn_wide` (w2's F-wide
+  // operand)
+  Status linear(GemmParams p, const LinW& w, int cls, hipStream_t st, const void* presplit = nullptr, bool ffn_wide = false);
   bool x3(int cls) const { return !bf16_ && (x3_classes_ & cls) != 0; }
   // A convolution of the DAC-VAE.  SAMAUDIO_OPT_X3_CLASSES bit CODEC: one with >= 256 output channels whose weight has a registered
   // "<name>.x3" twin ([N, K / Cin, 3 Cin]: every Cin-block of a weight row as [W_hi | W_lo | W_hi]) runs through gemm_codec_x3 - the fp32
@@ -170,8 +175,6 @@ class Engine {
   bool f32c(int cls) const { return bf16_ && (f32_classes_ & cls) != 0; }
   bool alt16(int cls) const { return bf16_ && (alt_classes_ & cls) != 0; }   // SAMAUDIO_OPT_ALT16_CLASSES (mixed mode)
   const void* opt(const std::string& name, std::vector<int64_t> shape) const;  // optional fp32 tensor, null if absent / mis-shaped
-  // optional 16-bit twin: [N, K] row-major, or [K/64, N, 64] K-tile-major (then sets `bit` of *ktm); null if absent / mis-shaped
-  const void* twin16(const std::string& name, int64_t N, int64_t K, int* ktm, int bit) const;
   struct ProfRec {
     std::string key;
     double flops, bytes;
@@ -190,8 +193,6 @@ class Engine {
   std::vector<hipEvent_t> ev_pool_;
   size_t ev_used_ = 0;
   Status prof_event(hipEvent_t* e);
-  const TensorRef* find(const std::string& name) const;
-  Status need(const std::string& name, int dtype, std::vector<int64_t> shape, const void** out);
 
   samaudio_config cfg_;
   bool bf16_;
@@ -211,7 +212,7 @@ class Engine {
   int quant_classes_ = 0, quant_fmt_ = 0;  // SAMAUDIO_OPT_QUANT_CLASSES / _FORMAT (fp32 contexts)
   size_t esz_;  // bytes per activation / GEMM-operand element
   int at_dtype_;
-  std::map<std::string, TensorRef> tensors_;
+  Registry reg_;
   bool dit_ready_ = false, codec_ready_ = false, enc_ready_ = false, prepared_ = false;
   char* ws_ = nullptr;
   size_t ws_bytes_ = 0;
@@ -223,25 +224,17 @@ class Engine {
   // resolved weights (pointers into caller memory)
   struct LayerW {
     const float *attn_norm, *ffn_norm, *mod_table, *q_norm, *k_norm, *c_q_norm;
-    const void *wqkv, *wo, *c_wq, *c_wo, *w13, *w2;
-    int ktm;   // which of (wqkv, wo, c_wq, w13, w2) - bits 0..4 - are registered K-tile-major [K/64][N][64] (samaudio.h)
-    // SAMAUDIO_OPT_X3_CLASSES (fp32 contexts): the "<name>.x3" split weights [W_hi | W_lo | W_hi], 16-bit; null = not registered
-    const void *wqkv3, *wo3, *c_wq3, *c_wo3, *w13_3, *w2_3;
-    int ktm3;  // which of them - bits 0..5 in that order - are K-tile-major [3K/64][N][64]
+    LinW wqkv, wo, c_wq, c_wo, w13, w2;   // (all but c_wo may be registered K-tile-major in a 16-bit context: samaudio.h)
   };
   // a big-five weight: [N, K] row-major or (16-bit contexts) [K/64, N, 64] K-tile-major
-  Status need_w5(const std::string& name, int N, int K, const void** out, int* ktm_bits, int bit);
+  Status need_w5(const std::string& name, int N, int K, LinW& w) const;
   std::vector<LayerW> layers_;
   struct {
     const float *final_table, *final_norm, *gn1_w, *gn1_b, *gn2_w, *gn2_b, *pb1, *pb2, *tb_b, *t_freqs, *mem_inv_freq,
         *rope_cos, *rope_sin, *proj_b, *mem_b, *vid_b, *vid_ln_w, *vid_ln_b, *vid_gate, *anc_emb, *c_k_norm_all;
-    const void *w_out, *pw1, *pw2, *y_w13, *y_w2, *t_w13, *t_w2, *tb_w, *proj_wy, *proj_wf, *mem_w, *vid_w, *anc_w,
-        *c_wkv_all;
-  } g_;
-  struct {  // SAMAUDIO_OPT_X3_CLASSES, classes PATCH and CKV: "patch1.w.x3", "patch2.w.x3" (per tap [W_hi | W_lo | W_hi]), "c_wkv_all.x3"
-    const void *pw1, *pw2, *c_wkv_all;
-    int ktm;   // bits 0..2 in that order: K-tile-major
-  } g3_;
+    const void *w_out, *y_w13, *y_w2, *t_w13, *t_w2, *tb_w, *proj_wy, *proj_wf, *mem_w, *vid_w, *anc_w;
+    LinW pw1, pw2, c_wkv_all;   // (x3 twins: classes PATCH - "patch<n>.w.x3", per tap [W_hi | W_lo | W_hi] - and CKV)
+  } g_{};
   struct {  // optional fp32 copies ("<name>.f32") of the weights of the SAMAUDIO_CLS_F32_CAPABLE classes
     const float *w_out, *t_w13, *t_w2, *tb_w, *proj_wy, *proj_wf, *mem_w, *vid_w, *anc_w, *y_w13, *y_w2;
   } g32_;
@@ -270,7 +263,7 @@ class Engine {
     float *temb32, *tu32, *tsilu32, *xn32, *prep32, *mem32, *yu32, *yemb32;  // fp32 operands of the f32 classes (16-bit contexts)
     unsigned char *pad_mask, *text_mask;
     double* gn_part;
-    size_t x3a_bytes, x3u_bytes;   // capacities of x3a / x3u (gemm_x3 refuses a split that would not fit)
+    size_t x3a_bytes, x3u_bytes;   // capacities of x3a / x3u (linear refuses a split that would not fit)
   } d_;
 };
 

@@ -10,18 +10,6 @@
 
 namespace sa {
 
-#define SA_TRY(expr)                     \
-  do {                                   \
-    Status _s = (expr);                  \
-    if (!_s.ok()) return _s;             \
-  } while (0)
-#define SA_HIP(expr)                                                                  \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    if (_e != hipSuccess)                                                             \
-      return Status{SAMAUDIO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)}; \
-  } while (0)
-
 static Status fail(int code, const std::string& m) { return Status{code, m}; }
 
 // SAMAUDIO_TRACE=1: after each stage of an evaluation, synchronise, copy the stage's buffer to the host and print how
@@ -121,15 +109,16 @@ Engine::Engine(const samaudio_config& c) : cfg_(c) {
   bf16_ = c.precision == SAMAUDIO_BF16;
   esz_ = bf16_ ? 2 : 4;
   at_dtype_ = bf16_ ? SAMAUDIO_DT_BF16 : SAMAUDIO_DT_F32;
-  std::memset(&g_, 0, sizeof(g_));
   std::memset(&g32_, 0, sizeof(g32_));
-  std::memset(&g3_, 0, sizeof(g3_));
   std::memset(&enc_, 0, sizeof(enc_));
   std::memset(&dec_, 0, sizeof(dec_));
   std::memset(&d_, 0, sizeof(d_));
 }
 
-Status Engine::set_tensor(const char* name, const void* p, int dtype, int ndim, const int64_t* shape) {
+// ---------------------------------------------------------------------------------------------------
+// the weight registry (host.h): every context's name -> borrowed tensor map
+// ---------------------------------------------------------------------------------------------------
+Status Registry::set(const char* name, const void* p, int dtype, int ndim, const int64_t* shape) {
   if (!name || !p || ndim < 0 || ndim > 4) return fail(SAMAUDIO_ERR_ARG, "set_tensor: bad argument");
   if ((reinterpret_cast<uintptr_t>(p) & 15) != 0)
     return fail(SAMAUDIO_ERR_ARG, std::string("set_tensor: ") + name + " is not 16-byte aligned");
@@ -137,19 +126,16 @@ Status Engine::set_tensor(const char* name, const void* p, int dtype, int ndim, 
   t.p = p;
   t.dtype = dtype;
   t.shape.assign(shape, shape + ndim);
-  // Re-registering a name invalidates the resolved pointers: finalize() must run again.  Adding new names
-  // (e.g. the codec set after the DiT set) leaves an already finalized set valid.
-  if (tensors_.count(name)) dit_ready_ = codec_ready_ = enc_ready_ = false;
   tensors_[name] = t;
   return Status{};
 }
 
-const TensorRef* Engine::find(const std::string& name) const {
+const TensorRef* Registry::find(const std::string& name) const {
   auto it = tensors_.find(name);
   return it == tensors_.end() ? nullptr : &it->second;
 }
 
-Status Engine::need(const std::string& name, int dtype, std::vector<int64_t> shape, const void** out) {
+Status Registry::need(const std::string& name, int dtype, std::vector<int64_t> shape, const void** out) const {
   const TensorRef* t = find(name);
   if (!t) return fail(SAMAUDIO_ERR_WEIGHT, "missing weight tensor '" + name + "'");
   if (t->dtype != dtype) return fail(SAMAUDIO_ERR_WEIGHT, "weight '" + name + "' has the wrong dtype");
@@ -164,26 +150,43 @@ Status Engine::need(const std::string& name, int dtype, std::vector<int64_t> sha
   return Status{};
 }
 
-const void* Engine::opt(const std::string& name, std::vector<int64_t> shape) const {
+void Registry::twin(const std::string& name, int64_t N, int64_t K3, LinW& w) const {
   const TensorRef* t = find(name);
+  w.w3 = nullptr;
+  w.ktm3 = t && t->dtype == SAMAUDIO_DT_BF16 && K3 % 64 == 0 && t->shape == std::vector<int64_t>{K3 / 64, N, 64};
+  if (w.ktm3 || (t && t->dtype == SAMAUDIO_DT_BF16 && t->shape == std::vector<int64_t>{N, K3})) w.w3 = t->p;
+}
+
+Status Registry::need_twin(const std::string& name, int64_t N, int64_t K3, LinW& w) const {
+  twin(name, N, K3, w);
+  if (w.w3) return Status{};
+  return fail(SAMAUDIO_ERR_WEIGHT, "SAMAUDIO_OPT_X3_CLASSES: the split weight '" + name + "' (16-bit, [" + std::to_string(N) + ", " +
+                                       std::to_string(K3) + "] or [" + std::to_string(K3 / 64) + ", " + std::to_string(N) +
+                                       ", 64]) of a class that is switched on is not registered");
+}
+
+Status Engine::set_tensor(const char* name, const void* p, int dtype, int ndim, const int64_t* shape) {
+  const bool known = name && reg_.has(name);
+  SA_TRY(reg_.set(name, p, dtype, ndim, shape));
+  // Re-registering a name invalidates the resolved pointers: finalize() must run again.  Adding new names
+  // (e.g. the codec set after the DiT set) leaves an already finalized set valid.
+  if (known) dit_ready_ = codec_ready_ = enc_ready_ = false;
+  return Status{};
+}
+
+const void* Engine::opt(const std::string& name, std::vector<int64_t> shape) const {
+  const TensorRef* t = reg_.find(name);
   return t && t->dtype == SAMAUDIO_DT_F32 && t->shape == shape ? t->p : nullptr;
 }
 
-Status Engine::need_w5(const std::string& name, int N, int K, const void** out, int* ktm_bits, int bit) {
-  const TensorRef* t = find(name);
-  if (t && bf16_ && t->dtype == at_dtype_ && t->shape == std::vector<int64_t>{K / 64, N, 64} && K % 64 == 0) {
-    *out = t->p;
-    *ktm_bits |= 1 << bit;
+Status Engine::need_w5(const std::string& name, int N, int K, LinW& w) const {
+  const TensorRef* t = reg_.find(name);
+  w.ktm = t && bf16_ && t->dtype == at_dtype_ && t->shape == std::vector<int64_t>{K / 64, N, 64} && K % 64 == 0;
+  if (w.ktm) {
+    w.w = t->p;
     return Status{};
   }
-  return need(name, at_dtype_, {N, K}, out);
-}
-
-const void* Engine::twin16(const std::string& name, int64_t N, int64_t K, int* ktm, int bit) const {
-  const TensorRef* t = find(name);
-  if (!t || t->dtype != SAMAUDIO_DT_BF16) return nullptr;
-  if (t->shape == std::vector<int64_t>{K / 64, N, 64}) { *ktm |= 1 << bit; return t->p; }
-  return t->shape == std::vector<int64_t>{N, K} ? t->p : nullptr;
+  return reg_.need(name, at_dtype_, {N, K}, &w.w);
 }
 
 static int kpad(int k, bool bf16) { return (int)round_up(k, bf16 ? 64 : 32); }
@@ -191,8 +194,8 @@ static int kpad(int k, bool bf16) { return (int)round_up(k, bf16 ? 64 : 32); }
 Status Engine::finalize(int what) {
   const int D = cfg_.dim, F = cfg_.ffn_hidden, L = cfg_.n_layers, C2 = cfg_.latent_channels;
   const int F32 = SAMAUDIO_DT_F32, AT = at_dtype_;
-#define NEEDF(field, name, ...) SA_TRY(need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
-#define NEEDW(field, name, ...) SA_TRY(need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
+#define NEEDF(field, name, ...) SA_TRY(reg_.need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
+#define NEEDW(field, name, ...) SA_TRY(reg_.need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
   if (what == 0) {
     // head_dim = dim / n_heads: 128 (every kernel tuned for it) or 64 (general forms of qkv_prep / the norms / cross-attention,
     // the self-attention kernel's 64-wide instantiation, no folded cross-attention projection)
@@ -211,17 +214,17 @@ Status Engine::finalize(int what) {
       NEEDF(w.q_norm, P + "q_norm", hd);
       NEEDF(w.k_norm, P + "k_norm", hd);
       NEEDF(w.c_q_norm, P + "c_q_norm", hd);
-      SA_TRY(need_w5(P + "wqkv", 3 * D, D, &w.wqkv, &w.ktm, 0));
-      SA_TRY(need_w5(P + "wo", D, D, &w.wo, &w.ktm, 1));
-      SA_TRY(need_w5(P + "c_wq", D, D, &w.c_wq, &w.ktm, 2));
-      NEEDW(w.c_wo, P + "c_wo", D, D);
-      SA_TRY(need_w5(P + "w13", 2 * F, D, &w.w13, &w.ktm, 3));
-      SA_TRY(need_w5(P + "w2", D, F, &w.w2, &w.ktm, 4));
+      SA_TRY(need_w5(P + "wqkv", 3 * D, D, w.wqkv));
+      SA_TRY(need_w5(P + "wo", D, D, w.wo));
+      SA_TRY(need_w5(P + "c_wq", D, D, w.c_wq));
+      NEEDW(w.c_wo.w, P + "c_wo", D, D);
+      SA_TRY(need_w5(P + "w13", 2 * F, D, w.w13));
+      SA_TRY(need_w5(P + "w2", D, F, w.w2));
       if (!bf16_) {   // SAMAUDIO_OPT_X3_CLASSES: optional split copies, checked when a class is switched on / at the end of finalize
-        const struct { const char* leaf; int N, K; const void** out; } x3w[6] = {
-            {"wqkv", 3 * D, D, &w.wqkv3}, {"wo", D, D, &w.wo3}, {"c_wq", D, D, &w.c_wq3},
-            {"c_wo", D, D, &w.c_wo3},     {"w13", 2 * F, D, &w.w13_3}, {"w2", D, F, &w.w2_3}};
-        for (int j = 0; j < 6; ++j) *x3w[j].out = twin16(P + x3w[j].leaf + ".x3", x3w[j].N, 3L * x3w[j].K, &w.ktm3, j);
+        const struct { const char* leaf; int N, K; LinW& w; } x3w[6] = {{"wqkv", 3 * D, D, w.wqkv}, {"wo", D, D, w.wo},
+                                                                        {"c_wq", D, D, w.c_wq},     {"c_wo", D, D, w.c_wo},
+                                                                        {"w13", 2 * F, D, w.w13},   {"w2", D, F, w.w2}};
+        for (const auto& t : x3w) reg_.twin(P + t.leaf + ".x3", t.N, 3L * t.K, t.w);
       }
     }
     NEEDF(g_.final_table, "final_table", 2, D);
@@ -229,11 +232,11 @@ Status Engine::finalize(int what) {
     NEEDW(g_.w_out, "w_out", C2, D);
     NEEDF(g_.gn1_w, "patch1.gn_w", D);
     NEEDF(g_.gn1_b, "patch1.gn_b", D);
-    NEEDW(g_.pw1, "patch1.w", D, 3 * D);
+    NEEDW(g_.pw1.w, "patch1.w", D, 3 * D);
     NEEDF(g_.pb1, "patch1.b", D);
     NEEDF(g_.gn2_w, "patch2.gn_w", D);
     NEEDF(g_.gn2_b, "patch2.gn_b", D);
-    NEEDW(g_.pw2, "patch2.w", D, 3 * D);
+    NEEDW(g_.pw2.w, "patch2.w", D, 3 * D);
     NEEDF(g_.pb2, "patch2.b", D);
     NEEDW(g_.y_w13, "y_w13", 2 * D, D);
     NEEDW(g_.y_w2, "y_w2", D, D);
@@ -259,7 +262,7 @@ Status Engine::finalize(int what) {
     NEEDW(g_.anc_w, "anc_w", D, cfg_.anchor_dim);
     // cross-attention K|V projections of ALL layers as one operand: the text memory changes with t only through
     // the y-embedder, so one GEMM per evaluation serves the 22 layers (reference transformer.py:382-388, :102-114)
-    NEEDW(g_.c_wkv_all, "c_wkv_all", (int64_t)L * 2 * D, D);
+    NEEDW(g_.c_wkv_all.w, "c_wkv_all", (int64_t)L * 2 * D, D);
     NEEDF(g_.c_k_norm_all, "c_k_norm_all", L, hd);
     if (bf16_) {  // fp32 copies for SAMAUDIO_OPT_F32_CLASSES: optional, checked when a class is switched on / used
 #define OPTF(field, name, ...) g32_.field = (const float*)opt(name ".f32", {__VA_ARGS__})
@@ -278,10 +281,9 @@ Status Engine::finalize(int what) {
       SA_TRY(check_f32_weights(f32_classes_));
     }
     if (!bf16_) {   // SAMAUDIO_OPT_X3_CLASSES, classes PATCH / CKV: optional split copies
-      std::memset(&g3_, 0, sizeof(g3_));
-      const struct { const char* name; int64_t N, K3; const void** out; } x3g[3] = {
-          {"patch1.w.x3", D, 9L * D, &g3_.pw1}, {"patch2.w.x3", D, 9L * D, &g3_.pw2}, {"c_wkv_all.x3", (int64_t)L * 2 * D, 3L * D, &g3_.c_wkv_all}};
-      for (int j = 0; j < 3; ++j) *x3g[j].out = twin16(x3g[j].name, x3g[j].N, x3g[j].K3, &g3_.ktm, j);
+      reg_.twin("patch1.w.x3", D, 9L * D, g_.pw1);
+      reg_.twin("patch2.w.x3", D, 9L * D, g_.pw2);
+      reg_.twin("c_wkv_all.x3", (int64_t)L * 2 * D, 3L * D, g_.c_wkv_all);
     }
     dit_ready_ = true;   // (check_x3_weights looks at the resolved layers)
     if (const Status s3 = check_x3_weights(x3_classes_); !s3.ok()) { dit_ready_ = false; return s3; }
@@ -327,13 +329,13 @@ Status Engine::finalize(int what) {
     // narrow convolutions' weights already split, in the layout the fp32 kernel's on-the-fly multiply reads (common.h GEMM_FLAG_W_FLY16)
     x3_codec_.clear();
     fly_codec_.clear();
-    for (const auto& kv : tensors_) {
+    for (const auto& kv : reg_.all()) {
       const std::string& name = kv.first;
       const size_t dot = name.rfind('.');
       const std::string ext = dot == std::string::npos ? "" : name.substr(dot);
       const bool x3t = ext == ".x3";
       if (bf16_ || (!x3t && ext != ".fly") || (name.rfind("enc.", 0) != 0 && name.rfind("dec.", 0) != 0)) continue;
-      const TensorRef* base = find(name.substr(0, dot));
+      const TensorRef* base = reg_.find(name.substr(0, dot));
       const TensorRef& t = kv.second;
       if (!base || base->shape.size() != 2 || t.dtype != SAMAUDIO_DT_BF16) continue;
       const int64_t N = base->shape[0], K = base->shape[1];
@@ -569,15 +571,15 @@ Status Engine::check_f32_weights(int classes) const {
 
 Status Engine::check_x3_weights(int classes) const {
   if (!classes) return Status{};
-  if ((classes & SAMAUDIO_CLS_PATCH) && !(g3_.pw1 && g3_.pw2))
+  if ((classes & SAMAUDIO_CLS_PATCH) && !(g_.pw1.w3 && g_.pw2.w3))
     return fail(SAMAUDIO_ERR_WEIGHT, "SAMAUDIO_OPT_X3_CLASSES: the split weights 'patch1.w.x3' / 'patch2.w.x3' (16-bit, [D, 9D] or [9D/64, D, 64]) are not registered");
-  if ((classes & SAMAUDIO_CLS_CKV) && !g3_.c_wkv_all)
+  if ((classes & SAMAUDIO_CLS_CKV) && !g_.c_wkv_all.w3)
     return fail(SAMAUDIO_ERR_WEIGHT, "SAMAUDIO_OPT_X3_CLASSES: the split weight 'c_wkv_all.x3' (16-bit, [L*2D, 3D] or [3D/64, L*2D, 64]) is not registered");
   for (size_t i = 0; i < layers_.size(); ++i) {
     const LayerW& w = layers_[i];
     const struct { int cls; const void* p; const char* leaf; } need[6] = {
-        {SAMAUDIO_CLS_QKV, w.wqkv3, "wqkv"}, {SAMAUDIO_CLS_WO, w.wo3, "wo"},     {SAMAUDIO_CLS_CWQ, w.c_wq3, "c_wq"},
-        {SAMAUDIO_CLS_CWO, w.c_wo3, "c_wo"}, {SAMAUDIO_CLS_W13, w.w13_3, "w13"}, {SAMAUDIO_CLS_W2, w.w2_3, "w2"}};
+        {SAMAUDIO_CLS_QKV, w.wqkv.w3, "wqkv"}, {SAMAUDIO_CLS_WO, w.wo.w3, "wo"},    {SAMAUDIO_CLS_CWQ, w.c_wq.w3, "c_wq"},
+        {SAMAUDIO_CLS_CWO, w.c_wo.w3, "c_wo"}, {SAMAUDIO_CLS_W13, w.w13.w3, "w13"}, {SAMAUDIO_CLS_W2, w.w2.w3, "w2"}};
     for (const auto& n : need)
       if ((classes & n.cls) && !n.p)
         return fail(SAMAUDIO_ERR_WEIGHT, "SAMAUDIO_OPT_X3_CLASSES: the split weight 'L" + std::to_string(i) + "." + n.leaf +
@@ -669,7 +671,7 @@ static int cls_slot(int cls) {   // the sentinel slot of a class
   return bit;
 }
 
-// the tag and flags a launch of gemm() runs with (x3_split3_out_ok dry-runs gemm_check on them)
+// the tag and flags a launch of gemm() runs with (the OUT_SPLIT3 dry run of eval_field asks gemm_check about them)
 GemmParams Engine::launch_params(const GemmParams& p_in, int cls, GemmKind kind) const {
   GemmParams p = p_in;
   p.tag = phase_ == Phase::Codec ? 1 : 0;  // codec launches run under their own kernel symbols
@@ -775,28 +777,25 @@ Status Engine::launch(GemmParams p, hipStream_t st, double alg_flops, int cls, G
   return Status{};
 }
 
-Status Engine::gemm_x3(GemmParams p, const void* w3, bool ktm, hipStream_t st, int cls, const void* presplit, bool ffn_wide) {
-  if (!w3 || !d_.x3a) return fail(SAMAUDIO_ERR_STATE, "SAMAUDIO_OPT_X3_CLASSES: split weight or scratch operand missing (set the option before samaudio_prepare)");
+Status Engine::linear(GemmParams p, const LinW& w, int cls, hipStream_t st, const void* presplit, bool ffn_wide) {
+  if (!x3(cls)) {
+    p.W = w.w;
+    if (w.ktm) p.flags |= GEMM_FLAG_W_KTM;
+    return gemm(p, st, -1.0, cls);
+  }
+  if (!w.w3 || !d_.x3a) return fail(SAMAUDIO_ERR_STATE, "SAMAUDIO_OPT_X3_CLASSES: split weight or scratch operand missing (set the option before samaudio_prepare)");
   if (p.nbatch != 1 || p.kc != p.K || p.a_off || p.tap_stride || (p.out_act && p.out_f32))
     return fail(SAMAUDIO_ERR_ARG, "SAMAUDIO_OPT_X3_CLASSES: plain single-batch launches with one output only");
   const int K = p.K;
   if (!presplit) {   // split the fp32 operand here: into x3a (D-wide rows), or - w2's F-wide hidden - into x3u
     void* const dst = ffn_wide ? d_.x3u : d_.x3a;
-    if ((size_t)p.M * 3 * K * 2 > (ffn_wide ? d_.x3u_bytes : d_.x3a_bytes))
-      return fail(SAMAUDIO_ERR_WORKSPACE, "SAMAUDIO_OPT_X3_CLASSES: the split operand does not fit the scratch the workspace plan holds");
+    SA_TRY(x3_fits(dst, ffn_wide ? d_.x3u_bytes : d_.x3a_bytes, p.M, K, "", "the split operand does not fit the scratch the workspace plan holds"));
     // algorithmic bytes of the split: the fp32 row in, three 16-bit copies out
     SA_TRY(op("split3", (double)p.M * K * (4 + 6), 0, st, [&] { return launch_split3((const float*)p.A, p.lda, dst, p.M, K, st); }));
     presplit = dst;
   }
-  x3_operands(p, presplit, w3, ktm);
+  x3_operands(p, presplit, w);
   return gemm(p, st, 2.0 * p.M * (double)p.N * K, cls, GemmKind::X3);   // flops as the reference counts them: one product over K
-}
-
-bool Engine::x3_split3_out_ok(GemmParams p, const void* w3, bool ktm, void* out3) const {
-  p.out_act = out3;
-  p.flags |= GEMM_FLAG_OUT_SPLIT3;
-  x3_operands(p, d_.x3a, w3, ktm);
-  return gemm_check(launch_params(p, SAMAUDIO_CLS_W13, GemmKind::X3), true) == nullptr;   // the parameters gemm() would launch
 }
 
 Status Engine::gemm_codec_x3(const GemmParams& p_in, const X3CodecW& w, hipStream_t st, double alg_flops) {
@@ -804,8 +803,7 @@ Status Engine::gemm_codec_x3(const GemmParams& p_in, const X3CodecW& w, hipStrea
   const long rows = (long)p_in.nbatch * (p_in.a_bstride / c);   // every row of the halo buffers the launch reads (halo rows are zeros)
   SA_TRY(op("split3", (double)rows * c * (4 + 6), 0, st, [&] { return launch_split3((const float*)p_in.A, c, x3_codec_scratch_, rows, c, st); }));
   GemmParams p = p_in;
-  p.A = x3_codec_scratch_; p.W = w.w;
-  p.a_off *= 3; p.a_bstride *= 3; p.lda *= 3; p.tap_stride *= 3; p.kc *= 3; p.K *= 3;
+  x3_block_operands(p, x3_codec_scratch_, w.w, false);   // ("one block": the whole K' is one [lo | hi | hi] x [W_hi | W_lo | W_hi], below)
   // the 16-bit launch writes the RAW fp32 result (into the raw stream, or - a launch with an activated output only - into that
   // buffer); the activation follows as an elementwise pass with the fp32 kernel's own expressions
   const int act = p_in.act;
@@ -930,13 +928,6 @@ Engine::~Engine() {
   }
 }
 
-static GemmParams lin(const void* A, long lda, const void* W, long M, int N, int K) {
-  GemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.A = A; p.W = W; p.lda = lda; p.kc = K; p.tap_stride = 0;
-  p.M = (int)M; p.N = N; p.K = K; p.nbatch = 1; p.alpha = 1.f; p.rows_per_gate = 1;
-  return p;
-}
 static void out_f32(GemmParams& p, float* o, long ld) { p.out_f32 = o; p.f32_ld = ld; }
 static void out_act(GemmParams& p, void* o, long ld, int act = ACT_NONE) { p.out_act = o; p.act_ld = ld; p.act = act; }
 static void with_res(GemmParams& p, const float* r, long ld) { p.res = r; p.res_ld = ld; }
@@ -1082,8 +1073,8 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_IN, f32_if(f)));
   }
   // patcher: (GroupNorm(1) -> SiLU -> conv k3) x 2 + skip           (patcher.py:138-141)
-  auto patch_conv = [&](const void* W, const void* W3, bool ktm3, const float* bias, const float* skip, float* dst) -> Status {
-    GemmParams p = lin(d_.gnbuf, D, W, T, D, 3 * D);
+  auto patch_conv = [&](const LinW& w, const float* bias, const float* skip, float* dst) -> Status {
+    GemmParams p = lin(d_.gnbuf, D, w.w, T, D, 3 * D);
     p.kc = D; p.tap_stride = D; p.a_off = 0; p.a_bstride = (long)(T + 2) * D; p.nbatch = rows;
     p.bias = bias;
     if (skip) { with_res(p, skip, D); p.res_bstride = (long)T * D; }
@@ -1092,11 +1083,10 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     if (!x3(SAMAUDIO_CLS_PATCH)) return gemm(p, st, -1.0, SAMAUDIO_CLS_PATCH);
     // compensated operands: every row of the halo-padded GroupNorm output (halo rows are zeros: they split into zeros) becomes
     // [lo | hi | hi], a tap of the convolution then is 3 D contiguous elements against that tap's [W_hi | W_lo | W_hi]
-    if (!W3 || !d_.x3a) return fail(SAMAUDIO_ERR_STATE, "SAMAUDIO_OPT_X3_CLASSES: patcher split weight or scratch operand missing");
+    if (!w.w3 || !d_.x3a) return fail(SAMAUDIO_ERR_STATE, "SAMAUDIO_OPT_X3_CLASSES: patcher split weight or scratch operand missing");
     const long prow = (long)rows * (T + 2);
     SA_TRY(op("split3", (double)prow * D * (4 + 6), 0, st, [&] { return launch_split3((const float*)d_.gnbuf, D, d_.x3a, prow, D, st); }));
-    p.A = d_.x3a; p.W = W3; p.lda = 3L * D; p.kc = 3 * D; p.tap_stride = 3L * D; p.a_bstride = (long)(T + 2) * 3 * D; p.K = 9 * D;
-    if (ktm3) p.flags |= GEMM_FLAG_W_KTM;
+    x3_block_operands(p, d_.x3a, w.w3, w.ktm3);   // K' split per tap: a plain walk
     return gemm(p, st, 2.0 * T * (double)D * 3 * D * rows, SAMAUDIO_CLS_PATCH, GemmKind::X3Block);
   };
   trace("cond", d_.cond, (size_t)M * D, false, st);
@@ -1104,11 +1094,11 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
   SA_TRY(op("groupnorm_silu", MD * (4 + esz_), 0, st, [&] {
     return launch_groupnorm_silu(d_.aligned, g_.gn1_w, g_.gn1_b, d_.gn_part, d_.gnbuf, bf16_, rows, T, D, 1, 1e-5f, st);
   }));
-  SA_TRY(patch_conv(g_.pw1, g3_.pw1, g3_.ktm & 1, g_.pb1, nullptr, d_.hp1));
+  SA_TRY(patch_conv(g_.pw1, g_.pb1, nullptr, d_.hp1));
   SA_TRY(op("groupnorm_silu", MD * (4 + esz_), 0, st, [&] {
     return launch_groupnorm_silu(d_.hp1, g_.gn2_w, g_.gn2_b, d_.gn_part, d_.gnbuf, bf16_, rows, T, D, 1, 1e-5f, st);
   }));
-  SA_TRY(patch_conv(g_.pw2, g3_.pw2, g3_.ktm & 2, g_.pb2, d_.aligned, d_.h));
+  SA_TRY(patch_conv(g_.pw2, g_.pb2, d_.aligned, d_.h));
 
   // timestep embeddings                                             (transformer.py:490-493, model.py:170)
   {
@@ -1181,10 +1171,9 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
   trace("yemb", d_.yemb, (size_t)Mt * D, bf16_, st);
   const long kv_ld = 2L * D * cfg_.n_layers;
   if (cfg_.n_layers > 0) {  // cross-attention keys / values of every layer (k-normed), [Mt, L*2D]
-    GemmParams p = lin(d_.yemb, D, g_.c_wkv_all, Mt, (int)kv_ld, D);
+    GemmParams p = lin(d_.yemb, D, nullptr, Mt, (int)kv_ld, D);   // (W: linear sets it from the record, here and below)
     out_act(p, d_.kvc, kv_ld);
-    if (x3(SAMAUDIO_CLS_CKV)) SA_TRY(gemm_x3(p, g3_.c_wkv_all, g3_.ktm & 4, st, SAMAUDIO_CLS_CKV));
-    else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_CKV));
+    SA_TRY(linear(p, g_.c_wkv_all, SAMAUDIO_CLS_CKV, st));
     SA_HIP(launch_headnorm_layers(d_.kvc, g_.c_k_norm_all, bf16_, (int)Mt, cfg_.n_layers, H, eps, st, hd));
   }
   trace("kvc", d_.kvc, (size_t)Mt * kv_ld, bf16_, st);
@@ -1195,7 +1184,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
   const bool fold_all = fold_ltp && !fold3 && cfg_.n_layers <= kMaxFoldLayers && !debug_flag(DBG_FOLD_PER_LAYER);   // (one launch per layer: A/B, tests)
   if (fold3) {   // x3 context: U = Wo V of every layer on split operands, [L][rows][D][3 kp] = [U_hi | U_lo | U_hi]
     const float* wos[kMaxFoldLayers];
-    for (int l = 0; l < cfg_.n_layers; ++l) wos[l] = (const float*)layers_[l].c_wo;
+    for (int l = 0; l < cfg_.n_layers; ++l) wos[l] = (const float*)layers_[l].c_wo.w;
     SA_TRY(op("cross_attn_fold3", ((double)D * D * 4 + (double)rows * D * fold_kp_ * 6 + (double)Mt * D * 4) * cfg_.n_layers, 0, st, [&] {
       return launch_cross_attn_fold3_layers(wos, cfg_.n_layers, (const float*)d_.kvc, kv_ld, d_.ut3, fold_kp_, rows, Lt, fold_ltp_, H, st);
     }));
@@ -1203,7 +1192,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
   const size_t ut_layer = (size_t)rows * D * fold_kp_ * esz_;
   if (fold_all) {
     const void* wos[kMaxFoldLayers];
-    for (int l = 0; l < cfg_.n_layers; ++l) wos[l] = layers_[l].c_wo;
+    for (int l = 0; l < cfg_.n_layers; ++l) wos[l] = layers_[l].c_wo.w;
     SA_TRY(op("cross_attn_fold", ((double)D * D + (double)rows * D * fold_kp_ + (double)Mt * D) * esz_ * cfg_.n_layers, 0, st, [&] {
       return launch_cross_attn_fold_layers(wos, cfg_.n_layers, d_.kvc, kv_ld, d_.ut, fold_kp_, rows, Lt, fold_ltp_, H, st);
     }));
@@ -1216,7 +1205,6 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
   auto prefetch = [&](GemmParams& p, const void* w_next, double elems) {
     if (pf_on && w_next) { p.pf_ptr = w_next; p.pf_bytes = (long)(elems * esz_); }
   };
-  auto ktm = [](GemmParams& p, const LayerW& w, int bit) { if (w.ktm & (1 << bit)) p.flags |= GEMM_FLAG_W_KTM; };
   // the modulated RMSNorm in front of class `cls` of layer l (k = 0: the attention norm, QKV; k = 1: the FFN norm, W13) and the scan of
   // its output; `pre`: it writes the class's split operand [lo | hi | hi] itself
   auto norm_for = [&](int l, int k, int cls, bool pre) -> Status {
@@ -1250,12 +1238,10 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     bool w2_pre = false;   // (decided with the w13 launch below)
     SA_TRY(norm_for(l, 0, SAMAUDIO_CLS_QKV, qkv_pre));
     {
-      GemmParams p = lin(d_.xn, D, w.wqkv, M, 3 * D, D);
-      ktm(p, w, 0);
-      prefetch(p, w.wo, (double)D * D);
+      GemmParams p = lin(d_.xn, D, nullptr, M, 3 * D, D);
+      prefetch(p, w.wo.w, (double)D * D);
       out_act(p, d_.qkv, 3L * D);
-      if (x3(SAMAUDIO_CLS_QKV)) SA_TRY(gemm_x3(p, w.wqkv3, w.ktm3 & 1, st, SAMAUDIO_CLS_QKV, qkv_pre ? d_.x3a : nullptr));
-      else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_QKV));
+      SA_TRY(linear(p, w.wqkv, SAMAUDIO_CLS_QKV, st, qkv_pre ? d_.x3a : nullptr));
     }
     SA_TRY(op("qkv_prep", 2 * 3 * MD * esz_, 0, st, [&] {
       if (x3(SAMAUDIO_X3_ATTENTION) && hd == 128)   // fp32 tensors, the fast access pattern (its consumer is the compensated attention)
@@ -1281,30 +1267,25 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     trace("  attn", d_.attn, (size_t)M * D, bf16_, st);
     SA_TRY(sentinel(15, d_.attn, !bf16_ ? 0 : (alt16(SAMAUDIO_CLS_WO) ? 2 : 1), M, D, D, st));
     {
-      GemmParams p = lin(d_.attn, D, w.wo, M, D, D);  // h = x + gate_msa * attn
+      GemmParams p = lin(d_.attn, D, nullptr, M, D, D);  // h = x + gate_msa * attn
       p.gate_tab = tab + 2 * D; p.gate = d_.t0 + 2 * D; p.gate_ld = t6; p.rows_per_gate = T;
       with_res(p, d_.h, D);
       out_f32(p, d_.h, D);
       out_act(p, d_.hbf, D);
       if (alt16(SAMAUDIO_CLS_CWQ)) p.flags |= GEMM_FLAG_OUT_ALT;   // hbf is c_wq's operand
-      ktm(p, w, 1);
-      prefetch(p, w.c_wq, (double)D * D);
-      if (x3(SAMAUDIO_CLS_WO)) {   // (fp32 outputs only: c_wq then reads h itself)
-        p.out_act = nullptr; p.act_ld = 0;
-        SA_TRY(gemm_x3(p, w.wo3, w.ktm3 & 2, st, SAMAUDIO_CLS_WO, wo_pre ? d_.x3a : nullptr));
-      } else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_WO));
+      prefetch(p, w.c_wq.w, (double)D * D);
+      if (x3(SAMAUDIO_CLS_WO)) { p.out_act = nullptr; p.act_ld = 0; }   // (fp32 outputs only: c_wq then reads h itself)
+      SA_TRY(linear(p, w.wo, SAMAUDIO_CLS_WO, st, wo_pre ? d_.x3a : nullptr));
     }
     trace("  h after wo", d_.h, (size_t)M * D, false, st);
     trace("  hbf", d_.hbf, (size_t)M * D, bf16_, st);
     // cross-attention branch: h = h + CA(h, y)   (no norm, no gate: quirk Q4)
     {
       // (an fp32 context whose wo ran on compensated operands has no second copy of h)
-      GemmParams p = lin(x3(SAMAUDIO_CLS_WO) ? (const void*)d_.h : d_.hbf, D, w.c_wq, M, D, D);
-      ktm(p, w, 2);
-      if (!fold_all) prefetch(p, w.c_wo, (double)D * D);   // (read by the per-layer fold kernel)
+      GemmParams p = lin(x3(SAMAUDIO_CLS_WO) ? (const void*)d_.h : d_.hbf, D, nullptr, M, D, D);
+      if (!fold_all) prefetch(p, w.c_wo.w, (double)D * D);   // (read by the per-layer fold kernel)
       out_act(p, d_.qc, D);
-      if (x3(SAMAUDIO_CLS_CWQ)) SA_TRY(gemm_x3(p, w.c_wq3, w.ktm3 & 4, st, SAMAUDIO_CLS_CWQ));
-      else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_CWQ));
+      SA_TRY(linear(p, w.c_wq, SAMAUDIO_CLS_CWQ, st));
     }
     const void* kv_l = (const char*)d_.kvc + (size_t)l * 2 * D * esz_;
     if (fold3) {
@@ -1325,7 +1306,7 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       const void* ut_l = fold_all ? (const void*)((const char*)d_.ut + (size_t)l * ut_layer) : d_.ut;
       if (!fold_all)
         SA_TRY(op("cross_attn_fold", ((double)D * D + (double)rows * D * fold_kp_ + (double)Mt * D) * esz_, 0, st, [&] {
-          return launch_cross_attn_fold(w.c_wo, kv_l, kv_ld, d_.ut, fold_kp_, rows, Lt, fold_ltp_, H, st);
+          return launch_cross_attn_fold(w.c_wo.w, kv_l, kv_ld, d_.ut, fold_kp_, rows, Lt, fold_ltp_, H, st);
         }));
       const GemmParams p = fold_gemm(d_.probs, ut_l, fold_kp_);
       trace("  probs", d_.probs, (size_t)M * fold_kp_, bf16_, st);
@@ -1335,41 +1316,35 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       SA_TRY(op("cross_attention", (2 * MD + (double)Mt * 2 * D) * esz_, 4.0 * M * Lt * D, st, [&] {
         return launch_cross_attention(d_.qc, w.c_q_norm, kv_l, kv_ld, d_.text_mask, d_.ca, bf16_, rows, T, Lt, H, eps, st, hd);
       }));
-      GemmParams p = lin(d_.ca, D, w.c_wo, M, D, D);
+      GemmParams p = lin(d_.ca, D, nullptr, M, D, D);
       with_res(p, d_.h, D);
       out_f32(p, d_.h, D);
-      if (x3(SAMAUDIO_CLS_CWO)) SA_TRY(gemm_x3(p, w.c_wo3, w.ktm3 & 8, st, SAMAUDIO_CLS_CWO));
-      else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_CWO));
+      SA_TRY(linear(p, w.c_wo, SAMAUDIO_CLS_CWO, st));
     }
     trace("  qc", d_.qc, (size_t)M * D, bf16_, st);
     trace("  h after cross", d_.h, (size_t)M * D, false, st);
     // feed-forward branch
     SA_TRY(norm_for(l, 1, SAMAUDIO_CLS_W13, w13_pre));
     {
-      GemmParams p = lin(d_.xn, D, w.w13, M, 2 * F, D);
+      GemmParams p = lin(d_.xn, D, nullptr, M, 2 * F, D);
       p.swiglu = 1;
       out_act(p, d_.u, F);
       if (alt16(SAMAUDIO_CLS_W2)) p.flags |= GEMM_FLAG_OUT_ALT;    // u is w2's operand
-      ktm(p, w, 3);
-      prefetch(p, w.w2, (double)D * F);
-      if (x3(SAMAUDIO_CLS_W13)) {
-        // the SwiGLU epilogue writes w2's split operand itself where the 8-phase family takes the launch (F % 32 == 0 among others);
-        // otherwise w2 splits u with the stand-alone kernel
-        w2_pre = x3(SAMAUDIO_CLS_W2) && x3_split3_out_ok(p, w.w13_3, w.ktm3 & 16, d_.x3u);
-        if (w2_pre) { p.out_act = d_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
-        SA_TRY(gemm_x3(p, w.w13_3, w.ktm3 & 16, st, SAMAUDIO_CLS_W13, w13_pre ? d_.x3a : nullptr));
-      }
-      else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_W13));
+      prefetch(p, w.w2.w, (double)D * F);
+      // the SwiGLU epilogue writes w2's split operand itself where the 8-phase family takes the launch gemm() would make of it
+      // (F % 32 == 0 among others); otherwise w2 splits u with the stand-alone kernel
+      w2_pre = x3(SAMAUDIO_CLS_W13) && x3(SAMAUDIO_CLS_W2) &&
+               !gemm_check(launch_params(x3_split3_out(p, d_.x3a, w.w13, d_.x3u), SAMAUDIO_CLS_W13, GemmKind::X3), true);
+      if (w2_pre) { p.out_act = d_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
+      SA_TRY(linear(p, w.w13, SAMAUDIO_CLS_W13, st, w13_pre ? d_.x3a : nullptr));
       trace("  xn (ffn)", d_.xn, (size_t)M * D, bf16_, st);
       trace("  u", d_.u, (size_t)M * F, bf16_, st);
-      p = lin(d_.u, F, w.w2, M, D, F);  // out = h + gate_mlp * ff
+      p = lin(d_.u, F, nullptr, M, D, F);  // out = h + gate_mlp * ff
       p.gate_tab = tab + 5 * D; p.gate = d_.t0 + 5 * D; p.gate_ld = t6; p.rows_per_gate = T;
       with_res(p, d_.h, D);
       out_f32(p, d_.h, D);
-      ktm(p, w, 4);
-      if (l + 1 < cfg_.n_layers) prefetch(p, layers_[l + 1].wqkv, 3.0 * D * D);
-      if (x3(SAMAUDIO_CLS_W2)) SA_TRY(gemm_x3(p, w.w2_3, w.ktm3 & 32, st, SAMAUDIO_CLS_W2, w2_pre ? d_.x3u : nullptr, true));
-      else SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_W2));
+      if (l + 1 < cfg_.n_layers) prefetch(p, layers_[l + 1].wqkv.w, 3.0 * D * D);
+      SA_TRY(linear(p, w.w2, SAMAUDIO_CLS_W2, st, w2_pre ? d_.x3u : nullptr, true));
       trace("  h after ffn", d_.h, (size_t)M * D, false, st);
     }
   }

@@ -12,28 +12,8 @@ struct samaudio_mbert {
 
 namespace sa {
 
-#define SA_TRY(expr)                     \
-  do {                                   \
-    Status _s = (expr);                  \
-    if (!_s.ok()) return _s;             \
-  } while (0)
-#define SA_HIP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return Status{SAMAUDIO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)}; \
-  } while (0)
-
 namespace {
 Status mfail(int code, const std::string& m) { return Status{code, m}; }
-
-GemmParams mlin(const void* A, long lda, const void* W, long M, int N, int K) {
-  GemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.A = A; p.W = W; p.lda = lda; p.kc = K; p.tap_stride = 0;
-  p.M = (int)M; p.N = N; p.K = K; p.nbatch = 1; p.alpha = 1.f; p.rows_per_gate = 1;
-  return p;
-}
 Status mgemm(const GemmParams& p, bool bf16, hipStream_t st) {
   if (const char* why = gemm_check(p, bf16)) return mfail(SAMAUDIO_ERR_ARG, std::string("text tower: ") + why);
   SA_HIP(launch_gemm(p, bf16, st));
@@ -143,7 +123,7 @@ Status MBertEncoder::encode(const long long* ids, const unsigned char* mask, int
     if (w.ln1) SA_HIP(launch_layernorm_rows(w_.h, D, w.ln1, g_.zeros, nullptr, w_.xn, bf16_, M, D, eps, st));
     else SA_HIP(launch_to_act(w_.h, 0, D, 0, w_.xn, 0, bf16_, 1, M, D, D, 0, st));   // layer 0: attn_norm = Identity
     {
-      GemmParams p = mlin(w_.xn, D, w.wqkv, M, 3 * D, D);
+      GemmParams p = lin(w_.xn, D, w.wqkv, M, 3 * D, D);
       p.out_act = w_.qkv; p.act_ld = 3L * D;
       SA_TRY(mgemm(p, bf16_, st));
     }
@@ -152,18 +132,18 @@ Status MBertEncoder::encode(const long long* ids, const unsigned char* mask, int
     SA_HIP(launch_t5_attention(w_.qkv, mask, nullptr, w_.attn, bf16_, rows, tokens, H, hd_, c.max_len, scale,
                                global ? 0 : c.window, st));
     {
-      GemmParams p = mlin(w_.attn, D, w.wo, M, D, D);  // h = h + Wo(attn)
+      GemmParams p = lin(w_.attn, D, w.wo, M, D, D);  // h = h + Wo(attn)
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
       SA_TRY(mgemm(p, bf16_, st));
     }
     SA_HIP(launch_layernorm_rows(w_.h, D, w.ln2, g_.zeros, nullptr, w_.xn, bf16_, M, D, eps, st));
     {
-      GemmParams p = mlin(w_.xn, D, w.wi, M, 2 * F, D);  // input | gate
+      GemmParams p = lin(w_.xn, D, w.wi, M, 2 * F, D);  // input | gate
       p.out_act = w_.u; p.act_ld = 2L * F;
       SA_TRY(mgemm(p, bf16_, st));
       SA_HIP(launch_geglu(w_.u, w_.u2, bf16_, M, F, st));
-      p = mlin(w_.u2, F, w.wo2, M, D, F);  // h = h + Wo(gelu(input) * gate)
+      p = lin(w_.u2, F, w.wo2, M, D, F);  // h = h + Wo(gelu(input) * gate)
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
       SA_TRY(mgemm(p, bf16_, st));

@@ -3,26 +3,13 @@
 // sam_audio/model/judge.py:90-132) and the PE-A-Frame frame logits.  Like Engine, these classes own no device
 // memory: weights are borrowed, scratch is one caller-provided workspace.
 #pragma once
-#include <map>
-#include <string>
-#include <vector>
-
 #include "engine.h"
 
 namespace sa {
 
-class Registry {  // name -> borrowed weight tensor
- public:
-  Status set(const char* name, const void* p, int dtype, int ndim, const int64_t* shape);
-  Status need(const std::string& name, int dtype, std::vector<int64_t> shape, const void** out) const;
-  bool has(const std::string& name) const { return tensors_.count(name) != 0; }
-  // SAMAUDIO_OPT_X3_CLASSES: the 16-bit split twin "<name>" of a weight, [N, K3] row-major or K-tile-major [K3 / 64, N, 64] (*ktm set);
-  // SAMAUDIO_ERR_WEIGHT names a twin that is not registered in either shape
-  Status need_twin(const std::string& name, int64_t N, int64_t K3, const void** out, bool* ktm) const;
-
- private:
-  std::map<std::string, TensorRef> tensors_;
-};
+// Where the split A operand of an x3 launch comes from: `split` = already split by its producer, else "split the fp32 rows here into
+// this scratch of this capacity".  per_tap: a k3 convolution on a split halo buffer - K' split per tap, the plain walk (never shares)
+struct X3Operand { const void* split; void* scratch; size_t bytes; bool per_tap = false; };
 
 // One PE-AV transformer: input projection -> [class token ; frames] -> ResNet block with masked GroupNorm ->
 // n_layers x (RMSNorm, qk-norm RoPE attention, RMSNorm, SwiGLU) -> RMSNorm -> output projection.
@@ -46,6 +33,9 @@ class PeavEncoder {
   // hidden states into it for cat_audio_proj)
   void* x3_scratch() const { return w_.x3a; }
   size_t x3_scratch_bytes() const { return w_.x3a_bytes; }
+  // One launch on the weight `w`: `p` = the context's plain launch, run as it is on w.w - or, class `cls` switched to compensated
+  // operands, as ONE 16-bit launch on w.w3 and the split operand `a` names (also the Judge's cat_audio_proj, on this encoder's mask)
+  Status linear(GemmParams p, const LinW& w, int cls, const X3Operand& a, hipStream_t st) const;
   int dim() const { return d_.dim; }
   int in_dim() const { return d_.in_dim; }
 
@@ -56,23 +46,16 @@ class PeavEncoder {
   std::string prefix_;
   bool ready_ = false;
   int x3_ = 0;
-  // one launch of an x3 class: `p` = the fp32 launch; A is `presplit` (already [lo | hi | hi], 3K per row) or split here into `scratch`
-  Status gemm_x3(GemmParams p, const void* w3, bool ktm, int cls, const void* presplit, void* scratch, size_t scratch_bytes,
-                 hipStream_t st) const;
   struct LayerW {
     const float *attn_norm, *ffn_norm, *q_norm, *k_norm, *bqkv, *bo;
-    const void *wqkv, *wo, *w13, *w2;
-    // x3: "<name>.x3" twins and the constant [gain | shift 0] tables "<norm>.gs" [2, D] of launch_rmsnorm_gs_split3
-    const void *wqkv3, *wo3, *w13_3, *w2_3;
-    bool ktm_qkv, ktm_wo, ktm_w13, ktm_w2;
-    const float *attn_gs, *ffn_gs;
+    LinW wqkv, wo, w13, w2;
+    const float *attn_gs, *ffn_gs;   // x3: the constant [gain | shift 0] tables "<norm>.gs" [2, D] of launch_rmsnorm_gs_split3
   };
   std::vector<LayerW> layers_;
   struct {
-    const void *in_w, *conv1_w, *conv2_w, *out_w;
+    const void* in_w;
+    LinW conv1, conv2, out;   // (x3 twins: the convolutions per tap [D, 3 taps x 3D], out.w [D, 3D])
     const float *in_b, *cls, *gn1_w, *gn1_b, *gn2_w, *gn2_b, *conv1_b, *conv2_b, *norm, *rope_cos, *rope_sin;
-    const void *conv1_w3, *conv2_w3, *out_w3;   // x3 twins: the convolutions per tap [D, 3 taps x 3D], out.w [D, 3D]
-    bool ktm_conv1, ktm_conv2, ktm_out;
     const float* norm_gs;
   } g_{};
   struct {
@@ -119,9 +102,8 @@ class Judge {
   char* ws_ = nullptr;
   size_t ws_bytes_ = 0;
   struct {
-    const void *cat_wh, *cat_wi, *tp1_w, *tp2_w, *pat_wa, *pat_wt;
-    const void *cat_wh3, *cat_wi3;   // x3 (class WO): "cat.wh.x3" / "cat.wi.x3" [Bn, 3D]
-    bool ktm_wh, ktm_wi;
+    LinW cat_wh, cat_wi;   // (x3, class WO: "cat.wh.x3" / "cat.wi.x3" [Bn, 3D])
+    const void *tp1_w, *tp2_w, *pat_wa, *pat_wt;
     const float *cat_b, *tp2_b, *ln_w, *ln_b, *pat_b, *head_w, *mean, *std_;
   } g_{};
   struct {

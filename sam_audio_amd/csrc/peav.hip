@@ -7,29 +7,10 @@
 
 namespace sa {
 
-#define SA_TRY(expr)                     \
-  do {                                   \
-    Status _s = (expr);                  \
-    if (!_s.ok()) return _s;             \
-  } while (0)
-#define SA_HIP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return Status{SAMAUDIO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)}; \
-  } while (0)
-
 namespace {
 Status fail(int code, const std::string& m) { return Status{code, m}; }
 long round_up(long v, long m) { return (v + m - 1) / m * m; }
 
-GemmParams lin(const void* A, long lda, const void* W, long M, int N, int K) {
-  GemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.A = A; p.W = W; p.lda = lda; p.kc = K; p.tap_stride = 0;
-  p.M = (int)M; p.N = N; p.K = K; p.nbatch = 1; p.alpha = 1.f; p.rows_per_gate = 1;
-  return p;
-}
 Status run_gemm(const GemmParams& p, bool bf16, hipStream_t st) {
   if (const char* why = gemm_check(p, bf16)) return fail(SAMAUDIO_ERR_ARG, why);
   SA_HIP(launch_gemm(p, bf16, st));
@@ -45,47 +26,6 @@ Status check_dims(const samaudio_peav_dims& d, const char* who) {
   return Status{};
 }
 }  // namespace
-
-// ---------------------------------------------------------------------------------------------------
-Status Registry::set(const char* name, const void* p, int dtype, int ndim, const int64_t* shape) {
-  if (!name || !p || ndim < 0 || ndim > 4) return fail(SAMAUDIO_ERR_ARG, "set_tensor: bad argument");
-  if ((reinterpret_cast<uintptr_t>(p) & 15) != 0)
-    return fail(SAMAUDIO_ERR_ARG, std::string("set_tensor: ") + name + " is not 16-byte aligned");
-  TensorRef t;
-  t.p = p;
-  t.dtype = dtype;
-  t.shape.assign(shape, shape + ndim);
-  tensors_[name] = t;
-  return Status{};
-}
-
-Status Registry::need(const std::string& name, int dtype, std::vector<int64_t> shape, const void** out) const {
-  auto it = tensors_.find(name);
-  if (it == tensors_.end()) return fail(SAMAUDIO_ERR_WEIGHT, "missing weight tensor '" + name + "'");
-  const TensorRef& t = it->second;
-  if (t.dtype != dtype) return fail(SAMAUDIO_ERR_WEIGHT, "weight '" + name + "' has the wrong dtype");
-  if (t.shape != shape) {
-    std::string s = "weight '" + name + "' has shape [";
-    for (auto v : t.shape) s += std::to_string(v) + ",";
-    s += "] expected [";
-    for (auto v : shape) s += std::to_string(v) + ",";
-    return fail(SAMAUDIO_ERR_WEIGHT, s + "]");
-  }
-  *out = t.p;
-  return Status{};
-}
-
-Status Registry::need_twin(const std::string& name, int64_t N, int64_t K3, const void** out, bool* ktm) const {
-  auto it = tensors_.find(name);
-  if (it != tensors_.end() && it->second.dtype == SAMAUDIO_DT_BF16) {
-    const TensorRef& t = it->second;
-    if (t.shape == std::vector<int64_t>{K3 / 64, N, 64} && K3 % 64 == 0) { *out = t.p; *ktm = true; return Status{}; }
-    if (t.shape == std::vector<int64_t>{N, K3}) { *out = t.p; *ktm = false; return Status{}; }
-  }
-  return fail(SAMAUDIO_ERR_WEIGHT, "SAMAUDIO_OPT_X3_CLASSES: the split weight '" + name + "' (16-bit, [" + std::to_string(N) + ", " +
-                                       std::to_string(K3) + "] or [" + std::to_string(K3 / 64) + ", " + std::to_string(N) +
-                                       ", 64]) of a class that is switched on is not registered");
-}
 
 // ---------------------------------------------------------------------------------------------------
 // PE-AV transformer
@@ -105,14 +45,14 @@ Status PeavEncoder::finalize(const Registry& reg) {
   NEEDF(g_.cls, P + "cls", D);
   NEEDF(g_.gn1_w, P + "gn1.w", D);
   NEEDF(g_.gn1_b, P + "gn1.b", D);
-  NEEDW(g_.conv1_w, P + "conv1.w", D, 3 * D);
+  NEEDW(g_.conv1.w, P + "conv1.w", D, 3 * D);
   NEEDF(g_.conv1_b, P + "conv1.b", D);
   NEEDF(g_.gn2_w, P + "gn2.w", D);
   NEEDF(g_.gn2_b, P + "gn2.b", D);
-  NEEDW(g_.conv2_w, P + "conv2.w", D, 3 * D);
+  NEEDW(g_.conv2.w, P + "conv2.w", D, 3 * D);
   NEEDF(g_.conv2_b, P + "conv2.b", D);
   NEEDF(g_.norm, P + "norm", D);
-  NEEDW(g_.out_w, P + "out.w", D, D);
+  NEEDW(g_.out.w, P + "out.w", D, D);
   NEEDF(g_.rope_cos, P + "rope_cos", d_.max_positions, 64);
   NEEDF(g_.rope_sin, P + "rope_sin", d_.max_positions, 64);
   layers_.assign(d_.n_layers, LayerW{});
@@ -123,10 +63,10 @@ Status PeavEncoder::finalize(const Registry& reg) {
     NEEDF(w.ffn_norm, L + "ffn_norm", D);
     NEEDF(w.q_norm, L + "q_norm", 128);
     NEEDF(w.k_norm, L + "k_norm", 128);
-    NEEDW(w.wqkv, L + "wqkv", 3 * D, D);
-    NEEDW(w.wo, L + "wo", D, D);
-    NEEDW(w.w13, L + "w13", 2 * F, D);
-    NEEDW(w.w2, L + "w2", D, F);
+    NEEDW(w.wqkv.w, L + "wqkv", 3 * D, D);
+    NEEDW(w.wo.w, L + "wo", D, D);
+    NEEDW(w.w13.w, L + "w13", 2 * F, D);
+    NEEDW(w.w2.w, L + "w2", D, F);
     w.bqkv = w.bo = nullptr;
     if (d_.attn_bias) {
       NEEDF(w.bqkv, L + "bqkv", 3 * D);
@@ -134,22 +74,22 @@ Status PeavEncoder::finalize(const Registry& reg) {
     }
     // SAMAUDIO_OPT_X3_CLASSES: the twins of the classes that are switched on, and the [gain | 0] tables of the norms in front of them
     if (x3(SAMAUDIO_CLS_QKV)) {
-      SA_TRY(reg.need_twin(L + "wqkv.x3", 3 * D, 3L * D, &w.wqkv3, &w.ktm_qkv));
+      SA_TRY(reg.need_twin(L + "wqkv.x3", 3 * D, 3L * D, w.wqkv));
       NEEDF(w.attn_gs, L + "attn_norm.gs", 2, D);
     }
-    if (x3(SAMAUDIO_CLS_WO)) SA_TRY(reg.need_twin(L + "wo.x3", D, 3L * D, &w.wo3, &w.ktm_wo));
+    if (x3(SAMAUDIO_CLS_WO)) SA_TRY(reg.need_twin(L + "wo.x3", D, 3L * D, w.wo));
     if (x3(SAMAUDIO_CLS_W13)) {
-      SA_TRY(reg.need_twin(L + "w13.x3", 2 * F, 3L * D, &w.w13_3, &w.ktm_w13));
+      SA_TRY(reg.need_twin(L + "w13.x3", 2 * F, 3L * D, w.w13));
       NEEDF(w.ffn_gs, L + "ffn_norm.gs", 2, D);
     }
-    if (x3(SAMAUDIO_CLS_W2)) SA_TRY(reg.need_twin(L + "w2.x3", D, 3L * F, &w.w2_3, &w.ktm_w2));
+    if (x3(SAMAUDIO_CLS_W2)) SA_TRY(reg.need_twin(L + "w2.x3", D, 3L * F, w.w2));
   }
   if (x3(SAMAUDIO_CLS_PATCH)) {
-    SA_TRY(reg.need_twin(P + "conv1.w.x3", D, 9L * D, &g_.conv1_w3, &g_.ktm_conv1));
-    SA_TRY(reg.need_twin(P + "conv2.w.x3", D, 9L * D, &g_.conv2_w3, &g_.ktm_conv2));
+    SA_TRY(reg.need_twin(P + "conv1.w.x3", D, 9L * D, g_.conv1));
+    SA_TRY(reg.need_twin(P + "conv2.w.x3", D, 9L * D, g_.conv2));
   }
   if (x3(SAMAUDIO_CLS_WO)) {
-    SA_TRY(reg.need_twin(P + "out.w.x3", D, 3L * D, &g_.out_w3, &g_.ktm_out));
+    SA_TRY(reg.need_twin(P + "out.w.x3", D, 3L * D, g_.out));
     NEEDF(g_.norm_gs, P + "norm.gs", 2, D);
   }
 #undef NEEDF
@@ -186,21 +126,24 @@ void PeavEncoder::plan(Bump& b, int rows, int frames, bool assign) {
   }
 }
 
-Status PeavEncoder::gemm_x3(GemmParams p, const void* w3, bool ktm, int cls, const void* presplit, void* scratch, size_t scratch_bytes,
-                            hipStream_t st) const {
-  if (!w3) return fail(SAMAUDIO_ERR_STATE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: split weight missing (set the option before finalize)");
+Status PeavEncoder::linear(GemmParams p, const LinW& w, int cls, const X3Operand& a, hipStream_t st) const {
+  p.W = w.w;
+  if (!x3(cls)) return run_gemm(p, bf16_, st);
+  if (!w.w3) return fail(SAMAUDIO_ERR_STATE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: split weight missing (set the option before finalize)");
+  if (a.per_tap) {   // the caller said so: K' split per tap, no operand sharing
+    x3_block_operands(p, a.split, w.w3, w.ktm3);
+    return run_gemm(p, true, st);
+  }
   if (p.kc != p.K || p.tap_stride || (p.out_act && p.out_f32))
     return fail(SAMAUDIO_ERR_ARG, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: plain launches with one output only");
-  const int K = p.K;
-  if (!presplit) {   // split the fp32 rows here (an operand no kernel wrote in split form)
+  const void* split = a.split;
+  if (!split) {   // split the fp32 rows here (an operand no kernel wrote in split form)
     if (p.nbatch != 1 || p.a_off) return fail(SAMAUDIO_ERR_ARG, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: a batched operand must arrive split");
-    if (!scratch || (size_t)p.M * 3 * K * 2 > scratch_bytes)
-      return fail(SAMAUDIO_ERR_WORKSPACE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: the split operand does not fit the scratch the workspace plan holds");
-    SA_HIP(launch_split3((const float*)p.A, p.lda, scratch, p.M, K, st));
-    presplit = scratch;
+    SA_TRY(x3_fits(a.scratch, a.bytes, p.M, p.K, prefix_ + ": ", "the split operand does not fit the scratch the workspace plan holds"));
+    SA_HIP(launch_split3((const float*)p.A, p.lda, a.scratch, p.M, p.K, st));
+    split = a.scratch;
   }
-  x3_operands(p, presplit, w3, ktm);
-  p.a_off *= 3; p.a_bstride *= 3;   // (a batched launch: offsets into the split copy of the same tensor)
+  x3_operands(p, split, w);
   return run_gemm(x3_share(p, cls), true, st);
 }
 
@@ -226,8 +169,7 @@ Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, in
   const bool patch3 = x3(SAMAUDIO_CLS_PATCH);
   // (weak launcher: absent in a library linked against the CPU emulation of the launchers - fp32 buffer + launch_split3 then)
   const bool gn_direct = patch3 && launch_masked_groupnorm_silu_split3 != nullptr;
-  if (patch3 && (!w_.gn3 || (size_t)rows * (S + 2) * 3 * D * 2 > w_.gn3_bytes))
-    return fail(SAMAUDIO_ERR_WORKSPACE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: the split halo buffer does not fit the workspace plan");
+  if (patch3) SA_TRY(x3_fits(w_.gn3, w_.gn3_bytes, (long)rows * (S + 2), D, prefix_ + ": ", "the split halo buffer does not fit the workspace plan"));
   // zero halo rows = 'same' padding (the split form of a zero row is a zero row)
   if (gn_direct) SA_HIP(hipMemsetAsync(w_.gn3, 0, (size_t)rows * (S + 2) * 3 * D * 2, st));
   else SA_HIP(hipMemsetAsync(w_.gnbuf, 0, (size_t)rows * (S + 2) * D * esz_, st));
@@ -240,22 +182,19 @@ Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, in
     if (patch3) SA_HIP(launch_split3((const float*)w_.gnbuf, D, w_.gn3, (long)rows * (S + 2), D, st));
     return Status{};
   };
-  auto conv3 = [&](const void* W, const void* W3, bool ktm3, const float* bias, const float* skip, float* dst) -> Status {
-    GemmParams p = lin(w_.gnbuf, D, W, S, D, 3 * D);
+  // (compensated operands: a tap of the convolution is 3 D contiguous elements [lo | hi | hi] of a halo-buffer row of gn3 against that
+  // tap's [W_hi | W_lo | W_hi])
+  auto conv3 = [&](const LinW& w, const float* bias, const float* skip, float* dst) -> Status {
+    GemmParams p = lin(w_.gnbuf, D, nullptr, S, D, 3 * D);
     p.kc = D; p.tap_stride = D; p.a_bstride = (long)(S + 2) * D; p.nbatch = rows; p.bias = bias;
     if (skip) { p.res = skip; p.res_ld = D; p.res_bstride = (long)S * D; }
     p.out_f32 = dst; p.f32_ld = D; p.f32_bstride = (long)S * D;
-    if (!patch3) return run_gemm(p, bf16_, st);
-    // compensated operands: a tap of the convolution is 3 D contiguous elements [lo | hi | hi] of a halo-buffer row against that
-    // tap's [W_hi | W_lo | W_hi]: K' split per tap, a plain walk (no operand sharing)
-    p.A = w_.gn3; p.W = W3; p.lda = 3L * D; p.kc = 3 * D; p.tap_stride = 3L * D; p.a_bstride = (long)(S + 2) * 3 * D; p.K = 9 * D;
-    if (ktm3) p.flags |= GEMM_FLAG_W_KTM;
-    return run_gemm(p, true, st);
+    return linear(p, w, SAMAUDIO_CLS_PATCH, X3Operand{w_.gn3, nullptr, 0, true}, st);
   };
   SA_TRY(gn_silu(w_.h0, g_.gn1_w, g_.gn1_b));
-  SA_TRY(conv3(g_.conv1_w, g_.conv1_w3, g_.ktm_conv1, g_.conv1_b, nullptr, w_.r1));
+  SA_TRY(conv3(g_.conv1, g_.conv1_b, nullptr, w_.r1));
   SA_TRY(gn_silu(w_.r1, g_.gn2_w, g_.gn2_b));
-  SA_TRY(conv3(g_.conv2_w, g_.conv2_w3, g_.ktm_conv2, g_.conv2_b, w_.h0, w_.h));
+  SA_TRY(conv3(g_.conv2, g_.conv2_b, w_.h0, w_.h));
 
   // RMSNorm in front of a GEMM: fp32 rows into xn, or - the GEMM's class on compensated operands - the split rows into x3a
   auto norm = [&](const float* w, const float* gs, bool split) -> Status {
@@ -263,8 +202,7 @@ Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, in
       SA_HIP(launch_rmsnorm_mod(w_.h, w, nullptr, nullptr, nullptr, 0, 0, 0, w_.xn, bf16_, (int)M, D, S, eps, st));
       return Status{};
     }
-    if (!w_.x3a || (size_t)M * 3 * D * 2 > w_.x3a_bytes)
-      return fail(SAMAUDIO_ERR_WORKSPACE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: the split operand does not fit the workspace plan");
+    SA_TRY(x3_fits(w_.x3a, w_.x3a_bytes, M, D, prefix_ + ": ", "the split operand does not fit the workspace plan"));
     SA_HIP(launch_rmsnorm_gs_split3(w_.h, gs, 0, w_.x3a, (int)M, D, S, eps, st));
     return Status{};
   };
@@ -274,16 +212,14 @@ Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, in
     const LayerW& w = layers_[l];
     SA_TRY(norm(w.attn_norm, w.attn_gs, qkv3));
     {
-      GemmParams p = lin(w_.xn, D, w.wqkv, M, 3 * D, D);
+      GemmParams p = lin(w_.xn, D, nullptr, M, 3 * D, D);   // (W: linear sets it from the record, here and below)
       p.bias = w.bqkv;
       p.out_act = w_.qkv; p.act_ld = 3L * D;
-      if (qkv3) SA_TRY(gemm_x3(p, w.wqkv3, w.ktm_qkv, SAMAUDIO_CLS_QKV, w_.x3a, nullptr, 0, st));
-      else SA_TRY(run_gemm(p, bf16_, st));
+      SA_TRY(linear(p, w.wqkv, SAMAUDIO_CLS_QKV, X3Operand{w_.x3a, nullptr, 0}, st));
     }
     const void* attn_split = nullptr;   // the context rows in split form, when the attention wrote them for wo
     if (att3) {   // fp32 tensors, both contractions on hi/lo-split operands (head width 128, Sp % 64 == 0)
-      if (wo3 && (!w_.attn3 || (size_t)M * 3 * D * 2 > w_.attn3_bytes))
-        return fail(SAMAUDIO_ERR_WORKSPACE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: the attention's split output does not fit the workspace plan");
+      if (wo3) SA_TRY(x3_fits(w_.attn3, w_.attn3_bytes, M, D, prefix_ + ": ", "the attention's split output does not fit the workspace plan"));
       SA_HIP(launch_qkv_prep_f32x((const float*)w_.qkv, w.q_norm, w.k_norm, g_.rope_cos, g_.rope_sin, (float*)w_.Q, (float*)w_.K,
                                   (float*)w_.Vt, rows, S, Sp, H, eps, st));
       SA_HIP(launch_self_attention_x3((const float*)w_.Q, (const float*)w_.K, (const float*)w_.Vt, w_.mask_s, (float*)w_.attn, rows, S,
@@ -295,49 +231,36 @@ Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, in
       SA_HIP(launch_self_attention(w_.Q, w_.K, w_.Vt, w_.mask_s, w_.attn, bf16_, rows, S, Sp, H, st));
     }
     {
-      GemmParams p = lin(w_.attn, D, w.wo, M, D, D);  // h = h + o_proj(attn)
+      GemmParams p = lin(w_.attn, D, nullptr, M, D, D);  // h = h + o_proj(attn)
       p.bias = w.bo;
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
-      if (wo3) SA_TRY(gemm_x3(p, w.wo3, w.ktm_wo, SAMAUDIO_CLS_WO, attn_split, w_.x3a, w_.x3a_bytes, st));
-      else SA_TRY(run_gemm(p, bf16_, st));
+      SA_TRY(linear(p, w.wo, SAMAUDIO_CLS_WO, X3Operand{attn_split, w_.x3a, w_.x3a_bytes}, st));
     }
     SA_TRY(norm(w.ffn_norm, w.ffn_gs, w13_3));
     {
-      GemmParams p = lin(w_.xn, D, w.w13, M, 2 * F, D);
+      GemmParams p = lin(w_.xn, D, nullptr, M, 2 * F, D);
       p.swiglu = 1;
       p.out_act = w_.u; p.act_ld = F;
-      bool w2_pre = false;   // w13 writes w2's operand in split form where the launch it would make passes gemm_check
-      if (w13_3) {
-        if (w2_3 && w_.x3u && (size_t)M * 3 * F * 2 <= w_.x3u_bytes) {
-          GemmParams q = p;
-          q.out_act = w_.x3u; q.flags |= GEMM_FLAG_OUT_SPLIT3;
-          x3_operands(q, w_.x3a, w.w13_3, w.ktm_w13);
-          w2_pre = gemm_check(x3_share(q, SAMAUDIO_CLS_W13), true) == nullptr;
-        }
-        if (w2_pre) { p.out_act = w_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
-        SA_TRY(gemm_x3(p, w.w13_3, w.ktm_w13, SAMAUDIO_CLS_W13, w_.x3a, nullptr, 0, st));
-      } else {
-        SA_TRY(run_gemm(p, bf16_, st));
-      }
-      p = lin(w_.u, F, w.w2, M, D, F);  // h = h + down_proj(...)
+      // w13 writes w2's operand in split form where the launch it would make passes gemm_check
+      const bool w2_pre = w13_3 && w2_3 && x3_room(w_.x3u, w_.x3u_bytes, M, F) &&
+                          !gemm_check(x3_share(x3_split3_out(p, w_.x3a, w.w13, w_.x3u), SAMAUDIO_CLS_W13), true);
+      if (w2_pre) { p.out_act = w_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
+      SA_TRY(linear(p, w.w13, SAMAUDIO_CLS_W13, X3Operand{w_.x3a, nullptr, 0}, st));
+      p = lin(w_.u, F, nullptr, M, D, F);  // h = h + down_proj(...)
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
-      if (w2_3) SA_TRY(gemm_x3(p, w.w2_3, w.ktm_w2, SAMAUDIO_CLS_W2, w2_pre ? w_.x3u : nullptr, w_.x3u, w_.x3u_bytes, st));
-      else SA_TRY(run_gemm(p, bf16_, st));
+      SA_TRY(linear(p, w.w2, SAMAUDIO_CLS_W2, X3Operand{w2_pre ? w_.x3u : nullptr, w_.x3u, w_.x3u_bytes}, st));
     }
   }
   // final norm + output projection                                                  (hf:672-673)
   SA_TRY(norm(g_.norm, g_.norm_gs, wo3));
   {
-    GemmParams p = lin(w_.xn, D, g_.out_w, M, D, D);
+    GemmParams p = lin(w_.xn, D, nullptr, M, D, D);
     p.out_f32 = w_.out; p.f32_ld = D;
-    if (wo3) {   // (one output: the 16-bit operand copy of an fp32 context is the same fp32 tensor - out_act() below)
-      SA_TRY(gemm_x3(p, g_.out_w3, g_.ktm_out, SAMAUDIO_CLS_WO, w_.x3a, nullptr, 0, st));
-    } else {
-      p.out_act = w_.out_act; p.act_ld = D;
-      SA_TRY(run_gemm(p, bf16_, st));
-    }
+    // (x3: one output - the 16-bit operand copy of an fp32 context is the same fp32 tensor, out_act() in peav.h)
+    if (!wo3) { p.out_act = w_.out_act; p.act_ld = D; }
+    SA_TRY(linear(p, g_.out, SAMAUDIO_CLS_WO, X3Operand{w_.x3a, nullptr, 0}, st));
   }
   return Status{};
 }
@@ -390,8 +313,8 @@ Status Judge::finalize() {
   const int F32 = SAMAUDIO_DT_F32, AT = at_dtype_;
 #define NEEDF(field, name, ...) SA_TRY(reg_.need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
 #define NEEDW(field, name, ...) SA_TRY(reg_.need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
-  NEEDW(g_.cat_wh, "cat.wh", Bn, D);      // cat_audio_proj.weight[:, :D]   (separated / hypothesis half, judge.py:113-115)
-  NEEDW(g_.cat_wi, "cat.wi", Bn, D);      // cat_audio_proj.weight[:, D:]   (mixture half)
+  NEEDW(g_.cat_wh.w, "cat.wh", Bn, D);     // cat_audio_proj.weight[:, :D]   (separated / hypothesis half, judge.py:113-115)
+  NEEDW(g_.cat_wi.w, "cat.wi", Bn, D);     // cat_audio_proj.weight[:, D:]   (mixture half)
   NEEDF(g_.cat_b, "cat.b", Bn);
   NEEDW(g_.tp1_w, "tp1.w", D, TH);        // text_proj1 (no bias)
   NEEDW(g_.tp2_w, "tp2.w", Bn, D);        // text_proj2
@@ -407,8 +330,8 @@ Status Judge::finalize() {
 #undef NEEDF
 #undef NEEDW
   if (x3_ & SAMAUDIO_CLS_WO) {   // cat_audio_proj reads the transformer's output rows: K = D over all frames, with out.w's class
-    SA_TRY(reg_.need_twin("cat.wh.x3", Bn, 3L * D, &g_.cat_wh3, &g_.ktm_wh));
-    SA_TRY(reg_.need_twin("cat.wi.x3", Bn, 3L * D, &g_.cat_wi3, &g_.ktm_wi));
+    SA_TRY(reg_.need_twin("cat.wh.x3", Bn, 3L * D, g_.cat_wh));
+    SA_TRY(reg_.need_twin("cat.wi.x3", Bn, 3L * D, g_.cat_wi));
   }
   if (D2 > 4096) return fail(SAMAUDIO_ERR_ARG, "judge: finetune_transformer.dim > 4096");
   ready_ = true;
@@ -484,28 +407,22 @@ Status Judge::score(const float* in_lat, const float* sep_lat, int Bi, int cand,
   const bool cat3 = (x3_ & SAMAUDIO_CLS_WO) != 0;
   const void* hid3 = nullptr;
   if (cat3) {   // the hidden states once in split form, into the encoder's D-wide scratch (free until the next forward)
-    if (!enc_.x3_scratch() || (size_t)N1 * S * 3 * D * 2 > enc_.x3_scratch_bytes())
-      return fail(SAMAUDIO_ERR_WORKSPACE, "judge_score: SAMAUDIO_OPT_X3_CLASSES: the split operand does not fit the workspace plan");
+    SA_TRY(x3_fits(enc_.x3_scratch(), enc_.x3_scratch_bytes(), (long)N1 * S, D, "judge_score: ", "the split operand does not fit the workspace plan"));
     SA_HIP(launch_split3(enc_.out_f32(), D, enc_.x3_scratch(), (long)N1 * S, D, st));
     hid3 = enc_.x3_scratch();
   }
-  auto cat_gemm = [&](GemmParams p, const void* w3, bool ktm) -> Status {
-    if (!cat3) return run_gemm(p, bf16_, st);
-    x3_operands(p, hid3, w3, ktm);
-    p.a_off *= 3; p.a_bstride *= 3;
-    return run_gemm(x3_share(p, SAMAUDIO_CLS_WO), true, st);
-  };
+  const X3Operand hid_op{hid3, nullptr, 0};   // (batched launches, rows 1..T of each item: offsets into the split copy)
   {
-    GemmParams p = lin(hid, D, g_.cat_wi, T, Bn, D);  // mixture half, once per clip, with the bias
+    GemmParams p = lin(hid, D, nullptr, T, Bn, D);  // mixture half, once per clip, with the bias
     p.nbatch = Bi; p.a_off = D; p.a_bstride = (long)S * D; p.bias = g_.cat_b;
     p.out_f32 = w_.inp_part; p.f32_ld = Bn; p.f32_bstride = (long)T * Bn;
-    SA_TRY(cat_gemm(p, g_.cat_wi3, g_.ktm_wi));
+    SA_TRY(enc_.linear(p, g_.cat_wi, SAMAUDIO_CLS_WO, hid_op, st));
     for (int c = 0; c < cand; ++c) {  // hypothesis half of candidate c of every clip + the clip's mixture half
-      GemmParams q = lin(hid, D, g_.cat_wh, T, Bn, D);
+      GemmParams q = lin(hid, D, nullptr, T, Bn, D);
       q.nbatch = Bi; q.a_off = ((long)(Bi + c) * S + 1) * D; q.a_bstride = (long)cand * S * D;
       q.res = w_.inp_part; q.res_ld = Bn; q.res_bstride = (long)T * Bn;
       q.out_act = w_.audio; q.act_ld = Bn; q.act_off = (long)c * T * Bn; q.act_bstride = (long)cand * T * Bn;
-      SA_TRY(cat_gemm(q, g_.cat_wh3, g_.ktm_wh));
+      SA_TRY(enc_.linear(q, g_.cat_wh, SAMAUDIO_CLS_WO, hid_op, st));
     }
   }
   // text branch: layer_norm(text_proj2(text_proj1(pooled)))                            (judge.py:98-100,116-120)

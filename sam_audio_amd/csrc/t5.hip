@@ -11,28 +11,8 @@ struct samaudio_t5 {
 
 namespace sa {
 
-#define SA_TRY(expr)                     \
-  do {                                   \
-    Status _s = (expr);                  \
-    if (!_s.ok()) return _s;             \
-  } while (0)
-#define SA_HIP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return Status{SAMAUDIO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)}; \
-  } while (0)
-
 namespace {
 Status tfail(int code, const std::string& m) { return Status{code, m}; }
-
-GemmParams tlin(const void* A, long lda, const void* W, long M, int N, int K) {
-  GemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.A = A; p.W = W; p.lda = lda; p.kc = K; p.tap_stride = 0;
-  p.M = (int)M; p.N = N; p.K = K; p.nbatch = 1; p.alpha = 1.f; p.rows_per_gate = 1;
-  return p;
-}
 Status tgemm(const GemmParams& p, bool bf16, hipStream_t st) {
   if (const char* why = gemm_check(p, bf16)) return tfail(SAMAUDIO_ERR_ARG, std::string("t5 encoder: ") + why);
   SA_HIP(launch_gemm(p, bf16, st));
@@ -132,24 +112,24 @@ Status T5Encoder::encode(const long long* ids, const unsigned char* mask, int ro
     const LayerW& w = layers_[l];
     SA_HIP(rms(w.ln1, w_.xn, true));
     {
-      GemmParams p = tlin(w_.xn, D, w.wqkv, M, 3 * I, D);
+      GemmParams p = lin(w_.xn, D, w.wqkv, M, 3 * I, D);
       p.out_act = w_.qkv; p.act_ld = 3L * I;
       SA_TRY(tgemm(p, bf16_, st));
     }
     SA_HIP(launch_t5_attention(w_.qkv, mask, g_.rel_bias, w_.attn, bf16_, rows, tokens, c.heads, c.d_kv, c.max_len, 1.f, 0, st));
     {
-      GemmParams p = tlin(w_.attn, I, w.wo, M, D, I);  // h = h + o(attn)
+      GemmParams p = lin(w_.attn, I, w.wo, M, D, I);  // h = h + o(attn)
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
       SA_TRY(tgemm(p, bf16_, st));
     }
     SA_HIP(rms(w.ln2, w_.xn, true));
     {
-      GemmParams p = tlin(w_.xn, D, w.wi, M, F, D);  // act(wi(x))
+      GemmParams p = lin(w_.xn, D, w.wi, M, F, D);  // act(wi(x))
       p.act = c.act;
       p.out_act = w_.u; p.act_ld = F;
       SA_TRY(tgemm(p, bf16_, st));
-      p = tlin(w_.u, F, w.wo2, M, D, F);  // h = h + wo(...)
+      p = lin(w_.u, F, w.wo2, M, D, F);  // h = h + wo(...)
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
       SA_TRY(tgemm(p, bf16_, st));

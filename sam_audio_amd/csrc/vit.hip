@@ -11,29 +11,9 @@ struct samaudio_vit {
 
 namespace sa {
 
-#define SA_TRY(expr)                     \
-  do {                                   \
-    Status _s = (expr);                  \
-    if (!_s.ok()) return _s;             \
-  } while (0)
-#define SA_HIP(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess)                                                                 \
-      return Status{SAMAUDIO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)}; \
-  } while (0)
-
 namespace {
 Status vfail(int code, const std::string& m) { return Status{code, m}; }
 long vround_up(long v, long m) { return (v + m - 1) / m * m; }
-
-GemmParams vlin(const void* A, long lda, const void* W, long M, int N, int K) {
-  GemmParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.A = A; p.W = W; p.lda = lda; p.kc = K; p.tap_stride = 0;
-  p.M = (int)M; p.N = N; p.K = K; p.nbatch = 1; p.alpha = 1.f; p.rows_per_gate = 1;
-  return p;
-}
 Status vgemm(const GemmParams& p, bool bf16, hipStream_t st) {
   if (const char* why = gemm_check(p, bf16)) return vfail(SAMAUDIO_ERR_ARG, std::string("vision tower: ") + why);
   SA_HIP(launch_gemm(p, bf16, st));
@@ -159,7 +139,7 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
   // patch embedding: conv1 (k = stride = P, no bias) as one GEMM per frame over im2col rows, + position rows 1..   (oracle: conv2d, + positional_embedding)
   SA_HIP(launch_patchify(frames, w_.patches, bf16_, n, c.image_size, c.patch_size, kp_, st));
   {
-    GemmParams p = vlin(w_.patches, kp_, g_.patch_w, G2, W, kp_);
+    GemmParams p = lin(w_.patches, kp_, g_.patch_w, G2, W, kp_);
     p.nbatch = n; p.a_bstride = (long)G2 * kp_;
     p.res = g_.pos; p.res_ld = W; p.res_off = (long)cls * W; p.res_bstride = 0;
     p.out_f32 = emb; p.f32_ld = W; p.f32_bstride = (long)S * W; p.f32_off = (long)cls * W;
@@ -177,7 +157,7 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
     const LayerW& w = layers_[l];
     SA_HIP(launch_layernorm_rows(w_.h, W, w.ln1_w, w.ln1_b, nullptr, w_.xn, bf16_, M, W, eps, st));
     {
-      GemmParams p = vlin(w_.xn, W, w.wqkv, M, 3 * W, W);
+      GemmParams p = lin(w_.xn, W, w.wqkv, M, 3 * W, W);
       p.bias = w.bqkv;
       p.out_act = w_.qkv; p.act_ld = 3L * W;
       SA_TRY(vgemm(p, bf16_, st));
@@ -185,7 +165,7 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
     SA_HIP(launch_rope2d_split(w_.qkv, g_.rope_cos, g_.rope_sin, w_.Q, w_.K, w_.Vt, bf16_, n, S, Sp, H, hd_, st));
     SA_HIP(launch_self_attention_hd(w_.Q, w_.K, w_.Vt, w_.mask, w_.attn, bf16_, n, S, Sp, H, hd_, st));
     {
-      GemmParams p = vlin(w_.attn, W, w.wo, M, W, W);  // x = x + out_proj(attn)
+      GemmParams p = lin(w_.attn, W, w.wo, M, W, W);  // x = x + out_proj(attn)
       p.bias = w.bo;
       p.res = w_.h; p.res_ld = W;
       p.out_f32 = w_.h; p.f32_ld = W;
@@ -193,11 +173,11 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
     }
     SA_HIP(launch_layernorm_rows(w_.h, W, w.ln2_w, w.ln2_b, nullptr, w_.xn, bf16_, M, W, eps, st));
     {
-      GemmParams p = vlin(w_.xn, W, w.w1, M, F, W);  // act(c_fc(x))
+      GemmParams p = lin(w_.xn, W, w.w1, M, F, W);  // act(c_fc(x))
       p.bias = w.b1; p.act = c.act;
       p.out_act = w_.u; p.act_ld = F;
       SA_TRY(vgemm(p, bf16_, st));
-      p = vlin(w_.u, F, w.w2, M, W, F);  // x = x + c_proj(...)
+      p = lin(w_.u, F, w.w2, M, W, F);  // x = x + c_proj(...)
       p.bias = w.b2;
       p.res = w_.h; p.res_ld = W;
       p.out_f32 = w_.h; p.f32_ld = W;
@@ -212,25 +192,25 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
     if (c.use_ln_post) SA_HIP(launch_layernorm_rows(w_.h, W, g_.ln_post_w, g_.ln_post_b, nullptr, w_.xn, bf16_, M, W, eps, st));
     else SA_HIP(launch_to_act(w_.h, 0, W, 0, w_.xn, 0, bf16_, 1, M, W, W, 0, st));
     {
-      GemmParams p = vlin(w_.xn, W, g_.pool_wkv, M, 2 * W, W);  // k | v of every token
+      GemmParams p = lin(w_.xn, W, g_.pool_wkv, M, 2 * W, W);  // k | v of every token
       p.bias = g_.pool_bkv;
       p.out_act = w_.kv; p.act_ld = 2L * W;
       SA_TRY(vgemm(p, bf16_, st));
     }
     SA_HIP(launch_pool_attention(g_.pool_q, w_.kv, w_.pooled, bf16_, n, S, c.pool_heads, pool_hd_, st));
     {
-      GemmParams p = vlin(w_.pooled, W, g_.pool_wo, n, W, W);  // y = out_proj(attention)
+      GemmParams p = lin(w_.pooled, W, g_.pool_wo, n, W, W);  // y = out_proj(attention)
       p.bias = g_.pool_bo;
       p.out_f32 = w_.y; p.f32_ld = W;
       SA_TRY(vgemm(p, bf16_, st));
     }
     SA_HIP(launch_layernorm_rows(w_.y, W, g_.pool_ln_w, g_.pool_ln_b, nullptr, w_.yn, bf16_, n, W, eps, st));
     {
-      GemmParams p = vlin(w_.yn, W, g_.pool_w1, n, F, W);
+      GemmParams p = lin(w_.yn, W, g_.pool_w1, n, F, W);
       p.bias = g_.pool_b1; p.act = c.act;
       p.out_act = w_.u2; p.act_ld = F;
       SA_TRY(vgemm(p, bf16_, st));
-      p = vlin(w_.u2, F, g_.pool_w2, n, W, F);  // z = y + mlp(layernorm(y))
+      p = lin(w_.u2, F, g_.pool_w2, n, W, F);  // z = y + mlp(layernorm(y))
       p.bias = g_.pool_b2;
       p.res = w_.y; p.res_ld = W;
       p.out_f32 = w_.z; p.f32_ld = W;
@@ -253,7 +233,7 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
     pooled_act = w_.z_act;
   }
   {
-    GemmParams p = vlin(pooled_act, W, g_.proj, n, c.output_dim, W);  // features = pooled @ proj
+    GemmParams p = lin(pooled_act, W, g_.proj, n, c.output_dim, W);  // features = pooled @ proj
     p.out_f32 = features; p.f32_ld = c.output_dim;
     SA_TRY(vgemm(p, bf16_, st));
   }

@@ -34,7 +34,7 @@ os.environ["SAMAUDIO_NO_FOLD"] = "1"  # the folded cross-attention projection is
 @pytest.fixture(scope="session")
 def emu():
     srcs = [os.path.join(ROOT, "oracle", "emu", f) for f in ("emu_kernels.cpp", "emu_hip.cpp", "build.sh")]
-    srcs += [os.path.join(ROOT, "sam_audio_amd", "csrc", f) for f in ("engine.hip", "peav.hip", "api.hip", "engine.h",
+    srcs += [os.path.join(ROOT, "sam_audio_amd", "csrc", f) for f in ("engine.hip", "peav.hip", "api.hip", "engine.h", "host.h",
                                                                         "peav.h", "kernels.h", "common.h")]
     if not os.path.exists(EMU) or any(os.path.getmtime(s) > os.path.getmtime(EMU) for s in srcs):
         subprocess.check_call(["bash", os.path.join(ROOT, "oracle", "emu", "build.sh")])

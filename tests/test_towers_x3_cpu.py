@@ -171,6 +171,7 @@ def test_x3_transformer_on_the_simulator_with_late_dma():
 
 def test_x3_towers_in_the_emulation_dry_run():
     """No kernel of the product is linked there, so the weak launcher of the split-form GroupNorm is absent: the x3 path runs its
-    fallback (fp32 halo buffer + launch_split3) through the Judge and the span predictor."""
-    out = _run("1", ["-k", "judge_x3_forward or dedup or frame_x3"], 1200)
-    assert "3 passed" in out and "failed" not in out
+    fallback (fp32 halo buffer + launch_split3) through the Judge and the span predictor, and one transformer under every
+    per-class mask."""
+    out = _run("1", ["-k", "judge_x3_forward or dedup or frame_x3 or per_class_masks"], 1200)
+    assert "4 passed" in out and "failed" not in out

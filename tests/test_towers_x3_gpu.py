@@ -117,6 +117,39 @@ def test_peav_transformer_x3_matches_oracle(gpu, prec, masked):
     util.report(f"peav x3 last_hidden {prec}", hidden[:, 1:] * valid, last * valid, _bar(last * valid))
 
 
+TOWER_BITS = ("qkv", "wo", "w13", "w2", "patch")
+
+
+@pytest.mark.parametrize("prec", X3)
+def test_peav_x3_per_class_masks(gpu, prec):
+    """Every class bit of SAMAUDIO_CLS_X3_TOWER alone, and all of them but wo, on one transformer through samaudio_judge_encode
+    (2 rows, T = 50 with lengths 50 / 9: S = 51 is no multiple of 64 and the second row has a masked tail).  Only the twins of the
+    classes that are switched on are registered; finalize takes that, and the result is inside the bound of the full-mask test above
+    (the classes left in fp32 are exact, so a subset cannot need a wider one)."""
+    from sam_audio_amd.judge import convert_judge, convert_judge_x3, _register
+    tc = PEAVTransformerConfig(**G.TINY_TC)
+    cfg, sd, z, mask = _transformer_case(tc, 2, 50, [50, 9])
+    last, pooled = _oracle_transformer(sd, tc, z, mask)
+    valid = mask[..., None]
+    single = [hip.CLS[b] for b in TOWER_BITS] + [hip.X3_ATTENTION]
+    assert sum(single) == hip.CLS_X3_TOWER
+    for classes in single + [hip.CLS_X3_TOWER & ~hip.CLS["wo"]]:
+        m = _judge_unloaded(cfg, prec, gpu)
+        hip.check(m._lib.samaudio_judge_set_option(m._h, hip.OPT_X3_CLASSES, classes))
+        tensors = convert_judge(sd, cfg, torch.float32, gpu)
+        tensors.update(convert_judge_x3(tensors, cfg, HALF[prec], classes))
+        _register(m._lib.samaudio_judge_set_tensor, m._h, m._tensors, tensors)
+        hip.check(m._lib.samaudio_judge_finalize(m._h))
+        hidden = _encode(m, z, mask, gpu)
+        util.report(f"peav x3 classes {classes:#x} pooled {prec}", hidden[:, 0], pooled, _bar(pooled))
+        util.report(f"peav x3 classes {classes:#x} last_hidden {prec}", hidden[:, 1:] * valid, last * valid, _bar(last * valid))
+
+
+def _judge_unloaded(cfg, prec, gpu):
+    from sam_audio_amd.judge import SAMAudioJudgeModel
+    return SAMAudioJudgeModel(cfg, precision=prec, device=str(gpu), text_model=G.text_tower(cfg))
+
+
 @pytest.mark.skipif(SIM, reason="the 256x256 sharing walk at pe-av-large width: MI355X only (hours on the simulator)")
 @pytest.mark.parametrize("prec", X3)
 def test_peav_layer_at_large_width_on_the_sharing_walk(gpu, prec):
