@@ -181,6 +181,8 @@ int samaudio_set_workspace(samaudio_ctx* ctx, void* workspace, size_t bytes);
 /* the bits samaudio_judge_set_option / samaudio_frame_set_option accept (the PE-AV towers, see there) */
 #define SAMAUDIO_CLS_X3_TOWER \
   (SAMAUDIO_CLS_QKV | SAMAUDIO_CLS_WO | SAMAUDIO_CLS_W13 | SAMAUDIO_CLS_W2 | SAMAUDIO_CLS_PATCH | SAMAUDIO_X3_ATTENTION)
+/* the bits samaudio_vit_set_option accepts (the PE-Core vision tower, see there) */
+#define SAMAUDIO_CLS_X3_VIT (SAMAUDIO_CLS_QKV | SAMAUDIO_CLS_WO | SAMAUDIO_CLS_W13 | SAMAUDIO_CLS_W2 | SAMAUDIO_X3_ATTENTION)
 #define SAMAUDIO_CLS_F32_CAPABLE (SAMAUDIO_CLS_TIME | SAMAUDIO_CLS_OUT | SAMAUDIO_CLS_IN | SAMAUDIO_CLS_PREP | SAMAUDIO_CLS_YEMB)
 int samaudio_set_option(samaudio_ctx* ctx, int option, int value);
 
@@ -348,7 +350,25 @@ int samaudio_vit_create(const samaudio_vit_config* cfg, samaudio_vit** out);
 void samaudio_vit_destroy(samaudio_vit* v);
 int samaudio_vit_set_tensor(samaudio_vit* v, const char* name, const void* data, int dtype, int ndim,
                             const int64_t* shape);
+/* SAMAUDIO_OPT_X3_CLASSES for the vision tower - the only option it takes (fp32 contexts only; set it BEFORE samaudio_vit_finalize, which
+ * resolves the twins; query the workspace after it): value = mask of SAMAUDIO_CLS_X3_VIT bits, 0 (default) = the exact-fp32 launches,
+ * bit for bit what a context that never set the option computes.  Per layer:
+ *   QKV                   L<i>.wqkv as one 16-bit launch over K' = 3K on "L<i>.wqkv.x3" ([3W, 3W] = [W_hi | W_lo | W_hi], or K-tile-major
+ *                         [3K/64, N, 64]); the LayerNorm in front writes the split rows [lo | hi | hi] itself.  The same bit switches the
+ *                         pooling head's k|v projection of every token ("pool.wkv.x3" [2W, 3W])
+ *   WO                    "L<i>.wo.x3" [W, 3W]
+ *   W13                   the c_fc projection (bias + GELU / quick GELU) on "L<i>.w1.x3" [F, 3W]; with W2 on as well its epilogue writes
+ *                         c_proj's operand in split form where the 8-phase family takes the launch
+ *   W2                    "L<i>.w2.x3" [W, 3F]
+ *   SAMAUDIO_X3_ATTENTION the self-attention's two contractions on split operands (head width 64 or 128)
+ * What stays exact fp32, like the small launches of the PE-AV towers: the patch embedding (0.2 % of the flops, a batched launch with a
+ * row offset), ln_pre, the pooling attention itself, every launch of one row per frame (pool.wo, pool.w1, pool.w2, proj) and the L2
+ * normalisation.  Any other option or bit, or a 16-bit context: SAMAUDIO_ERR_ARG.  A twin that is missing: SAMAUDIO_ERR_WEIGHT from
+ * finalize, naming it.  Setting the option marks the context as not finalized, as samaudio_vit_set_tensor does. */
+int samaudio_vit_set_option(samaudio_vit* v, int option, int value);
 int samaudio_vit_finalize(samaudio_vit* v);
+/* Scratch of `frames` frames per encode; with SAMAUDIO_OPT_X3_CLASSES also the split operands of the classes that are on (tokens * 3 *
+ * width 16-bit elements for QKV / WO / W13, tokens * 3 * mlp_width for W2): query it AFTER setting the option. */
 size_t samaudio_vit_workspace_bytes(samaudio_vit* v, int frames);
 int samaudio_vit_set_workspace(samaudio_vit* v, void* workspace, size_t bytes);
 /* frames [n, 3, image_size, image_size] f32 (resized, scaled, normalised) -> features [n, output_dim] f32, L2-normalised
@@ -501,6 +521,12 @@ int samaudio_op_masked_groupnorm_silu_split3(const float* x, const float* w, con
                                              float eps, samaudio_stream stream);
 int samaudio_op_layernorm_rows(const float* x, int64_t x_ld, const float* w, const float* b, float* out_f32,
                                void* out_act, int precision, int64_t rows, int dim, float eps, samaudio_stream stream);
+/* the same with the output as a compensated GEMM operand (SAMAUDIO_OPT_X3_CLASSES; the PE-Core vision tower's LayerNorms in front of
+ * q|k|v, c_fc and pool.wkv): out3 [rows, 3 dim] in the library's 16-bit format = [lo | hi | hi] of the fp32 value, bitwise what
+ * samaudio_op_layernorm_rows (fp32 output) followed by samaudio_op_split3 writes.  dim % 8 == 0, dim <= 2048.  SAMAUDIO_ERR_STATE in a
+ * build of the library without the kernel. */
+int samaudio_op_layernorm_rows_split3(const float* x, int64_t x_ld, const float* w, const float* b, void* out3, int64_t rows,
+                                      int dim, float eps, samaudio_stream stream);
 /* SAMAUDIO_OPT_X3_CLASSES: the activation operand of a compensated GEMM - x [rows, k] f32 (row stride x_ld) -> out [rows, 3k]
  * in the library's 16-bit format = [lo | hi | hi] per row, hi = rn16(x) (clamped to the largest finite value), lo = rn16(x - hi) */
 int samaudio_op_split3(const float* x, int64_t x_ld, void* out, int64_t rows, int k, samaudio_stream stream);

@@ -294,6 +294,17 @@ int samaudio_op_layernorm_rows(const float* x, int64_t x_ld, const float* w, con
                                            (hipStream_t)stream), "layernorm_rows");
 }
 
+int samaudio_op_layernorm_rows_split3(const float* x, int64_t x_ld, const float* w, const float* b, void* out3, int64_t rows,
+                                      int dim, float eps, samaudio_stream stream) {
+  if (!x || !w || !b || !out3 || rows <= 0 || dim <= 0 || dim % 8 || dim > 2048 || x_ld % 4)
+    return bad("layernorm_rows_split3: null argument / dim % 8, dim <= 2048, x_ld % 4");
+  if (!sa::launch_layernorm_rows_split3) {
+    g_err = "layernorm_rows_split3: not in this build of the library";
+    return SAMAUDIO_ERR_STATE;
+  }
+  return hip_ret(sa::launch_layernorm_rows_split3(x, x_ld, w, b, out3, rows, dim, eps, (hipStream_t)stream), "layernorm_rows_split3");
+}
+
 int samaudio_op_split3(const float* x, int64_t x_ld, void* out, int64_t rows, int k, samaudio_stream stream) {
   if (!x || !out || rows <= 0 || k <= 0 || k % 8 || x_ld % 4) return bad("split3: k % 8, x_ld % 4");
   return hip_ret(sa::launch_split3(x, x_ld, out, rows, k, (hipStream_t)stream), "split3");

@@ -250,9 +250,11 @@ constexpr int GEMM_FLAG_OPND_ALT = 1024;
 // bit 11: W is K-TILE-MAJOR, [K/64][N][64] - the 64-element K slab of ALL N rows contiguous, so a launch streams W front to back
 // (8-phase family only, plain operands; weights.py ktm_layout)
 constexpr int GEMM_FLAG_W_KTM = 2048;
-// flags bit 12 (8-phase family, SwiGLU launches with a 16-bit output only): out_act receives the COMPENSATED-operand form of the
-// result - row stride act_ld = 3 * (N / 2), [lo | hi | hi] with hi = rn16(v), lo = rn16(v - hi) - i.e. the next GEMM's split
-// activation operand straight from the fp32 accumulators (SAMAUDIO_OPT_X3_CLASSES; kernels.hip split3_kernel is the stand-alone form)
+// flags bit 12 (8-phase family, launches with a 16-bit output only): out_act receives the COMPENSATED-operand form of the
+// result - [lo | hi | hi] with hi = rn16(v), lo = rn16(v - hi) - i.e. the next GEMM's split activation operand straight from the
+// fp32 accumulators (SAMAUDIO_OPT_X3_CLASSES; kernels.hip split3_kernel is the stand-alone form).  Two launch forms carry it: SwiGLU
+// (row stride act_ld = 3 * (N / 2)), and v = act(acc + bias) with act none / GELU / quick GELU (row stride act_ld = 3 * N, N % 64 == 0,
+// hi clamped to the format's largest finite value as split3_kernel does; no fp32 output, residual or gate) - the vision tower's c_fc
 constexpr int GEMM_FLAG_OUT_SPLIT3 = 4096;
 // flags bit 13 (fp32 kernel of gemm.hip only): COMPENSATED 16-bit multiply of fp32 operands, split ON THE FLY - the fp32 fragments of
 // a K slab are split in registers into hi = rn16(x), lo = rn16(x - hi) and multiplied as lo*hi + hi*lo + hi*hi on the 16-bit MFMA

@@ -580,8 +580,9 @@ const char* gemm_check(const GemmParams& p, bool is_bf16) {
   if (p.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_OPND_ALT))   // mixed mode: alt-format output / operands
     if (const char* e = need_8phase(p, is_bf16, gemm8_alt_ok, "gemm: alt 16-bit format: plain 16-bit launches with a lean epilogue only",
                                     "gemm: alt 16-bit format: the tile policy did not pick the 8-phase family for this launch")) return e;
-  if (p.flags & GEMM_FLAG_OUT_SPLIT3)   // compensated-operand output: the register epilogue, SwiGLU launches
-    if (const char* e = need_8phase(p, is_bf16, gemm8_split3_ok, "gemm: split3 output: 16-bit SwiGLU launches with a lean epilogue only",
+  if (p.flags & GEMM_FLAG_OUT_SPLIT3)   // compensated-operand output: the register epilogue, SwiGLU or bias + GELU launches
+    if (const char* e = need_8phase(p, is_bf16, gemm8_split3_ok,
+                                    "gemm: split3 output: 16-bit launches with the register epilogue only (SwiGLU, or bias + none / GELU / quick GELU; one 16-bit output, no residual, gate or fp32 output)",
                                     "gemm: split3 output: the tile policy did not pick the 8-phase family for this launch")) return e;
   if (p.flags & GEMM_FLAG_X3_SHARE)   // operand-sharing walk of K-concatenated split operands: plain launches
     if (const char* e = need_8phase(p, is_bf16, gemm8_share_ok, "gemm: shared split operands (flags bit 15): plain 16-bit launches with K' = 3K, K % 64 == 0",

@@ -319,6 +319,64 @@ __device__ __forceinline__ void epilogue8_linear(const GemmParams& p, f32x4_t (&
   }
 }
 
+// Bias + activation with the result in the compensated-operand form (GEMM_FLAG_OUT_SPLIT3 on a launch without SwiGLU: the vision
+// tower's c_fc feeding c_proj): v = act(acc + bias), act = none | GELU | quick GELU, ONE 16-bit output with rows of 3 N elements
+// [lo | hi | hi] - nothing else (gemm8_linear_epilogue).  Register form like epilogue8_linear (a lane's 4 columns, two column blocks
+// paired with v_permlane16_swap into 16-byte stores).  The same expressions as the general epilogue (alpha is 1) and the split of
+// split3_kernel (hi clamped to the format's largest finite value): the bits of an fp32 output followed by launch_split3.  It lives in
+// kernel instantiations of its own (template parameter ACT3 of the three kernels below, chosen by the launchers): the erf expansion
+// of 8 x 16 elements per wave is large, and inside the shared epilogue it moved register spills of the 256x256 kernels into their K
+// loops (tests/test_isa_cpu.py) - the instantiations every other launch runs on are the code they were.
+template <int NH>
+__device__ __forceinline__ void epilogue8_act_split3(const GemmParams& p, f32x4_t (&acc)[NH * 4][4], const int b,
+                                                     const int m_wave0, const int n_wave0, const int lane) {
+#pragma clang fp contract(off)
+  constexpr int NI = NH * 4;
+  const int lr = lane & 15, lg = lane >> 4;
+  if (n_wave0 >= p.N) return;   // N % 64 == 0: a wave's 64 columns are all inside or all outside
+  const int m_last = p.M - 1;
+  bf16_t* const act0 = (bf16_t*)p.out_act + p.act_off + (long)b * p.act_bstride;
+  const bool has_b = p.bias != nullptr;
+  const int nc0 = n_wave0 + lg * 4;                                   // + 16 j: the lane's own 4 columns
+  const int cs0 = n_wave0 + (lg & 1) * 16 + (lg >> 1) * 8;            // + 32 jp: 8 consecutive columns after the swap
+  const int act = p.act;
+  float4 cb[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cb[j] = has_b ? *(const float4*)(p.bias + nc0 + 16 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
+  auto activate = [&](float x) { return act == ACT_GELU ? gelu_f(x) : (act == ACT_QUICK_GELU ? quick_gelu_f(x) : x); };
+  auto clamp16 = [](float x) { return fminf(fmaxf(x, -kH16Max), kH16Max); };
+#pragma unroll
+  for (int I = 0; I < NI; ++I) {
+    const int m = m_wave0 + I * 16 + lr;
+#pragma unroll
+    for (int jp = 0; jp < 2; ++jp) {
+      unsigned lo[2], hi[2], rlo[2], rhi[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int j = 2 * jp + h;
+        float v0 = acc[I][j][0], v1 = acc[I][j][1], v2 = acc[I][j][2], v3 = acc[I][j][3];
+        if (has_b) { v0 += cb[j].x; v1 += cb[j].y; v2 += cb[j].z; v3 += cb[j].w; }
+        v0 = activate(v0); v1 = activate(v1); v2 = activate(v2); v3 = activate(v3);
+        lo[h] = pack_h16x2(clamp16(v0), clamp16(v1));
+        hi[h] = pack_h16x2(clamp16(v2), clamp16(v3));
+        rlo[h] = pack_h16x2(v0 - h16_lo(lo[h]), v1 - h16_hi(lo[h]));
+        rhi[h] = pack_h16x2(v2 - h16_lo(hi[h]), v3 - h16_hi(hi[h]));
+      }
+      const auto s0 = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
+      const auto s1 = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
+      const auto t0 = __builtin_amdgcn_permlane16_swap(rlo[0], rlo[1], false, false);
+      const auto t1 = __builtin_amdgcn_permlane16_swap(rhi[0], rhi[1], false, false);
+      if (m <= m_last) {
+        bf16_t* row = act0 + (long)m * p.act_ld + cs0 + 32 * jp;
+        const uint4 h4 = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+        *(uint4*)row = make_uint4(t0[0], t1[0], t0[1], t1[1]);
+        *(uint4*)(row + p.N) = h4;
+        *(uint4*)(row + 2 * p.N) = h4;
+      }
+    }
+  }
+}
+
 // The same contract as epilogue8_linear for launches WITH an fp32 output / residual (the adaLN-gated residual updates of
 // the DiT: wo, w2, the folded cross-attention projection, the patcher): those move 10 bytes per element and are bound by
 // memory transactions, and the accumulator layout gives a wave instruction 16 rows x 64 bytes - sixteen half lines (round 4,
@@ -484,7 +542,7 @@ __device__ __forceinline__ void prefetch_lines(const GemmParams& p, const int wg
 // CONV: A's k axis is split into taps (implicit convolutions: kc < K); plain GEMMs compile the per-K-tile tap walk - a per-lane loop
 // under an exec mask, twice per K-tile - out of the K loop (3 - 5 % faster, round 3).
 // ALT: the operands are in the alt 16-bit format (mixed mode: bf16 inside the fp16 build) - the MFMA opcode is the only difference
-template <bool CONV, bool ALT = false>
+template <bool CONV, bool ALT = false, bool ACT3 = false>   // ACT3: epilogue8_act_split3 only
 __global__ __launch_bounds__(512) void gemm8_kernel(const GemmParams p, const int tile_count) {
   constexpr int BM = 256, BN = 256, BK = 64, HT = 128 * 128;
   // [HA0, HA1, HB0, HB1][K-tile buffer]: the two buffers of a half-tile are 16 KiB apart, so that every fragment read of a wave
@@ -708,7 +766,9 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmParams p, const in
 #undef SA_G8P_READ_W
 #undef SA_G8P_READ_A
 
-  if (p.flags & GEMM_FLAG_EPI_LINEAR) {
+  if constexpr (ACT3) {
+    epilogue8_act_split3<2>(p, acc, b, m0 + wr * 128, n0 + wc * 64, lane);
+  } else if (p.flags & GEMM_FLAG_EPI_LINEAR) {
     epilogue8_linear<2>(p, acc, b, m0 + wr * 128, n0 + wc * 64, lane);
   } else {
     __syncthreads();
@@ -741,6 +801,7 @@ __global__ __launch_bounds__(512) void gemm8_kernel(const GemmParams p, const in
 // phases in front of its vmcnt(4) instead of 2 - 3; profiles/r6_call24: no gain) - the loop does not wait for its loads - and issuing the
 // last 2 / 4 MFMAs of a phase behind its closing barrier (the wave arrives early, the other group's MFMAs queue behind its own:
 // profiles/r6_call25, 5 % SLOWER - the strict alternation of the two groups is what the loop lives on).
+template <bool ACT3 = false>   // ACT3: epilogue8_act_split3 only
 __global__ __launch_bounds__(512) void gemm8x_kernel(const GemmParams p, const int tile_count) {
   constexpr int BM = 256, BN = 256, HT = 128 * 128;
   __shared__ __attribute__((aligned(16))) char smem[4 * 2 * HT];   // [HA0, HA1, HB0, HB1][buffer] as gemm8_kernel
@@ -936,7 +997,9 @@ __global__ __launch_bounds__(512) void gemm8x_kernel(const GemmParams p, const i
 #undef SA_G8X_READ_W
 #undef SA_G8X_READ_A
 
-  if (p.flags & GEMM_FLAG_EPI_LINEAR) {
+  if constexpr (ACT3) {
+    epilogue8_act_split3<2>(p, acc, b, m0 + wr * 128, n0 + wc * 64, lane);
+  } else if (p.flags & GEMM_FLAG_EPI_LINEAR) {
     epilogue8_linear<2>(p, acc, b, m0 + wr * 128, n0 + wc * 64, lane);
   } else {
     __syncthreads();
@@ -987,7 +1050,7 @@ template <int N> __device__ __forceinline__ void wait_vm_lit() {   // literal co
   else if constexpr (N == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
 }
-template <bool PIPE, bool CONV, bool ALT = false, int PROD = -1>
+template <bool PIPE, bool CONV, bool ALT = false, int PROD = -1, bool ACT3 = false>   // ACT3: epilogue8_act_split3 only
 __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const GemmParams p, const int skip256) {
   constexpr int BM = 128, BN = 128, BK = 64, TB = 128 * 128;  // TB: bytes of one operand tile (128 rows x 128 B)
   constexpr int S = PIPE ? 4 : 2;
@@ -1201,6 +1264,10 @@ __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const Gem
     } else {
       step(t, I0{}, std::false_type{});
     }
+    if constexpr (ACT3) {
+      epilogue8_act_split3<1>(p, acc, b, m0 + wr * 64, n0 + wc * 64, lane);
+      return;
+    }
     if (p.flags & GEMM_FLAG_EPI_LINEAR) {
       epilogue8_linear<1>(p, acc, b, m0 + wr * 64, n0 + wc * 64, lane);
       return;
@@ -1240,6 +1307,10 @@ __global__ __launch_bounds__(PROD >= 0 ? 512 : 256) void gemm8s_kernel(const Gem
         for (int i = 0; i < 4; ++i)
           acc[i][j] = ALT ? SA_MFMA_16x16x32_ALT(wf[j][ks], af[i][ks], acc[i][j]) : SA_MFMA_16x16x32(wf[j][ks], af[i][ks], acc[i][j]);
   }
+  if constexpr (ACT3) {
+    epilogue8_act_split3<1>(p, acc, b, m0 + wr * 64, n0 + wc * 64, lane);
+    return;
+  }
   if (p.flags & GEMM_FLAG_EPI_LINEAR) {
     epilogue8_linear<1>(p, acc, b, m0 + wr * 64, n0 + wc * 64, lane);
     return;
@@ -1261,10 +1332,15 @@ static bool gemm8_wide(const GemmParams& p) {
 static int gemm8_linear_epilogue(const GemmParams& p) {
   const int mode = debug_flag(DBG_GEMM8_EPILOGUE);
   if (mode == DBG_EPI_GENERAL) return 0;
-  if (p.act != ACT_NONE || p.chan_mod || p.c_ld_rel || (p.flags & GEMM_FLAG_EPI_ACC) || p.N % 64 || p.alpha != 1.f) return 0;
+  // split-form output without SwiGLU: v = act(acc + bias) with GELU / quick GELU allowed, one 16-bit output and nothing else.  A launch
+  // WITHOUT the flag that carries an activation keeps the general epilogue
+  const bool split3 = (p.flags & GEMM_FLAG_OUT_SPLIT3) != 0, split3_act = split3 && !p.swiglu;
+  if (p.act != ACT_NONE && !(split3_act && (p.act == ACT_GELU || p.act == ACT_QUICK_GELU))) return 0;
+  if (p.chan_mod || p.c_ld_rel || (p.flags & GEMM_FLAG_EPI_ACC) || p.N % 64 || p.alpha != 1.f) return 0;
   if (!p.out_act && !p.out_f32) return 0;
   if (p.swiglu && (!p.out_act || p.out_f32 || p.bias || p.gate || p.res)) return 0;
-  if ((p.flags & GEMM_FLAG_OUT_SPLIT3) && (!p.swiglu || (p.flags & GEMM_FLAG_OUT_ALT) || (p.N / 2) % 8)) return 0;   // (gemm8_split3_ok)
+  if (split3 && ((p.flags & GEMM_FLAG_OUT_ALT) || (p.swiglu && (p.N / 2) % 8))) return 0;   // (gemm8_split3_ok)
+  if (split3_act && (!p.out_act || p.out_f32 || p.res || p.gate || p.gate_tab || gemm8_wide(p) || (p.flags & GEMM_FLAG_OPND_ALT))) return 0;
   if (p.bias && (p.gate || p.gate_tab)) return 0;
   if (p.gate_tab && !p.gate) return 0;
   auto al = [](long v, long a) { return v % a == 0; };
@@ -1272,10 +1348,13 @@ static int gemm8_linear_epilogue(const GemmParams& p) {
     return 0;
   if (p.gate && (p.rows_per_gate <= 0 || (long)p.M * p.nbatch >= (1L << 31))) return 0;
   // 16-byte alignment of the fp32 operands: gemm2_ok(), checked by the policy for every launch of this file
-  if (p.swiglu || mode == DBG_EPI_LINEAR) return GEMM_FLAG_EPI_LINEAR;
+  if (p.swiglu || split3 || mode == DBG_EPI_LINEAR) return GEMM_FLAG_EPI_LINEAR;
   if (mode == DBG_EPI_ROWS) return GEMM_FLAG_EPI_ROWS;
   return p.out_f32 || p.res ? GEMM_FLAG_EPI_ROWS : GEMM_FLAG_EPI_LINEAR;
 }
+// the launch runs on the ACT3 instantiations: GEMM_FLAG_OUT_SPLIT3 without SwiGLU (well-formed: gemm8_split3_ok - plain operands of the
+// library's own format, the register epilogue)
+static bool gemm8_act3(const GemmParams& p) { return (p.flags & GEMM_FLAG_OUT_SPLIT3) && !p.swiglu; }
 static GemmParams with_epilogue_choice(const GemmParams& p) {
   GemmParams q = p;
   q.flags = (q.flags & ~GEMM_FLAG_EPI_LEAN) | gemm8_linear_epilogue(p);
@@ -1294,7 +1373,8 @@ static GemmParams with_epilogue_choice(const GemmParams& p) {
 template <bool PIPE, int PROD>
 static void launch_gemm8s_as(const GemmParams& p, bool conv, dim3 grid, int skip256, hipStream_t st) {
   const dim3 block(PROD >= 0 ? 512 : 256);
-  if (conv) hipLaunchKernelGGL((gemm8s_kernel<PIPE, true, false, PROD>), grid, block, 0, st, p, skip256);
+  if (gemm8_act3(p)) hipLaunchKernelGGL((gemm8s_kernel<PIPE, false, false, PROD, true>), grid, block, 0, st, p, skip256);
+  else if (conv) hipLaunchKernelGGL((gemm8s_kernel<PIPE, true, false, PROD>), grid, block, 0, st, p, skip256);
   else if (p.flags & GEMM_FLAG_OPND_ALT) hipLaunchKernelGGL((gemm8s_kernel<PIPE, false, true, PROD>), grid, block, 0, st, p, skip256);
   else hipLaunchKernelGGL((gemm8s_kernel<PIPE, false, false, PROD>), grid, block, 0, st, p, skip256);
 }
@@ -1307,9 +1387,10 @@ static void launch_gemm8s_grid(const GemmParams& p, bool pipe, bool conv, dim3 g
     default: return launch_gemm8s_as<true, 2>(p, conv, grid, skip256, st);   // (DBG_ROLES_PROD2 = the shipped form)
   }
 }
-// GEMM_FLAG_OUT_SPLIT3 is well-formed: only the register epilogue of a SwiGLU launch writes the split form
+// GEMM_FLAG_OUT_SPLIT3 is well-formed: only the register epilogue writes the split form - of a SwiGLU launch, or of a bias + (none | GELU |
+// quick GELU) launch with that one output (no fp32 output, residual or gate: gemm8_linear_epilogue)
 bool gemm8_split3_ok(const GemmParams& p) {
-  return !(p.flags & GEMM_FLAG_OUT_SPLIT3) || (p.swiglu && p.out_act && gemm8_linear_epilogue(p) == GEMM_FLAG_EPI_LINEAR);
+  return !(p.flags & GEMM_FLAG_OUT_SPLIT3) || (p.out_act && gemm8_linear_epilogue(p) == GEMM_FLAG_EPI_LINEAR);
 }
 // GEMM_FLAG_X3_SHARE is well-formed: plain operands within 32-bit offsets (no implicit convolution), K' = 3K with K a multiple of 64, the
 // library's own operand format
@@ -1345,7 +1426,11 @@ static void launch_gemm8_tiles(const GemmParams& p, dim3 grid, int tile_count, h
   // the other group's launch after every tile.
   if (debug_flag(DBG_GEMM8_NOT_PERSISTENT) != 1 && grid.x > 256) grid.x = 256;
   if (p.pf_ptr && p.pf_bytes > 0 && tile_count == 0 && grid.x < 256) grid.x = 256;   // idle CUs warm the next launch's weights
-  if ((p.flags & GEMM_FLAG_X3_SHARE) && !gemm8_wide(p) && !(p.flags & GEMM_FLAG_OPND_ALT)) hipLaunchKernelGGL(gemm8x_kernel, grid, block, 0, st, p, tile_count);
+  const bool act3 = gemm8_act3(p);
+  if ((p.flags & GEMM_FLAG_X3_SHARE) && !gemm8_wide(p) && !(p.flags & GEMM_FLAG_OPND_ALT)) {
+    if (act3) hipLaunchKernelGGL(gemm8x_kernel<true>, grid, block, 0, st, p, tile_count);
+    else hipLaunchKernelGGL(gemm8x_kernel<false>, grid, block, 0, st, p, tile_count);
+  } else if (act3) hipLaunchKernelGGL((gemm8_kernel<false, false, true>), grid, block, 0, st, p, tile_count);
   else if (gemm8_wide(p)) hipLaunchKernelGGL((gemm8_kernel<true>), grid, block, 0, st, p, tile_count);
   else if (p.flags & GEMM_FLAG_OPND_ALT) hipLaunchKernelGGL((gemm8_kernel<false, true>), grid, block, 0, st, p, tile_count);   // alt-format operands
   else hipLaunchKernelGGL((gemm8_kernel<false>), grid, block, 0, st, p, tile_count);

@@ -144,8 +144,8 @@ hipError_t launch_gemm8s(const GemmParams& p, hipStream_t st);
 // gemm8.hip: GEMM_FLAG_OUT_ALT / GEMM_FLAG_OPND_ALT (mixed mode: out_act written / operands read in the alt 16-bit format) are
 // well-formed; only the 8-phase family implements them
 bool gemm8_alt_ok(const GemmParams& p);
-// gemm8.hip: GEMM_FLAG_OUT_SPLIT3 (out_act in the compensated-operand form [lo | hi | hi]) is well-formed: SwiGLU launches of the
-// 8-phase family with a 16-bit output only
+// gemm8.hip: GEMM_FLAG_OUT_SPLIT3 (out_act in the compensated-operand form [lo | hi | hi]) is well-formed: launches of the 8-phase
+// family with that 16-bit output only - SwiGLU, or bias + (none | GELU | quick GELU) without residual, gate or fp32 output
 bool gemm8_split3_ok(const GemmParams& p);
 // gemm2.hip: dilated k = 7 'same' convolution C -> C (C = 64 / 96 / 128 / 192) with the activation halo tile resident in
 // LDS; bitwise equal to the implicit GEMM of the 32x32x16 family
@@ -319,6 +319,11 @@ __attribute__((weak)) hipError_t launch_masked_groupnorm_silu_split3(const float
 // out[m,:] = LayerNorm(x[m,:]) * w + b; either output may be null
 hipError_t launch_layernorm_rows(const float* x, long x_ld, const float* w, const float* b, float* out_f32,
                                  void* out_act, bool bf16, long M, int D, float eps, hipStream_t st);
+// the same with the result as a compensated GEMM operand (SAMAUDIO_OPT_X3_CLASSES): out3 [M, 3D] 16-bit = [lo | hi | hi] of the fp32
+// value - the bits of launch_layernorm_rows(..., out_f32) followed by launch_split3; D <= 2048.  weak: the CPU emulation of the
+// launchers (oracle/emu) does not define it - the parity hook then answers SAMAUDIO_ERR_STATE (api.hip)
+__attribute__((weak)) hipError_t launch_layernorm_rows_split3(const float* x, long x_ld, const float* w, const float* b, void* out3,
+                                                              long M, int D, float eps, hipStream_t st);
 // scores[b][j] = (masked mean over frames of hidden[b][1+t][:]) . head_w[j][:] * std[j] + mean[j]
 hipError_t launch_judge_pool_head(const float* hidden, const unsigned char* mask_s, const float* head_w,
                                   const float* mean, const float* std_, float* out, int B, int T, int D,

@@ -299,6 +299,72 @@ __global__ __launch_bounds__(256) void layernorm_rows_reg_kernel(const float* __
   }
 }
 
+// The register form with the result written as a compensated GEMM operand (SAMAUDIO_OPT_X3_CLASSES, kernels.hip split3_kernel):
+// out [M, 3D] 16-bit = [lo | hi | hi] per row, hi = rn16(o) clamped to the format's largest finite value, lo = rn16(o - hi), both
+// roundings the hardware conversion.  The row arithmetic is layernorm_rows_reg_kernel's, expression for expression (same per-lane
+// summation order, same fp32 expression for o), so the bits are those of launch_layernorm_rows(..., out_f32) followed by
+// launch_split3 - without the M x D fp32 round trip and the second launch (the vision tower's LayerNorms in front of q|k|v, c_fc
+// and the pooling head's k|v projection).
+template <int MAXV>
+__global__ __launch_bounds__(256) void layernorm_rows_split3_kernel(const float* __restrict__ x, long x_ld,
+                                                                    const float* __restrict__ w, const float* __restrict__ b,
+                                                                    bf16_t* __restrict__ out, long M, int D, float eps) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int lane = threadIdx.x & 63;
+  const float4* xr = (const float4*)(x + row * x_ld);
+  const int n4 = D >> 2;
+  float4 v[MAXV], ww[MAXV], bb[MAXV];
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < MAXV; ++k) {
+    const int i = lane + 64 * k;
+    const bool in = i < n4;
+    v[k] = in ? xr[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    ww[k] = in ? ((const float4*)w)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    bb[k] = in ? ((const float4*)b)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (in) s += v[k].x + v[k].y + v[k].z + v[k].w;
+  }
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < MAXV; ++k) {
+    if (lane + 64 * k >= n4) continue;
+    const float a = v[k].x - mean, c = v[k].y - mean, d = v[k].z - mean, e = v[k].w - mean;
+    q += a * a + c * c + d * d + e * e;
+  }
+  const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
+  bf16_t* orow = out + row * 3 * D;
+#pragma unroll
+  for (int k = 0; k < MAXV; ++k) {
+    const int i = lane + 64 * k;
+    if (i >= n4) continue;
+    const float o0 = (v[k].x - mean) * rstd * ww[k].x + bb[k].x, o1 = (v[k].y - mean) * rstd * ww[k].y + bb[k].y,
+                o2 = (v[k].z - mean) * rstd * ww[k].z + bb[k].z, o3 = (v[k].w - mean) * rstd * ww[k].w + bb[k].w;
+    uint2 hi, lo;
+    hi.x = pack_h16x2(fminf(fmaxf(o0, -kH16Max), kH16Max), fminf(fmaxf(o1, -kH16Max), kH16Max));
+    hi.y = pack_h16x2(fminf(fmaxf(o2, -kH16Max), kH16Max), fminf(fmaxf(o3, -kH16Max), kH16Max));
+    lo.x = pack_h16x2(o0 - h16_lo(hi.x), o1 - h16_hi(hi.x));
+    lo.y = pack_h16x2(o2 - h16_lo(hi.y), o3 - h16_hi(hi.y));
+    bf16_t* dst = orow + 4 * i;
+    *(uint2*)dst = lo;
+    *(uint2*)(dst + D) = hi;
+    *(uint2*)(dst + 2L * D) = hi;
+  }
+}
+
+hipError_t launch_layernorm_rows_split3(const float* x, long x_ld, const float* w, const float* b, void* out3, long M, int D,
+                                        float eps, hipStream_t st) {
+  if (D % 4 || D > 256 * 8 || x_ld % 4 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)b & 15) || ((uintptr_t)out3 & 7))
+    return hipErrorInvalidValue;
+  dim3 grid((unsigned)((M + 3) / 4)), block(256);
+  if (D <= 256 * 4)   // the vision tower's width (1024) and smaller
+    hipLaunchKernelGGL((layernorm_rows_split3_kernel<4>), grid, block, 0, st, x, x_ld, w, b, (bf16_t*)out3, M, D, eps);
+  else
+    hipLaunchKernelGGL((layernorm_rows_split3_kernel<8>), grid, block, 0, st, x, x_ld, w, b, (bf16_t*)out3, M, D, eps);
+  return hipGetLastError();
+}
+
 hipError_t launch_layernorm_rows(const float* x, long x_ld, const float* w, const float* b, float* out_f32,
                                  void* out_act, bool bf16, long M, int D, float eps, hipStream_t st) {
   dim3 grid((unsigned)((M + 3) / 4)), block(256);

@@ -35,6 +35,18 @@ Status VisionTower::set_tensor(const char* name, const void* p, int dtype, int n
   return reg_.set(name, p, dtype, ndim, shape);
 }
 
+Status VisionTower::set_option(int option, int value) {
+  if (option != SAMAUDIO_OPT_X3_CLASSES) return vfail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: unknown option");
+  if (bf16_)
+    return vfail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: SAMAUDIO_OPT_X3_CLASSES applies to fp32 contexts (compensated 16-bit operands under fp32 storage)");
+  if (value & ~SAMAUDIO_CLS_X3_VIT)
+    return vfail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: SAMAUDIO_OPT_X3_CLASSES: only qkv, wo, w13, w2 and SAMAUDIO_X3_ATTENTION");
+  x3_ = value;
+  ready_ = false;     // finalize resolves the twins of the switched classes
+  planned_n_ = 0;     // ... and the workspace plan holds the split scratch of the classes that are on
+  return Status{};
+}
+
 Status VisionTower::finalize() {
   const samaudio_vit_config& c = cfg_;
   if (c.image_size <= 0 || c.patch_size <= 0 || c.image_size % c.patch_size || c.width <= 0 || c.layers < 0 ||
@@ -63,15 +75,21 @@ Status VisionTower::finalize() {
     const std::string L = "L" + std::to_string(i) + ".";
     LayerW& w = layers_[i];
     NEEDF(w.ln1_w, L + "ln1.w", W); NEEDF(w.ln1_b, L + "ln1.b", W);
-    NEEDW(w.wqkv, L + "wqkv", 3 * W, W); NEEDF(w.bqkv, L + "bqkv", 3 * W);
-    NEEDW(w.wo, L + "wo", W, W); NEEDF(w.bo, L + "bo", W);
+    NEEDW(w.wqkv.w, L + "wqkv", 3 * W, W); NEEDF(w.bqkv, L + "bqkv", 3 * W);
+    NEEDW(w.wo.w, L + "wo", W, W); NEEDF(w.bo, L + "bo", W);
     NEEDF(w.ln2_w, L + "ln2.w", W); NEEDF(w.ln2_b, L + "ln2.b", W);
-    NEEDW(w.w1, L + "w1", F, W); NEEDF(w.b1, L + "b1", F);
-    NEEDW(w.w2, L + "w2", W, F); NEEDF(w.b2, L + "b2", W);
+    NEEDW(w.w1.w, L + "w1", F, W); NEEDF(w.b1, L + "b1", F);
+    NEEDW(w.w2.w, L + "w2", W, F); NEEDF(w.b2, L + "b2", W);
+    // SAMAUDIO_OPT_X3_CLASSES: the twins [W_hi | W_lo | W_hi] of the classes that are switched on
+    if (x3(SAMAUDIO_CLS_QKV)) SA_TRY(reg_.need_twin(L + "wqkv.x3", 3 * W, 3L * W, w.wqkv));
+    if (x3(SAMAUDIO_CLS_WO)) SA_TRY(reg_.need_twin(L + "wo.x3", W, 3L * W, w.wo));
+    if (x3(SAMAUDIO_CLS_W13)) SA_TRY(reg_.need_twin(L + "w1.x3", F, 3L * W, w.w1));
+    if (x3(SAMAUDIO_CLS_W2)) SA_TRY(reg_.need_twin(L + "w2.x3", W, 3L * F, w.w2));
   }
   if (c.pool_type == 2) {
     NEEDF(g_.pool_q, "pool.q", W);             // in_proj_q(probe): the same query for every frame
-    NEEDW(g_.pool_wkv, "pool.wkv", 2 * W, W); NEEDF(g_.pool_bkv, "pool.bkv", 2 * W);
+    NEEDW(g_.pool_wkv.w, "pool.wkv", 2 * W, W); NEEDF(g_.pool_bkv, "pool.bkv", 2 * W);
+    if (x3(SAMAUDIO_CLS_QKV)) SA_TRY(reg_.need_twin("pool.wkv.x3", 2 * W, 3L * W, g_.pool_wkv));   // the same launch form on every token
     NEEDW(g_.pool_wo, "pool.wo", W, W); NEEDF(g_.pool_bo, "pool.bo", W);
     NEEDF(g_.pool_ln_w, "pool.ln.w", W); NEEDF(g_.pool_ln_b, "pool.ln.b", W);
     NEEDW(g_.pool_w1, "pool.w1", F, W); NEEDF(g_.pool_b1, "pool.b1", F);
@@ -80,6 +98,7 @@ Status VisionTower::finalize() {
   NEEDW(g_.proj, "proj", c.output_dim, W);     // proj^T (features = pooled @ proj)
 #undef NEEDF
 #undef NEEDW
+  if (x3_ && W > 256 * 8) return vfail(SAMAUDIO_ERR_ARG, "vision tower: SAMAUDIO_OPT_X3_CLASSES needs width <= 2048 (launch_layernorm_rows_split3)");
   ready_ = true;
   return Status{};
 }
@@ -98,7 +117,14 @@ void VisionTower::plan(Bump& b, int n, bool assign) {
   unsigned char* mask = (unsigned char*)b.take((size_t)M);
   void* kv = act(M * 2 * W); void* pooled = act((long)n * W); float* y = f32((long)n * W); void* yn = act((long)n * W);
   void* u2 = act((long)n * F); float* z = f32((long)n * W); void* z_act = act((long)n * W);
+  // SAMAUDIO_OPT_X3_CLASSES: the split operands, 3 x 16 bits per element, only those a switched class reads.  x3a serves the W-wide
+  // operands one after the other: the LayerNorm rows (QKV, W13, pool.wkv), then the attention's split output / the split of its fp32
+  // output (WO) - each is consumed by the next launch; x3u is the MLP hidden (W2)
+  const size_t x3a_bytes = x3(SAMAUDIO_CLS_QKV | SAMAUDIO_CLS_WO | SAMAUDIO_CLS_W13) ? (size_t)M * 3 * W * 2 : 0;
+  const size_t x3u_bytes = x3(SAMAUDIO_CLS_W2) ? (size_t)M * 3 * F * 2 : 0;
+  void* x3a = x3a_bytes ? b.take(x3a_bytes) : nullptr; void* x3u = x3u_bytes ? b.take(x3u_bytes) : nullptr;
   if (assign) {
+    w_.x3a = x3a; w_.x3u = x3u; w_.x3a_bytes = x3a_bytes; w_.x3u_bytes = x3u_bytes;
     w_.h = h; w_.xn = xn; w_.qkv = qkv; w_.Q = Q; w_.K = K; w_.Vt = Vt; w_.attn = attn; w_.u = u; w_.patches = patches;
     w_.mask = mask; w_.kv = kv; w_.pooled = pooled; w_.y = y; w_.yn = yn; w_.u2 = u2; w_.z = z; w_.z_act = z_act;
   }
@@ -117,6 +143,23 @@ Status VisionTower::set_workspace(void* p, size_t bytes) {
   ws_bytes_ = bytes;
   planned_n_ = 0;
   return Status{};
+}
+
+Status VisionTower::linear(GemmParams p, const LinW& w, int cls, const void* split, hipStream_t st) const {
+  p.W = w.w;
+  if (!x3(cls)) return vgemm(p, bf16_, st);
+  if (!w.w3) return vfail(SAMAUDIO_ERR_STATE, "vision tower: SAMAUDIO_OPT_X3_CLASSES: split weight missing (set the option before finalize)");
+  if (p.kc != p.K || p.tap_stride || p.nbatch != 1 || p.a_off || (p.out_act && p.out_f32))
+    return vfail(SAMAUDIO_ERR_ARG, "vision tower: SAMAUDIO_OPT_X3_CLASSES: plain launches with one output only");
+  if (!split) {   // an operand no kernel wrote in split form: split the fp32 rows here
+    const bool wide = cls == SAMAUDIO_CLS_W2;   // the MLP hidden; every other operand is W wide
+    void* scratch = wide ? w_.x3u : w_.x3a;
+    SA_TRY(x3_fits(scratch, wide ? w_.x3u_bytes : w_.x3a_bytes, p.M, p.K, "vision tower: ", "the split operand does not fit the scratch the workspace plan holds"));
+    SA_HIP(launch_split3((const float*)p.A, p.lda, scratch, p.M, p.K, st));
+    split = scratch;
+  }
+  x3_operands(p, split, w);
+  return vgemm(x3_share(p, cls), true, st);
 }
 
 Status VisionTower::encode(const float* frames, int n, bool normalize, float* features, float* tokens_out, hipStream_t st) {
@@ -153,35 +196,61 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
   }
   if (c.use_ln_pre) SA_HIP(launch_layernorm_rows(emb, W, g_.ln_pre_w, g_.ln_pre_b, w_.h, nullptr, bf16_, M, W, eps, st));
 
+  // LayerNorm in front of a GEMM: the GEMM-operand rows into xn, or - the GEMM's class on compensated operands - the split rows
+  // [lo | hi | hi] into x3a in the same launch
+  auto norm = [&](const float* x, const float* lw, const float* lb, bool split) -> Status {
+    if (!split) {
+      SA_HIP(launch_layernorm_rows(x, W, lw, lb, nullptr, w_.xn, bf16_, M, W, eps, st));
+      return Status{};
+    }
+    SA_TRY(x3_fits(w_.x3a, w_.x3a_bytes, M, W, "vision tower: ", "the split LayerNorm rows do not fit the workspace plan"));
+    SA_HIP(launch_layernorm_rows_split3(x, W, lw, lb, w_.x3a, M, W, eps, st));
+    return Status{};
+  };
+  const bool qkv3 = x3(SAMAUDIO_CLS_QKV), wo3 = x3(SAMAUDIO_CLS_WO), w13_3 = x3(SAMAUDIO_CLS_W13), w2_3 = x3(SAMAUDIO_CLS_W2),
+             att3 = x3(SAMAUDIO_X3_ATTENTION);
   for (int l = 0; l < c.layers; ++l) {  // oracle: resblocks
     const LayerW& w = layers_[l];
-    SA_HIP(launch_layernorm_rows(w_.h, W, w.ln1_w, w.ln1_b, nullptr, w_.xn, bf16_, M, W, eps, st));
+    SA_TRY(norm(w_.h, w.ln1_w, w.ln1_b, qkv3));
     {
-      GemmParams p = lin(w_.xn, W, w.wqkv, M, 3 * W, W);
+      GemmParams p = lin(w_.xn, W, nullptr, M, 3 * W, W);   // (W: linear sets it from the record, here and below)
       p.bias = w.bqkv;
       p.out_act = w_.qkv; p.act_ld = 3L * W;
-      SA_TRY(vgemm(p, bf16_, st));
+      SA_TRY(linear(p, w.wqkv, SAMAUDIO_CLS_QKV, w_.x3a, st));
     }
     SA_HIP(launch_rope2d_split(w_.qkv, g_.rope_cos, g_.rope_sin, w_.Q, w_.K, w_.Vt, bf16_, n, S, Sp, H, hd_, st));
-    SA_HIP(launch_self_attention_hd(w_.Q, w_.K, w_.Vt, w_.mask, w_.attn, bf16_, n, S, Sp, H, hd_, st));
+    const void* attn_split = nullptr;   // the context rows in split form, when the attention wrote them for wo
+    if (att3) {   // fp32 tensors, both contractions on hi/lo-split operands (Sp % 128 == 0)
+      if (wo3) SA_TRY(x3_fits(w_.x3a, w_.x3a_bytes, M, W, "vision tower: ", "the attention's split output does not fit the workspace plan"));
+      SA_HIP(launch_self_attention_x3((const float*)w_.Q, (const float*)w_.K, (const float*)w_.Vt, w_.mask, (float*)w_.attn, n, S, Sp, H,
+                                      hd_, st, wo3 ? w_.x3a : nullptr));
+      if (wo3) attn_split = w_.x3a;
+    } else {
+      SA_HIP(launch_self_attention_hd(w_.Q, w_.K, w_.Vt, w_.mask, w_.attn, bf16_, n, S, Sp, H, hd_, st));
+    }
     {
-      GemmParams p = lin(w_.attn, W, w.wo, M, W, W);  // x = x + out_proj(attn)
+      GemmParams p = lin(w_.attn, W, nullptr, M, W, W);  // x = x + out_proj(attn)
       p.bias = w.bo;
       p.res = w_.h; p.res_ld = W;
       p.out_f32 = w_.h; p.f32_ld = W;
-      SA_TRY(vgemm(p, bf16_, st));
+      SA_TRY(linear(p, w.wo, SAMAUDIO_CLS_WO, attn_split, st));
     }
-    SA_HIP(launch_layernorm_rows(w_.h, W, w.ln2_w, w.ln2_b, nullptr, w_.xn, bf16_, M, W, eps, st));
+    SA_TRY(norm(w_.h, w.ln2_w, w.ln2_b, w13_3));
     {
-      GemmParams p = lin(w_.xn, W, w.w1, M, F, W);  // act(c_fc(x))
+      GemmParams p = lin(w_.xn, W, nullptr, M, F, W);  // act(c_fc(x))
       p.bias = w.b1; p.act = c.act;
       p.out_act = w_.u; p.act_ld = F;
-      SA_TRY(vgemm(p, bf16_, st));
-      p = lin(w_.u, F, w.w2, M, W, F);  // x = x + c_proj(...)
+      // c_fc writes c_proj's operand in split form where the launch it would make passes gemm_check (the register epilogue of the
+      // 8-phase family: bias + GELU with a split output); otherwise fp32 output + launch_split3 in front of c_proj
+      const bool w2_pre = w13_3 && w2_3 && x3_room(w_.x3u, w_.x3u_bytes, M, F) &&
+                          !gemm_check(x3_share(x3_split3_out(p, w_.x3a, w.w1, w_.x3u), SAMAUDIO_CLS_W13), true);
+      if (w2_pre) { p.out_act = w_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
+      SA_TRY(linear(p, w.w1, SAMAUDIO_CLS_W13, w_.x3a, st));
+      p = lin(w_.u, F, nullptr, M, W, F);  // x = x + c_proj(...)
       p.bias = w.b2;
       p.res = w_.h; p.res_ld = W;
       p.out_f32 = w_.h; p.f32_ld = W;
-      SA_TRY(vgemm(p, bf16_, st));
+      SA_TRY(linear(p, w.w2, SAMAUDIO_CLS_W2, w2_pre ? w_.x3u : nullptr, st));
     }
   }
   if (tokens_out) SA_HIP(hipMemcpyAsync(tokens_out, w_.h, (size_t)M * W * 4, hipMemcpyDeviceToDevice, st));
@@ -189,13 +258,18 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
   // ln_post on every token, then pooling                                                   (oracle: ln_post, _pool)
   const void* pooled_act = nullptr;  // [n, W] GEMM operand of the projection
   if (c.pool_type == 2) {
-    if (c.use_ln_post) SA_HIP(launch_layernorm_rows(w_.h, W, g_.ln_post_w, g_.ln_post_b, nullptr, w_.xn, bf16_, M, W, eps, st));
-    else SA_HIP(launch_to_act(w_.h, 0, W, 0, w_.xn, 0, bf16_, 1, M, W, W, 0, st));
+    const void* kv_split = nullptr;   // class QKV: ln_post writes the split rows; without ln_post, linear splits h itself
+    if (c.use_ln_post) {
+      SA_TRY(norm(w_.h, g_.ln_post_w, g_.ln_post_b, qkv3));
+      if (qkv3) kv_split = w_.x3a;
+    } else if (!qkv3) {
+      SA_HIP(launch_to_act(w_.h, 0, W, 0, w_.xn, 0, bf16_, 1, M, W, W, 0, st));
+    }
     {
-      GemmParams p = lin(w_.xn, W, g_.pool_wkv, M, 2 * W, W);  // k | v of every token
+      GemmParams p = lin(qkv3 && !c.use_ln_post ? (const void*)w_.h : w_.xn, W, nullptr, M, 2 * W, W);  // k | v of every token
       p.bias = g_.pool_bkv;
       p.out_act = w_.kv; p.act_ld = 2L * W;
-      SA_TRY(vgemm(p, bf16_, st));
+      SA_TRY(linear(p, g_.pool_wkv, SAMAUDIO_CLS_QKV, kv_split, st));
     }
     SA_HIP(launch_pool_attention(g_.pool_q, w_.kv, w_.pooled, bf16_, n, S, c.pool_heads, pool_hd_, st));
     {
@@ -274,6 +348,11 @@ void samaudio_vit_destroy(samaudio_vit* v) {
 int samaudio_vit_set_tensor(samaudio_vit* v, const char* name, const void* data, int dtype, int ndim, const int64_t* shape) {
   if (!v) return vbad("null vision tower");
   return vret(v->tower->set_tensor(name, data, dtype, ndim, shape));
+}
+
+int samaudio_vit_set_option(samaudio_vit* v, int option, int value) {
+  if (!v) return vbad("null vision tower");
+  return vret(v->tower->set_option(option, value));
 }
 
 int samaudio_vit_finalize(samaudio_vit* v) {

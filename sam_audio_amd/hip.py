@@ -42,9 +42,10 @@ def storage_precision(precision: str) -> str:
 
 def tower_precision(precision: str) -> str:
     """The DEFAULT precision of the towers beside the DiT (Judge, span predictor, vision tower): beside an x3 DiT they run on the
-    library's plain 16-bit operands, as they do beside a plain 16-bit one.  The Judge and the span predictor do have a compensated
-    mode (precision="fp16x3" / "bf16x3" of their classes); it is opt-in through `tower_precision=` of SAMAudio.from_pretrained /
-    attach_rankers / create_ranker."""
+    library's plain 16-bit operands, as they do beside a plain 16-bit one.  All three do have a compensated mode
+    (precision="fp16x3" / "bf16x3" of their classes); it is opt-in through `tower_precision=` - of SAMAudio.from_pretrained /
+    attach_rankers / create_ranker for the Judge and the span predictor, of SAMAudio(...) /
+    from_pretrained for the PE-Core vision tower built in load_state_dict."""
     return {"fp16x3": "fp16", "bf16x3": "bf16"}.get(precision, precision)
 
 
@@ -106,6 +107,10 @@ X3_WEIGHTS = {"wqkv": "qkv", "wo": "wo", "c_wq": "cwq", "c_wo": "cwo", "w13": "w
 # the PE-AV towers (Judge, span predictor; samaudio.h SAMAUDIO_CLS_X3_TOWER): what samaudio_judge_set_option / samaudio_frame_set_option
 # accept, and what precision="fp16x3" / "bf16x3" towers switch on
 CLS_X3_TOWER = CLS["qkv"] | CLS["wo"] | CLS["w13"] | CLS["w2"] | CLS["patch"] | X3_ATTENTION
+# the PE-Core vision tower (samaudio.h SAMAUDIO_CLS_X3_VIT): what samaudio_vit_set_option accepts and precision="fp16x3" / "bf16x3" of
+# PEVisionTower switches on; engine weight L<i>.<name> (and pool.wkv, with qkv) -> class
+CLS_X3_VIT = CLS["qkv"] | CLS["wo"] | CLS["w13"] | CLS["w2"] | X3_ATTENTION
+X3_VIT_WEIGHTS = {"wqkv": "qkv", "wo": "wo", "w1": "w13", "w2": "w2"}
 X3_TOWER_WEIGHTS = {"wqkv": "qkv", "wo": "wo", "w13": "w13", "w2": "w2"}
 QUANT_FORMATS = {"bf16": 1, "fp16": 2}
 SENTINEL_NAMES = CLASSES + ("norm", "attn")
@@ -298,6 +303,7 @@ _PROTOS = {
     "samaudio_op_masked_groupnorm_silu_split3": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "samaudio_op_layernorm_rows": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_int,
                                                                                           C.c_float, C.c_void_p]),
+    "samaudio_op_layernorm_rows_split3": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_float, C.c_void_p]),
     "samaudio_op_split3": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "samaudio_op_mod_tables": (C.c_int, [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_int)] * 2 + [C.c_int, C.c_void_p, C.c_int64,
                                                                                                  C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -345,6 +351,7 @@ _PROTOS = {
     "samaudio_vit_create": (C.c_int, [C.POINTER(VitConfig), C.POINTER(C.c_void_p)]),
     "samaudio_vit_destroy": (None, [C.c_void_p]),
     "samaudio_vit_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "samaudio_vit_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "samaudio_vit_finalize": (C.c_int, [C.c_void_p]),
     "samaudio_vit_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "samaudio_vit_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

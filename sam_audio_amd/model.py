@@ -155,8 +155,11 @@ class SAMAudio:
     def __init__(self, cfg: SAMAudioConfig, precision: str = "fp16x3", device: Optional[str] = None,
                  text_encoder: Optional[Callable] = None, streams: int = 1, f32_classes="auto",
                  weight_layout: str = "auto", prefetch_rows: Optional[int] = None, x3_classes="auto",
-                 codec_decode: str = "auto"):
-        """`precision`: "fp16x3" (default: the reference computes in fp32, README.md:48 - fp32 storage and every big contraction on
+                 codec_decode: str = "auto", tower_precision: Optional[str] = None):
+        """`tower_precision`: the precision of the PE-Core vision tower that load_state_dict builds when the checkpoint carries one.
+        None (default) = hip.tower_precision(precision): plain 16-bit operands beside an x3 DiT.  "fp16x3" / "bf16x3" opt the tower
+        into its compensated mode.
+        `precision`: "fp16x3" (default: the reference computes in fp32, README.md:48 - fp32 storage and every big contraction on
         hi/lo-split IEEE-half operands hold its results to 1e-3 on benign and trained-like weights) | "fp16" |
         "mixed" | "bf16" (plain 16-bit GEMM operands: ~3x the throughput, inside 1e-3 on benign weights only / not at all) | "fp32"
         (exact-fp32 MFMA) | "bf16x3".
@@ -171,8 +174,11 @@ class SAMAudio:
         "yemb" can be added - DESIGN.md section 4)."""
         cfg.check_supported()
         hip.check_precision(precision, x3_ok=True)
+        if tower_precision is not None:
+            hip.check_precision(tower_precision, x3_ok=True)
         self.cfg = cfg
         self.precision = precision
+        self.tower_precision = tower_precision
         # precision "fp16x3" (and "bf16x3"): fp32 storage and fp32 small classes, the six big GEMM classes of the layers on
         # compensated 16-bit operands (samaudio.h SAMAUDIO_OPT_X3_CLASSES; `x3_classes`: names or a mask, "auto" = all six)
         self.x3_classes = 0 if not hip.is_x3(precision) else (
@@ -284,10 +290,10 @@ class SAMAudio:
         """Local directory with the reference's `config.json` + `checkpoint.pt`
         (reference base.py:17-62; hub download needs network access this build does not have).
 
-        `tower_precision`: the precision of the rankers built here.  None (default) = hip.tower_precision(precision): plain 16-bit
-        operands beside an x3 DiT.  "fp16x3" / "bf16x3" opt the Judge into its compensated mode (fp32 storage, the big contractions
-        on hi/lo-split 16-bit operands).  The PE-Core vision tower has no compensated mode: it keeps the
-        plain mapping whatever is passed here."""
+        `tower_precision`: the precision of the rankers built here and of the PE-Core vision tower built by load_state_dict.  None
+        (default) = hip.tower_precision(precision): plain 16-bit operands beside an x3 DiT.  "fp16x3" / "bf16x3" opt the Judge and
+        the vision tower into their compensated modes (fp32 storage, the big contractions on hi/lo-split 16-bit operands; DESIGN.md
+        sections 10.1 and 10.2)."""
         if not os.path.isdir(model_id):
             raise FileNotFoundError(f"{model_id}: only local checkpoint directories are supported offline")
         with open(os.path.join(model_id, "config.json")) as fin:
@@ -295,7 +301,7 @@ class SAMAudio:
         for key, value in model_kwargs.items():
             if key in config:
                 config[key] = value
-        model = cls(SAMAudioConfig(**config), precision=precision, device=device)
+        model = cls(SAMAudioConfig(**config), precision=precision, device=device, tower_precision=tower_precision)
         sd = torch.load(os.path.join(model_id, "checkpoint.pt"), weights_only=True, map_location=map_location)
         model.load_state_dict(sd, strict=strict)
         # the reference builds its T5 encoder and rankers in __init__ from hub ids (model.py:82,94-95); offline they
@@ -326,7 +332,7 @@ class SAMAudio:
             # really carries the PE-Core tower (a text-only deployment pays nothing for it)
             from .vision_encoder import PerceptionEncoder
             self.vision_encoder = PerceptionEncoder(self.cfg.vision_encoder, device=self.device,
-                                                    precision=hip.tower_precision(self.precision))
+                                                    precision=self.tower_precision or hip.tower_precision(self.precision))
         if vis and hasattr(self.vision_encoder, "load_state_dict"):
             # The tower's key list is restated from the published PE-Core architecture (perception_models is not
             # importable offline), so it is validated for what the engine NEEDS, not for what a genuine checkpoint may carry

@@ -431,3 +431,32 @@ def make_hostile_peav(sd: Dict[str, torch.Tensor], prefix: str, tc, seed: int = 
             out[L + name] = out[L + name] * lognormal(out[L + name].shape, norm_std)
     out[prefix + "norm.weight"] = out[prefix + "norm.weight"] * lognormal((D,), norm_std)
     return out
+
+
+def make_hostile_vision(sd: Dict[str, torch.Tensor], cfg, seed: int = 0, outliers: int = 4, gain: float = 30.0,
+                        norm_std: float = 0.5, prefix: str = "") -> Dict[str, torch.Tensor]:
+    """The vision-tower sibling of make_hostile_peav: a copy of a synthetic PE-Core tower checkpoint (init_vision_state_dict; `cfg`: its
+    PEVisionConfig, `prefix` as there) with the statistics trained ViTs show and seeded init does not:
+
+    * a few RESIDUAL-STREAM OUTLIER CHANNELS - the `conv1.weight` rows of `outliers` random channels x `gain`, and every block's
+      attn.out_proj / mlp.c_proj weight and bias rows of those channels x `gain`: LayerNorm statistics and 16-bit copies of the stream
+      are dominated by a handful of large values;
+    * LOG-NORMAL ln_1 / ln_2 GAINS (sigma `norm_std`) instead of 1 +- 0.1.
+
+    Test infrastructure of the tower's precision claims (tests/test_vit_x3_*.py); the values stay finite in fp32 by construction, and
+    the defaults keep the fp32 oracle within 1e-4 x max(1, |value|) of the same oracle in float64 (checked on the CPU by
+    tests/test_vit_x3_cpu.py) - a yardstick that does not hold that cannot judge a 1e-3 bar."""
+    g = torch.Generator().manual_seed(3000 + seed)
+    W = cfg.width
+    out = {k: v.clone() for k, v in sd.items()}
+    dev = next(iter(out.values())).device
+    ch = torch.randperm(W, generator=g)[:outliers].to(dev)
+    out[prefix + "conv1.weight"][ch] *= gain
+    for i in range(cfg.layers):
+        p = f"{prefix}transformer.resblocks.{i}."
+        for name in ("attn.out_proj", "mlp.c_proj"):
+            out[p + name + ".weight"][ch] *= gain
+            out[p + name + ".bias"][ch] *= gain
+        for name in ("ln_1.weight", "ln_2.weight"):
+            out[p + name] = out[p + name] * torch.exp(torch.randn(W, generator=g) * norm_std).to(dev)
+    return out

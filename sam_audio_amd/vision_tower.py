@@ -21,6 +21,10 @@ reference key (below `visual.`)                         engine tensor
   attn_pool.attn.out_proj / layernorm / mlp.*           pool.wo, pool.bo, pool.ln.w/.b, pool.w1, pool.b1, pool.w2, pool.b2
   proj [W, O]                                           proj [O, W]      (transposed: features = pooled @ proj)
   (2-D RoPE has no parameters)                          rope_cos / rope_sin [S, hd/2]
+
+precision "fp16x3" / "bf16x3" (DESIGN.md section 10.2): an fp32 context of the matching library with SAMAUDIO_OPT_X3_CLASSES =
+hip.CLS_X3_VIT - the four GEMMs of every block, pool.wkv and the self-attention on compensated 16-bit operands.  `convert_vision`
+then adds the split twins "L{i}.wqkv.x3", ".wo.x3", ".w1.x3", ".w2.x3" and "pool.wkv.x3" ([W_hi | W_lo | W_hi], weights.x3_tower_weight).
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ import torch
 from . import hip
 from .config import PE_VISION_CONFIGS, PEVisionConfig
 from .judge import _ensure_ws, _register
+from .weights import x3_tower_weight
 
 POOL_TYPES = {"tok": 0, "avg": 1, "attn": 2}
 ACTS = {"gelu": hip.ACT_GELU, "quick_gelu": hip.ACT_QUICK_GELU}
@@ -92,7 +97,12 @@ def expected_keys(cfg: PEVisionConfig) -> List[str]:
     return keys
 
 
-def convert_vision(sd: Dict[str, torch.Tensor], cfg: PEVisionConfig, act_dtype: torch.dtype, device) -> Dict[str, torch.Tensor]:
+def convert_vision(sd: Dict[str, torch.Tensor], cfg: PEVisionConfig, act_dtype: torch.dtype, device,
+                   x3_half: Optional[torch.dtype] = None, x3_classes: int = hip.CLS_X3_VIT) -> Dict[str, torch.Tensor]:
+    """`x3_half` (torch.float16 / torch.bfloat16; act_dtype float32): also the split twins "<name>.x3" = [W_hi | W_lo | W_hi] of the
+    GEMM classes in the mask `x3_classes` (hip.CLS_X3_VIT bits) that samaudio_vit_set_option(SAMAUDIO_OPT_X3_CLASSES) needs."""
+    if x3_half is not None and act_dtype != torch.float32:
+        raise ValueError("convert_vision: the x3 twins belong to an fp32 context (act_dtype float32)")
     W, S = cfg.width, cfg.tokens
     f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()   # noqa: E731
     act = lambda t: t.detach().to(device=device, dtype=torch.float32).to(act_dtype).contiguous()  # noqa: E731
@@ -133,6 +143,13 @@ def convert_vision(sd: Dict[str, torch.Tensor], cfg: PEVisionConfig, act_dtype: 
         out["pool.w1"], out["pool.b1"] = act(sd[p + "mlp.c_fc.weight"]), f32(sd[p + "mlp.c_fc.bias"])
         out["pool.w2"], out["pool.b2"] = act(sd[p + "mlp.c_proj.weight"]), f32(sd[p + "mlp.c_proj.bias"])
     out["proj"] = act(sd["proj"]).t().contiguous()
+    if x3_half is not None:
+        for i in range(cfg.layers):
+            for leaf, cls in hip.X3_VIT_WEIGHTS.items():
+                if x3_classes & hip.CLS[cls]:
+                    out[f"L{i}.{leaf}.x3"] = x3_tower_weight(out[f"L{i}.{leaf}"], x3_half)
+        if cfg.pool_type == "attn" and x3_classes & hip.CLS["qkv"]:
+            out["pool.wkv.x3"] = x3_tower_weight(out["pool.wkv"], x3_half)
     return out
 
 
@@ -141,8 +158,11 @@ class PEVisionTower:
     callable (`tower(frames, normalize=...)`), which is the signature `PerceptionEncoder(tower=...)` expects."""
 
     def __init__(self, cfg: Optional[PEVisionConfig] = None, precision: str = "bf16", device: Optional[str] = None,
-                 name: str = "PE-Core-L14-336", streams: int = 2):
-        hip.check_precision(precision)
+                 name: str = "PE-Core-L14-336", streams: int = 2, x3_classes="auto"):
+        """`precision`: "bf16" | "fp16" (plain 16-bit GEMM operands) | "fp32" (exact-fp32 MFMA) | "fp16x3" | "bf16x3" (fp32 storage, the
+        big contractions on hi/lo-split 16-bit operands: the mode that holds the 1e-3 bar on trained-like weights, DESIGN.md section
+        10.2).  `x3_classes` (x3 precisions; hip.CLASSES names, "attn", or a mask of hip.CLS_X3_VIT bits): "auto" = all of them."""
+        hip.check_precision(precision, x3_ok=True)
         streams = int(os.environ.get("SAMAUDIO_VIT_STREAMS", streams))   # tuning only: A/B of the two-stream encode
         if streams not in (1, 2):
             raise ValueError("streams must be 1 or 2")
@@ -161,6 +181,10 @@ class PEVisionTower:
         self.cfg = cfg
         self.precision = precision
         self.device = torch.device(device) if device is not None else None
+        self.x3_classes = 0 if not hip.is_x3(precision) else (
+            hip.CLS_X3_VIT if x3_classes == "auto" else hip.class_mask(x3_classes))
+        if self.x3_classes & ~hip.CLS_X3_VIT:
+            raise ValueError("x3_classes: the vision tower takes qkv, wo, w13, w2 and attn only")
         self._lib = hip.lib(hip.operands_for(precision))
         self._h = C.c_void_p()
         self._tensors: Dict[str, torch.Tensor] = {}
@@ -174,6 +198,12 @@ class PEVisionTower:
             act=ACTS[cfg.act], ln_eps=cfg.ln_eps)
         self._vc = vc
         hip.check(self._lib.samaudio_vit_create(C.byref(vc), C.byref(self._h)))
+        self._set_options(self._h)
+
+    def _set_options(self, handle):
+        """x3 precisions: the compensated classes, BEFORE finalize (it resolves the twins) - on the main and the side context"""
+        if self.x3_classes:
+            hip.check(self._lib.samaudio_vit_set_option(handle, hip.OPT_X3_CLASSES, self.x3_classes))
 
     def __del__(self):
         if getattr(self, "_side", None):
@@ -218,7 +248,8 @@ class PEVisionTower:
         if not missing:
             with torch.cuda.device(self.device):
                 _register(self._lib.samaudio_vit_set_tensor, self._h, self._tensors,
-                          convert_vision(sd, self.cfg, self.act_dtype, self.device))
+                          convert_vision(sd, self.cfg, self.act_dtype, self.device,
+                                         hip.half_dtype(self.precision) if self.x3_classes else None, self.x3_classes))
                 hip.check(self._lib.samaudio_vit_finalize(self._h))
             self._loaded = True
         return missing, unexpected
@@ -231,6 +262,7 @@ class PEVisionTower:
             holder.device, holder._workspace = self.device, None
             h = C.c_void_p()
             hip.check(self._lib.samaudio_vit_create(C.byref(self._vc), C.byref(h)))
+            self._set_options(h)
             _register(self._lib.samaudio_vit_set_tensor, h, {}, self._tensors)   # borrowed: the same device tensors
             hip.check(self._lib.samaudio_vit_finalize(h))
             self._side = (h, holder, torch.cuda.Stream(device=self.device))
