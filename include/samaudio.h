@@ -329,10 +329,11 @@ int samaudio_frame_logits(samaudio_frame* f, const float* codec_features, const 
 
 /* ---- visual-prompt tower -------------------------------------------------------
  * PE-Core vision tower behind `PerceptionEncoder.encode` (reference sam_audio/model/vision_encoder.py:80-89:
- * `pe.CLIP.from_config("PE-Core-L14-336")`, `encode_image(x, normalize=...)`).  Resize / scaling / normalisation of the
- * frames (vision_encoder.py:91-113) stay with the caller; everything from the patch embedding to the L2-normalised
- * feature runs here.  Engine tensor names: sam_audio_amd/vision_tower.py documents the mapping from the `visual.*`
- * state_dict keys. */
+ * `pe.CLIP.from_config("PE-Core-L14-336")`, `encode_image(x, normalize=...)`).  samaudio_vit_encode takes frames the caller has
+ * resized, scaled and normalised (vision_encoder.py:91-113) and runs everything from the patch embedding to the L2-normalised
+ * feature; samaudio_vit_encode_frames takes the raw uint8 frames and does the resize, the rounding and the normalisation as
+ * well, in the launch that writes the patch embedding's operand.  Engine tensor names: sam_audio_amd/vision_tower.py documents
+ * the mapping from the `visual.*` state_dict keys. */
 typedef struct {
   int32_t precision;                          /* SAMAUDIO_F32 | SAMAUDIO_BF16 */
   int32_t image_size, patch_size;             /* 336, 14 */
@@ -376,6 +377,25 @@ int samaudio_vit_set_workspace(samaudio_vit* v, void* workspace, size_t bytes);
  * [n, tokens, width] f32 (before ln_post). */
 int samaudio_vit_encode(samaudio_vit* v, const float* frames, int n, int normalize, float* features, float* tokens_out,
                         samaudio_stream stream);
+/* Resize of uint8 frames to a square target, as torch's F.interpolate(x.float(), (S, S), mode, antialias=True, align_corners=False)
+ * (NEAREST: mode="nearest") followed by round-half-to-even, clamp to 0..255 and (v / 255 - 0.5) / 0.5.  Per axis with `in` source
+ * pixels and `out` = S: scale = in / out, support = max(scale, 1) * r (r = 2 bicubic, 1 bilinear), inv = 1 / max(scale, 1); output i:
+ * c = scale (i + 0.5), taps lo = max(0, int(c - support + 0.5)) .. hi = min(in, int(c + support + 0.5)) with weights
+ * f((s - c + 0.5) inv) normalised to sum 1, f = the triangle filter | the cubic convolution filter with a = -0.5; the horizontal
+ * pass, then the vertical pass, accumulated in fp32.  NEAREST: source min(floor(i * (float)in / (float)out), in - 1). */
+#define SAMAUDIO_RESIZE_NEAREST  0
+#define SAMAUDIO_RESIZE_BILINEAR 1
+#define SAMAUDIO_RESIZE_BICUBIC  2
+/* kernel-level hook: frames [n,3,height,width] u8 -> out [n,3,out_size,out_size] f32, resized, rounded, normalised.
+ * SAMAUDIO_ERR_STATE in a build of the library without the kernel. */
+int samaudio_op_resize_frames(const uint8_t* frames, int n, int height, int width, int out_size, int mode,
+                              float* out, samaudio_stream stream);
+/* samaudio_vit_encode on raw frames [n, 3, height, width] u8 (any height, width >= 1; frames that already have the target size take
+ * the same path): the resize writes the patch-embedding operand itself - no float copy of the source and no resized image in memory;
+ * everything behind it is samaudio_vit_encode's, bit for bit what it computes from samaudio_op_resize_frames' output.  Same workspace
+ * (samaudio_vit_workspace_bytes is unchanged).  A null pointer, n <= 0, height / width < 1 or an unknown mode: SAMAUDIO_ERR_ARG. */
+int samaudio_vit_encode_frames(samaudio_vit* v, const uint8_t* frames, int n, int height, int width, int mode,
+                               int normalize, float* features, float* tokens_out, samaudio_stream stream);
 
 /* ---- text-prompt encoder ---------------------------------------------------------
  * T5 encoder stack behind `T5TextEncoder.forward` (reference sam_audio/model/text_encoder.py:19-37:

@@ -305,6 +305,20 @@ int samaudio_op_layernorm_rows_split3(const float* x, int64_t x_ld, const float*
   return hip_ret(sa::launch_layernorm_rows_split3(x, x_ld, w, b, out3, rows, dim, eps, (hipStream_t)stream), "layernorm_rows_split3");
 }
 
+int samaudio_op_resize_frames(const uint8_t* frames, int n, int height, int width, int out_size, int mode, float* out,
+                              samaudio_stream stream) {
+  if (!frames || !out || n <= 0 || height < 1 || width < 1 || out_size < 1)
+    return bad("resize_frames: null argument / n, height, width, out_size < 1");
+  if (mode != SAMAUDIO_RESIZE_NEAREST && mode != SAMAUDIO_RESIZE_BILINEAR && mode != SAMAUDIO_RESIZE_BICUBIC)
+    return bad("resize_frames: unknown mode");
+  if (!sa::launch_resize_frames) {
+    g_err = "resize_frames: not in this build of the library";
+    return SAMAUDIO_ERR_STATE;
+  }
+  return hip_ret(sa::launch_resize_frames(frames, n, height, width, out_size, mode, out, false, 0, 0, (hipStream_t)stream),
+                 "resize_frames");
+}
+
 int samaudio_op_split3(const float* x, int64_t x_ld, void* out, int64_t rows, int k, samaudio_stream stream) {
   if (!x || !out || rows <= 0 || k <= 0 || k % 8 || x_ld % 4) return bad("split3: k % 8, x_ld % 4");
   return hip_ret(sa::launch_split3(x, x_ld, out, rows, k, (hipStream_t)stream), "split3");

@@ -335,6 +335,12 @@ hipError_t launch_frame_logits(const float* audio, long a_bstride, long a_off, c
 // ---- PE-Core vision tower (vit_kernels.hip) ---------------------------------------------------------------------
 // im2col of the k = stride = P patch convolution: frames [n,3,S,S] f32 -> rows [n*(S/P)^2, Kp], column c*P*P + py*P + px
 hipError_t launch_patchify(const float* frames, void* out, bool bf16, int n, int S, int P, int Kp, hipStream_t st);
+// uint8 frames [n,3,H,W] -> S x S (mode = SAMAUDIO_RESIZE_*: nearest | antialiased bilinear | antialiased bicubic), rounded half to
+// even, clamped to 0..255, (v / 255 - 0.5) / 0.5.  Kp == 0: planar f32 [n,3,S,S] (bf16 false).  Kp > 0: launch_patchify's rows of
+// that image, [n*(S/P)^2, Kp] in the operand type.  weak: the CPU emulation of the launchers (oracle/emu) does not define it - the
+// parity hook then answers SAMAUDIO_ERR_STATE (api.hip)
+__attribute__((weak)) hipError_t launch_resize_frames(const unsigned char* frames, int n, int H, int W, int S, int mode, void* out,
+                                                      bool bf16, int P, int Kp, hipStream_t st);
 // q|k|v rows [n*T, 3*H*hd] -> Q, K [n,H,Tp,hd] (adjacent-pair rotation by rc / rs [T, hd/2]; null = none), V^T [n,H,hd,Tp]
 hipError_t launch_rope2d_split(const void* qkv, const float* rc, const float* rs, void* Q, void* K, void* Vt, bool bf16,
                                int n, int T, int Tp, int H, int head_dim, hipStream_t st);

@@ -21,9 +21,15 @@ class VisionTower {
   size_t workspace_bytes(int frames);
   Status set_workspace(void* p, size_t bytes);
   Status encode(const float* frames, int n, bool normalize, float* features, float* tokens_out, hipStream_t st);
+  // the same on raw uint8 frames [n, 3, height, width]: resized (mode = SAMAUDIO_RESIZE_*), rounded and normalised by the launch that
+  // writes the patch embedding's operand
+  Status encode_frames(const uint8_t* frames, int n, int height, int width, int mode, bool normalize, float* features,
+                       float* tokens_out, hipStream_t st);
 
  private:
   void plan(Bump& b, int n, bool assign);
+  Status prepare(const void* frames, const float* features, int n);   // argument / state / workspace checks, the plan for n frames
+  Status encode_patches(int n, bool normalize, float* features, float* tokens_out, hipStream_t st);   // everything behind w_.patches
   bool x3(int cls) const { return (x3_ & cls) != 0; }
   // One launch on the weight `w`: `p` = the context's plain launch, run as it is on w.w - or, class `cls` switched to compensated
   // operands, as ONE 16-bit launch over K' = 3K on w.w3 and the split rows `split` (null: the fp32 rows of p.A are split here, into

@@ -162,7 +162,7 @@ Status VisionTower::linear(GemmParams p, const LinW& w, int cls, const void* spl
   return vgemm(x3_share(p, cls), true, st);
 }
 
-Status VisionTower::encode(const float* frames, int n, bool normalize, float* features, float* tokens_out, hipStream_t st) {
+Status VisionTower::prepare(const void* frames, const float* features, int n) {
   if (!ready_) return vfail(SAMAUDIO_ERR_STATE, "vision tower: weights not finalized");
   if (!frames || !features || n <= 0) return vfail(SAMAUDIO_ERR_ARG, "vision tower: bad argument");
   if (!ws_) return vfail(SAMAUDIO_ERR_WORKSPACE, "vision tower: no workspace");
@@ -172,6 +172,28 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
     if (!b.fits()) return vfail(SAMAUDIO_ERR_WORKSPACE, "vision tower: workspace too small for " + std::to_string(n) + " frames");
     planned_n_ = n;
   }
+  return Status{};
+}
+
+// im2col rows of frames the caller has resized and normalised
+Status VisionTower::encode(const float* frames, int n, bool normalize, float* features, float* tokens_out, hipStream_t st) {
+  SA_TRY(prepare(frames, features, n));
+  SA_HIP(launch_patchify(frames, w_.patches, bf16_, n, cfg_.image_size, cfg_.patch_size, kp_, st));
+  return encode_patches(n, normalize, features, tokens_out, st);
+}
+
+// ... of raw uint8 frames: resize, rounding and normalisation in the launch that writes the rows
+Status VisionTower::encode_frames(const uint8_t* frames, int n, int height, int width, int mode, bool normalize, float* features,
+                                  float* tokens_out, hipStream_t st) {
+  if (height < 1 || width < 1) return vfail(SAMAUDIO_ERR_ARG, "vision tower: frame height / width < 1");
+  if (mode != SAMAUDIO_RESIZE_NEAREST && mode != SAMAUDIO_RESIZE_BILINEAR && mode != SAMAUDIO_RESIZE_BICUBIC)
+    return vfail(SAMAUDIO_ERR_ARG, "vision tower: unknown resize mode");
+  SA_TRY(prepare(frames, features, n));
+  SA_HIP(launch_resize_frames(frames, n, height, width, cfg_.image_size, mode, w_.patches, bf16_, cfg_.patch_size, kp_, st));
+  return encode_patches(n, normalize, features, tokens_out, st);
+}
+
+Status VisionTower::encode_patches(int n, bool normalize, float* features, float* tokens_out, hipStream_t st) {
   const samaudio_vit_config& c = cfg_;
   const int W = c.width, F = c.mlp_width, H = c.heads, S = tokens(), Sp = (int)vround_up(S, 128), G2 = grid_ * grid_;
   const int cls = c.use_cls_token ? 1 : 0;
@@ -179,8 +201,7 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
   const float eps = c.ln_eps;
   float* emb = c.use_ln_pre ? (float*)w_.u : w_.h;  // the pre-LN embedding lives in the (still unused) MLP scratch
 
-  // patch embedding: conv1 (k = stride = P, no bias) as one GEMM per frame over im2col rows, + position rows 1..   (oracle: conv2d, + positional_embedding)
-  SA_HIP(launch_patchify(frames, w_.patches, bf16_, n, c.image_size, c.patch_size, kp_, st));
+  // patch embedding: conv1 (k = stride = P, no bias) as one GEMM per frame over the im2col rows in w_.patches, + position rows 1..   (oracle: conv2d, + positional_embedding)
   {
     GemmParams p = lin(w_.patches, kp_, g_.patch_w, G2, W, kp_);
     p.nbatch = n; p.a_bstride = (long)G2 * kp_;
@@ -374,6 +395,12 @@ int samaudio_vit_encode(samaudio_vit* v, const float* frames, int n, int normali
                         samaudio_stream stream) {
   if (!v) return vbad("null vision tower");
   return vret(v->tower->encode(frames, n, normalize != 0, features, tokens_out, (hipStream_t)stream));
+}
+
+int samaudio_vit_encode_frames(samaudio_vit* v, const uint8_t* frames, int n, int height, int width, int mode, int normalize,
+                               float* features, float* tokens_out, samaudio_stream stream) {
+  if (!v) return vbad("null vision tower");
+  return vret(v->tower->encode_frames(frames, n, height, width, mode, normalize != 0, features, tokens_out, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -2,10 +2,13 @@
 // sam_audio/model/vision_encoder.py:80-89 -> `pe.CLIP.encode_image`, architecture restated in oracle/vit_oracle.py).
 // All of them are HBM-bound re-layouts around the GEMMs and the flash attention kernel (attention.hip):
 //   patchify        frames [n,3,S,S] f32 -> im2col rows [n*G*G, Kp] (the k = stride = patch conv becomes one GEMM)
+//   resize_frames   uint8 frames [n,3,H,W] -> resized, rounded, normalised: planar f32 or those im2col rows directly
 //   rope2d_split    fused q|k|v rows -> Q, K [n,H,Sp,hd] with the 2-D rotary embedding, V^T [n,H,hd,Sp]
 //   pool_attention  one learned query per head over all tokens (attention pooling head)
 //   l2_normalize    rows of the projected features
 #include "kernels.h"
+
+#include "../../include/samaudio.h"   // SAMAUDIO_RESIZE_*
 
 namespace sa {
 
@@ -38,6 +41,212 @@ hipError_t launch_patchify(const float* frames, void* out, bool bf16, int n, int
   if (bf16) hipLaunchKernelGGL(patchify_kernel<bf16_t>, grid, block, 0, st, frames, (bf16_t*)out, S, P, G, Kp);
   else hipLaunchKernelGGL(patchify_kernel<float>, grid, block, 0, st, frames, (float*)out, S, P, G, Kp);
   return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// resize_frames: uint8 frames [n,3,H,W] -> S x S, rounded to a level, normalised - what PerceptionEncoder.transform computes in torch:
+// F.interpolate(x.float(), (S, S), mode, antialias=True, align_corners=False) -> round half to even -> clamp 0..255 ->
+// (v / 255 - 0.5) / 0.5.  Output: planar f32 [n,3,S,S] (Kp == 0) or directly the im2col rows [n*G*G, Kp] of patchify_kernel
+// (columns >= 3*P*P zero), so that neither a float copy of the source nor a planar intermediate ever reaches HBM.
+//
+// Per axis (in source pixels -> out = S), output index i:   scale = in / out, support = max(scale, 1) * r (r = 2 bicubic, 1 bilinear),
+// inv = 1 / max(scale, 1), c = scale (i + 0.5), taps lo = max(0, int(c - support + 0.5)) .. hi = min(in, int(c + support + 0.5)),
+// w_s = f((s - c + 0.5) inv) normalised to sum 1; f = triangle | cubic convolution with a = -0.5.  Nearest: the one tap
+// min(floor(i * scale), in - 1).  lo / hi are formed in fp32 as torch forms them; the tap's distance to the centre is formed from the
+// centre's integer part and fraction (fp64: in (2i + 1) / (2 out) is then exact), so the weights carry no error of a large fp32 c.
+// The 2-D result is the horizontal pass followed by the vertical pass, both accumulated in fp32.
+//
+// One workgroup per (frame, channel, band of RZ_BAND output rows, tile of TX <= RZ_TX output columns).  It walks the source rows the
+// band needs in chunks of RZ_HR, and inside a chunk the source columns the tile needs in chunks of RZ_CW: u8 rows are staged in LDS by
+// aligned 16-byte loads (the row's misalignment is kept as a byte shift of the LDS row), the horizontal pass leaves fp32 rows in LDS,
+// the vertical pass accumulates them into registers - any scale fits, a large one only loops longer.  Weights are formed in the kernel
+// from the integer geometry: no tap table, no scratch.  Thread (xl, g) = (tid % TX, tid / TX): output column x0 + xl; source rows
+// g, g + ng, ... of a chunk in the horizontal pass and output rows r0 + g, r0 + g + ng, ... in the vertical pass (ng = 256 / TX >= 2).
+// grid (n * 3 * bands * tiles), 256 threads; static LDS 50 KB.
+// ------------------------------------------------------------------------------------------------
+constexpr int RZ_BAND = 14;              // output rows per workgroup
+constexpr int RZ_TX = 128;               // most output columns per workgroup
+constexpr int RZ_HR = 40;                // source rows per chunk
+constexpr int RZ_CW = 768;               // source columns per chunk
+constexpr int RZ_CWP = RZ_CW + 16;       // LDS row: the chunk behind a shift of up to 15 bytes, in whole 16-byte pieces
+constexpr int RZ_NA = RZ_HR / 2;         // source rows of a chunk per thread (ng >= 2)
+constexpr int RZ_NV = RZ_BAND / 2;       // output rows of the band per thread
+
+struct ResizeTaps {
+  int lo, hi;    // source pixels [lo, hi)
+  int ci;        // centre: integer part ...
+  float t, inv;  // ... and 0.5 - fraction; distance of source pixel s to the centre, in filter units = ((s - ci) + t) * inv
+};
+
+template <int MODE>
+__device__ __forceinline__ ResizeTaps resize_taps(int in, int out, int i) {
+  ResizeTaps p;
+  const float scale = (float)in / (float)out;
+  if (MODE == SAMAUDIO_RESIZE_NEAREST) {
+    const int s = (int)floorf((float)i * scale);
+    p.lo = s < in - 1 ? s : in - 1;
+    p.hi = p.lo + 1; p.ci = p.lo; p.t = 0.f; p.inv = 1.f;
+    return p;
+  }
+  const float support = (scale >= 1.f ? scale : 1.f) * (MODE == SAMAUDIO_RESIZE_BICUBIC ? 2.f : 1.f);
+  const float c = scale * ((float)i + 0.5f);
+  const int lo = (int)(c - support + 0.5f), hi = (int)(c + support + 0.5f);
+  p.lo = lo > 0 ? lo : 0;
+  p.hi = hi < in ? hi : in;
+  p.inv = scale >= 1.f ? 1.f / scale : 1.f;
+  const double cd = (double)in * (double)(2 * i + 1) / (2.0 * (double)out);
+  p.ci = (int)cd;
+  p.t = 0.5f - (float)(cd - (double)p.ci);
+  return p;
+}
+
+template <int MODE>
+__device__ __forceinline__ float resize_weight(const ResizeTaps& p, int s) {
+  if (MODE == SAMAUDIO_RESIZE_NEAREST) return 1.f;
+  const float x = fabsf(((float)(s - p.ci) + p.t) * p.inv);
+  if (MODE == SAMAUDIO_RESIZE_BILINEAR) return x < 1.f ? 1.f - x : 0.f;
+  constexpr float A = -0.5f;   // the antialiased bicubic filter's a (not the -0.75 of the plain one)
+  if (x < 1.f) return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+  if (x < 2.f) return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
+  return 0.f;
+}
+
+template <int MODE, typename TA>
+__global__ __launch_bounds__(256) void resize_frames_kernel(const unsigned char* __restrict__ frames, long total,
+                                                            TA* __restrict__ out, int H, int W, int S, int TX, int tiles,
+                                                            int bands, int P, int Kp) {
+  __shared__ __attribute__((aligned(16))) unsigned char src[RZ_HR * RZ_CWP];
+  __shared__ float hrow[RZ_HR][RZ_TX];
+  int wg = blockIdx.x;
+  const int tile = wg % tiles; wg /= tiles;
+  const int band = wg % bands; wg /= bands;
+  const int c = wg % 3, f = wg / 3;
+  const int r0 = band * RZ_BAND, r1 = r0 + RZ_BAND < S ? r0 + RZ_BAND : S;
+  const int x0 = tile * TX, x1 = x0 + TX < S ? x0 + TX : S;
+  if (x1 <= x0) return;   // (the whole workgroup)
+  const int tid = threadIdx.x;
+  const int ng = 256 / TX;
+  const int xl = tid % TX, g = tid / TX;
+  const bool active = g < ng && x0 + xl < x1;
+  const int x = active ? x0 + xl : x0;
+  const ResizeTaps hx = resize_taps<MODE>(W, S, x);
+  // lo and hi do not decrease with the output index: the source window of the tile and of the band
+  const int cl = resize_taps<MODE>(W, S, x0).lo, ch = resize_taps<MODE>(W, S, x1 - 1).hi;
+  const int rl = resize_taps<MODE>(H, S, r0).lo, rh = resize_taps<MODE>(H, S, r1 - 1).hi;
+  ResizeTaps vy[RZ_NV];
+  float acc[RZ_NV], ws[RZ_NV];
+#pragma unroll
+  for (int a = 0; a < RZ_NV; ++a) {
+    const int r = r0 + g + a * ng;
+    vy[a] = resize_taps<MODE>(H, S, r < r1 ? r : r1 - 1);
+    if (!active || r >= r1) vy[a].hi = vy[a].lo;   // no taps
+    acc[a] = ws[a] = 0.f;
+  }
+  const long plane = ((long)f * 3 + c) * H;   // first source row of this (frame, channel)
+  constexpr int PCS = RZ_CWP / 16;            // 16-byte pieces per LDS row
+
+  for (int j0 = rl; j0 < rh; j0 += RZ_HR) {
+    const int nr = rh - j0 < RZ_HR ? rh - j0 : RZ_HR;
+    float hacc[RZ_NA], hws = 0.f;
+#pragma unroll
+    for (int a = 0; a < RZ_NA; ++a) hacc[a] = 0.f;
+    for (int q0 = cl; q0 < ch; q0 += RZ_CW) {
+      const int nc = ch - q0 < RZ_CW ? ch - q0 : RZ_CW;
+      // stage rows j0 .. j0 + nr, columns q0 .. q0 + nc: LDS row `row` holds them from byte (address of its first byte) & 15 on
+      for (int idx = tid; idx < nr * PCS; idx += 256) {
+        const int row = idx / PCS, pc = idx - row * PCS;
+        const long o = (plane + j0 + row) * W + q0;
+        const int sh = (int)((uintptr_t)(frames + o) & 15);
+        if (pc * 16 < sh + nc) {
+          const long b = o - sh + pc * 16;   // an aligned piece; it may begin before the tensor or end behind it
+          uint4 v;
+          if (b >= 0 && b + 16 <= total) {
+            v = *(const uint4*)(frames + b);
+          } else {
+            unsigned w4[4] = {0u, 0u, 0u, 0u};
+            for (int e = 0; e < 16; ++e)
+              if (b + e >= 0 && b + e < total) w4[e >> 2] |= (unsigned)frames[b + e] << (8 * (e & 3));
+            v = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+          }
+          *(uint4*)(src + row * RZ_CWP + pc * 16) = v;
+        }
+      }
+      __syncthreads();
+      if (active) {
+        int off[RZ_NA];   // LDS byte of (row, source column 0); rows past the chunk read row 0 and are dropped below
+#pragma unroll
+        for (int a = 0; a < RZ_NA; ++a) {
+          const int row = g + a * ng < nr ? g + a * ng : 0;
+          off[a] = row * RZ_CWP + (int)((uintptr_t)(frames + (plane + j0 + row) * W + q0) & 15) - q0;
+        }
+        const int s0 = hx.lo > q0 ? hx.lo : q0, s1 = hx.hi < q0 + nc ? hx.hi : q0 + nc;
+        for (int s = s0; s < s1; ++s) {
+          const float w = resize_weight<MODE>(hx, s);
+          hws += w;
+#pragma unroll
+          for (int a = 0; a < RZ_NA; ++a) hacc[a] += w * (float)src[off[a] + s];
+        }
+      }
+      __syncthreads();
+    }
+    if (active) {
+      const float hn = hws != 0.f ? 1.f / hws : 0.f;
+#pragma unroll
+      for (int a = 0; a < RZ_NA; ++a)
+        if (g + a * ng < nr) hrow[g + a * ng][xl] = hacc[a] * hn;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < RZ_NV; ++a) {
+      const int s0 = vy[a].lo > j0 ? vy[a].lo : j0, s1 = vy[a].hi < j0 + nr ? vy[a].hi : j0 + nr;
+      for (int s = s0; s < s1; ++s) {
+        const float w = resize_weight<MODE>(vy[a], s);
+        ws[a] += w;
+        acc[a] += w * hrow[s - j0][xl];
+      }
+    }
+    __syncthreads();
+  }
+
+  const int G = Kp ? S / P : 0, kk = 3 * P * P;
+#pragma unroll
+  for (int a = 0; a < RZ_NV; ++a) {
+    const int r = r0 + g + a * ng;
+    if (!active || r >= r1) continue;
+    float v = ws[a] != 0.f ? acc[a] / ws[a] : 0.f;
+    v = fminf(fmaxf(rintf(v), 0.f), 255.f);   // the level: round half to even, clamped (bicubic overshoot ends here)
+    const float y = (v / 255.0f - 0.5f) / 0.5f;
+    if (!Kp) {
+      Elem<TA>::store(out + (((long)f * 3 + c) * S + r) * S + x, y);
+      continue;
+    }
+    const int gy = r / P, py = r - gy * P, gx = x / P, px = x - gx * P;
+    TA* dst = out + (((long)f * G + gy) * G + gx) * Kp;
+    Elem<TA>::store(dst + c * P * P + py * P + px, y);
+    if (c == 0 && py == 0 && px == 0)   // the patch's first pixel: its owner zeroes the K padding of the row
+      for (int k = kk; k < Kp; ++k) Elem<TA>::store(dst + k, 0.f);
+  }
+}
+
+template <int MODE>
+static hipError_t launch_resize_frames_m(const unsigned char* frames, int n, int H, int W, int S, void* out, bool bf16, int P,
+                                         int Kp, hipStream_t st) {
+  const int tiles = (S + RZ_TX - 1) / RZ_TX, TX = (S + tiles - 1) / tiles, bands = (S + RZ_BAND - 1) / RZ_BAND;
+  const long wgs = (long)n * 3 * bands * tiles, total = (long)n * 3 * H * W;
+  if (wgs >= (1L << 24)) return hipErrorInvalidValue;
+  dim3 grid((unsigned)wgs), block(256);
+  if (bf16) hipLaunchKernelGGL((resize_frames_kernel<MODE, bf16_t>), grid, block, 0, st, frames, total, (bf16_t*)out, H, W, S, TX, tiles, bands, P, Kp);
+  else hipLaunchKernelGGL((resize_frames_kernel<MODE, float>), grid, block, 0, st, frames, total, (float*)out, H, W, S, TX, tiles, bands, P, Kp);
+  return hipGetLastError();
+}
+
+hipError_t launch_resize_frames(const unsigned char* frames, int n, int H, int W, int S, int mode, void* out, bool bf16, int P,
+                                int Kp, hipStream_t st) {
+  if (n <= 0 || H < 1 || W < 1 || S < 1 || (Kp && (P < 1 || S % P || Kp < 3 * P * P))) return hipErrorInvalidValue;
+  if (mode == SAMAUDIO_RESIZE_NEAREST) return launch_resize_frames_m<SAMAUDIO_RESIZE_NEAREST>(frames, n, H, W, S, out, bf16, P, Kp, st);
+  if (mode == SAMAUDIO_RESIZE_BILINEAR) return launch_resize_frames_m<SAMAUDIO_RESIZE_BILINEAR>(frames, n, H, W, S, out, bf16, P, Kp, st);
+  if (mode == SAMAUDIO_RESIZE_BICUBIC) return launch_resize_frames_m<SAMAUDIO_RESIZE_BICUBIC>(frames, n, H, W, S, out, bf16, P, Kp, st);
+  return hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------------

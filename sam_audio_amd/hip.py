@@ -154,6 +154,9 @@ DBG_WS_ALWAYS, DBG_WS_NEVER, DBG_WS_ALWAYS_GRID3 = 1, 2, 3
 DBG_EPI_GENERAL, DBG_EPI_LINEAR, DBG_EPI_ROWS = 1, 2, 3
 DBG_ROLES_NONE, DBG_ROLES_PROD0, DBG_ROLES_PROD2 = 1, 2, 3
 
+RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1, 2   # samaudio.h SAMAUDIO_RESIZE_*
+RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR, "bicubic": RESIZE_BICUBIC}
+
 ERR_ARG, ERR_WEIGHT, ERR_WORKSPACE, ERR_HIP, ERR_STATE = -1, -2, -3, -4, -5
 
 
@@ -356,6 +359,8 @@ _PROTOS = {
     "samaudio_vit_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "samaudio_vit_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_vit_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "samaudio_vit_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
+    "samaudio_op_resize_frames": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -2,8 +2,9 @@
 (reference sam_audio/model/vision_encoder.py:40-113; SURVEY.md section 8 row a4 / "next" row f3).
 
 This wrapper owns what the reference file owns - resize, scaling, normalisation, chunking by `batch_size`, time
-padding.  The tower is `pe.CLIP.from_config(cfg.name)` in the reference (un-vendored perception_models); here it is
-`sam_audio_amd.vision_tower.PEVisionTower`, the same network on the HIP library (built by default for the config
+padding.  With `frame_transform="hip"` the first three run inside the tower's first kernel
+(`PEVisionTower.encode_frames`).  The tower is `pe.CLIP.from_config(cfg.name)` in the reference (un-vendored
+perception_models); here it is `sam_audio_amd.vision_tower.PEVisionTower`, the same network on the HIP library (built by default for the config
 names in `config.PE_VISION_CONFIGS`), or any injected callable `encode_image(frames [N,3,S,S] float, normalize=bool)
 -> [N, dim]`.  `SAMAudio.vision_encoder = PerceptionEncoder(cfg.vision_encoder, device=...)` + `load_state_dict`
 enables `separate()` with `masked_videos`.
@@ -17,11 +18,21 @@ import torch
 from .config import PerceptionEncoderConfig
 
 _MODES = {"NEAREST": "nearest", "BILINEAR": "bilinear", "BICUBIC": "bicubic"}
+FRAME_TRANSFORMS = ("torch", "hip")
 
 
 class PerceptionEncoder:
     def __init__(self, cfg: Optional[PerceptionEncoderConfig] = None, tower: Optional[Callable] = None, device=None,
-                 precision: str = "bf16"):
+                 precision: str = "bf16", frame_transform: str = "torch"):
+        """`frame_transform`: who resizes, rounds and normalises the frames.
+        "torch" (default): `transform` - torch ops on a float copy of the whole video, then the tower in chunks of `batch_size`.
+        "hip": a uint8 video on a tower that has `encode_frames` (PEVisionTower) is chunked by `batch_size` AS uint8 and every chunk goes
+        through `tower.encode_frames`, where one HIP kernel resizes, rounds, normalises and writes the patch embedding's operand: no
+        float copy of the video exists, whatever its resolution; frames that already have the target size take the same path.  A
+        video of any other dtype, or an injected tower without `encode_frames`, takes the "torch" path."""
+        if frame_transform not in FRAME_TRANSFORMS:
+            raise ValueError(f"frame_transform must be one of {FRAME_TRANSFORMS}, not {frame_transform!r}")
+        self.frame_transform = frame_transform
         self.cfg = cfg or PerceptionEncoderConfig()
         self.batch_size, self.dim = self.cfg.batch_size, self.cfg.dim
         self.normalize_feature, self.image_size = self.cfg.normalize_feature, self.cfg.image_size
@@ -78,12 +89,16 @@ class PerceptionEncoder:
         """list of [T_i, 3, H, W] -> [B, max T_i, dim], zero-padded along time (reference vision_encoder.py:47-70)."""
         result = []
         for video in videos:
-            video = self.transform(video.to(self.device) if self.device is not None else video)
+            video = video.to(self.device) if self.device is not None else video
+            if self.frame_transform == "hip" and video.dtype == torch.uint8 and hasattr(self.tower, "encode_frames"):
+                encode = lambda v: self.tower.encode_frames(v, self.mode, normalize=self.normalize_feature)   # noqa: E731
+            else:
+                video, encode = self.transform(video), self.encode
             if self.batch_size > 0 and video.size(0) > self.batch_size:
-                parts = [self.encode(video[i: i + self.batch_size]) for i in range(0, video.size(0), self.batch_size)]
+                parts = [encode(video[i: i + self.batch_size]) for i in range(0, video.size(0), self.batch_size)]
                 result.append(torch.cat(parts, dim=0))
             else:
-                result.append(self.encode(video))
+                result.append(encode(video))
         return torch.nn.utils.rnn.pad_sequence(result, batch_first=True, padding_value=0.0)
 
     __call__ = forward

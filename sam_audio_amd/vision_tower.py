@@ -155,7 +155,9 @@ def convert_vision(sd: Dict[str, torch.Tensor], cfg: PEVisionConfig, act_dtype: 
 
 class PEVisionTower:
     """`pe.CLIP`'s image side: `tower.encode_image(frames [N,3,S,S] float, normalize=bool) -> [N, output_dim]`; also
-    callable (`tower(frames, normalize=...)`), which is the signature `PerceptionEncoder(tower=...)` expects."""
+    callable (`tower(frames, normalize=...)`), which is the signature `PerceptionEncoder(tower=...)` expects.
+    `tower.encode_frames(frames [N,3,H,W] uint8, mode, normalize=bool)` is the same on raw frames: resize, rounding and
+    normalisation run in the library too (`PerceptionEncoder(frame_transform="hip")`)."""
 
     def __init__(self, cfg: Optional[PEVisionConfig] = None, precision: str = "bf16", device: Optional[str] = None,
                  name: str = "PE-Core-L14-336", streams: int = 2, x3_classes="auto"):
@@ -268,23 +270,23 @@ class PEVisionTower:
             self._side = (h, holder, torch.cuda.Stream(device=self.device))
         return self._side
 
-    def _encode_on(self, handle, owner, x, normalize, feats, tokens):
+    def _encode_on(self, handle, owner, x, normalize, feats, tokens, mode=None):
+        """One context's encode of the frames `x`: float [n,3,S,S] (samaudio_vit_encode), or - `mode` a hip.RESIZE_* code - raw uint8
+        [n,3,H,W] (samaudio_vit_encode_frames)."""
         n = x.shape[0]
         need = self._lib.samaudio_vit_workspace_bytes(handle, n)
         _ensure_ws(owner, need, lambda p, b: self._lib.samaudio_vit_set_workspace(handle, p, b))
-        hip.check(self._lib.samaudio_vit_encode(handle, hip.ptr(x), n, int(bool(normalize)), hip.ptr(feats),
-                                                hip.ptr(tokens), hip.current_stream_ptr()))
+        tail = (int(bool(normalize)), hip.ptr(feats), hip.ptr(tokens), hip.current_stream_ptr())
+        if mode is None:
+            hip.check(self._lib.samaudio_vit_encode(handle, hip.ptr(x), n, *tail))
+        else:
+            hip.check(self._lib.samaudio_vit_encode_frames(handle, hip.ptr(x), n, x.shape[2], x.shape[3], mode, *tail))
 
-    @torch.inference_mode()
-    def encode_image(self, frames: torch.Tensor, normalize: bool = False, return_tokens: bool = False):
-        if not self._loaded:
-            raise hip.SamAudioHipError("PEVisionTower: no weights loaded")
+    def _encode(self, x, normalize, return_tokens, mode=None):
+        """Workspace, outputs and the two-stream split of a frame batch `x` on the device (see _encode_on)."""
         cfg = self.cfg
-        assert frames.dim() == 4 and frames.shape[1:] == (3, cfg.image_size, cfg.image_size), \
-            f"frames must be [N, 3, {cfg.image_size}, {cfg.image_size}]"
-        n = frames.shape[0]
+        n = x.shape[0]
         with torch.cuda.device(self.device):
-            x = frames.to(self.device, torch.float32).contiguous()
             feats = torch.empty(n, cfg.output_dim, device=self.device, dtype=torch.float32)
             tokens = torch.empty(n, cfg.tokens, cfg.width, device=self.device, dtype=torch.float32) if return_tokens else None
             if self.streams == 2 and n >= 64:
@@ -298,19 +300,48 @@ class PEVisionTower:
                 def second():
                     try:
                         with torch.inference_mode(), torch.cuda.device(self.device), torch.cuda.stream(side):
-                            self._encode_on(h2, holder, x[k:], normalize, feats[k:], None if tokens is None else tokens[k:])
+                            self._encode_on(h2, holder, x[k:], normalize, feats[k:], None if tokens is None else tokens[k:], mode)
                     except BaseException as exc:   # re-raised on the caller's thread
                         errors.append(exc)
                 th = threading.Thread(target=second)
                 th.start()
-                self._encode_on(self._h, self, x[:k], normalize, feats[:k], None if tokens is None else tokens[:k])
+                self._encode_on(self._h, self, x[:k], normalize, feats[:k], None if tokens is None else tokens[:k], mode)
                 th.join()
                 main.wait_stream(side)
                 if errors:
                     raise errors[0]
             else:
-                self._encode_on(self._h, self, x, normalize, feats, tokens)
+                self._encode_on(self._h, self, x, normalize, feats, tokens, mode)
         return (feats, tokens) if return_tokens else feats
+
+    @torch.inference_mode()
+    def encode_image(self, frames: torch.Tensor, normalize: bool = False, return_tokens: bool = False):
+        if not self._loaded:
+            raise hip.SamAudioHipError("PEVisionTower: no weights loaded")
+        cfg = self.cfg
+        assert frames.dim() == 4 and frames.shape[1:] == (3, cfg.image_size, cfg.image_size), \
+            f"frames must be [N, 3, {cfg.image_size}, {cfg.image_size}]"
+        with torch.cuda.device(self.device):
+            x = frames.to(self.device, torch.float32).contiguous()
+        return self._encode(x, normalize, return_tokens)
+
+    @torch.inference_mode()
+    def encode_frames(self, frames_u8: torch.Tensor, mode: str = "bicubic", normalize: bool = False, return_tokens: bool = False):
+        """`encode_image` on raw uint8 frames [N, 3, H, W] of any size (H, W >= 1; frames of the target size included): the HIP library
+        resizes (`mode`: "nearest" | "bilinear" | "bicubic", the last two antialiased - torch's F.interpolate(x.float(), (S, S), mode,
+        antialias=True, align_corners=False)), rounds half to even, clamps to 0..255 and normalises (v / 255 - 0.5) / 0.5 in the launch
+        that writes the patch embedding's operand (samaudio_vit_encode_frames).  No float copy of the frames is made: hand it slices
+        of the uint8 tensor.  Same workspace and two-stream split as encode_image."""
+        if not self._loaded:
+            raise hip.SamAudioHipError("PEVisionTower: no weights loaded")
+        if mode not in hip.RESIZE_MODES:
+            raise ValueError(f"mode must be one of {sorted(hip.RESIZE_MODES)}")
+        if frames_u8.dtype != torch.uint8:
+            raise TypeError(f"encode_frames takes uint8 frames, not {frames_u8.dtype} (float frames: encode_image)")
+        assert frames_u8.dim() == 4 and frames_u8.shape[1] == 3 and min(frames_u8.shape) >= 1, "frames must be [N, 3, H, W], N, H, W >= 1"
+        with torch.cuda.device(self.device):
+            x = frames_u8.to(self.device).contiguous()
+        return self._encode(x, normalize, return_tokens, hip.RESIZE_MODES[mode])
 
     def __call__(self, frames: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         return self.encode_image(frames, normalize=normalize)
