@@ -22,19 +22,13 @@ namespace sa {
 void set_last_error(const std::string& msg) { g_err = msg; }  // for the C entry points that live in other files (vit.hip)
 }  // namespace sa
 namespace {
-int ret(const sa::Status& s) {
-  if (!s.ok()) g_err = s.msg;
-  return s.code;
-}
 int hip_ret(hipError_t e, const char* what) {
   if (e == hipSuccess) return SAMAUDIO_OK;
   g_err = std::string(what) + ": " + hipGetErrorString(e);
   return SAMAUDIO_ERR_HIP;
 }
-int bad(const char* msg) {
-  g_err = msg;
-  return SAMAUDIO_ERR_ARG;
-}
+using sa::bad;
+using sa::ret;
 }  // namespace
 
 extern "C" {
@@ -64,18 +58,15 @@ void samaudio_destroy(samaudio_ctx* ctx) {
 
 int samaudio_set_tensor(samaudio_ctx* ctx, const char* name, const void* data, int dtype, int ndim,
                         const int64_t* shape) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->set_tensor(name, data, dtype, ndim, shape));
+  return SA_ENTRY(ctx, "null context", ctx->engine->set_tensor(name, data, dtype, ndim, shape));
 }
 
 int samaudio_set_option(samaudio_ctx* ctx, int option, int value) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->set_option(option, value));
+  return SA_ENTRY(ctx, "null context", ctx->engine->set_option(option, value));
 }
 
 int samaudio_finalize(samaudio_ctx* ctx, int what) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->finalize(what));
+  return SA_ENTRY(ctx, "null context", ctx->engine->finalize(what));
 }
 
 size_t samaudio_workspace_bytes(samaudio_ctx* ctx, int rows, int frames, int text_len, int codec_items,
@@ -85,37 +76,34 @@ size_t samaudio_workspace_bytes(samaudio_ctx* ctx, int rows, int frames, int tex
 }
 
 int samaudio_set_workspace(samaudio_ctx* ctx, void* workspace, size_t bytes) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->set_workspace(workspace, bytes));
+  return SA_ENTRY(ctx, "null context", ctx->engine->set_workspace(workspace, bytes));
 }
 
 int samaudio_prepare(samaudio_ctx* ctx, int rows, int frames, int text_len, const float* audio_features,
                      const float* text, const uint8_t* text_mask, const float* video, const int64_t* anchor_ids,
                      int n_ids, const int64_t* anchor_alignment, const uint8_t* audio_pad_mask,
                      samaudio_stream stream) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->prepare(rows, frames, text_len, audio_features, text, text_mask, video, anchor_ids, n_ids,
-                                  anchor_alignment, audio_pad_mask, (hipStream_t)stream));
+  return SA_ENTRY(ctx, "null context",
+                  ctx->engine->prepare(rows, frames, text_len, audio_features, text, text_mask, video, anchor_ids, n_ids,
+                      anchor_alignment, audio_pad_mask, (hipStream_t)stream));
 }
 
 int samaudio_prepare_latent(samaudio_ctx* ctx, int rows, int frames, int text_len, int candidates, const float* latent,
                             const float* text, const uint8_t* text_mask, const float* video, const int64_t* anchor_ids,
                             int n_ids, const int64_t* anchor_alignment, const uint8_t* audio_pad_mask, samaudio_stream stream) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->prepare(rows, frames, text_len, latent, text, text_mask, video, anchor_ids, n_ids, anchor_alignment,
-                                  audio_pad_mask, (hipStream_t)stream, candidates, true));
+  return SA_ENTRY(ctx, "null context",
+                  ctx->engine->prepare(rows, frames, text_len, latent, text, text_mask, video, anchor_ids, n_ids,
+                      anchor_alignment, audio_pad_mask, (hipStream_t)stream, candidates, true));
 }
 
 int samaudio_forward(samaudio_ctx* ctx, const float* noisy, const float* time, int n_time, float* out,
                      samaudio_stream stream) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->forward(noisy, time, n_time, out, (hipStream_t)stream));
+  return SA_ENTRY(ctx, "null context", ctx->engine->forward(noisy, time, n_time, out, (hipStream_t)stream));
 }
 
 int samaudio_ode_solve(samaudio_ctx* ctx, float* state, int method, const float* grid_host, int n_grid,
                        samaudio_stream stream) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->ode_solve(state, method, grid_host, n_grid, (hipStream_t)stream));
+  return SA_ENTRY(ctx, "null context", ctx->engine->ode_solve(state, method, grid_host, n_grid, (hipStream_t)stream));
 }
 
 size_t samaudio_ode_stage_bytes(samaudio_ctx* ctx, int method, int rows, int frames) {
@@ -124,20 +112,17 @@ size_t samaudio_ode_stage_bytes(samaudio_ctx* ctx, int method, int rows, int fra
 }
 
 int samaudio_set_ode_stages(samaudio_ctx* ctx, void* stages, size_t bytes) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->set_ode_stages(stages, bytes));
+  return SA_ENTRY(ctx, "null context", ctx->engine->set_ode_stages(stages, bytes));
 }
 
 int samaudio_codec_encode(samaudio_ctx* ctx, const float* wav, int items, int64_t samples, float* latent,
                           samaudio_stream stream) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->codec_encode(wav, items, samples, latent, (hipStream_t)stream));
+  return SA_ENTRY(ctx, "null context", ctx->engine->codec_encode(wav, items, samples, latent, (hipStream_t)stream));
 }
 
 int samaudio_codec_decode(samaudio_ctx* ctx, const float* latent, int items, int frames, float* wav,
                           samaudio_stream stream) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->codec_decode(latent, items, frames, wav, (hipStream_t)stream));
+  return SA_ENTRY(ctx, "null context", ctx->engine->codec_decode(latent, items, frames, wav, (hipStream_t)stream));
 }
 
 int samaudio_codec_decode_pairs(samaudio_ctx* ctx, const float* state, int rows, int frames, float* wav, samaudio_stream stream) {
@@ -153,8 +138,7 @@ int samaudio_debug_poison_lds(samaudio_stream stream) {
 }
 
 int samaudio_profile_begin(samaudio_ctx* ctx) {
-  if (!ctx) return bad("null context");
-  return ret(ctx->engine->profile_begin());
+  return SA_ENTRY(ctx, "null context", ctx->engine->profile_begin());
 }
 
 int samaudio_sentinel_read(samaudio_ctx* ctx, float* absmax, double* nonfinite, samaudio_stream stream) {
@@ -449,18 +433,15 @@ void samaudio_judge_destroy(samaudio_judge* j) {
 
 int samaudio_judge_set_tensor(samaudio_judge* j, const char* name, const void* data, int dtype, int ndim,
                               const int64_t* shape) {
-  if (!j) return bad("null judge");
-  return ret(j->judge->set_tensor(name, data, dtype, ndim, shape));
+  return SA_ENTRY(j, "null judge", j->judge->set_tensor(name, data, dtype, ndim, shape));
 }
 
 int samaudio_judge_set_option(samaudio_judge* j, int option, int value) {
-  if (!j) return bad("null judge");
-  return ret(j->judge->set_option(option, value));
+  return SA_ENTRY(j, "null judge", j->judge->set_option(option, value));
 }
 
 int samaudio_judge_finalize(samaudio_judge* j) {
-  if (!j) return bad("null judge");
-  return ret(j->judge->finalize());
+  return SA_ENTRY(j, "null judge", j->judge->finalize());
 }
 
 size_t samaudio_judge_workspace_bytes(samaudio_judge* j, int inputs, int candidates, int frames) {
@@ -469,22 +450,20 @@ size_t samaudio_judge_workspace_bytes(samaudio_judge* j, int inputs, int candida
 }
 
 int samaudio_judge_set_workspace(samaudio_judge* j, void* workspace, size_t bytes) {
-  if (!j) return bad("null judge");
-  return ret(j->judge->set_workspace(workspace, bytes));
+  return SA_ENTRY(j, "null judge", j->judge->set_workspace(workspace, bytes));
 }
 
 int samaudio_judge_score(samaudio_judge* j, const float* input_latent, const float* separated_latent, int inputs,
                          int candidates, int frames, const float* text_pooled, const uint8_t* pad_mask, float* scores,
                          samaudio_stream stream) {
-  if (!j) return bad("null judge");
-  return ret(j->judge->score(input_latent, separated_latent, inputs, candidates, frames, text_pooled, pad_mask, scores,
-                             (hipStream_t)stream));
+  return SA_ENTRY(j, "null judge",
+                  j->judge->score(input_latent, separated_latent, inputs, candidates, frames, text_pooled, pad_mask, scores,
+                      (hipStream_t)stream));
 }
 
 int samaudio_judge_encode(samaudio_judge* j, int which, const float* x, const uint8_t* pad_mask, int rows, int frames,
                           float* hidden, samaudio_stream stream) {
-  if (!j) return bad("null judge");
-  return ret(j->judge->encode(which, x, pad_mask, rows, frames, hidden, (hipStream_t)stream));
+  return SA_ENTRY(j, "null judge", j->judge->encode(which, x, pad_mask, rows, frames, hidden, (hipStream_t)stream));
 }
 
 // ---- PE-A-Frame span predictor -------------------------------------------------------------------------
@@ -505,18 +484,15 @@ void samaudio_frame_destroy(samaudio_frame* f) {
 
 int samaudio_frame_set_tensor(samaudio_frame* f, const char* name, const void* data, int dtype, int ndim,
                               const int64_t* shape) {
-  if (!f) return bad("null frame predictor");
-  return ret(f->frame->set_tensor(name, data, dtype, ndim, shape));
+  return SA_ENTRY(f, "null frame predictor", f->frame->set_tensor(name, data, dtype, ndim, shape));
 }
 
 int samaudio_frame_set_option(samaudio_frame* f, int option, int value) {
-  if (!f) return bad("null frame predictor");
-  return ret(f->frame->set_option(option, value));
+  return SA_ENTRY(f, "null frame predictor", f->frame->set_option(option, value));
 }
 
 int samaudio_frame_finalize(samaudio_frame* f) {
-  if (!f) return bad("null frame predictor");
-  return ret(f->frame->finalize());
+  return SA_ENTRY(f, "null frame predictor", f->frame->finalize());
 }
 
 size_t samaudio_frame_workspace_bytes(samaudio_frame* f, int rows, int frames) {
@@ -525,14 +501,13 @@ size_t samaudio_frame_workspace_bytes(samaudio_frame* f, int rows, int frames) {
 }
 
 int samaudio_frame_set_workspace(samaudio_frame* f, void* workspace, size_t bytes) {
-  if (!f) return bad("null frame predictor");
-  return ret(f->frame->set_workspace(workspace, bytes));
+  return SA_ENTRY(f, "null frame predictor", f->frame->set_workspace(workspace, bytes));
 }
 
 int samaudio_frame_logits(samaudio_frame* f, const float* codec_features, const float* text_pooled,
                           const uint8_t* pad_mask, int rows, int frames, float* logits, samaudio_stream stream) {
-  if (!f) return bad("null frame predictor");
-  return ret(f->frame->logits(codec_features, text_pooled, pad_mask, rows, frames, logits, (hipStream_t)stream));
+  return SA_ENTRY(f, "null frame predictor",
+                  f->frame->logits(codec_features, text_pooled, pad_mask, rows, frames, logits, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -279,16 +279,16 @@ __global__ __launch_bounds__(256) void self_attn_f32_kernel(const float* __restr
 // (810 ms of a 5.7 s step at 32 clips, profiles/r6_call1/).  Tiling = self_attn_bf16_kernel: NW waves x 16 query rows, keys in tiles
 // of 64; LDS = hi + lo images of the K tile and of the V^T tile (4 x 16 KiB at HD 128) + per-wave P tiles.
 // ---------------------------------------------------------------------------------------------------
-// The hi half is clamped to the largest finite 16-bit value, as in split3: an fp32 value beyond it (IEEE half: |x| > 65504) keeps a
-// finite hi and the rest in lo instead of turning into inf and inf - inf = NaN.
+// Eight values into four packed hi and four packed lo words (the split and its clamp: common.h split_h16x2, as in split3)
 __device__ __forceinline__ void split8(const float4 a, const float4 b, uint4& hi, uint4& lo) {
 #pragma clang fp contract(off)
   const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
   unsigned h[4], l[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    h[e] = pack_h16x2(fminf(fmaxf(v[2 * e], -kH16Max), kH16Max), fminf(fmaxf(v[2 * e + 1], -kH16Max), kH16Max));
-    l[e] = pack_h16x2(v[2 * e] - h16_lo(h[e]), v[2 * e + 1] - h16_hi(h[e]));
+    const H16Split s = split_h16x2(v[2 * e], v[2 * e + 1]);
+    h[e] = s.hi;
+    l[e] = s.lo;
   }
   hi = make_uint4(h[0], h[1], h[2], h[3]);
   lo = make_uint4(l[0], l[1], l[2], l[3]);
@@ -973,7 +973,8 @@ __global__ __launch_bounds__(256) void cross_attn_probs3_kernel(const float* __r
   const float* qrow = q + m * D + h * 128 + lg * 8;
   const float* krow = kv + (b * Lt + (lr < Lt ? lr : 0)) * kv_ld + h * 128 + lg * 8;
   const float* wrow = qw + lg * 8;
-  // (NaN passes: v_med3_f32 would turn it into -kH16Max, and a fully masked text row must stay NaN like the reference's softmax)
+  // (not common.h clamp_h16 / split_h16x2: v_med3_f32, one instruction, on purpose - with NaN passed around it: v_med3_f32 would turn
+  // it into -kH16Max, and a fully masked text row must stay NaN like the reference's softmax)
   auto cl = [](float x) { return x != x ? x : __builtin_amdgcn_fmed3f(x, -kH16Max, kH16Max); };
   f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
   float ss = 0.f;

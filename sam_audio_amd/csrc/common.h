@@ -69,6 +69,25 @@ constexpr float kH16Max = 65504.f;
 constexpr float kH16Max = 3.3895313892515355e38f;
 #endif
 
+// Compensated 16-bit GEMM operands (SAMAUDIO_OPT_X3_CLASSES): an fp32 activation row x[K] becomes the
+// 16-bit row [lo | hi | hi] of 3K elements with hi = rn16(x), lo = rn16(x - hi), i.e. x = hi + lo to ~2^-22 relative.  Against a
+// weight row laid out [W_hi | W_lo | W_hi] one plain 16-bit GEMM over K' = 3K then accumulates, in fp32 and small terms first,
+// x_lo W_hi + x_hi W_lo + x_hi W_hi = x W - x_lo W_lo: the product of the fp32 operands to ~2^-21.  hi is clamped to the format's
+// largest finite value (IEEE half: 65504), so a value up to twice that still splits exactly instead of becoming inf - inf.
+// The kernels that emit a split operand split with split_h16x2, so "the bits of the fp32 result followed by launch_split3" holds by
+// construction - but for three sites that keep the expressions written out: epilogue8_act_split3 (gemm8.hip: clamp_h16 only, both hi
+// words before both residuals - the pair form compiled to other machine code there), and the two v_med3_f32 forms (gemm.hip's fly
+// split, cross_attn_probs3_kernel).  The arithmetic in front (norm, gain, activation) stays with the caller, under the caller's
+// fp contract(off).
+__device__ __forceinline__ float clamp_h16(float x) { return fminf(fmaxf(x, -kH16Max), kH16Max); }
+// two values -> the packed hi word and the packed lo word
+struct H16Split { unsigned hi, lo; };
+__device__ __forceinline__ H16Split split_h16x2(float v0, float v1) {
+#pragma clang fp contract(off)
+  const unsigned hi = pack_h16x2(clamp_h16(v0), clamp_h16(v1));
+  return H16Split{hi, pack_h16x2(v0 - h16_lo(hi), v1 - h16_hi(hi))};
+}
+
 // ---- the OTHER 16-bit format (mixed mode) ------------------------------------------------------------------------------
 // precision = "mixed" runs on the fp16 build of the library with the five big GEMM classes of the DiT (qkv, wo, c_wq, w13, w2:
 // 96 % of the flops, 2e-4 of the error each in bf16 - DESIGN.md section 4) on bfloat16 operands, i.e. BASELINE's dtype where

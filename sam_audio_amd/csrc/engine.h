@@ -4,80 +4,7 @@
 
 namespace sa {
 
-// SAMAUDIO_OPT_X3_CLASSES, shared by the DiT engine and the PE-AV towers (peav.hip).
-// A launch stated on an fp32 tensor, restated on that tensor's split copy (every element of the K axis became three): the one place
-// offsets, strides and extents along K are scaled.  It does not say how K' is laid out - the two functions below do, and the caller
-// picks one (a helper that infers it was the bug)
-inline void x3_scale_k(GemmParams& p) { p.a_off *= 3; p.a_bstride *= 3; p.lda *= 3; p.tap_stride *= 3; p.kc *= 3; p.K *= 3; }
-// K' split per input block (the k3 convolutions: a tap is [lo | hi | hi] of a row against that tap's [W_hi | W_lo | W_hi]; the codec's
-// wide convolutions: per Cin-block): the geometry of `p` on the split buffer `a3`.  A plain walk over K' - never x3_share
-inline void x3_block_operands(GemmParams& p, const void* a3, const void* w3, bool ktm3) {
-  p.A = a3; p.W = w3;
-  x3_scale_k(p);
-  if (ktm3) p.flags |= GEMM_FLAG_W_KTM;
-}
-// K' split over the whole K: the 16-bit launch over K' = 3K that an x3 class makes of its fp32 GemmParams (kc == K, no taps).
-// A = the split operand [lo | hi | hi] (dense rows of 3K; a batched launch keeps its offsets, into the split copy of the same tensor),
-// W = the split weight [W_hi | W_lo | W_hi]
-inline void x3_operands(GemmParams& p, const void* a3, const LinW& w) {
-  p.lda = p.K;
-  x3_block_operands(p, a3, w.w3, w.ktm3);
-  if (p.out_act) {   // an fp32 context's "activation" outputs are fp32 tensors: the 16-bit kernel writes them as its fp32 output
-    p.out_f32 = (float*)p.out_act; p.f32_ld = p.act_ld; p.f32_bstride = p.act_bstride; p.f32_off = p.act_off;
-    p.f32_act = p.act != ACT_NONE;
-    p.out_act = nullptr; p.act_ld = p.act_bstride = p.act_off = 0;
-  }
-  if ((p.flags & GEMM_FLAG_OUT_SPLIT3) && p.out_f32) {   // the result leaves as the next GEMM's split operand (16-bit, 3 x n_out per row)
-    p.out_act = p.out_f32; p.act_ld = 3L * (p.swiglu ? p.N / 2 : p.N); p.act_bstride = p.act_off = 0;
-    p.out_f32 = nullptr; p.f32_ld = p.f32_bstride = p.f32_off = 0; p.f32_act = 0;
-  }
-}
-// An x3 launch on K-concatenated split operands: let the 8-phase kernels share the operand tiles the three products have in common
-// (common.h GEMM_FLAG_X3_SHARE) wherever the launch qualifies; DBG_X3_PLAIN_WALK = 1: the plain walk over K' (A/B, tests), >= 2: a class
-// mask << 1 that keeps the sharing order for those classes only (diagnosis).  Launches with K' split per input block (the
-// convolutions) never come here.
-inline GemmParams x3_share(const GemmParams& p, int cls) {
-  const int plain_walk = debug_flag(DBG_X3_PLAIN_WALK);
-  if (plain_walk == 1 || (plain_walk >= 2 && !(cls & (plain_walk >> 1)))) return p;
-  GemmParams q = p;
-  q.flags |= GEMM_FLAG_X3_SHARE;
-  return q.kc == q.K && q.K % 192 == 0 && !gemm_check(q, true) ? q : p;
-}
-
-// The launch of `p` (an x3 class's fp32 launch on the split operand a3) that writes its result as the NEXT GEMM's split operand into
-// `out3`: the caller finishes it the way it launches (launch_params / x3_share) and asks gemm_check whether the 8-phase family takes it
-inline GemmParams x3_split3_out(GemmParams p, const void* a3, const LinW& w, void* out3) {
-  p.out_act = out3;
-  p.flags |= GEMM_FLAG_OUT_SPLIT3;
-  x3_operands(p, a3, w);
-  return p;
-}
-// `rows` split rows of 3 k 16-bit elements fit the scratch `buf` of `cap` bytes; x3_fits: ... or `who` + `what`, the context's message
-inline bool x3_room(const void* buf, size_t cap, long rows, long k) { return buf && (size_t)rows * 3 * k * 2 <= cap; }
-inline Status x3_fits(const void* buf, size_t cap, long rows, long k, const std::string& who, const char* what) {
-  return x3_room(buf, cap, rows, k) ? Status{} : Status{SAMAUDIO_ERR_WORKSPACE, who + "SAMAUDIO_OPT_X3_CLASSES: " + what};
-}
-
 constexpr int HALO = 40;  // zero rows either side of codec activations (>= 4 * max dilation 9)
-
-class Bump {  // workspace carving (also used dry to size the workspace)
- public:
-  explicit Bump(char* base = nullptr, size_t cap = 0) : base_(base), cap_(cap) {}
-  void* take(size_t bytes) {
-    size_t off = (used_ + 255) & ~size_t(255);
-    used_ = off + bytes;
-    return base_ ? base_ + off : nullptr;
-  }
-  size_t used() const { return (used_ + 255) & ~size_t(255); }
-  bool fits() const { return used() <= cap_; }
-  void reset_to(size_t mark) { used_ = mark; }
-  size_t mark() const { return used_; }
-
- private:
-  char* base_;
-  size_t cap_;
-  size_t used_ = 0;
-};
 
 class Engine {
  public:

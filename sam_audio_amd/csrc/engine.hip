@@ -10,8 +10,6 @@
 
 namespace sa {
 
-static Status fail(int code, const std::string& m) { return Status{code, m}; }
-
 // SAMAUDIO_TRACE=1: after each stage of an evaluation, synchronise, copy the stage's buffer to the host and print how
 // many values are non-finite plus the largest magnitude (debugging aid; never on in timed runs).
 static bool trace_on() {
@@ -103,7 +101,6 @@ static void trace(const char* name, const void* dev, size_t count, bool is_bf16,
   }
   std::fprintf(stderr, "[samaudio trace] %-22s n=%zu non-finite=%zu max|x|=%.4g\n", name, count, bad, mx);
 }
-static long round_up(long v, long m) { return (v + m - 1) / m * m; }
 
 Engine::Engine(const samaudio_config& c) : cfg_(c) {
   bf16_ = c.precision == SAMAUDIO_BF16;
@@ -193,9 +190,7 @@ static int kpad(int k, bool bf16) { return (int)round_up(k, bf16 ? 64 : 32); }
 
 Status Engine::finalize(int what) {
   const int D = cfg_.dim, F = cfg_.ffn_hidden, L = cfg_.n_layers, C2 = cfg_.latent_channels;
-  const int F32 = SAMAUDIO_DT_F32, AT = at_dtype_;
-#define NEEDF(field, name, ...) SA_TRY(reg_.need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
-#define NEEDW(field, name, ...) SA_TRY(reg_.need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
+  const int AT = at_dtype_;
   if (what == 0) {
     // head_dim = dim / n_heads: 128 (every kernel tuned for it) or 64 (general forms of qkv_prep / the norms / cross-attention,
     // the self-attention kernel's 64-wide instantiation, no folded cross-attention projection)
@@ -208,16 +203,16 @@ Status Engine::finalize(int what) {
     for (int i = 0; i < L; ++i) {
       const std::string P = "L" + std::to_string(i) + ".";
       LayerW& w = layers_[i];
-      NEEDF(w.attn_norm, P + "attn_norm", D);
-      NEEDF(w.ffn_norm, P + "ffn_norm", D);
-      NEEDF(w.mod_table, P + "mod_table", 6, D);
-      NEEDF(w.q_norm, P + "q_norm", hd);
-      NEEDF(w.k_norm, P + "k_norm", hd);
-      NEEDF(w.c_q_norm, P + "c_q_norm", hd);
+      NEEDF(reg_, w.attn_norm, P + "attn_norm", D);
+      NEEDF(reg_, w.ffn_norm, P + "ffn_norm", D);
+      NEEDF(reg_, w.mod_table, P + "mod_table", 6, D);
+      NEEDF(reg_, w.q_norm, P + "q_norm", hd);
+      NEEDF(reg_, w.k_norm, P + "k_norm", hd);
+      NEEDF(reg_, w.c_q_norm, P + "c_q_norm", hd);
       SA_TRY(need_w5(P + "wqkv", 3 * D, D, w.wqkv));
       SA_TRY(need_w5(P + "wo", D, D, w.wo));
       SA_TRY(need_w5(P + "c_wq", D, D, w.c_wq));
-      NEEDW(w.c_wo.w, P + "c_wo", D, D);
+      NEEDW(reg_, AT, w.c_wo.w, P + "c_wo", D, D);
       SA_TRY(need_w5(P + "w13", 2 * F, D, w.w13));
       SA_TRY(need_w5(P + "w2", D, F, w.w2));
       if (!bf16_) {   // SAMAUDIO_OPT_X3_CLASSES: optional split copies, checked when a class is switched on / at the end of finalize
@@ -227,43 +222,43 @@ Status Engine::finalize(int what) {
         for (const auto& t : x3w) reg_.twin(P + t.leaf + ".x3", t.N, 3L * t.K, t.w);
       }
     }
-    NEEDF(g_.final_table, "final_table", 2, D);
-    NEEDF(g_.final_norm, "final_norm", D);
-    NEEDW(g_.w_out, "w_out", C2, D);
-    NEEDF(g_.gn1_w, "patch1.gn_w", D);
-    NEEDF(g_.gn1_b, "patch1.gn_b", D);
-    NEEDW(g_.pw1.w, "patch1.w", D, 3 * D);
-    NEEDF(g_.pb1, "patch1.b", D);
-    NEEDF(g_.gn2_w, "patch2.gn_w", D);
-    NEEDF(g_.gn2_b, "patch2.gn_b", D);
-    NEEDW(g_.pw2.w, "patch2.w", D, 3 * D);
-    NEEDF(g_.pb2, "patch2.b", D);
-    NEEDW(g_.y_w13, "y_w13", 2 * D, D);
-    NEEDW(g_.y_w2, "y_w2", D, D);
-    NEEDW(g_.t_w13, "t_w13", 2 * D, cfg_.freq_dim);
-    NEEDW(g_.t_w2, "t_w2", D, D);
-    NEEDW(g_.tb_w, "tb_w", 6 * D, D);
-    NEEDF(g_.tb_b, "tb_b", 6 * D);
-    NEEDF(g_.t_freqs, "t_freqs", cfg_.freq_dim / 2);
-    NEEDF(g_.mem_inv_freq, "mem_inv_freq", D / 2);
-    NEEDF(g_.rope_cos, "rope_cos", cfg_.max_positions, hd / 2);
-    NEEDF(g_.rope_sin, "rope_sin", cfg_.max_positions, hd / 2);
-    NEEDW(g_.proj_wy, "proj_wy", D, C2);
-    NEEDW(g_.proj_wf, "proj_wf", D, C2);
-    NEEDF(g_.proj_b, "proj_b", D);
-    NEEDW(g_.mem_w, "mem_w", D, cfg_.text_dim);
-    NEEDF(g_.mem_b, "mem_b", D);
-    NEEDW(g_.vid_w, "vid_w", D, cfg_.video_dim);
-    NEEDF(g_.vid_b, "vid_b", D);
-    NEEDF(g_.vid_ln_w, "vid_ln_w", D);
-    NEEDF(g_.vid_ln_b, "vid_ln_b", D);
-    NEEDF(g_.vid_gate, "vid_gate", 1);
-    NEEDF(g_.anc_emb, "anc_emb", cfg_.anchor_vocab, cfg_.anchor_dim);
-    NEEDW(g_.anc_w, "anc_w", D, cfg_.anchor_dim);
+    NEEDF(reg_, g_.final_table, "final_table", 2, D);
+    NEEDF(reg_, g_.final_norm, "final_norm", D);
+    NEEDW(reg_, AT, g_.w_out, "w_out", C2, D);
+    NEEDF(reg_, g_.gn1_w, "patch1.gn_w", D);
+    NEEDF(reg_, g_.gn1_b, "patch1.gn_b", D);
+    NEEDW(reg_, AT, g_.pw1.w, "patch1.w", D, 3 * D);
+    NEEDF(reg_, g_.pb1, "patch1.b", D);
+    NEEDF(reg_, g_.gn2_w, "patch2.gn_w", D);
+    NEEDF(reg_, g_.gn2_b, "patch2.gn_b", D);
+    NEEDW(reg_, AT, g_.pw2.w, "patch2.w", D, 3 * D);
+    NEEDF(reg_, g_.pb2, "patch2.b", D);
+    NEEDW(reg_, AT, g_.y_w13, "y_w13", 2 * D, D);
+    NEEDW(reg_, AT, g_.y_w2, "y_w2", D, D);
+    NEEDW(reg_, AT, g_.t_w13, "t_w13", 2 * D, cfg_.freq_dim);
+    NEEDW(reg_, AT, g_.t_w2, "t_w2", D, D);
+    NEEDW(reg_, AT, g_.tb_w, "tb_w", 6 * D, D);
+    NEEDF(reg_, g_.tb_b, "tb_b", 6 * D);
+    NEEDF(reg_, g_.t_freqs, "t_freqs", cfg_.freq_dim / 2);
+    NEEDF(reg_, g_.mem_inv_freq, "mem_inv_freq", D / 2);
+    NEEDF(reg_, g_.rope_cos, "rope_cos", cfg_.max_positions, hd / 2);
+    NEEDF(reg_, g_.rope_sin, "rope_sin", cfg_.max_positions, hd / 2);
+    NEEDW(reg_, AT, g_.proj_wy, "proj_wy", D, C2);
+    NEEDW(reg_, AT, g_.proj_wf, "proj_wf", D, C2);
+    NEEDF(reg_, g_.proj_b, "proj_b", D);
+    NEEDW(reg_, AT, g_.mem_w, "mem_w", D, cfg_.text_dim);
+    NEEDF(reg_, g_.mem_b, "mem_b", D);
+    NEEDW(reg_, AT, g_.vid_w, "vid_w", D, cfg_.video_dim);
+    NEEDF(reg_, g_.vid_b, "vid_b", D);
+    NEEDF(reg_, g_.vid_ln_w, "vid_ln_w", D);
+    NEEDF(reg_, g_.vid_ln_b, "vid_ln_b", D);
+    NEEDF(reg_, g_.vid_gate, "vid_gate", 1);
+    NEEDF(reg_, g_.anc_emb, "anc_emb", cfg_.anchor_vocab, cfg_.anchor_dim);
+    NEEDW(reg_, AT, g_.anc_w, "anc_w", D, cfg_.anchor_dim);
     // cross-attention K|V projections of ALL layers as one operand: the text memory changes with t only through
     // the y-embedder, so one GEMM per evaluation serves the 22 layers (reference transformer.py:382-388, :102-114)
-    NEEDW(g_.c_wkv_all.w, "c_wkv_all", (int64_t)L * 2 * D, D);
-    NEEDF(g_.c_k_norm_all, "c_k_norm_all", L, hd);
+    NEEDW(reg_, AT, g_.c_wkv_all.w, "c_wkv_all", (int64_t)L * 2 * D, D);
+    NEEDF(reg_, g_.c_k_norm_all, "c_k_norm_all", L, hd);
     if (bf16_) {  // fp32 copies for SAMAUDIO_OPT_F32_CLASSES: optional, checked when a class is switched on / used
 #define OPTF(field, name, ...) g32_.field = (const float*)opt(name ".f32", {__VA_ARGS__})
       OPTF(w_out, "w_out", C2, D);
@@ -295,34 +290,34 @@ Status Engine::finalize(int what) {
         ResUnitW& r = s.r[j];
         r.k1pad = kpad(7 * C, bf16_);
         r.k2pad = kpad(C, bf16_);
-        NEEDF(r.a1, R + "a1", C);
-        NEEDW(r.w1, R + "w1", C, r.k1pad);
-        NEEDF(r.b1, R + "b1", C);
-        NEEDF(r.a2, R + "a2", C);
-        NEEDW(r.w2, R + "w2", C, r.k2pad);
-        NEEDF(r.b2, R + "b2", C);
+        NEEDF(reg_, r.a1, R + "a1", C);
+        NEEDW(reg_, AT, r.w1, R + "w1", C, r.k1pad);
+        NEEDF(reg_, r.b1, R + "b1", C);
+        NEEDF(reg_, r.a2, R + "a2", C);
+        NEEDW(reg_, AT, r.w2, R + "w2", C, r.k2pad);
+        NEEDF(reg_, r.b2, R + "b2", C);
       }
       return Status{};
     };
     // encoder
-    NEEDW(enc_.in_w, "enc.in.w", cfg_.enc_dim, 64);
-    NEEDF(enc_.in_b, "enc.in.b", cfg_.enc_dim);
+    NEEDW(reg_, AT, enc_.in_w, "enc.in.w", cfg_.enc_dim, 64);
+    NEEDF(reg_, enc_.in_b, "enc.in.b", cfg_.enc_dim);
     int C = cfg_.enc_dim;
     for (int i = 0; i < 4; ++i) {
       const std::string P = "enc.s" + std::to_string(i) + ".";
       const int s = cfg_.enc_rates[i];
       if (s % 2) return fail(SAMAUDIO_ERR_ARG, "codec strides must be even");
       SA_TRY(res_units(P, enc_.s[i], C));
-      NEEDF(enc_.s[i].a, P + "a", C);
-      NEEDW(enc_.s[i].w, P + "down.w", 2 * C, 2 * s * C);
-      NEEDF(enc_.s[i].b, P + "down.b", 2 * C);
+      NEEDF(reg_, enc_.s[i].a, P + "a", C);
+      NEEDW(reg_, AT, enc_.s[i].w, P + "down.w", 2 * C, 2 * s * C);
+      NEEDF(reg_, enc_.s[i].b, P + "down.b", 2 * C);
       C *= 2;
     }
-    NEEDF(enc_.out_a, "enc.out.a", C);
-    NEEDW(enc_.out_w, "enc.out.w", CL, 3 * C);
-    NEEDF(enc_.out_b, "enc.out.b", CL);
-    NEEDW(enc_.proj_w, "enc.proj.w", CD, CL);
-    NEEDF(enc_.proj_b, "enc.proj.b", CD);
+    NEEDF(reg_, enc_.out_a, "enc.out.a", C);
+    NEEDW(reg_, AT, enc_.out_w, "enc.out.w", CL, 3 * C);
+    NEEDF(reg_, enc_.out_b, "enc.out.b", CL);
+    NEEDW(reg_, AT, enc_.proj_w, "enc.proj.w", CD, CL);
+    NEEDF(reg_, enc_.proj_b, "enc.proj.b", CD);
     enc_ready_ = true;
     // SAMAUDIO_OPT_X3_CLASSES bit CODEC: twins of registered codec weights, keyed by the weight's own pointer.  "<name>.x3": every
     // Cin-block of a row as [W_hi | W_lo | W_hi] (the wide convolutions, gemm_codec_x3); "<name>.fly" (weights.py convert_codec_fly16): the
@@ -348,29 +343,27 @@ Status Engine::finalize(int what) {
     }
     if (what == 2) return Status{};  // encoder only: the Judge's DACVAEEncoder (reference codec.py:42-78)
     // decoder
-    NEEDW(dec_.proj_w, "dec.proj.w", CL, CD);
-    NEEDF(dec_.proj_b, "dec.proj.b", CL);
-    NEEDW(dec_.in_w, "dec.in.w", cfg_.dec_dim, 7 * CL);
-    NEEDF(dec_.in_b, "dec.in.b", cfg_.dec_dim);
+    NEEDW(reg_, AT, dec_.proj_w, "dec.proj.w", CL, CD);
+    NEEDF(reg_, dec_.proj_b, "dec.proj.b", CL);
+    NEEDW(reg_, AT, dec_.in_w, "dec.in.w", cfg_.dec_dim, 7 * CL);
+    NEEDF(reg_, dec_.in_b, "dec.in.b", cfg_.dec_dim);
     C = cfg_.dec_dim;
     for (int i = 0; i < 4; ++i) {
       const std::string P = "dec.s" + std::to_string(i) + ".";
       const int s = cfg_.dec_rates[i];
       if (s % 2) return fail(SAMAUDIO_ERR_ARG, "codec strides must be even");
-      NEEDF(dec_.s[i].a, P + "a", C);
-      NEEDW(dec_.s[i].w, P + "up.w", s * (C / 2), 2 * C);
-      NEEDF(dec_.s[i].b, P + "up.b", C / 2);
+      NEEDF(reg_, dec_.s[i].a, P + "a", C);
+      NEEDW(reg_, AT, dec_.s[i].w, P + "up.w", s * (C / 2), 2 * C);
+      NEEDF(reg_, dec_.s[i].b, P + "up.b", C / 2);
       C /= 2;
       SA_TRY(res_units(P, dec_.s[i], C));
     }
     dec_.out_kpad = kpad(7 * C, bf16_);
-    NEEDF(dec_.out_a, "dec.out.a", C);
-    NEEDW(dec_.out_w, "dec.out.w", 1, dec_.out_kpad);
-    NEEDF(dec_.out_b, "dec.out.b", 1);
+    NEEDF(reg_, dec_.out_a, "dec.out.a", C);
+    NEEDW(reg_, AT, dec_.out_w, "dec.out.w", 1, dec_.out_kpad);
+    NEEDF(reg_, dec_.out_b, "dec.out.b", 1);
     codec_ready_ = true;
   }
-#undef NEEDF
-#undef NEEDW
   return Status{};
 }
 
@@ -679,7 +672,7 @@ GemmParams Engine::launch_params(const GemmParams& p_in, int cls, GemmKind kind)
   // the classes with operands in the alt format (SAMAUDIO_OPT_ALT16_CLASSES, mixed mode)
   p.flags = (p_in.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split_ ? 0 : GEMM_FLAG_NO_TAIL_SPLIT) |
             (alt16(cls) && kind != GemmKind::F32 ? GEMM_FLAG_OPND_ALT : 0);
-  // an x3 launch on K-concatenated split operands shares operand tiles wherever it qualifies (engine.h x3_share); X3Block (the
+  // an x3 launch on K-concatenated split operands shares operand tiles wherever it qualifies (host.h x3_share); X3Block (the
   // convolutions: every Cin-block of K' is its own [hi | lo | hi]) never does
   if (kind == GemmKind::X3) p = x3_share(p, cls);
   return p;
@@ -784,7 +777,7 @@ Status Engine::linear(GemmParams p, const LinW& w, int cls, hipStream_t st, cons
     return gemm(p, st, -1.0, cls);
   }
   if (!w.w3 || !d_.x3a) return fail(SAMAUDIO_ERR_STATE, "SAMAUDIO_OPT_X3_CLASSES: split weight or scratch operand missing (set the option before samaudio_prepare)");
-  if (p.nbatch != 1 || p.kc != p.K || p.a_off || p.tap_stride || (p.out_act && p.out_f32))
+  if (!x3_whole_k(p) || p.nbatch != 1 || p.a_off)
     return fail(SAMAUDIO_ERR_ARG, "SAMAUDIO_OPT_X3_CLASSES: plain single-batch launches with one output only");
   const int K = p.K;
   if (!presplit) {   // split the fp32 operand here: into x3a (D-wide rows), or - w2's F-wide hidden - into x3u
@@ -1334,7 +1327,8 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
       // the SwiGLU epilogue writes w2's split operand itself where the 8-phase family takes the launch gemm() would make of it
       // (F % 32 == 0 among others); otherwise w2 splits u with the stand-alone kernel
       w2_pre = x3(SAMAUDIO_CLS_W13) && x3(SAMAUDIO_CLS_W2) &&
-               !gemm_check(launch_params(x3_split3_out(p, d_.x3a, w.w13, d_.x3u), SAMAUDIO_CLS_W13, GemmKind::X3), true);
+               x3_w2_pre(p, d_.x3a, w.w13, d_.x3u, d_.x3u_bytes, M, F,
+                         [&](const GemmParams& q) { return launch_params(q, SAMAUDIO_CLS_W13, GemmKind::X3); });
       if (w2_pre) { p.out_act = d_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
       SA_TRY(linear(p, w.w13, SAMAUDIO_CLS_W13, st, w13_pre ? d_.x3a : nullptr));
       trace("  xn (ffn)", d_.xn, (size_t)M * D, bf16_, st);

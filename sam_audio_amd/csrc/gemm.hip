@@ -164,7 +164,8 @@ __global__ __launch_bounds__(256, (FLY ? 2 : 1)) void gemm_kernel(const GemmPara
         // one 16x16x32 fragment; A and W use the same lane -> k map, so the MFMA pairs equal k.  Small terms first.
 #pragma clang fp contract(off)
         bf16x8_t ah[FM], al[FM], bh[FN], bl[FN];
-        auto cl = [](float x) { return __builtin_amdgcn_fmed3f(x, -kH16Max, kH16Max); };   // (one instruction; finite x: fmin(fmax()))
+        // (not common.h clamp_h16 / split_h16x2: v_med3_f32, one instruction in the K loop, on purpose; finite x: the same fmin(fmax()))
+        auto cl = [](float x) { return __builtin_amdgcn_fmed3f(x, -kH16Max, kH16Max); };
         auto split = [&](const char* base, int row, bf16x8_t& hi, bf16x8_t& lo) {
           const int sw = (row >> 1) & 7;
           const f32x4_t v0 = *(const f32x4_t*)(base + row * 128 + ((lg ^ sw) << 4));

@@ -344,7 +344,6 @@ __device__ __forceinline__ void epilogue8_act_split3(const GemmParams& p, f32x4_
 #pragma unroll
   for (int j = 0; j < 4; ++j) cb[j] = has_b ? *(const float4*)(p.bias + nc0 + 16 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
   auto activate = [&](float x) { return act == ACT_GELU ? gelu_f(x) : (act == ACT_QUICK_GELU ? quick_gelu_f(x) : x); };
-  auto clamp16 = [](float x) { return fminf(fmaxf(x, -kH16Max), kH16Max); };
 #pragma unroll
   for (int I = 0; I < NI; ++I) {
     const int m = m_wave0 + I * 16 + lr;
@@ -357,8 +356,9 @@ __device__ __forceinline__ void epilogue8_act_split3(const GemmParams& p, f32x4_
         float v0 = acc[I][j][0], v1 = acc[I][j][1], v2 = acc[I][j][2], v3 = acc[I][j][3];
         if (has_b) { v0 += cb[j].x; v1 += cb[j].y; v2 += cb[j].z; v3 += cb[j].w; }
         v0 = activate(v0); v1 = activate(v1); v2 = activate(v2); v3 = activate(v3);
-        lo[h] = pack_h16x2(clamp16(v0), clamp16(v1));
-        hi[h] = pack_h16x2(clamp16(v2), clamp16(v3));
+        // (common.h split_h16x2 written out, both hi words first: the pair form compiles to other machine code here)
+        lo[h] = pack_h16x2(clamp_h16(v0), clamp_h16(v1));
+        hi[h] = pack_h16x2(clamp_h16(v2), clamp_h16(v3));
         rlo[h] = pack_h16x2(v0 - h16_lo(lo[h]), v1 - h16_hi(lo[h]));
         rhi[h] = pack_h16x2(v2 - h16_lo(hi[h]), v3 - h16_hi(hi[h]));
       }

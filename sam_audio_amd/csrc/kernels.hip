@@ -189,12 +189,10 @@ __global__ __launch_bounds__(256) void rmsnorm_gs_split3_kernel(const float* __r
     const float4 gg = g[i], sv = s[i];
     const float o0 = v[k].x * inv * gg.x + sv.x, o1 = v[k].y * inv * gg.y + sv.y, o2 = v[k].z * inv * gg.z + sv.z,
                 o3 = v[k].w * inv * gg.w + sv.w;
-    const unsigned h0 = pack_h16x2(fminf(fmaxf(o0, -kH16Max), kH16Max), fminf(fmaxf(o1, -kH16Max), kH16Max));
-    const unsigned h1 = pack_h16x2(fminf(fmaxf(o2, -kH16Max), kH16Max), fminf(fmaxf(o3, -kH16Max), kH16Max));
-    const unsigned l0 = pack_h16x2(o0 - h16_lo(h0), o1 - h16_hi(h0)), l1 = pack_h16x2(o2 - h16_lo(h1), o3 - h16_hi(h1));
-    *(uint2*)(orow + 4 * i) = make_uint2(l0, l1);
-    *(uint2*)(orow + D + 4 * i) = make_uint2(h0, h1);
-    *(uint2*)(orow + 2 * D + 4 * i) = make_uint2(h0, h1);
+    const H16Split s0 = split_h16x2(o0, o1), s1 = split_h16x2(o2, o3);   // (common.h: the split of launch_split3)
+    *(uint2*)(orow + 4 * i) = make_uint2(s0.lo, s1.lo);
+    *(uint2*)(orow + D + 4 * i) = make_uint2(s0.hi, s1.hi);
+    *(uint2*)(orow + 2 * D + 4 * i) = make_uint2(s0.hi, s1.hi);
   }
 }
 hipError_t launch_rmsnorm_gs_split3(const float* x, const float* gs, long gs_ld, void* out, int M, int D, int rows_per_b, float eps,
@@ -904,12 +902,8 @@ hipError_t launch_to_act(const float* in, long in_bstride, long in_ld, int in_co
 }
 
 // ------------------------------------------------------------------------------------------------
-// Compensated 16-bit GEMM operands (SAMAUDIO_OPT_X3_CLASSES): an fp32 activation row x[K] becomes the
-// 16-bit row [lo | hi | hi] of 3K elements with hi = rn16(x), lo = rn16(x - hi), i.e. x = hi + lo to ~2^-22 relative.  Against a
-// weight row laid out [W_hi | W_lo | W_hi] one plain 16-bit GEMM over K' = 3K then accumulates, in fp32 and small terms first,
-// x_lo W_hi + x_hi W_lo + x_hi W_hi = x W - x_lo W_lo: the product of the fp32 operands to ~2^-21.  hi is clamped to the format's
-// largest finite value (IEEE half: 65504), so a value up to twice that still splits exactly instead of becoming inf - inf.
-// One thread = 8 consecutive elements: two 16-byte loads, three 16-byte stores.
+// An fp32 activation row x[K] into the compensated 16-bit row [lo | hi | hi] of 3K elements (the split and its clamp: common.h
+// split_h16x2).  One thread = 8 consecutive elements: two 16-byte loads, three 16-byte stores.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ x, long ldx, bf16_t* __restrict__ out,
                                                      long chunks, int cpr, int K) {
@@ -923,9 +917,9 @@ __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ x
     unsigned hi[4], lo[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float v0 = v[2 * e], v1 = v[2 * e + 1];
-      hi[e] = pack_h16x2(fminf(fmaxf(v0, -kH16Max), kH16Max), fminf(fmaxf(v1, -kH16Max), kH16Max));
-      lo[e] = pack_h16x2(v0 - h16_lo(hi[e]), v1 - h16_hi(hi[e]));
+      const H16Split s = split_h16x2(v[2 * e], v[2 * e + 1]);
+      hi[e] = s.hi;
+      lo[e] = s.lo;
     }
     bf16_t* dst = out + m * (3L * K) + c;
     *(uint4*)dst = make_uint4(lo[0], lo[1], lo[2], lo[3]);

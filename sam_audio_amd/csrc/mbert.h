@@ -5,7 +5,7 @@
 // (+residual) ; LayerNorm, Wi, gelu(input) * gate, Wo (+residual) } -> final LayerNorm.  No biases anywhere.
 // Like Engine / VisionTower / T5Encoder it owns no device memory: borrowed weights, one caller-provided workspace.
 #pragma once
-#include "peav.h"
+#include "host.h"
 
 namespace sa {
 

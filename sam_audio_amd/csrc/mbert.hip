@@ -12,15 +12,6 @@ struct samaudio_mbert {
 
 namespace sa {
 
-namespace {
-Status mfail(int code, const std::string& m) { return Status{code, m}; }
-Status mgemm(const GemmParams& p, bool bf16, hipStream_t st) {
-  if (const char* why = gemm_check(p, bf16)) return mfail(SAMAUDIO_ERR_ARG, std::string("text tower: ") + why);
-  SA_HIP(launch_gemm(p, bf16, st));
-  return Status{};
-}
-}  // namespace
-
 MBertEncoder::MBertEncoder(const samaudio_mbert_config& c)
     : cfg_(c), bf16_(c.precision == SAMAUDIO_BF16), esz_(bf16_ ? 2 : 4),
       at_dtype_(bf16_ ? SAMAUDIO_DT_BF16 : SAMAUDIO_DT_F32), hd_(c.heads > 0 ? c.hidden / c.heads : 0) {}
@@ -34,36 +25,32 @@ Status MBertEncoder::finalize() {
   const samaudio_mbert_config& c = cfg_;
   if (c.vocab <= 0 || c.hidden <= 0 || c.heads <= 0 || c.intermediate <= 0 || c.layers < 0 || c.max_len <= 0 ||
       c.global_every <= 0 || c.window < 0)
-    return mfail(SAMAUDIO_ERR_ARG, "text tower: non-positive dimension");
+    return fail(SAMAUDIO_ERR_ARG, "text tower: non-positive dimension");
   const int kq = bf16_ ? 64 : 32;   // K granule of the GEMM kernels
   if (c.hidden % kq || c.intermediate % kq || c.hidden % c.heads)
-    return mfail(SAMAUDIO_ERR_ARG, "text tower: hidden and intermediate must be multiples of 64 (fp32 mode: 32), hidden of heads");
-  if (hd_ > 128 || hd_ % 2) return mfail(SAMAUDIO_ERR_ARG, "text tower: head dim must be even and <= 128");
-  if (c.max_len > 512) return mfail(SAMAUDIO_ERR_ARG, "text tower: max_len must be <= 512");
+    return fail(SAMAUDIO_ERR_ARG, "text tower: hidden and intermediate must be multiples of 64 (fp32 mode: 32), hidden of heads");
+  if (hd_ > 128 || hd_ % 2) return fail(SAMAUDIO_ERR_ARG, "text tower: head dim must be even and <= 128");
+  if (c.max_len > 512) return fail(SAMAUDIO_ERR_ARG, "text tower: max_len must be <= 512");
   const int D = c.hidden, F = c.intermediate;
-  const int F32 = SAMAUDIO_DT_F32, AT = at_dtype_;
-#define NEEDF(field, name, ...) SA_TRY(reg_.need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
-#define NEEDW(field, name, ...) SA_TRY(reg_.need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
-  NEEDF(g_.emb, "emb", c.vocab, D);                  // embeddings.tok_embeddings.weight
-  NEEDF(g_.emb_ln, "emb_ln", D);                     // embeddings.norm.weight
-  NEEDF(g_.final_ln, "final_ln", D);
-  NEEDF(g_.zeros, "zeros", D);                       // the (absent) LayerNorm bias
-  NEEDF(g_.rope_cos, "rope_cos", 2, c.max_len, hd_); // [0] global layers, [1] sliding-window layers
-  NEEDF(g_.rope_sin, "rope_sin", 2, c.max_len, hd_);
+  const int AT = at_dtype_;
+  NEEDF(reg_, g_.emb, "emb", c.vocab, D);                  // embeddings.tok_embeddings.weight
+  NEEDF(reg_, g_.emb_ln, "emb_ln", D);                     // embeddings.norm.weight
+  NEEDF(reg_, g_.final_ln, "final_ln", D);
+  NEEDF(reg_, g_.zeros, "zeros", D);                       // the (absent) LayerNorm bias
+  NEEDF(reg_, g_.rope_cos, "rope_cos", 2, c.max_len, hd_); // [0] global layers, [1] sliding-window layers
+  NEEDF(reg_, g_.rope_sin, "rope_sin", 2, c.max_len, hd_);
   layers_.assign(c.layers, LayerW{});
   for (int i = 0; i < c.layers; ++i) {
     const std::string L = "L" + std::to_string(i) + ".";
     LayerW& w = layers_[i];
     w.ln1 = nullptr;
-    if (i > 0) NEEDF(w.ln1, L + "ln1", D);
-    NEEDW(w.wqkv, L + "wqkv", 3 * D, D);
-    NEEDW(w.wo, L + "wo", D, D);
-    NEEDF(w.ln2, L + "ln2", D);
-    NEEDW(w.wi, L + "wi", 2 * F, D);
-    NEEDW(w.wo2, L + "wo2", D, F);
+    if (i > 0) NEEDF(reg_, w.ln1, L + "ln1", D);
+    NEEDW(reg_, AT, w.wqkv, L + "wqkv", 3 * D, D);
+    NEEDW(reg_, AT, w.wo, L + "wo", D, D);
+    NEEDF(reg_, w.ln2, L + "ln2", D);
+    NEEDW(reg_, AT, w.wi, L + "wi", 2 * F, D);
+    NEEDW(reg_, AT, w.wo2, L + "wo2", D, F);
   }
-#undef NEEDF
-#undef NEEDW
   ready_ = true;
   return Status{};
 }
@@ -88,7 +75,7 @@ size_t MBertEncoder::workspace_bytes(int rows, int tokens) {
 }
 
 Status MBertEncoder::set_workspace(void* p, size_t bytes) {
-  if (!p || (reinterpret_cast<uintptr_t>(p) & 255)) return mfail(SAMAUDIO_ERR_WORKSPACE, "text tower: workspace must be 256-byte aligned");
+  if (!p || (reinterpret_cast<uintptr_t>(p) & 255)) return fail(SAMAUDIO_ERR_WORKSPACE, "text tower: workspace must be 256-byte aligned");
   ws_ = (char*)p;
   ws_bytes_ = bytes;
   planned_m_ = 0;
@@ -97,17 +84,17 @@ Status MBertEncoder::set_workspace(void* p, size_t bytes) {
 
 Status MBertEncoder::encode(const long long* ids, const unsigned char* mask, int rows, int tokens, int nth, float* out,
                             hipStream_t st) {
-  if (!ready_) return mfail(SAMAUDIO_ERR_STATE, "text tower: weights not finalized");
-  if (!ids || !mask || !out || rows <= 0 || tokens <= 0) return mfail(SAMAUDIO_ERR_ARG, "text tower: bad argument");
+  if (!ready_) return fail(SAMAUDIO_ERR_STATE, "text tower: weights not finalized");
+  if (!ids || !mask || !out || rows <= 0 || tokens <= 0) return fail(SAMAUDIO_ERR_ARG, "text tower: bad argument");
   if (tokens > cfg_.max_len)
-    return mfail(SAMAUDIO_ERR_ARG, "text tower: " + std::to_string(tokens) + " tokens exceed max_len " + std::to_string(cfg_.max_len));
-  if (nth > cfg_.layers) return mfail(SAMAUDIO_ERR_ARG, "text tower: hidden state index beyond the last layer");
-  if (!ws_) return mfail(SAMAUDIO_ERR_WORKSPACE, "text tower: no workspace");
+    return fail(SAMAUDIO_ERR_ARG, "text tower: " + std::to_string(tokens) + " tokens exceed max_len " + std::to_string(cfg_.max_len));
+  if (nth > cfg_.layers) return fail(SAMAUDIO_ERR_ARG, "text tower: hidden state index beyond the last layer");
+  if (!ws_) return fail(SAMAUDIO_ERR_WORKSPACE, "text tower: no workspace");
   const long M = (long)rows * tokens;
   if (planned_m_ != M) {
     Bump b(ws_, ws_bytes_);
     plan(b, M, true);
-    if (!b.fits()) return mfail(SAMAUDIO_ERR_WORKSPACE, "text tower: workspace too small for " + std::to_string(M) + " token rows");
+    if (!b.fits()) return fail(SAMAUDIO_ERR_WORKSPACE, "text tower: workspace too small for " + std::to_string(M) + " token rows");
     planned_m_ = M;
   }
   const samaudio_mbert_config& c = cfg_;
@@ -125,7 +112,7 @@ Status MBertEncoder::encode(const long long* ids, const unsigned char* mask, int
     {
       GemmParams p = lin(w_.xn, D, w.wqkv, M, 3 * D, D);
       p.out_act = w_.qkv; p.act_ld = 3L * D;
-      SA_TRY(mgemm(p, bf16_, st));
+      SA_TRY(run_gemm(p, bf16_, "text tower: ", st));
     }
     const long roff = (global ? 0L : 1L) * c.max_len * hd_;
     SA_HIP(launch_mbert_rope(w_.qkv, g_.rope_cos + roff, g_.rope_sin + roff, bf16_, M, tokens, H, hd_, st));
@@ -135,18 +122,18 @@ Status MBertEncoder::encode(const long long* ids, const unsigned char* mask, int
       GemmParams p = lin(w_.attn, D, w.wo, M, D, D);  // h = h + Wo(attn)
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
-      SA_TRY(mgemm(p, bf16_, st));
+      SA_TRY(run_gemm(p, bf16_, "text tower: ", st));
     }
     SA_HIP(launch_layernorm_rows(w_.h, D, w.ln2, g_.zeros, nullptr, w_.xn, bf16_, M, D, eps, st));
     {
       GemmParams p = lin(w_.xn, D, w.wi, M, 2 * F, D);  // input | gate
       p.out_act = w_.u; p.act_ld = 2L * F;
-      SA_TRY(mgemm(p, bf16_, st));
+      SA_TRY(run_gemm(p, bf16_, "text tower: ", st));
       SA_HIP(launch_geglu(w_.u, w_.u2, bf16_, M, F, st));
       p = lin(w_.u2, F, w.wo2, M, D, F);  // h = h + Wo(gelu(input) * gate)
       p.res = w_.h; p.res_ld = D;
       p.out_f32 = w_.h; p.f32_ld = D;
-      SA_TRY(mgemm(p, bf16_, st));
+      SA_TRY(run_gemm(p, bf16_, "text tower: ", st));
     }
   }
   // nth in [0, layers]: the residual stream after nth layers, never normalised (nth == layers: what transformers 4.48 - 4.5x
@@ -158,22 +145,11 @@ Status MBertEncoder::encode(const long long* ids, const unsigned char* mask, int
 
 }  // namespace sa
 
-namespace {
-int mret(const sa::Status& s) {
-  if (!s.ok()) sa::set_last_error(s.msg);
-  return s.code;
-}
-int mbad(const char* msg) {
-  sa::set_last_error(msg);
-  return SAMAUDIO_ERR_ARG;
-}
-}  // namespace
-
 extern "C" {
 
 int samaudio_mbert_create(const samaudio_mbert_config* cfg, samaudio_mbert** out) {
-  if (!cfg || !out) return mbad("samaudio_mbert_create: null argument");
-  if (cfg->precision != SAMAUDIO_F32 && cfg->precision != SAMAUDIO_BF16) return mbad("samaudio_mbert_create: precision");
+  if (!cfg || !out) return sa::bad("samaudio_mbert_create: null argument");
+  if (cfg->precision != SAMAUDIO_F32 && cfg->precision != SAMAUDIO_BF16) return sa::bad("samaudio_mbert_create: precision");
   samaudio_mbert* t = new samaudio_mbert;
   t->enc = new sa::MBertEncoder(*cfg);
   *out = t;
@@ -187,13 +163,11 @@ void samaudio_mbert_destroy(samaudio_mbert* t) {
 }
 
 int samaudio_mbert_set_tensor(samaudio_mbert* t, const char* name, const void* data, int dtype, int ndim, const int64_t* shape) {
-  if (!t) return mbad("null text tower");
-  return mret(t->enc->set_tensor(name, data, dtype, ndim, shape));
+  return SA_ENTRY(t, "null text tower", t->enc->set_tensor(name, data, dtype, ndim, shape));
 }
 
 int samaudio_mbert_finalize(samaudio_mbert* t) {
-  if (!t) return mbad("null text tower");
-  return mret(t->enc->finalize());
+  return SA_ENTRY(t, "null text tower", t->enc->finalize());
 }
 
 size_t samaudio_mbert_workspace_bytes(samaudio_mbert* t, int rows, int tokens) {
@@ -202,15 +176,14 @@ size_t samaudio_mbert_workspace_bytes(samaudio_mbert* t, int rows, int tokens) {
 }
 
 int samaudio_mbert_set_workspace(samaudio_mbert* t, void* workspace, size_t bytes) {
-  if (!t) return mbad("null text tower");
-  return mret(t->enc->set_workspace(workspace, bytes));
+  return SA_ENTRY(t, "null text tower", t->enc->set_workspace(workspace, bytes));
 }
 
 int samaudio_mbert_encode(samaudio_mbert* t, const int64_t* input_ids, const unsigned char* attention_mask, int rows, int tokens,
                           int nth_hidden_state, float* hidden, samaudio_stream stream) {
-  if (!t) return mbad("null text tower");
-  return mret(t->enc->encode((const long long*)input_ids, attention_mask, rows, tokens, nth_hidden_state, hidden,
-                             (hipStream_t)stream));
+  return SA_ENTRY(t, "null text tower",
+                  t->enc->encode((const long long*)input_ids, attention_mask, rows, tokens, nth_hidden_state, hidden,
+                      (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -3,13 +3,9 @@
 // sam_audio/model/judge.py:90-132) and the PE-A-Frame frame logits.  Like Engine, these classes own no device
 // memory: weights are borrowed, scratch is one caller-provided workspace.
 #pragma once
-#include "engine.h"
+#include "host.h"
 
 namespace sa {
-
-// Where the split A operand of an x3 launch comes from: `split` = already split by its producer, else "split the fp32 rows here into
-// this scratch of this capacity".  per_tap: a k3 convolution on a split halo buffer - K' split per tap, the plain walk (never shares)
-struct X3Operand { const void* split; void* scratch; size_t bytes; bool per_tap = false; };
 
 // One PE-AV transformer: input projection -> [class token ; frames] -> ResNet block with masked GroupNorm ->
 // n_layers x (RMSNorm, qk-norm RoPE attention, RMSNorm, SwiGLU) -> RMSNorm -> output projection.
@@ -35,7 +31,9 @@ class PeavEncoder {
   size_t x3_scratch_bytes() const { return w_.x3a_bytes; }
   // One launch on the weight `w`: `p` = the context's plain launch, run as it is on w.w - or, class `cls` switched to compensated
   // operands, as ONE 16-bit launch on w.w3 and the split operand `a` names (also the Judge's cat_audio_proj, on this encoder's mask)
-  Status linear(GemmParams p, const LinW& w, int cls, const X3Operand& a, hipStream_t st) const;
+  Status linear(const GemmParams& p, const LinW& w, int cls, const X3Operand& a, hipStream_t st) const {
+    return x3_linear(p, w, cls, x3(cls), bf16_, a, who_.c_str(), "", st);
+  }
   int dim() const { return d_.dim; }
   int in_dim() const { return d_.in_dim; }
 
@@ -43,7 +41,7 @@ class PeavEncoder {
   samaudio_peav_dims d_;
   bool bf16_;
   size_t esz_;
-  std::string prefix_;
+  std::string prefix_, who_;   // who_ = prefix_ + ": ", what the messages of linear start with
   bool ready_ = false;
   int x3_ = 0;
   struct LayerW {

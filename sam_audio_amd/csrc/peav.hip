@@ -8,14 +8,6 @@
 namespace sa {
 
 namespace {
-Status fail(int code, const std::string& m) { return Status{code, m}; }
-long round_up(long v, long m) { return (v + m - 1) / m * m; }
-
-Status run_gemm(const GemmParams& p, bool bf16, hipStream_t st) {
-  if (const char* why = gemm_check(p, bf16)) return fail(SAMAUDIO_ERR_ARG, why);
-  SA_HIP(launch_gemm(p, bf16, st));
-  return Status{};
-}
 Status check_dims(const samaudio_peav_dims& d, const char* who) {
   if (d.dim <= 0 || d.n_heads <= 0 || d.n_layers < 0 || d.ffn_hidden <= 0 || d.in_dim <= 0 || d.max_positions <= 0)
     return fail(SAMAUDIO_ERR_ARG, std::string(who) + ": non-positive dimension");
@@ -31,56 +23,54 @@ Status check_dims(const samaudio_peav_dims& d, const char* who) {
 // PE-AV transformer
 // ---------------------------------------------------------------------------------------------------
 PeavEncoder::PeavEncoder(const samaudio_peav_dims& d, bool bf16, std::string prefix)
-    : d_(d), bf16_(bf16), esz_(bf16 ? 2 : 4), prefix_(std::move(prefix)) {}
+    : d_(d), bf16_(bf16), esz_(bf16 ? 2 : 4), prefix_(std::move(prefix)), who_(prefix_ + ": ") {}
 
 Status PeavEncoder::finalize(const Registry& reg) {
   SA_TRY(check_dims(d_, prefix_.c_str()));
   const int D = d_.dim, F = d_.ffn_hidden;
-  const int F32 = SAMAUDIO_DT_F32, AT = bf16_ ? SAMAUDIO_DT_BF16 : SAMAUDIO_DT_F32;
+  const int AT = bf16_ ? SAMAUDIO_DT_BF16 : SAMAUDIO_DT_F32;
   const std::string& P = prefix_;
-#define NEEDF(field, name, ...) SA_TRY(reg.need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
-#define NEEDW(field, name, ...) SA_TRY(reg.need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
-  NEEDW(g_.in_w, P + "in.w", D, d_.in_dim);
-  NEEDF(g_.in_b, P + "in.b", D);
-  NEEDF(g_.cls, P + "cls", D);
-  NEEDF(g_.gn1_w, P + "gn1.w", D);
-  NEEDF(g_.gn1_b, P + "gn1.b", D);
-  NEEDW(g_.conv1.w, P + "conv1.w", D, 3 * D);
-  NEEDF(g_.conv1_b, P + "conv1.b", D);
-  NEEDF(g_.gn2_w, P + "gn2.w", D);
-  NEEDF(g_.gn2_b, P + "gn2.b", D);
-  NEEDW(g_.conv2.w, P + "conv2.w", D, 3 * D);
-  NEEDF(g_.conv2_b, P + "conv2.b", D);
-  NEEDF(g_.norm, P + "norm", D);
-  NEEDW(g_.out.w, P + "out.w", D, D);
-  NEEDF(g_.rope_cos, P + "rope_cos", d_.max_positions, 64);
-  NEEDF(g_.rope_sin, P + "rope_sin", d_.max_positions, 64);
+  NEEDW(reg, AT, g_.in_w, P + "in.w", D, d_.in_dim);
+  NEEDF(reg, g_.in_b, P + "in.b", D);
+  NEEDF(reg, g_.cls, P + "cls", D);
+  NEEDF(reg, g_.gn1_w, P + "gn1.w", D);
+  NEEDF(reg, g_.gn1_b, P + "gn1.b", D);
+  NEEDW(reg, AT, g_.conv1.w, P + "conv1.w", D, 3 * D);
+  NEEDF(reg, g_.conv1_b, P + "conv1.b", D);
+  NEEDF(reg, g_.gn2_w, P + "gn2.w", D);
+  NEEDF(reg, g_.gn2_b, P + "gn2.b", D);
+  NEEDW(reg, AT, g_.conv2.w, P + "conv2.w", D, 3 * D);
+  NEEDF(reg, g_.conv2_b, P + "conv2.b", D);
+  NEEDF(reg, g_.norm, P + "norm", D);
+  NEEDW(reg, AT, g_.out.w, P + "out.w", D, D);
+  NEEDF(reg, g_.rope_cos, P + "rope_cos", d_.max_positions, 64);
+  NEEDF(reg, g_.rope_sin, P + "rope_sin", d_.max_positions, 64);
   layers_.assign(d_.n_layers, LayerW{});
   for (int i = 0; i < d_.n_layers; ++i) {
     const std::string L = P + "L" + std::to_string(i) + ".";
     LayerW& w = layers_[i];
-    NEEDF(w.attn_norm, L + "attn_norm", D);
-    NEEDF(w.ffn_norm, L + "ffn_norm", D);
-    NEEDF(w.q_norm, L + "q_norm", 128);
-    NEEDF(w.k_norm, L + "k_norm", 128);
-    NEEDW(w.wqkv.w, L + "wqkv", 3 * D, D);
-    NEEDW(w.wo.w, L + "wo", D, D);
-    NEEDW(w.w13.w, L + "w13", 2 * F, D);
-    NEEDW(w.w2.w, L + "w2", D, F);
+    NEEDF(reg, w.attn_norm, L + "attn_norm", D);
+    NEEDF(reg, w.ffn_norm, L + "ffn_norm", D);
+    NEEDF(reg, w.q_norm, L + "q_norm", 128);
+    NEEDF(reg, w.k_norm, L + "k_norm", 128);
+    NEEDW(reg, AT, w.wqkv.w, L + "wqkv", 3 * D, D);
+    NEEDW(reg, AT, w.wo.w, L + "wo", D, D);
+    NEEDW(reg, AT, w.w13.w, L + "w13", 2 * F, D);
+    NEEDW(reg, AT, w.w2.w, L + "w2", D, F);
     w.bqkv = w.bo = nullptr;
     if (d_.attn_bias) {
-      NEEDF(w.bqkv, L + "bqkv", 3 * D);
-      NEEDF(w.bo, L + "bo", D);
+      NEEDF(reg, w.bqkv, L + "bqkv", 3 * D);
+      NEEDF(reg, w.bo, L + "bo", D);
     }
     // SAMAUDIO_OPT_X3_CLASSES: the twins of the classes that are switched on, and the [gain | 0] tables of the norms in front of them
     if (x3(SAMAUDIO_CLS_QKV)) {
       SA_TRY(reg.need_twin(L + "wqkv.x3", 3 * D, 3L * D, w.wqkv));
-      NEEDF(w.attn_gs, L + "attn_norm.gs", 2, D);
+      NEEDF(reg, w.attn_gs, L + "attn_norm.gs", 2, D);
     }
     if (x3(SAMAUDIO_CLS_WO)) SA_TRY(reg.need_twin(L + "wo.x3", D, 3L * D, w.wo));
     if (x3(SAMAUDIO_CLS_W13)) {
       SA_TRY(reg.need_twin(L + "w13.x3", 2 * F, 3L * D, w.w13));
-      NEEDF(w.ffn_gs, L + "ffn_norm.gs", 2, D);
+      NEEDF(reg, w.ffn_gs, L + "ffn_norm.gs", 2, D);
     }
     if (x3(SAMAUDIO_CLS_W2)) SA_TRY(reg.need_twin(L + "w2.x3", D, 3L * F, w.w2));
   }
@@ -90,10 +80,8 @@ Status PeavEncoder::finalize(const Registry& reg) {
   }
   if (x3(SAMAUDIO_CLS_WO)) {
     SA_TRY(reg.need_twin(P + "out.w.x3", D, 3L * D, g_.out));
-    NEEDF(g_.norm_gs, P + "norm.gs", 2, D);
+    NEEDF(reg, g_.norm_gs, P + "norm.gs", 2, D);
   }
-#undef NEEDF
-#undef NEEDW
   if (x3_ && D > 256 * 12) return fail(SAMAUDIO_ERR_ARG, P + ": SAMAUDIO_OPT_X3_CLASSES needs dim <= 3072 (launch_rmsnorm_gs_split3)");
   ready_ = true;
   return Status{};
@@ -126,27 +114,6 @@ void PeavEncoder::plan(Bump& b, int rows, int frames, bool assign) {
   }
 }
 
-Status PeavEncoder::linear(GemmParams p, const LinW& w, int cls, const X3Operand& a, hipStream_t st) const {
-  p.W = w.w;
-  if (!x3(cls)) return run_gemm(p, bf16_, st);
-  if (!w.w3) return fail(SAMAUDIO_ERR_STATE, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: split weight missing (set the option before finalize)");
-  if (a.per_tap) {   // the caller said so: K' split per tap, no operand sharing
-    x3_block_operands(p, a.split, w.w3, w.ktm3);
-    return run_gemm(p, true, st);
-  }
-  if (p.kc != p.K || p.tap_stride || (p.out_act && p.out_f32))
-    return fail(SAMAUDIO_ERR_ARG, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: plain launches with one output only");
-  const void* split = a.split;
-  if (!split) {   // split the fp32 rows here (an operand no kernel wrote in split form)
-    if (p.nbatch != 1 || p.a_off) return fail(SAMAUDIO_ERR_ARG, prefix_ + ": SAMAUDIO_OPT_X3_CLASSES: a batched operand must arrive split");
-    SA_TRY(x3_fits(a.scratch, a.bytes, p.M, p.K, prefix_ + ": ", "the split operand does not fit the scratch the workspace plan holds"));
-    SA_HIP(launch_split3((const float*)p.A, p.lda, a.scratch, p.M, p.K, st));
-    split = a.scratch;
-  }
-  x3_operands(p, split, w);
-  return run_gemm(x3_share(p, cls), true, st);
-}
-
 Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, int rows, int T, hipStream_t st) {
   if (!ready_) return fail(SAMAUDIO_ERR_STATE, prefix_ + ": weights not finalized");
   if (!x_act || rows <= 0 || T <= 0) return fail(SAMAUDIO_ERR_ARG, prefix_ + ": bad shape");
@@ -161,7 +128,7 @@ Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, in
     GemmParams p = lin(x_act, d_.in_dim, g_.in_w, T, D, d_.in_dim);
     p.nbatch = rows; p.a_bstride = (long)T * d_.in_dim; p.bias = g_.in_b;
     p.out_f32 = w_.h0; p.f32_bstride = (long)S * D; p.f32_ld = D; p.f32_off = D;
-    SA_TRY(run_gemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, "", st));
   }
   // class token + sequence mask                                                    (hf:273-285)
   SA_HIP(launch_peav_cls_mask(w_.h0, g_.cls, pad_mask, w_.mask_s, rows, T, D, st));
@@ -243,8 +210,9 @@ Status PeavEncoder::forward(const void* x_act, const unsigned char* pad_mask, in
       p.swiglu = 1;
       p.out_act = w_.u; p.act_ld = F;
       // w13 writes w2's operand in split form where the launch it would make passes gemm_check
-      const bool w2_pre = w13_3 && w2_3 && x3_room(w_.x3u, w_.x3u_bytes, M, F) &&
-                          !gemm_check(x3_share(x3_split3_out(p, w_.x3a, w.w13, w_.x3u), SAMAUDIO_CLS_W13), true);
+      const bool w2_pre = w13_3 && w2_3 && x3_w2_pre(p, w_.x3a, w.w13, w_.x3u, w_.x3u_bytes, M, F, [](const GemmParams& q) {
+        return x3_share(q, SAMAUDIO_CLS_W13);
+      });
       if (w2_pre) { p.out_act = w_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
       SA_TRY(linear(p, w.w13, SAMAUDIO_CLS_W13, X3Operand{w_.x3a, nullptr, 0}, st));
       p = lin(w_.u, F, nullptr, M, D, F);  // h = h + down_proj(...)
@@ -310,25 +278,21 @@ Status Judge::finalize() {
     return fail(SAMAUDIO_ERR_ARG, "judge: bottleneck_dim / text_hidden / codec_dim must be positive multiples of 64");
   SA_TRY(enc_.finalize(reg_));
   SA_TRY(fin_.finalize(reg_));
-  const int F32 = SAMAUDIO_DT_F32, AT = at_dtype_;
-#define NEEDF(field, name, ...) SA_TRY(reg_.need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
-#define NEEDW(field, name, ...) SA_TRY(reg_.need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
-  NEEDW(g_.cat_wh.w, "cat.wh", Bn, D);     // cat_audio_proj.weight[:, :D]   (separated / hypothesis half, judge.py:113-115)
-  NEEDW(g_.cat_wi.w, "cat.wi", Bn, D);     // cat_audio_proj.weight[:, D:]   (mixture half)
-  NEEDF(g_.cat_b, "cat.b", Bn);
-  NEEDW(g_.tp1_w, "tp1.w", D, TH);        // text_proj1 (no bias)
-  NEEDW(g_.tp2_w, "tp2.w", Bn, D);        // text_proj2
-  NEEDF(g_.tp2_b, "tp2.b", Bn);
-  NEEDF(g_.ln_w, "ln.w", Bn);
-  NEEDF(g_.ln_b, "ln.b", Bn);
-  NEEDW(g_.pat_wa, "pat.wa", Bn, Bn);     // proj_audio_and_text.weight[:, :Bn]  (audio half, judge.py:121-123)
-  NEEDW(g_.pat_wt, "pat.wt", Bn, Bn);     // proj_audio_and_text.weight[:, Bn:]  (text half)
-  NEEDF(g_.pat_b, "pat.b", Bn);
-  NEEDF(g_.head_w, "head.w", 4, D2);
-  NEEDF(g_.mean, "mean", 4);
-  NEEDF(g_.std_, "std", 4);
-#undef NEEDF
-#undef NEEDW
+  const int AT = at_dtype_;
+  NEEDW(reg_, AT, g_.cat_wh.w, "cat.wh", Bn, D);     // cat_audio_proj.weight[:, :D]   (separated / hypothesis half, judge.py:113-115)
+  NEEDW(reg_, AT, g_.cat_wi.w, "cat.wi", Bn, D);     // cat_audio_proj.weight[:, D:]   (mixture half)
+  NEEDF(reg_, g_.cat_b, "cat.b", Bn);
+  NEEDW(reg_, AT, g_.tp1_w, "tp1.w", D, TH);        // text_proj1 (no bias)
+  NEEDW(reg_, AT, g_.tp2_w, "tp2.w", Bn, D);        // text_proj2
+  NEEDF(reg_, g_.tp2_b, "tp2.b", Bn);
+  NEEDF(reg_, g_.ln_w, "ln.w", Bn);
+  NEEDF(reg_, g_.ln_b, "ln.b", Bn);
+  NEEDW(reg_, AT, g_.pat_wa, "pat.wa", Bn, Bn);     // proj_audio_and_text.weight[:, :Bn]  (audio half, judge.py:121-123)
+  NEEDW(reg_, AT, g_.pat_wt, "pat.wt", Bn, Bn);     // proj_audio_and_text.weight[:, Bn:]  (text half)
+  NEEDF(reg_, g_.pat_b, "pat.b", Bn);
+  NEEDF(reg_, g_.head_w, "head.w", 4, D2);
+  NEEDF(reg_, g_.mean, "mean", 4);
+  NEEDF(reg_, g_.std_, "std", 4);
   if (x3_ & SAMAUDIO_CLS_WO) {   // cat_audio_proj reads the transformer's output rows: K = D over all frames, with out.w's class
     SA_TRY(reg_.need_twin("cat.wh.x3", Bn, 3L * D, g_.cat_wh));
     SA_TRY(reg_.need_twin("cat.wi.x3", Bn, 3L * D, g_.cat_wi));
@@ -430,17 +394,17 @@ Status Judge::score(const float* in_lat, const float* sep_lat, int Bi, int cand,
   {
     GemmParams p = lin(w_.tp_act, TH, g_.tp1_w, Bp, D, TH);
     p.out_act = w_.t1; p.act_ld = D;
-    SA_TRY(run_gemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, "", st));
     p = lin(w_.t1, D, g_.tp2_w, Bp, Bn, D);
     p.bias = g_.tp2_b;
     p.out_f32 = w_.t2; p.f32_ld = Bn;
-    SA_TRY(run_gemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, "", st));
     SA_HIP(launch_layernorm_rows(w_.t2, Bn, g_.ln_w, g_.ln_b, nullptr, w_.tl, bf16_, Bp, Bn, 1e-5f, st));
     // text half of proj_audio_and_text, once per pair (the expanded text is constant over frames)
     p = lin(w_.tl, Bn, g_.pat_wt, Bp, Bn, Bn);
     p.bias = g_.pat_b;
     p.out_f32 = w_.tpart; p.f32_ld = Bn;
-    SA_TRY(run_gemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, "", st));
   }
   // audio_and_text = proj_audio_and_text(cat[audio_features, expanded_text])            (judge.py:121-123)
   {
@@ -448,7 +412,7 @@ Status Judge::score(const float* in_lat, const float* sep_lat, int Bi, int cand,
     p.nbatch = Bp; p.a_bstride = (long)T * Bn;
     p.res = w_.tpart; p.res_ld = 0; p.res_bstride = Bn;  // one row per pair, broadcast over its frames
     p.out_act = w_.at; p.act_ld = Bn; p.act_bstride = (long)T * Bn;
-    SA_TRY(run_gemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, "", st));
   }
   // finetune_transformer(finetune_data_proj(audio_and_text))                            (judge.py:124-126)
   SA_TRY(fin_.forward(w_.at, mask2, Bp, T, st));
@@ -499,19 +463,15 @@ Status FramePredictor::finalize() {
   if (E <= 0 || E % 64 || cfg_.codec_dim % 64)
     return fail(SAMAUDIO_ERR_ARG, "frame: embed_dim / codec_dim must be positive multiples of 64");
   SA_TRY(enc_.finalize(reg_));
-  const int F32 = SAMAUDIO_DT_F32, AT = at_dtype_;
-#define NEEDF(field, name, ...) SA_TRY(reg_.need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
-#define NEEDW(field, name, ...) SA_TRY(reg_.need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
-  NEEDF(g_.ah_ln_w, "ah.ln_w", D);   // audio_head: LayerNorm(eps 1e-6) + bias-free projection (hf:184-195)
-  NEEDF(g_.ah_ln_b, "ah.ln_b", D);
-  NEEDW(g_.ah_w, "ah.w", E, D);
-  NEEDF(g_.th_ln_w, "th.ln_w", E);   // text_audio_head
-  NEEDF(g_.th_ln_b, "th.ln_b", E);
-  NEEDW(g_.th_w, "th.w", E, E);
-  NEEDF(g_.scale, "logit_scale", 1);
-  NEEDF(g_.bias, "logit_bias", 1);
-#undef NEEDF
-#undef NEEDW
+  const int AT = at_dtype_;
+  NEEDF(reg_, g_.ah_ln_w, "ah.ln_w", D);   // audio_head: LayerNorm(eps 1e-6) + bias-free projection (hf:184-195)
+  NEEDF(reg_, g_.ah_ln_b, "ah.ln_b", D);
+  NEEDW(reg_, AT, g_.ah_w, "ah.w", E, D);
+  NEEDF(reg_, g_.th_ln_w, "th.ln_w", E);   // text_audio_head
+  NEEDF(reg_, g_.th_ln_b, "th.ln_b", E);
+  NEEDW(reg_, AT, g_.th_w, "th.w", E, E);
+  NEEDF(reg_, g_.scale, "logit_scale", 1);
+  NEEDF(reg_, g_.bias, "logit_bias", 1);
   ready_ = true;
   return Status{};
 }
@@ -558,14 +518,14 @@ Status FramePredictor::logits(const float* codec, const float* text_pooled, cons
   {
     GemmParams p = lin(w_.a_ln, D, g_.ah_w, M, E, D);
     p.out_f32 = w_.a_emb; p.f32_ld = E;
-    SA_TRY(run_gemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, "", st));
   }
   // text_audio_embeds = text_audio_head(text hidden state of token 0)                   hf:847-848
   SA_HIP(launch_layernorm_rows(text_pooled, E, g_.th_ln_w, g_.th_ln_b, nullptr, w_.t_ln, bf16_, rows, E, 1e-6f, st));
   {
     GemmParams p = lin(w_.t_ln, E, g_.th_w, rows, E, E);
     p.out_f32 = w_.t_emb; p.f32_ld = E;
-    SA_TRY(run_gemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, "", st));
   }
   // logits[b][t] = <audio_embeds[b][t], text_embeds[b]> * scale + bias                  hf:850-851, model.py:234-243
   SA_HIP(launch_frame_logits(w_.a_emb, (long)S * E, E, w_.t_emb, g_.scale, g_.bias, out, rows, T, E, st));

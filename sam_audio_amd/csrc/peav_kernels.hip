@@ -193,10 +193,9 @@ __global__ __launch_bounds__(256) void mgn_apply_split3_kernel(const float* __re
       const float4 v = xs[i], ww = ((const float4*)w)[c4], bb = ((const float4*)bias)[c4];
       const float o0 = silu_f((v.x - mean) * rstd * ww.x + bb.x), o1 = silu_f((v.y - mean) * rstd * ww.y + bb.y),
                   o2 = silu_f((v.z - mean) * rstd * ww.z + bb.z), o3 = silu_f((v.w - mean) * rstd * ww.w + bb.w);
-      hi.x = pack_h16x2(fminf(fmaxf(o0, -kH16Max), kH16Max), fminf(fmaxf(o1, -kH16Max), kH16Max));
-      hi.y = pack_h16x2(fminf(fmaxf(o2, -kH16Max), kH16Max), fminf(fmaxf(o3, -kH16Max), kH16Max));
-      lo.x = pack_h16x2(o0 - h16_lo(hi.x), o1 - h16_hi(hi.x));
-      lo.y = pack_h16x2(o2 - h16_lo(hi.y), o3 - h16_hi(hi.y));
+      const H16Split s0 = split_h16x2(o0, o1), s1 = split_h16x2(o2, o3);   // (common.h: the split of launch_split3)
+      hi.x = s0.hi; hi.y = s1.hi;
+      lo.x = s0.lo; lo.y = s1.lo;
     }
     bf16_t* dst = ob + (long)t * 3 * C + 4 * c4;
     *(uint2*)dst = lo;
@@ -341,11 +340,8 @@ __global__ __launch_bounds__(256) void layernorm_rows_split3_kernel(const float*
     if (i >= n4) continue;
     const float o0 = (v[k].x - mean) * rstd * ww[k].x + bb[k].x, o1 = (v[k].y - mean) * rstd * ww[k].y + bb[k].y,
                 o2 = (v[k].z - mean) * rstd * ww[k].z + bb[k].z, o3 = (v[k].w - mean) * rstd * ww[k].w + bb[k].w;
-    uint2 hi, lo;
-    hi.x = pack_h16x2(fminf(fmaxf(o0, -kH16Max), kH16Max), fminf(fmaxf(o1, -kH16Max), kH16Max));
-    hi.y = pack_h16x2(fminf(fmaxf(o2, -kH16Max), kH16Max), fminf(fmaxf(o3, -kH16Max), kH16Max));
-    lo.x = pack_h16x2(o0 - h16_lo(hi.x), o1 - h16_hi(hi.x));
-    lo.y = pack_h16x2(o2 - h16_lo(hi.y), o3 - h16_hi(hi.y));
+    const H16Split s0 = split_h16x2(o0, o1), s1 = split_h16x2(o2, o3);   // (common.h: the split of launch_split3)
+    const uint2 hi = make_uint2(s0.hi, s1.hi), lo = make_uint2(s0.lo, s1.lo);
     bf16_t* dst = orow + 4 * i;
     *(uint2*)dst = lo;
     *(uint2*)(dst + D) = hi;

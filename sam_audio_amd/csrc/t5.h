@@ -4,7 +4,7 @@
 // Reference: sam_audio/model/text_encoder.py:19-37 (`transformers.T5EncoderModel`); restated in oracle/t5_oracle.py.
 // Like Engine / VisionTower it owns no device memory: borrowed weights, one caller-provided workspace.
 #pragma once
-#include "peav.h"
+#include "host.h"
 
 namespace sa {
 

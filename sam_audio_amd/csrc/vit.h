@@ -8,7 +8,7 @@
 // pool.wkv, with QKV) and the self-attention multiply compensated 16-bit operands; the patch embedding, ln_pre, the pooling attention,
 // every n-row launch (pool.wo / w1 / w2, proj) and the L2 normalisation stay exact fp32.  0 = today's exact-fp32 launches, bit for bit.
 #pragma once
-#include "peav.h"
+#include "host.h"
 
 namespace sa {
 
@@ -32,9 +32,11 @@ class VisionTower {
   Status encode_patches(int n, bool normalize, float* features, float* tokens_out, hipStream_t st);   // everything behind w_.patches
   bool x3(int cls) const { return (x3_ & cls) != 0; }
   // One launch on the weight `w`: `p` = the context's plain launch, run as it is on w.w - or, class `cls` switched to compensated
-  // operands, as ONE 16-bit launch over K' = 3K on w.w3 and the split rows `split` (null: the fp32 rows of p.A are split here, into
-  // the scratch of their width)
-  Status linear(GemmParams p, const LinW& w, int cls, const void* split, hipStream_t st) const;
+  // operands, as ONE 16-bit launch over K' = 3K on w.w3 and the split operand `a` names (host.h x3_linear)
+  Status linear(const GemmParams& p, const LinW& w, int cls, const X3Operand& a, hipStream_t st) const {
+    return x3_linear(p, w, cls, x3(cls), bf16_, a, kWho, kWho, st);
+  }
+  static constexpr const char* kWho = "vision tower: ";   // the prefix of the context's messages
   int tokens() const { return grid_ * grid_ + (cfg_.use_cls_token ? 1 : 0); }
   samaudio_vit_config cfg_;
   bool bf16_;

@@ -11,21 +11,11 @@ struct samaudio_vit {
 
 namespace sa {
 
-namespace {
-Status vfail(int code, const std::string& m) { return Status{code, m}; }
-long vround_up(long v, long m) { return (v + m - 1) / m * m; }
-Status vgemm(const GemmParams& p, bool bf16, hipStream_t st) {
-  if (const char* why = gemm_check(p, bf16)) return vfail(SAMAUDIO_ERR_ARG, std::string("vision tower: ") + why);
-  SA_HIP(launch_gemm(p, bf16, st));
-  return Status{};
-}
-}  // namespace
-
 VisionTower::VisionTower(const samaudio_vit_config& c)
     : cfg_(c), bf16_(c.precision == SAMAUDIO_BF16), esz_(bf16_ ? 2 : 4),
       at_dtype_(bf16_ ? SAMAUDIO_DT_BF16 : SAMAUDIO_DT_F32) {
   grid_ = c.patch_size > 0 ? c.image_size / c.patch_size : 0;
-  kp_ = (int)vround_up(3L * c.patch_size * c.patch_size, 64);
+  kp_ = (int)round_up(3L * c.patch_size * c.patch_size, 64);
   hd_ = c.heads > 0 ? c.width / c.heads : 0;
   pool_hd_ = c.pool_heads > 0 ? c.width / c.pool_heads : 0;
 }
@@ -36,11 +26,11 @@ Status VisionTower::set_tensor(const char* name, const void* p, int dtype, int n
 }
 
 Status VisionTower::set_option(int option, int value) {
-  if (option != SAMAUDIO_OPT_X3_CLASSES) return vfail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: unknown option");
+  if (option != SAMAUDIO_OPT_X3_CLASSES) return fail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: unknown option");
   if (bf16_)
-    return vfail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: SAMAUDIO_OPT_X3_CLASSES applies to fp32 contexts (compensated 16-bit operands under fp32 storage)");
+    return fail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: SAMAUDIO_OPT_X3_CLASSES applies to fp32 contexts (compensated 16-bit operands under fp32 storage)");
   if (value & ~SAMAUDIO_CLS_X3_VIT)
-    return vfail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: SAMAUDIO_OPT_X3_CLASSES: only qkv, wo, w13, w2 and SAMAUDIO_X3_ATTENTION");
+    return fail(SAMAUDIO_ERR_ARG, "samaudio_vit_set_option: SAMAUDIO_OPT_X3_CLASSES: only qkv, wo, w13, w2 and SAMAUDIO_X3_ATTENTION");
   x3_ = value;
   ready_ = false;     // finalize resolves the twins of the switched classes
   planned_n_ = 0;     // ... and the workspace plan holds the split scratch of the classes that are on
@@ -51,35 +41,33 @@ Status VisionTower::finalize() {
   const samaudio_vit_config& c = cfg_;
   if (c.image_size <= 0 || c.patch_size <= 0 || c.image_size % c.patch_size || c.width <= 0 || c.layers < 0 ||
       c.heads <= 0 || c.mlp_width <= 0 || c.output_dim <= 0)
-    return vfail(SAMAUDIO_ERR_ARG, "vision tower: non-positive dimension / image_size % patch_size");
+    return fail(SAMAUDIO_ERR_ARG, "vision tower: non-positive dimension / image_size % patch_size");
   if (c.width % 64 || c.mlp_width % 64 || c.output_dim % 4)
-    return vfail(SAMAUDIO_ERR_ARG, "vision tower: width / mlp_width must be multiples of 64, output_dim of 4");
-  if (c.width % c.heads || (hd_ != 64 && hd_ != 128)) return vfail(SAMAUDIO_ERR_ARG, "vision tower: head dim must be 64 or 128");
-  if (c.pool_type < 0 || c.pool_type > 2) return vfail(SAMAUDIO_ERR_ARG, "vision tower: pool_type");
-  if (c.pool_type == 0 && !c.use_cls_token) return vfail(SAMAUDIO_ERR_ARG, "vision tower: class-token pooling without a class token");
+    return fail(SAMAUDIO_ERR_ARG, "vision tower: width / mlp_width must be multiples of 64, output_dim of 4");
+  if (c.width % c.heads || (hd_ != 64 && hd_ != 128)) return fail(SAMAUDIO_ERR_ARG, "vision tower: head dim must be 64 or 128");
+  if (c.pool_type < 0 || c.pool_type > 2) return fail(SAMAUDIO_ERR_ARG, "vision tower: pool_type");
+  if (c.pool_type == 0 && !c.use_cls_token) return fail(SAMAUDIO_ERR_ARG, "vision tower: class-token pooling without a class token");
   if (c.pool_type == 2 && (c.pool_heads <= 0 || c.width % c.pool_heads || (pool_hd_ != 64 && pool_hd_ != 128)))
-    return vfail(SAMAUDIO_ERR_ARG, "vision tower: pooling head dim must be 64 or 128");
-  if (c.act != ACT_GELU && c.act != ACT_QUICK_GELU) return vfail(SAMAUDIO_ERR_ARG, "vision tower: act must be 4 (gelu) or 5 (quick gelu)");
+    return fail(SAMAUDIO_ERR_ARG, "vision tower: pooling head dim must be 64 or 128");
+  if (c.act != ACT_GELU && c.act != ACT_QUICK_GELU) return fail(SAMAUDIO_ERR_ARG, "vision tower: act must be 4 (gelu) or 5 (quick gelu)");
   const int W = c.width, F = c.mlp_width, S = tokens();
-  const int F32 = SAMAUDIO_DT_F32, AT = at_dtype_;
-#define NEEDF(field, name, ...) SA_TRY(reg_.need(name, F32, {__VA_ARGS__}, (const void**)&(field)))
-#define NEEDW(field, name, ...) SA_TRY(reg_.need(name, AT, {__VA_ARGS__}, (const void**)&(field)))
-  NEEDW(g_.patch_w, "patch.w", W, kp_);        // conv1.weight [W,3,P,P] flattened, K zero-padded to a multiple of 64
-  NEEDF(g_.pos, "pos", S, W);                  // positional_embedding (zeros without it); row 0 += class_embedding
+  const int AT = at_dtype_;
+  NEEDW(reg_, AT, g_.patch_w, "patch.w", W, kp_);        // conv1.weight [W,3,P,P] flattened, K zero-padded to a multiple of 64
+  NEEDF(reg_, g_.pos, "pos", S, W);                  // positional_embedding (zeros without it); row 0 += class_embedding
   g_.ln_pre_w = g_.ln_pre_b = g_.ln_post_w = g_.ln_post_b = g_.rope_cos = g_.rope_sin = nullptr;
-  if (c.use_ln_pre) { NEEDF(g_.ln_pre_w, "ln_pre.w", W); NEEDF(g_.ln_pre_b, "ln_pre.b", W); }
-  if (c.use_ln_post) { NEEDF(g_.ln_post_w, "ln_post.w", W); NEEDF(g_.ln_post_b, "ln_post.b", W); }
-  if (c.use_rope2d) { NEEDF(g_.rope_cos, "rope_cos", S, hd_ / 2); NEEDF(g_.rope_sin, "rope_sin", S, hd_ / 2); }
+  if (c.use_ln_pre) { NEEDF(reg_, g_.ln_pre_w, "ln_pre.w", W); NEEDF(reg_, g_.ln_pre_b, "ln_pre.b", W); }
+  if (c.use_ln_post) { NEEDF(reg_, g_.ln_post_w, "ln_post.w", W); NEEDF(reg_, g_.ln_post_b, "ln_post.b", W); }
+  if (c.use_rope2d) { NEEDF(reg_, g_.rope_cos, "rope_cos", S, hd_ / 2); NEEDF(reg_, g_.rope_sin, "rope_sin", S, hd_ / 2); }
   layers_.assign(c.layers, LayerW{});
   for (int i = 0; i < c.layers; ++i) {
     const std::string L = "L" + std::to_string(i) + ".";
     LayerW& w = layers_[i];
-    NEEDF(w.ln1_w, L + "ln1.w", W); NEEDF(w.ln1_b, L + "ln1.b", W);
-    NEEDW(w.wqkv.w, L + "wqkv", 3 * W, W); NEEDF(w.bqkv, L + "bqkv", 3 * W);
-    NEEDW(w.wo.w, L + "wo", W, W); NEEDF(w.bo, L + "bo", W);
-    NEEDF(w.ln2_w, L + "ln2.w", W); NEEDF(w.ln2_b, L + "ln2.b", W);
-    NEEDW(w.w1.w, L + "w1", F, W); NEEDF(w.b1, L + "b1", F);
-    NEEDW(w.w2.w, L + "w2", W, F); NEEDF(w.b2, L + "b2", W);
+    NEEDF(reg_, w.ln1_w, L + "ln1.w", W); NEEDF(reg_, w.ln1_b, L + "ln1.b", W);
+    NEEDW(reg_, AT, w.wqkv.w, L + "wqkv", 3 * W, W); NEEDF(reg_, w.bqkv, L + "bqkv", 3 * W);
+    NEEDW(reg_, AT, w.wo.w, L + "wo", W, W); NEEDF(reg_, w.bo, L + "bo", W);
+    NEEDF(reg_, w.ln2_w, L + "ln2.w", W); NEEDF(reg_, w.ln2_b, L + "ln2.b", W);
+    NEEDW(reg_, AT, w.w1.w, L + "w1", F, W); NEEDF(reg_, w.b1, L + "b1", F);
+    NEEDW(reg_, AT, w.w2.w, L + "w2", W, F); NEEDF(reg_, w.b2, L + "b2", W);
     // SAMAUDIO_OPT_X3_CLASSES: the twins [W_hi | W_lo | W_hi] of the classes that are switched on
     if (x3(SAMAUDIO_CLS_QKV)) SA_TRY(reg_.need_twin(L + "wqkv.x3", 3 * W, 3L * W, w.wqkv));
     if (x3(SAMAUDIO_CLS_WO)) SA_TRY(reg_.need_twin(L + "wo.x3", W, 3L * W, w.wo));
@@ -87,24 +75,22 @@ Status VisionTower::finalize() {
     if (x3(SAMAUDIO_CLS_W2)) SA_TRY(reg_.need_twin(L + "w2.x3", W, 3L * F, w.w2));
   }
   if (c.pool_type == 2) {
-    NEEDF(g_.pool_q, "pool.q", W);             // in_proj_q(probe): the same query for every frame
-    NEEDW(g_.pool_wkv.w, "pool.wkv", 2 * W, W); NEEDF(g_.pool_bkv, "pool.bkv", 2 * W);
+    NEEDF(reg_, g_.pool_q, "pool.q", W);             // in_proj_q(probe): the same query for every frame
+    NEEDW(reg_, AT, g_.pool_wkv.w, "pool.wkv", 2 * W, W); NEEDF(reg_, g_.pool_bkv, "pool.bkv", 2 * W);
     if (x3(SAMAUDIO_CLS_QKV)) SA_TRY(reg_.need_twin("pool.wkv.x3", 2 * W, 3L * W, g_.pool_wkv));   // the same launch form on every token
-    NEEDW(g_.pool_wo, "pool.wo", W, W); NEEDF(g_.pool_bo, "pool.bo", W);
-    NEEDF(g_.pool_ln_w, "pool.ln.w", W); NEEDF(g_.pool_ln_b, "pool.ln.b", W);
-    NEEDW(g_.pool_w1, "pool.w1", F, W); NEEDF(g_.pool_b1, "pool.b1", F);
-    NEEDW(g_.pool_w2, "pool.w2", W, F); NEEDF(g_.pool_b2, "pool.b2", W);
+    NEEDW(reg_, AT, g_.pool_wo, "pool.wo", W, W); NEEDF(reg_, g_.pool_bo, "pool.bo", W);
+    NEEDF(reg_, g_.pool_ln_w, "pool.ln.w", W); NEEDF(reg_, g_.pool_ln_b, "pool.ln.b", W);
+    NEEDW(reg_, AT, g_.pool_w1, "pool.w1", F, W); NEEDF(reg_, g_.pool_b1, "pool.b1", F);
+    NEEDW(reg_, AT, g_.pool_w2, "pool.w2", W, F); NEEDF(reg_, g_.pool_b2, "pool.b2", W);
   }
-  NEEDW(g_.proj, "proj", c.output_dim, W);     // proj^T (features = pooled @ proj)
-#undef NEEDF
-#undef NEEDW
-  if (x3_ && W > 256 * 8) return vfail(SAMAUDIO_ERR_ARG, "vision tower: SAMAUDIO_OPT_X3_CLASSES needs width <= 2048 (launch_layernorm_rows_split3)");
+  NEEDW(reg_, AT, g_.proj, "proj", c.output_dim, W);     // proj^T (features = pooled @ proj)
+  if (x3_ && W > 256 * 8) return fail(SAMAUDIO_ERR_ARG, "vision tower: SAMAUDIO_OPT_X3_CLASSES needs width <= 2048 (launch_layernorm_rows_split3)");
   ready_ = true;
   return Status{};
 }
 
 void VisionTower::plan(Bump& b, int n, bool assign) {
-  const long W = cfg_.width, F = cfg_.mlp_width, H = cfg_.heads, S = tokens(), Sp = vround_up(S, 128);
+  const long W = cfg_.width, F = cfg_.mlp_width, H = cfg_.heads, S = tokens(), Sp = round_up(S, 128);
   const long M = (long)n * S;
   auto f32 = [&](long k) { return (float*)b.take((size_t)k * 4); };
   auto act = [&](long k) { return b.take((size_t)k * esz_); };
@@ -138,38 +124,21 @@ size_t VisionTower::workspace_bytes(int n) {
 }
 
 Status VisionTower::set_workspace(void* p, size_t bytes) {
-  if (!p || (reinterpret_cast<uintptr_t>(p) & 255)) return vfail(SAMAUDIO_ERR_WORKSPACE, "vision tower: workspace must be 256-byte aligned");
+  if (!p || (reinterpret_cast<uintptr_t>(p) & 255)) return fail(SAMAUDIO_ERR_WORKSPACE, "vision tower: workspace must be 256-byte aligned");
   ws_ = (char*)p;
   ws_bytes_ = bytes;
   planned_n_ = 0;
   return Status{};
 }
 
-Status VisionTower::linear(GemmParams p, const LinW& w, int cls, const void* split, hipStream_t st) const {
-  p.W = w.w;
-  if (!x3(cls)) return vgemm(p, bf16_, st);
-  if (!w.w3) return vfail(SAMAUDIO_ERR_STATE, "vision tower: SAMAUDIO_OPT_X3_CLASSES: split weight missing (set the option before finalize)");
-  if (p.kc != p.K || p.tap_stride || p.nbatch != 1 || p.a_off || (p.out_act && p.out_f32))
-    return vfail(SAMAUDIO_ERR_ARG, "vision tower: SAMAUDIO_OPT_X3_CLASSES: plain launches with one output only");
-  if (!split) {   // an operand no kernel wrote in split form: split the fp32 rows here
-    const bool wide = cls == SAMAUDIO_CLS_W2;   // the MLP hidden; every other operand is W wide
-    void* scratch = wide ? w_.x3u : w_.x3a;
-    SA_TRY(x3_fits(scratch, wide ? w_.x3u_bytes : w_.x3a_bytes, p.M, p.K, "vision tower: ", "the split operand does not fit the scratch the workspace plan holds"));
-    SA_HIP(launch_split3((const float*)p.A, p.lda, scratch, p.M, p.K, st));
-    split = scratch;
-  }
-  x3_operands(p, split, w);
-  return vgemm(x3_share(p, cls), true, st);
-}
-
 Status VisionTower::prepare(const void* frames, const float* features, int n) {
-  if (!ready_) return vfail(SAMAUDIO_ERR_STATE, "vision tower: weights not finalized");
-  if (!frames || !features || n <= 0) return vfail(SAMAUDIO_ERR_ARG, "vision tower: bad argument");
-  if (!ws_) return vfail(SAMAUDIO_ERR_WORKSPACE, "vision tower: no workspace");
+  if (!ready_) return fail(SAMAUDIO_ERR_STATE, "vision tower: weights not finalized");
+  if (!frames || !features || n <= 0) return fail(SAMAUDIO_ERR_ARG, "vision tower: bad argument");
+  if (!ws_) return fail(SAMAUDIO_ERR_WORKSPACE, "vision tower: no workspace");
   if (planned_n_ != n) {
     Bump b(ws_, ws_bytes_);
     plan(b, n, true);
-    if (!b.fits()) return vfail(SAMAUDIO_ERR_WORKSPACE, "vision tower: workspace too small for " + std::to_string(n) + " frames");
+    if (!b.fits()) return fail(SAMAUDIO_ERR_WORKSPACE, "vision tower: workspace too small for " + std::to_string(n) + " frames");
     planned_n_ = n;
   }
   return Status{};
@@ -185,9 +154,9 @@ Status VisionTower::encode(const float* frames, int n, bool normalize, float* fe
 // ... of raw uint8 frames: resize, rounding and normalisation in the launch that writes the rows
 Status VisionTower::encode_frames(const uint8_t* frames, int n, int height, int width, int mode, bool normalize, float* features,
                                   float* tokens_out, hipStream_t st) {
-  if (height < 1 || width < 1) return vfail(SAMAUDIO_ERR_ARG, "vision tower: frame height / width < 1");
+  if (height < 1 || width < 1) return fail(SAMAUDIO_ERR_ARG, "vision tower: frame height / width < 1");
   if (mode != SAMAUDIO_RESIZE_NEAREST && mode != SAMAUDIO_RESIZE_BILINEAR && mode != SAMAUDIO_RESIZE_BICUBIC)
-    return vfail(SAMAUDIO_ERR_ARG, "vision tower: unknown resize mode");
+    return fail(SAMAUDIO_ERR_ARG, "vision tower: unknown resize mode");
   SA_TRY(prepare(frames, features, n));
   SA_HIP(launch_resize_frames(frames, n, height, width, cfg_.image_size, mode, w_.patches, bf16_, cfg_.patch_size, kp_, st));
   return encode_patches(n, normalize, features, tokens_out, st);
@@ -195,7 +164,7 @@ Status VisionTower::encode_frames(const uint8_t* frames, int n, int height, int 
 
 Status VisionTower::encode_patches(int n, bool normalize, float* features, float* tokens_out, hipStream_t st) {
   const samaudio_vit_config& c = cfg_;
-  const int W = c.width, F = c.mlp_width, H = c.heads, S = tokens(), Sp = (int)vround_up(S, 128), G2 = grid_ * grid_;
+  const int W = c.width, F = c.mlp_width, H = c.heads, S = tokens(), Sp = (int)round_up(S, 128), G2 = grid_ * grid_;
   const int cls = c.use_cls_token ? 1 : 0;
   const long M = (long)n * S;
   const float eps = c.ln_eps;
@@ -207,7 +176,7 @@ Status VisionTower::encode_patches(int n, bool normalize, float* features, float
     p.nbatch = n; p.a_bstride = (long)G2 * kp_;
     p.res = g_.pos; p.res_ld = W; p.res_off = (long)cls * W; p.res_bstride = 0;
     p.out_f32 = emb; p.f32_ld = W; p.f32_bstride = (long)S * W; p.f32_off = (long)cls * W;
-    SA_TRY(vgemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, kWho, st));
   }
   // class-token row (= class_embedding + positional_embedding[0], folded at load) and the all-valid key mask
   if (cls) {
@@ -237,7 +206,7 @@ Status VisionTower::encode_patches(int n, bool normalize, float* features, float
       GemmParams p = lin(w_.xn, W, nullptr, M, 3 * W, W);   // (W: linear sets it from the record, here and below)
       p.bias = w.bqkv;
       p.out_act = w_.qkv; p.act_ld = 3L * W;
-      SA_TRY(linear(p, w.wqkv, SAMAUDIO_CLS_QKV, w_.x3a, st));
+      SA_TRY(linear(p, w.wqkv, SAMAUDIO_CLS_QKV, X3Operand{w_.x3a, nullptr, 0}, st));
     }
     SA_HIP(launch_rope2d_split(w_.qkv, g_.rope_cos, g_.rope_sin, w_.Q, w_.K, w_.Vt, bf16_, n, S, Sp, H, hd_, st));
     const void* attn_split = nullptr;   // the context rows in split form, when the attention wrote them for wo
@@ -254,7 +223,7 @@ Status VisionTower::encode_patches(int n, bool normalize, float* features, float
       p.bias = w.bo;
       p.res = w_.h; p.res_ld = W;
       p.out_f32 = w_.h; p.f32_ld = W;
-      SA_TRY(linear(p, w.wo, SAMAUDIO_CLS_WO, attn_split, st));
+      SA_TRY(linear(p, w.wo, SAMAUDIO_CLS_WO, X3Operand{attn_split, w_.x3a, w_.x3a_bytes}, st));
     }
     SA_TRY(norm(w_.h, w.ln2_w, w.ln2_b, w13_3));
     {
@@ -263,15 +232,16 @@ Status VisionTower::encode_patches(int n, bool normalize, float* features, float
       p.out_act = w_.u; p.act_ld = F;
       // c_fc writes c_proj's operand in split form where the launch it would make passes gemm_check (the register epilogue of the
       // 8-phase family: bias + GELU with a split output); otherwise fp32 output + launch_split3 in front of c_proj
-      const bool w2_pre = w13_3 && w2_3 && x3_room(w_.x3u, w_.x3u_bytes, M, F) &&
-                          !gemm_check(x3_share(x3_split3_out(p, w_.x3a, w.w1, w_.x3u), SAMAUDIO_CLS_W13), true);
+      const bool w2_pre = w13_3 && w2_3 && x3_w2_pre(p, w_.x3a, w.w1, w_.x3u, w_.x3u_bytes, M, F, [](const GemmParams& q) {
+        return x3_share(q, SAMAUDIO_CLS_W13);
+      });
       if (w2_pre) { p.out_act = w_.x3u; p.flags |= GEMM_FLAG_OUT_SPLIT3; }
-      SA_TRY(linear(p, w.w1, SAMAUDIO_CLS_W13, w_.x3a, st));
+      SA_TRY(linear(p, w.w1, SAMAUDIO_CLS_W13, X3Operand{w_.x3a, nullptr, 0}, st));
       p = lin(w_.u, F, nullptr, M, W, F);  // x = x + c_proj(...)
       p.bias = w.b2;
       p.res = w_.h; p.res_ld = W;
       p.out_f32 = w_.h; p.f32_ld = W;
-      SA_TRY(linear(p, w.w2, SAMAUDIO_CLS_W2, w2_pre ? w_.x3u : nullptr, st));
+      SA_TRY(linear(p, w.w2, SAMAUDIO_CLS_W2, X3Operand{w2_pre ? w_.x3u : nullptr, w_.x3u, w_.x3u_bytes}, st));
     }
   }
   if (tokens_out) SA_HIP(hipMemcpyAsync(tokens_out, w_.h, (size_t)M * W * 4, hipMemcpyDeviceToDevice, st));
@@ -290,27 +260,27 @@ Status VisionTower::encode_patches(int n, bool normalize, float* features, float
       GemmParams p = lin(qkv3 && !c.use_ln_post ? (const void*)w_.h : w_.xn, W, nullptr, M, 2 * W, W);  // k | v of every token
       p.bias = g_.pool_bkv;
       p.out_act = w_.kv; p.act_ld = 2L * W;
-      SA_TRY(linear(p, g_.pool_wkv, SAMAUDIO_CLS_QKV, kv_split, st));
+      SA_TRY(linear(p, g_.pool_wkv, SAMAUDIO_CLS_QKV, X3Operand{kv_split, w_.x3a, w_.x3a_bytes}, st));
     }
     SA_HIP(launch_pool_attention(g_.pool_q, w_.kv, w_.pooled, bf16_, n, S, c.pool_heads, pool_hd_, st));
     {
       GemmParams p = lin(w_.pooled, W, g_.pool_wo, n, W, W);  // y = out_proj(attention)
       p.bias = g_.pool_bo;
       p.out_f32 = w_.y; p.f32_ld = W;
-      SA_TRY(vgemm(p, bf16_, st));
+      SA_TRY(run_gemm(p, bf16_, kWho, st));
     }
     SA_HIP(launch_layernorm_rows(w_.y, W, g_.pool_ln_w, g_.pool_ln_b, nullptr, w_.yn, bf16_, n, W, eps, st));
     {
       GemmParams p = lin(w_.yn, W, g_.pool_w1, n, F, W);
       p.bias = g_.pool_b1; p.act = c.act;
       p.out_act = w_.u2; p.act_ld = F;
-      SA_TRY(vgemm(p, bf16_, st));
+      SA_TRY(run_gemm(p, bf16_, kWho, st));
       p = lin(w_.u2, F, g_.pool_w2, n, W, F);  // z = y + mlp(layernorm(y))
       p.bias = g_.pool_b2;
       p.res = w_.y; p.res_ld = W;
       p.out_f32 = w_.z; p.f32_ld = W;
       p.out_act = w_.z_act; p.act_ld = W;
-      SA_TRY(vgemm(p, bf16_, st));
+      SA_TRY(run_gemm(p, bf16_, kWho, st));
     }
     pooled_act = w_.z_act;
   } else if (c.pool_type == 0) {
@@ -330,7 +300,7 @@ Status VisionTower::encode_patches(int n, bool normalize, float* features, float
   {
     GemmParams p = lin(pooled_act, W, g_.proj, n, c.output_dim, W);  // features = pooled @ proj
     p.out_f32 = features; p.f32_ld = c.output_dim;
-    SA_TRY(vgemm(p, bf16_, st));
+    SA_TRY(run_gemm(p, bf16_, kWho, st));
   }
   if (normalize) SA_HIP(launch_l2_normalize(features, n, c.output_dim, st));
   return Status{};
@@ -338,22 +308,11 @@ Status VisionTower::encode_patches(int n, bool normalize, float* features, float
 
 }  // namespace sa
 
-namespace {
-int vret(const sa::Status& s) {
-  if (!s.ok()) sa::set_last_error(s.msg);
-  return s.code;
-}
-int vbad(const char* msg) {
-  sa::set_last_error(msg);
-  return SAMAUDIO_ERR_ARG;
-}
-}  // namespace
-
 extern "C" {
 
 int samaudio_vit_create(const samaudio_vit_config* cfg, samaudio_vit** out) {
-  if (!cfg || !out) return vbad("samaudio_vit_create: null argument");
-  if (cfg->precision != SAMAUDIO_F32 && cfg->precision != SAMAUDIO_BF16) return vbad("samaudio_vit_create: precision");
+  if (!cfg || !out) return sa::bad("samaudio_vit_create: null argument");
+  if (cfg->precision != SAMAUDIO_F32 && cfg->precision != SAMAUDIO_BF16) return sa::bad("samaudio_vit_create: precision");
   samaudio_vit* v = new samaudio_vit;
   v->tower = new sa::VisionTower(*cfg);
   *out = v;
@@ -367,18 +326,15 @@ void samaudio_vit_destroy(samaudio_vit* v) {
 }
 
 int samaudio_vit_set_tensor(samaudio_vit* v, const char* name, const void* data, int dtype, int ndim, const int64_t* shape) {
-  if (!v) return vbad("null vision tower");
-  return vret(v->tower->set_tensor(name, data, dtype, ndim, shape));
+  return SA_ENTRY(v, "null vision tower", v->tower->set_tensor(name, data, dtype, ndim, shape));
 }
 
 int samaudio_vit_set_option(samaudio_vit* v, int option, int value) {
-  if (!v) return vbad("null vision tower");
-  return vret(v->tower->set_option(option, value));
+  return SA_ENTRY(v, "null vision tower", v->tower->set_option(option, value));
 }
 
 int samaudio_vit_finalize(samaudio_vit* v) {
-  if (!v) return vbad("null vision tower");
-  return vret(v->tower->finalize());
+  return SA_ENTRY(v, "null vision tower", v->tower->finalize());
 }
 
 size_t samaudio_vit_workspace_bytes(samaudio_vit* v, int frames) {
@@ -387,20 +343,19 @@ size_t samaudio_vit_workspace_bytes(samaudio_vit* v, int frames) {
 }
 
 int samaudio_vit_set_workspace(samaudio_vit* v, void* workspace, size_t bytes) {
-  if (!v) return vbad("null vision tower");
-  return vret(v->tower->set_workspace(workspace, bytes));
+  return SA_ENTRY(v, "null vision tower", v->tower->set_workspace(workspace, bytes));
 }
 
 int samaudio_vit_encode(samaudio_vit* v, const float* frames, int n, int normalize, float* features, float* tokens_out,
                         samaudio_stream stream) {
-  if (!v) return vbad("null vision tower");
-  return vret(v->tower->encode(frames, n, normalize != 0, features, tokens_out, (hipStream_t)stream));
+  return SA_ENTRY(v, "null vision tower", v->tower->encode(frames, n, normalize != 0, features, tokens_out, (hipStream_t)stream));
 }
 
 int samaudio_vit_encode_frames(samaudio_vit* v, const uint8_t* frames, int n, int height, int width, int mode, int normalize,
                                float* features, float* tokens_out, samaudio_stream stream) {
-  if (!v) return vbad("null vision tower");
-  return vret(v->tower->encode_frames(frames, n, height, width, mode, normalize != 0, features, tokens_out, (hipStream_t)stream));
+  return SA_ENTRY(v, "null vision tower",
+                  v->tower->encode_frames(frames, n, height, width, mode, normalize != 0, features, tokens_out,
+                      (hipStream_t)stream));
 }
 
 }  // extern "C"
