@@ -397,6 +397,32 @@ int samaudio_op_resize_frames(const uint8_t* frames, int n, int height, int widt
 int samaudio_vit_encode_frames(samaudio_vit* v, const uint8_t* frames, int n, int height, int width, int mode,
                                int normalize, float* features, float* tokens_out, samaudio_stream stream);
 
+/* ---- audio front end: resample, mix down and pad one PCM clip ------------------------------
+ * What the reference does with torchaudio before batching (sam_audio/processor.py:23-36: load, functional.resample, mean over
+ * channels, right zero padding), as one kernel per clip.  The resampler is the band-limited Hann-windowed sinc interpolation of
+ * sam_audio_amd/processor.py resample, which stays the CPU statement.  With g = gcd(orig, new), o = orig / g (`step`), n = new / g
+ * (`phases`), base = min(o, n) rolloff, width = ceil(lw o / base):
+ *     y[j] = sum_d h(p, d) x[f o + d],   f = j / n,  p = j % n,  d in [-width, width + o),  x = 0 outside [0, samples),
+ *            j < ceil(n samples / o)
+ *     h(p, d) = sinc(pi t) cos^2(pi t / (2 lw)) base / o,   t = clamp((d / o - p / n) base, -lw, lw),  sinc(0) = 1
+ * Rounded to fp32 the non-zero weights of a phase form one run; the caller hands the runs over in compact form
+ * (sam_audio_amd/audio.py filter_bank): first [phases] i32 = the d of each phase's first tap, taps [taps_per_phase][phases] f32
+ * (tap-major: taps[t * phases + p] weighs x[f o + first[p] + t]; zeros behind a run).  x is the mean over the channels, taken before
+ * the filter; every output sums its taps in ascending d in fp32 (one fma per tap), so sample j does not depend on the launch geometry,
+ * on out_capacity or on other clips.  Same rate = (phases, step, taps_per_phase) = (1, 1, 1), first = {0}, taps = {1}: convert, mix, pad.
+ * pcm: element (c, i) at pcm[c * ch_stride + i * s_stride] (strides in elements: interleaved frames = (1, channels), planar =
+ * (samples, 1)), aligned to its element size only; S16 values are scaled by exactly 1 / 32768. */
+#define SAMAUDIO_PCM_S16 0
+#define SAMAUDIO_PCM_F32 1
+/* ceil(phases * samples / step): the length of a resampled clip; -1 when an argument is below 1 */
+int64_t samaudio_resample_length(int64_t samples, int step, int phases);
+/* out[0, length) = the resampled mono mix, out[length, out_capacity) = 0; nothing is written behind out_capacity.  Stateless, like
+ * samaudio_op_resize_frames.  SAMAUDIO_ERR_ARG before any launch for a null pointer, channels / samples / step / phases /
+ * taps_per_phase < 1, an unknown format or out_capacity < length; SAMAUDIO_ERR_STATE in a build of the library without the kernel. */
+int samaudio_op_resample(const void* pcm, int fmt, int channels, int64_t samples, int64_t ch_stride, int64_t s_stride,
+                         const float* taps, const int32_t* first, int phases, int step, int taps_per_phase, float* out,
+                         int64_t out_capacity, samaudio_stream stream);
+
 /* ---- text-prompt encoder ---------------------------------------------------------
  * T5 encoder stack behind `T5TextEncoder.forward` (reference sam_audio/model/text_encoder.py:19-37:
  * `transformers.T5EncoderModel("t5-base")(input_ids, attention_mask)["last_hidden_state"]`).  Tokenisation stays with the

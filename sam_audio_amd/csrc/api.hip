@@ -303,6 +303,30 @@ int samaudio_op_resize_frames(const uint8_t* frames, int n, int height, int widt
                  "resize_frames");
 }
 
+int64_t samaudio_resample_length(int64_t samples, int step, int phases) {
+  if (samples < 1 || step < 1 || phases < 1) return -1;
+  const int64_t whole = samples / step, rest = samples % step;   // (phases * rest < 2^62; phases * samples may not fit)
+  if (whole > (INT64_MAX >> 32)) return -1;
+  return phases * whole + (phases * rest + step - 1) / step;
+}
+
+int samaudio_op_resample(const void* pcm, int fmt, int channels, int64_t samples, int64_t ch_stride, int64_t s_stride,
+                         const float* taps, const int32_t* first, int phases, int step, int taps_per_phase, float* out,
+                         int64_t out_capacity, samaudio_stream stream) {
+  if (!pcm || !taps || !first || !out || channels < 1 || samples < 1 || step < 1 || phases < 1 || taps_per_phase < 1)
+    return bad("resample: null argument / channels, samples, step, phases, taps_per_phase < 1");
+  if (fmt != SAMAUDIO_PCM_S16 && fmt != SAMAUDIO_PCM_F32) return bad("resample: unknown format");
+  const int64_t length = samaudio_resample_length(samples, step, phases);
+  if (length < 0 || out_capacity < length) return bad("resample: out_capacity below the resampled length");
+  if (!sa::launch_resample_mix) {
+    g_err = "resample: not in this build of the library";
+    return SAMAUDIO_ERR_STATE;
+  }
+  return hip_ret(sa::launch_resample_mix(pcm, fmt == SAMAUDIO_PCM_S16, channels, samples, ch_stride, s_stride, taps, first, phases,
+                                         step, taps_per_phase, out, length, out_capacity, (hipStream_t)stream),
+                 "resample");
+}
+
 int samaudio_op_split3(const float* x, int64_t x_ld, void* out, int64_t rows, int k, samaudio_stream stream) {
   if (!x || !out || rows <= 0 || k <= 0 || k % 8 || x_ld % 4) return bad("split3: k % 8, x_ld % 4");
   return hip_ret(sa::launch_split3(x, x_ld, out, rows, k, (hipStream_t)stream), "split3");

@@ -332,6 +332,15 @@ hipError_t launch_judge_pool_head(const float* hidden, const unsigned char* mask
 hipError_t launch_frame_logits(const float* audio, long a_bstride, long a_off, const float* text, const float* scale,
                                const float* bias, float* out, int B, int T, int E, hipStream_t st);
 
+// ---- audio front end (kernels.hip) -------------------------------------------------------------------------------
+// One PCM clip (int16 scaled by 1 / 32768 | fp32; element (c, i) at pcm[c * ch_stride + i * s_stride]) -> out[0, out_len) = the mean
+// over the channels resampled by the compact polyphase bank of samaudio.h (taps [K][phases] tap-major, first [phases]; `step` input
+// samples per `phases` outputs), out[out_len, out_capacity) = 0.  weak: the CPU emulation of the launchers (oracle/emu) does not
+// define it - the hook then answers SAMAUDIO_ERR_STATE (api.hip)
+__attribute__((weak)) hipError_t launch_resample_mix(const void* pcm, bool s16, int channels, long samples, long ch_stride,
+                                                     long s_stride, const float* taps, const int* first, int phases, int step, int K,
+                                                     float* out, long out_len, long out_capacity, hipStream_t st);
+
 // ---- PE-Core vision tower (vit_kernels.hip) ---------------------------------------------------------------------
 // im2col of the k = stride = P patch convolution: frames [n,3,S,S] f32 -> rows [n*(S/P)^2, Kp], column c*P*P + py*P + px
 hipError_t launch_patchify(const float* frames, void* out, bool bf16, int n, int S, int P, int Kp, hipStream_t st);

@@ -997,6 +997,109 @@ hipError_t launch_zero_halo(void* buf, bool bf16, int B, long T, int C, int halo
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Audio front end (samaudio.h samaudio_op_resample): one PCM clip -> its mono mix at the model's rate, right
+// padded with zeros.  A workgroup owns `tile` consecutive outputs.  Its lanes are consecutive j, so consecutive phases p: the
+// tap-major bank is read at consecutive addresses.  The input window the tile's taps reach is converted and mixed to mono ONCE into
+// LDS (the launcher sizes `tile` so that it fits for a well-formed bank); a tile whose window does not fit - a ratio with more than
+// ~8000 inputs per 256 outputs, or a `first` table that jumps about - reads the same mono values straight from memory, so both
+// paths give the same bits.  Output j is one fma chain over its K taps in ascending d, whoever computes it.
+// ------------------------------------------------------------------------------------------------
+constexpr int kResampleWindow = 8192;    // fp32 input samples of LDS per workgroup (32 KiB: four workgroups per CU)
+constexpr int kResampleTileMax = 2048;   // outputs per workgroup (8 per thread)
+
+__device__ __forceinline__ float pcm_value(float v) { return v; }
+__device__ __forceinline__ float pcm_value(short v) { return (float)v * (1.f / 32768.f); }
+
+// mean over the channels of input sample i (0 outside the clip): channel 0 first, fp32, one division
+template <typename T>
+__device__ __forceinline__ float pcm_mono(const T* __restrict__ pcm, int C, long samples, long ch_stride, long s_stride, long i) {
+  if (i < 0 || i >= samples) return 0.f;
+  const T* p = pcm + i * s_stride;
+  float s = pcm_value(p[0]);
+  if (C == 1) return s;
+  for (int c = 1; c < C; ++c) s += pcm_value(p[c * ch_stride]);
+  return s / (float)C;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void resample_mix_kernel(const T* __restrict__ pcm, int C, long samples, long ch_stride,
+                                                           long s_stride, const float* __restrict__ taps,
+                                                           const int* __restrict__ first, int n, int o, int K,
+                                                           float* __restrict__ out, long out_len, long out_capacity, int tile) {
+  __shared__ float win[kResampleWindow];
+  __shared__ long long red_lo[256], red_hi[256];
+  const int tid = threadIdx.x;
+  const long j0 = (long)blockIdx.x * tile;
+  const long room = out_capacity - j0, left = out_len - j0;
+  const int nout = room < tile ? (int)room : tile;                       // outputs this workgroup writes
+  const int nlive = left <= 0 ? 0 : (left < nout ? (int)left : nout);    // ... of which this many are samples, the rest padding
+  const long f0 = j0 / n;                                                // j = j0 + r: f = f0 + (p0 + r) / n, p = (p0 + r) % n
+  const unsigned p0 = (unsigned)(j0 - f0 * n);
+  bool in_lds = false;
+  long lo = 0;
+  if (nlive > 0) {   // (uniform over the workgroup)
+    // the window: from the first tap of any live output to the last one
+    long long mn = 0x7fffffffffffffffLL, mx = -0x7fffffffffffffffLL;
+    for (int r = tid; r < nlive; r += 256) {
+      const unsigned q = p0 + (unsigned)r, df = q / (unsigned)n, p = q - df * (unsigned)n;
+      const long long s = (f0 + df) * (long long)o + first[p];
+      mn = s < mn ? s : mn;
+      mx = s + (K - 1) > mx ? s + (K - 1) : mx;
+    }
+    red_lo[tid] = mn;
+    red_hi[tid] = mx;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+      if (tid < h) {
+        red_lo[tid] = red_lo[tid + h] < red_lo[tid] ? red_lo[tid + h] : red_lo[tid];
+        red_hi[tid] = red_hi[tid + h] > red_hi[tid] ? red_hi[tid + h] : red_hi[tid];
+      }
+      __syncthreads();
+    }
+    lo = red_lo[0];
+    const long long span = red_hi[0] - red_lo[0] + 1;
+    in_lds = span <= kResampleWindow;
+    if (in_lds) {
+      for (int i = tid; i < (int)span; i += 256) win[i] = pcm_mono<T>(pcm, C, samples, ch_stride, s_stride, lo + i);
+      __syncthreads();
+    }
+  }
+  for (int r = tid; r < nout; r += 256) {
+    float acc = 0.f;
+    if (r < nlive) {
+      const unsigned q = p0 + (unsigned)r, df = q / (unsigned)n, p = q - df * (unsigned)n;
+      const long s = (f0 + df) * (long)o + first[p];
+      const float* w = taps + p;
+      if (in_lds) {
+        const float* x = win + (int)(s - lo);
+        for (int t = 0; t < K; ++t) acc = fmaf(w[(long)t * n], x[t], acc);
+      } else {
+        for (int t = 0; t < K; ++t) acc = fmaf(w[(long)t * n], pcm_mono<T>(pcm, C, samples, ch_stride, s_stride, s + t), acc);
+      }
+    }
+    out[j0 + r] = acc;
+  }
+}
+
+hipError_t launch_resample_mix(const void* pcm, bool s16, int channels, long samples, long ch_stride, long s_stride,
+                               const float* taps, const int* first, int phases, int step, int K, float* out, long out_len,
+                               long out_capacity, hipStream_t st) {
+  if (out_capacity <= 0) return hipSuccess;
+  // the most outputs whose window - (tile - 1) step / phases inputs plus, for a well-formed bank, at most 2 K + 4 - fits the LDS array
+  const long fit = (long)(kResampleWindow - 2 * (long)K - 4) * phases / step + 1;
+  const int tile = fit >= kResampleTileMax ? kResampleTileMax : (fit < 512 ? 256 : (int)(fit / 256) * 256);
+  const long tiles = (out_capacity + tile - 1) / tile;
+  if (tiles > 0x7fffffffL) return hipErrorInvalidValue;
+  if (s16)
+    hipLaunchKernelGGL(resample_mix_kernel<short>, dim3((unsigned)tiles), dim3(256), 0, st, (const short*)pcm, channels, samples,
+                       ch_stride, s_stride, taps, first, phases, step, K, out, out_len, out_capacity, tile);
+  else
+    hipLaunchKernelGGL(resample_mix_kernel<float>, dim3((unsigned)tiles), dim3(256), 0, st, (const float*)pcm, channels, samples,
+                       ch_stride, s_stride, taps, first, phases, step, K, out, out_len, out_capacity, tile);
+  return hipGetLastError();
+}
+
 // SAMAUDIO_OPT_SENTINEL (engine.hip): largest magnitude and number of non-finite values of a 16-bit (or fp32) tensor [rows, cols]
 // with row pitch ld, folded into a per-class slot {float absmax, float nonfinite count} - two launches on the launch stream, no
 // atomics (partials per workgroup, then one workgroup folds them into the slot; launches of a stream are ordered).  A debugging /

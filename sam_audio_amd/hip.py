@@ -156,6 +156,7 @@ DBG_ROLES_NONE, DBG_ROLES_PROD0, DBG_ROLES_PROD2 = 1, 2, 3
 
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1, 2   # samaudio.h SAMAUDIO_RESIZE_*
 RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR, "bicubic": RESIZE_BICUBIC}
+PCM_S16, PCM_F32 = 0, 1   # samaudio.h SAMAUDIO_PCM_*
 
 ERR_ARG, ERR_WEIGHT, ERR_WORKSPACE, ERR_HIP, ERR_STATE = -1, -2, -3, -4, -5
 
@@ -361,6 +362,9 @@ _PROTOS = {
     "samaudio_vit_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "samaudio_vit_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
     "samaudio_op_resize_frames": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "samaudio_resample_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "samaudio_op_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -800,12 +800,25 @@ class SAMAudio:
     @torch.inference_mode()
     def separate(self, batch: Batch, noise: Optional[torch.Tensor] = None,
                  ode_opt: Dict[str, Any] = DFLT_ODE_OPT, reranking_candidates: int = 1,
-                 predict_spans: bool = False) -> SeparationResult:
+                 predict_spans: bool = False, output_sampling_rate: Optional[int] = None) -> SeparationResult:
         """Reference model.py:247-338.  `reranking_candidates > 1` draws that many ODE solutions per clip and lets
         `visual_ranker` / `text_ranker` pick one (model.py:306-330); `predict_spans` runs `span_predictor` first
-        (model.py:259-268; mind quirk Q13 below)."""
+        (model.py:259-268; mind quirk Q13 below).  `output_sampling_rate`: when set and different from the codec's rate, the chosen
+        target and residual of every clip are resampled to it on the device (sam_audio_amd/audio.py resample: what the reference's
+        evaluation does with torchaudio behind separate()); None leaves the results as the codec wrote them."""
         if not (self._has_dit and self._has_codec):
             raise RuntimeError("load_state_dict() first")
+        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans)
+        if output_sampling_rate is None or int(output_sampling_rate) == self.sample_rate:
+            return res
+        from . import audio
+        with torch.cuda.device(self.device):
+            return SeparationResult(target=[audio.resample(w, self.sample_rate, output_sampling_rate) for w in res.target],
+                                    residual=[audio.resample(w, self.sample_rate, output_sampling_rate) for w in res.residual],
+                                    noise=res.noise)
+
+    def _separate(self, batch: Batch, noise: Optional[torch.Tensor], ode_opt: Dict[str, Any], reranking_candidates: int,
+                  predict_spans: bool) -> SeparationResult:
         cand = int(reranking_candidates)
         with torch.cuda.device(self.device):
             # Nothing of torch's own arithmetic runs between the first and the last kernel of a step: the noise is drawn first

@@ -1,9 +1,10 @@
 """Host-side batching for SAMAudio.separate(): the reference's `SAMAudioProcessor` / `Batch` API
 (reference sam_audio/processor.py:39-124, 158-260) for tensor inputs.
 
-This is small integer / memcpy work and stays on the CPU.  File decoding in the reference goes
-through torchaudio / torchcodec, which are not part of this build's environment: audio paths are accepted for
-uncompressed PCM WAV at the model's sampling rate (standard library decoder), video paths raise.
+This is small integer / memcpy work and stays on the CPU, except that `audio_transform="hip"` hands the
+resampling, the mono mix and the padding of the clips to one HIP kernel per clip (sam_audio_amd/audio.py).  File decoding in the
+reference goes through torchaudio / torchcodec, which are not part of this build's environment: audio paths are accepted for
+uncompressed PCM WAV at any sampling rate (standard library decoder), video paths raise.
 Bit-exact parity of ``anchor_ids`` / ``anchor_alignment`` / ``sizes`` with the reference is pinned
 by tests/golden/anchors.npz (minted from the reference's own Batch class).
 """
@@ -61,19 +62,20 @@ def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_wi
     return y.to(wav.dtype if wav.is_floating_point() else torch.float32).reshape(*shape[:-1], -1)
 
 
-def load_wav(path: str, sampling_rate: int) -> torch.Tensor:
-    """PCM WAV file -> float32 [channels, samples] in [-1, 1) with torchaudio.load's integer normalisation, resampled to
-    the model's rate when the file's differs (reference processor.py:27-30: torchaudio.load + functional.resample).
-    torchaudio / torchcodec are not part of this build's environment, so only what the standard library decodes is
-    accepted - uncompressed PCM (8 / 16 / 24 / 32 bit)."""
+def read_wav(path: str) -> Tuple[int, int, int, bytes]:
+    """PCM WAV file -> (sampling rate, channels, bytes per sample, the interleaved frames as the file holds them)."""
     import wave
-    import numpy as np
     try:
         with wave.open(path, "rb") as f:
-            sr, ch, width, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
-            raw = f.readframes(n)
+            return f.getframerate(), f.getnchannels(), f.getsampwidth(), f.readframes(f.getnframes())
     except (wave.Error, EOFError) as exc:
         raise ValueError(f"{path}: only uncompressed PCM WAV files can be decoded without torchaudio ({exc})") from exc
+
+
+def decode_pcm(raw: bytes, width: int, ch: int, path: str = "<pcm>") -> torch.Tensor:
+    """Interleaved PCM frames of `width` bytes per sample -> float32 [channels, samples] in [-1, 1) with torchaudio.load's integer
+    normalisation."""
+    import numpy as np
     if width == 1:
         x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
     elif width == 2:
@@ -86,16 +88,37 @@ def load_wav(path: str, sampling_rate: int) -> torch.Tensor:
         x = (np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0).astype(np.float32)
     else:
         raise ValueError(f"{path}: unsupported sample width {width}")
-    wav = torch.from_numpy(x.reshape(-1, ch).T.copy())
+    return torch.from_numpy(x.reshape(-1, ch).T.copy())
+
+
+def load_wav(path: str, sampling_rate: int) -> torch.Tensor:
+    """PCM WAV file -> float32 [channels, samples] in [-1, 1) with torchaudio.load's integer normalisation, resampled to
+    the model's rate when the file's differs (reference processor.py:27-30: torchaudio.load + functional.resample).
+    torchaudio / torchcodec are not part of this build's environment, so only what the standard library decodes is
+    accepted - uncompressed PCM (8 / 16 / 24 / 32 bit)."""
+    sr, ch, width, raw = read_wav(path)
+    wav = decode_pcm(raw, width, ch, path)
     return resample(wav, sr, sampling_rate) if sr != sampling_rate else wav
 
 
-def batch_audio(audios: Sequence[torch.Tensor], audio_sampling_rate: int = 48_000) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Mono mix-down + right zero-padding (reference processor.py:23-36)."""
+def _check_rates(audios: Sequence, sampling_rates: Optional[Sequence[Optional[int]]]) -> Sequence[Optional[int]]:
+    if sampling_rates is None:
+        return [None] * len(audios)
+    if len(sampling_rates) != len(audios):
+        raise ValueError("sampling_rates: one entry per audio (the entry of a file path is ignored: a WAV file keeps its own rate)")
+    return sampling_rates
+
+
+def batch_audio(audios: Sequence[torch.Tensor], audio_sampling_rate: int = 48_000,
+                sampling_rates: Optional[Sequence[Optional[int]]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Mono mix-down + right zero-padding (reference processor.py:23-36).  `sampling_rates`: the source rate of each tensor clip
+    (None = the model's); a clip at another rate goes through `resample` first, as a file does."""
     mono = []
-    for a in audios:
+    for a, rate in zip(audios, _check_rates(audios, sampling_rates)):
         if isinstance(a, str):
             a = load_wav(a, audio_sampling_rate)
+        elif rate is not None and int(rate) != audio_sampling_rate:
+            a = resample(a, rate, audio_sampling_rate)
         if a.dim() != 2:
             raise ValueError(f"expected a (channels, samples) tensor, got shape {tuple(a.shape)}")
         mono.append(a.float().mean(0))
@@ -220,24 +243,67 @@ def sample_video_frames(sizes: torch.Tensor, videos: Sequence[torch.Tensor]) -> 
     return picked
 
 
+def batch_audio_hip(audios: Sequence, audio_sampling_rate: int, sampling_rates: Optional[Sequence[Optional[int]]],
+                    device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`batch_audio` with one HIP kernel per clip (sam_audio_amd/audio.py mix_into): the clip is uploaded as
+    it is - the int16 frames of a 16-bit WAV file interleaved, every other width and tensors as fp32 (channels, samples) - and the
+    kernel resamples it to the model's rate, mixes it down and writes its row of the [B, 1, Lmax] device tensor, padding included.
+    The lengths are integer arithmetic on the source lengths; nothing is read back."""
+    from . import audio
+    device = torch.device(device)
+    clips = []   # (device tensor, channels, samples, channel stride, sample stride, source rate)
+    for a, rate in zip(audios, _check_rates(audios, sampling_rates)):
+        if isinstance(a, str):
+            rate, ch, width, raw = read_wav(a)
+            if width == 2:
+                pcm = torch.frombuffer(bytearray(raw), dtype=torch.int16)   # little-endian frames, as the file holds them
+                clips.append((pcm.to(device), ch, pcm.numel() // ch, 1, ch, rate))
+                continue
+            a = decode_pcm(raw, width, ch, a)
+        if a.dim() != 2:
+            raise ValueError(f"expected a (channels, samples) tensor, got shape {tuple(a.shape)}")
+        pcm = a.float().contiguous().to(device)
+        clips.append((pcm, pcm.shape[0], pcm.shape[1], pcm.shape[1], 1, audio_sampling_rate if rate is None else int(rate)))
+    lengths = [audio.resample_length(samples, rate, audio_sampling_rate) for _, _, samples, _, _, rate in clips]
+    if min(samples for _, _, samples, _, _, _ in clips) < 1:
+        raise ValueError("an audio clip is empty")
+    out = torch.empty(len(clips), 1, max(lengths), dtype=torch.float32, device=device)
+    for row, (pcm, ch, samples, cs, ss, rate) in zip(out, clips):
+        audio.mix_into(row[0], pcm, ch, samples, cs, ss, rate, audio_sampling_rate)
+    return out, torch.tensor(lengths)
+
+
+AUDIO_TRANSFORMS = ("torch", "hip")
+
+
 class SAMAudioProcessor:
-    def __init__(self, audio_hop_length: int, audio_sampling_rate: int):
+    def __init__(self, audio_hop_length: int, audio_sampling_rate: int, audio_transform: str = "torch", device=None):
+        """`audio_transform`: who resamples, mixes down and pads the clips.
+        "torch" (default): the CPU, `batch_audio`; the Batch lives on the CPU until `.to(device)`.
+        "hip": one HIP kernel per clip on `device` (required), `batch_audio_hip`; `Batch.audios` is born on the device, everything
+        else on the CPU as before."""
+        if audio_transform not in AUDIO_TRANSFORMS:
+            raise ValueError(f"audio_transform must be one of {AUDIO_TRANSFORMS}")
+        if audio_transform == "hip" and device is None:
+            raise ValueError('audio_transform="hip" needs a device')
         self.audio_hop_length = audio_hop_length
         self.audio_sampling_rate = audio_sampling_rate
+        self.audio_transform = audio_transform
+        self.device = None if device is None else torch.device(device)
 
     @classmethod
-    def from_config(cls, cfg: SAMAudioConfig) -> "SAMAudioProcessor":
-        return cls(cfg.audio_codec.hop_length, cfg.audio_codec.sample_rate)
+    def from_config(cls, cfg: SAMAudioConfig, audio_transform: str = "torch", device=None) -> "SAMAudioProcessor":
+        return cls(cfg.audio_codec.hop_length, cfg.audio_codec.sample_rate, audio_transform=audio_transform, device=device)
 
     @classmethod
-    def from_pretrained(cls, model_name_or_path: str) -> "SAMAudioProcessor":
+    def from_pretrained(cls, model_name_or_path: str, audio_transform: str = "torch", device=None) -> "SAMAudioProcessor":
         """Local directory holding the reference's config.json (processor.py:165-185); hub ids need
         network access this build does not have."""
         path = os.path.join(model_name_or_path, "config.json")
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path}: only local checkpoints are supported offline")
         with open(path) as fin:
-            return cls.from_config(SAMAudioConfig(**json.load(fin)))
+            return cls.from_config(SAMAudioConfig(**json.load(fin)), audio_transform=audio_transform, device=device)
 
     def feature_to_wav_idx(self, feature_idx):
         return feature_idx * self.audio_hop_length
@@ -255,11 +321,16 @@ class SAMAudioProcessor:
                  anchors: Optional[List[List[Anchor]]] = None,
                  masked_videos: Optional[Sequence[torch.Tensor]] = None,
                  text_features: Optional[torch.Tensor] = None,
-                 text_mask: Optional[torch.Tensor] = None) -> Batch:
+                 text_mask: Optional[torch.Tensor] = None,
+                 sampling_rates: Optional[Sequence[Optional[int]]] = None) -> Batch:
+        """`sampling_rates`: one source rate per clip for tensor clips (None = the model's rate); a WAV file keeps its own."""
         assert len(descriptions) == len(audios)
         assert anchors is None or len(descriptions) == len(anchors)
         assert masked_videos is None or len(descriptions) == len(masked_videos)
-        wavs, wav_sizes = batch_audio(audios, self.audio_sampling_rate)
+        if self.audio_transform == "hip":
+            wavs, wav_sizes = batch_audio_hip(audios, self.audio_sampling_rate, sampling_rates, self.device)
+        else:
+            wavs, wav_sizes = batch_audio(audios, self.audio_sampling_rate, sampling_rates)
         sizes = self.wav_to_feature_idx(wav_sizes)
         pad_mask = mask_from_sizes(sizes)
         video = None if masked_videos is None else sample_video_frames(sizes, masked_videos)
