@@ -396,6 +396,27 @@ int samaudio_op_resize_frames(const uint8_t* frames, int n, int height, int widt
  * (samaudio_vit_workspace_bytes is unchanged).  A null pointer, n <= 0, height / width < 1 or an unknown mode: SAMAUDIO_ERR_ARG. */
 int samaudio_vit_encode_frames(samaudio_vit* v, const uint8_t* frames, int n, int height, int width, int mode,
                                int normalize, float* features, float* tokens_out, samaudio_stream stream);
+/* The visual prompt without its two host passes (reference sam_audio/processor.py:147-153, 197-204: `v * m.eq(0)` over the whole video,
+ * then `video[idx]`): samaudio_op_resize_frames on n frames PICKED from a video, MASKED while they are read.  frames
+ * [src_frames, 3, height, width] u8; output frame f is computed from source frame pick[f] (`pick`: device array of n i32; NULL = the
+ * identity, n must then equal src_frames).  The table is built and range-checked by the caller on the host; the kernel clamps every
+ * entry into [0, src_frames), so a bad table reads a wrong frame, never outside the tensors.  mask [src_frames, mask_channels, height,
+ * width] u8 (bool storage included), mask_channels = 1 (one plane for the three channels) or 3: a source pixel counts as 0 where its
+ * mask byte is non-zero; NULL = no mask, mask_channels is then ignored.  The masked value 0 goes through the same taps in the same
+ * order with the same weights: out [n, 3, out_size, out_size] f32 is bit-identical to samaudio_op_resize_frames on
+ * (frames * (mask == 0))[pick] materialised.  Neither pointer needs any alignment.  SAMAUDIO_ERR_ARG before any launch for a null
+ * frames / out, src_frames / n / height / width / out_size < 1, mask_channels not 1 or 3 with a mask, an unknown mode, or pick == NULL
+ * with n != src_frames; SAMAUDIO_ERR_STATE in a build of the library without the kernel. */
+int samaudio_op_resize_video(const uint8_t* frames, int64_t src_frames, int height, int width, const uint8_t* mask,
+                             int mask_channels, const int32_t* pick, int n, int out_size, int mode, float* out,
+                             samaudio_stream stream);
+/* samaudio_vit_encode_frames on such a video: the picked, masked frames exist only as the patch-embedding operand; everything behind
+ * that launch is samaudio_vit_encode's, so features (and tokens_out) are bit for bit what samaudio_vit_encode_frames computes from the
+ * materialised frames.  Same workspace, sized for the n picked frames (samaudio_vit_workspace_bytes(n) is unchanged).  Errors as
+ * samaudio_op_resize_video (features in the place of out), checked before the context's state. */
+int samaudio_vit_encode_video(samaudio_vit* v, const uint8_t* frames, int64_t src_frames, int height, int width,
+                              const uint8_t* mask, int mask_channels, const int32_t* pick, int n, int mode, int normalize,
+                              float* features, float* tokens_out, samaudio_stream stream);
 
 /* ---- audio front end: resample, mix down and pad one PCM clip ------------------------------
  * What the reference does with torchaudio before batching (sam_audio/processor.py:23-36: load, functional.resample, mean over

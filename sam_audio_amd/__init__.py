@@ -4,7 +4,7 @@ Public surface mirrors `sam_audio` (reference sam_audio/__init__.py:3-4) for tha
 SAMAudio, SAMAudioProcessor, Batch, SeparationResult.
 """
 from .config import SAMAudioConfig, preset_config  # noqa: F401
-from .processor import Batch, SAMAudioJudgeProcessor, SAMAudioProcessor  # noqa: F401
+from .processor import Batch, MaskedVideo, SAMAudioJudgeProcessor, SAMAudioProcessor  # noqa: F401
 
 
 def __getattr__(name):
@@ -20,4 +20,4 @@ def __getattr__(name):
 
 
 __all__ = ["SAMAudio", "SAMAudioProcessor", "SAMAudioJudgeProcessor", "SAMAudioJudgeModel", "Batch", "SeparationResult",
-           "SAMAudioConfig", "preset_config"]
+           "SAMAudioConfig", "preset_config", "MaskedVideo"]

@@ -303,6 +303,23 @@ int samaudio_op_resize_frames(const uint8_t* frames, int n, int height, int widt
                  "resize_frames");
 }
 
+int samaudio_op_resize_video(const uint8_t* frames, int64_t src_frames, int height, int width, const uint8_t* mask, int mask_channels,
+                             const int32_t* pick, int n, int out_size, int mode, float* out, samaudio_stream stream) {
+  if (!frames || !out || src_frames < 1 || src_frames > INT32_MAX || n < 1 || height < 1 || width < 1 || out_size < 1)
+    return bad("resize_video: null argument / src_frames, n, height, width, out_size < 1");
+  if (mask && mask_channels != 1 && mask_channels != 3) return bad("resize_video: mask_channels must be 1 or 3");
+  if (mode != SAMAUDIO_RESIZE_NEAREST && mode != SAMAUDIO_RESIZE_BILINEAR && mode != SAMAUDIO_RESIZE_BICUBIC)
+    return bad("resize_video: unknown mode");
+  if (!pick && n != src_frames) return bad("resize_video: no pick table, but n != src_frames");
+  if (!sa::launch_resize_video) {
+    g_err = "resize_video: not in this build of the library";
+    return SAMAUDIO_ERR_STATE;
+  }
+  return hip_ret(sa::launch_resize_video(frames, (long)src_frames, height, width, mask, mask_channels, pick, n, out_size, mode, out,
+                                         false, 0, 0, (hipStream_t)stream),
+                 "resize_video");
+}
+
 int64_t samaudio_resample_length(int64_t samples, int step, int phases) {
   if (samples < 1 || step < 1 || phases < 1) return -1;
   const int64_t whole = samples / step, rest = samples % step;   // (phases * rest < 2^62; phases * samples may not fit)

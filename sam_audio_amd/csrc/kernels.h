@@ -350,6 +350,12 @@ hipError_t launch_patchify(const float* frames, void* out, bool bf16, int n, int
 // parity hook then answers SAMAUDIO_ERR_STATE (api.hip)
 __attribute__((weak)) hipError_t launch_resize_frames(const unsigned char* frames, int n, int H, int W, int S, int mode, void* out,
                                                       bool bf16, int P, int Kp, hipStream_t st);
+// launch_resize_frames on n frames picked from a video [src_frames,3,H,W]: output frame f from source frame pick[f] (device i32 [n];
+// null = f, n == src_frames; values are clamped into the video), source pixels whose byte of mask [src_frames,mc,H,W] (mc = 1 | 3;
+// null = no mask) is non-zero count as 0.  Bit-identical to launch_resize_frames on (frames * (mask == 0))[pick].  weak: as above
+__attribute__((weak)) hipError_t launch_resize_video(const unsigned char* frames, long src_frames, int H, int W,
+                                                     const unsigned char* mask, int mc, const int* pick, int n, int S, int mode,
+                                                     void* out, bool bf16, int P, int Kp, hipStream_t st);
 // q|k|v rows [n*T, 3*H*hd] -> Q, K [n,H,Tp,hd] (adjacent-pair rotation by rc / rs [T, hd/2]; null = none), V^T [n,H,hd,Tp]
 hipError_t launch_rope2d_split(const void* qkv, const float* rc, const float* rs, void* Q, void* K, void* Vt, bool bf16,
                                int n, int T, int Tp, int H, int head_dim, hipStream_t st);

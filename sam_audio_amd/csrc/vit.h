@@ -25,6 +25,10 @@ class VisionTower {
   // writes the patch embedding's operand
   Status encode_frames(const uint8_t* frames, int n, int height, int width, int mode, bool normalize, float* features,
                        float* tokens_out, hipStream_t st);
+  // ... on n frames picked from a video [src_frames, 3, height, width] by the device table `pick` (null = all of them, in order), source
+  // pixels under a non-zero byte of `mask` [src_frames, mask_channels, height, width] (null = none) zeroed - both inside that launch
+  Status encode_video(const uint8_t* frames, int64_t src_frames, int height, int width, const uint8_t* mask, int mask_channels,
+                      const int32_t* pick, int n, int mode, bool normalize, float* features, float* tokens_out, hipStream_t st);
 
  private:
   void plan(Bump& b, int n, bool assign);

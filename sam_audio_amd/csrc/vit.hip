@@ -162,6 +162,24 @@ Status VisionTower::encode_frames(const uint8_t* frames, int n, int height, int 
   return encode_patches(n, normalize, features, tokens_out, st);
 }
 
+// ... of frames picked from a raw uint8 video, masked on the way: the same launch with an index table and a mask
+Status VisionTower::encode_video(const uint8_t* frames, int64_t src_frames, int height, int width, const uint8_t* mask,
+                                 int mask_channels, const int32_t* pick, int n, int mode, bool normalize, float* features,
+                                 float* tokens_out, hipStream_t st) {
+  if (!frames || !features || src_frames < 1 || src_frames > INT32_MAX || n < 1 || height < 1 || width < 1)
+    return fail(SAMAUDIO_ERR_ARG, "samaudio_vit_encode_video: null argument / src_frames, n, height, width < 1");
+  if (mask && mask_channels != 1 && mask_channels != 3)
+    return fail(SAMAUDIO_ERR_ARG, "samaudio_vit_encode_video: mask_channels must be 1 or 3");
+  if (mode != SAMAUDIO_RESIZE_NEAREST && mode != SAMAUDIO_RESIZE_BILINEAR && mode != SAMAUDIO_RESIZE_BICUBIC)
+    return fail(SAMAUDIO_ERR_ARG, "samaudio_vit_encode_video: unknown resize mode");
+  if (!pick && n != src_frames) return fail(SAMAUDIO_ERR_ARG, "samaudio_vit_encode_video: no pick table, but n != src_frames");
+  if (!launch_resize_video) return fail(SAMAUDIO_ERR_STATE, "samaudio_vit_encode_video: not in this build of the library");
+  SA_TRY(prepare(frames, features, n));
+  SA_HIP(launch_resize_video(frames, (long)src_frames, height, width, mask, mask_channels, pick, n, cfg_.image_size, mode, w_.patches,
+                             bf16_, cfg_.patch_size, kp_, st));
+  return encode_patches(n, normalize, features, tokens_out, st);
+}
+
 Status VisionTower::encode_patches(int n, bool normalize, float* features, float* tokens_out, hipStream_t st) {
   const samaudio_vit_config& c = cfg_;
   const int W = c.width, F = c.mlp_width, H = c.heads, S = tokens(), Sp = (int)round_up(S, 128), G2 = grid_ * grid_;
@@ -356,6 +374,14 @@ int samaudio_vit_encode_frames(samaudio_vit* v, const uint8_t* frames, int n, in
   return SA_ENTRY(v, "null vision tower",
                   v->tower->encode_frames(frames, n, height, width, mode, normalize != 0, features, tokens_out,
                       (hipStream_t)stream));
+}
+
+int samaudio_vit_encode_video(samaudio_vit* v, const uint8_t* frames, int64_t src_frames, int height, int width, const uint8_t* mask,
+                              int mask_channels, const int32_t* pick, int n, int mode, int normalize, float* features,
+                              float* tokens_out, samaudio_stream stream) {
+  return SA_ENTRY(v, "samaudio_vit_encode_video: null vision tower",
+                  v->tower->encode_video(frames, src_frames, height, width, mask, mask_channels, pick, n, mode, normalize != 0,
+                      features, tokens_out, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // All of them are HBM-bound re-layouts around the GEMMs and the flash attention kernel (attention.hip):
 //   patchify        frames [n,3,S,S] f32 -> im2col rows [n*G*G, Kp] (the k = stride = patch conv becomes one GEMM)
 //   resize_frames   uint8 frames [n,3,H,W] -> resized, rounded, normalised: planar f32 or those im2col rows directly
+//   resize_video    the same on frames picked by an index table from a video, with an object mask zeroing source pixels
 //   rope2d_split    fused q|k|v rows -> Q, K [n,H,Sp,hd] with the 2-D rotary embedding, V^T [n,H,hd,Sp]
 //   pool_attention  one learned query per head over all tokens (attention pooling head)
 //   l2_normalize    rows of the projected features
@@ -111,10 +112,70 @@ __device__ __forceinline__ float resize_weight(const ResizeTaps& p, int s) {
   return 0.f;
 }
 
-template <int MODE, typename TA>
+// The video form (a ResizeVideo argument; samaudio_op_resize_video / samaudio_vit_encode_video): output frame f is computed from source
+// frame pick[f] (null = f; clamped into [0, src_frames), so that no table can lead outside the tensors) of a video of src_frames frames,
+// and a source pixel counts as 0 where its byte of `mask` [src_frames, mc, H, W] (mc = 1: one plane for the three channels | 3) is
+// non-zero - the reference's `(v * m.eq(0))[idx]` without either copy.  The mask is applied while the aligned pieces are staged: a frame piece's 16
+// bytes are source columns whose mask bytes start at the mask row's own (mis)alignment, so they are fetched as the one or two aligned
+// 16-byte mask pieces that cover them, shifted into the frame's byte positions and turned into a byte-wise keep / zero - no second
+// staging area in LDS, and everything behind the staging (taps, order, weights) is the code of the plain form: bit-identical to it on
+// the materialised frames.  It is a compile-time property of the instantiation: the plain ones carry none of this.
+
+// the aligned 16 bytes at mask + a (a % 16 == 0 in address terms) as two little-endian 64-bit words; bytes outside [0, mtotal) read 0
+__device__ __forceinline__ void resize_mask_load(const unsigned char* __restrict__ mask, long mtotal, long a,
+                                                 unsigned long long& w0, unsigned long long& w1) {
+  if (a >= 0 && a + 16 <= mtotal) {
+    const uint4 v = *(const uint4*)(mask + a);
+    w0 = (unsigned long long)v.x | ((unsigned long long)v.y << 32);
+    w1 = (unsigned long long)v.z | ((unsigned long long)v.w << 32);
+    return;
+  }
+  w0 = w1 = 0ull;
+  for (int e = 0; e < 16; ++e)
+    if (a + e >= 0 && a + e < mtotal) {
+      const unsigned long long m = (unsigned long long)mask[a + e] << (8 * (e & 7));
+      if (e < 8) w0 |= m; else w1 |= m;
+    }
+}
+
+// 0xFF in every byte of `m` that is non-zero, 0x00 elsewhere
+__device__ __forceinline__ unsigned long long resize_mask_nonzero(unsigned long long m) {
+  m |= m >> 4; m |= m >> 2; m |= m >> 1;   // bit 0 of a byte = the OR of its eight bits (what crosses a byte boundary lands above bit 0)
+  return (m & 0x0101010101010101ull) * 0xFFull;
+}
+
+// the frame piece `v` with the bytes zeroed whose mask bytes mask[mb .. mb + 16) are non-zero (mb: any alignment, may lie partly outside)
+__device__ __forceinline__ uint4 resize_mask_piece(uint4 v, const unsigned char* __restrict__ mask, long mtotal, long mb) {
+  const int ms = (int)(((uintptr_t)mask + (uintptr_t)mb) & 15);
+  unsigned long long l0, l1, l2 = 0ull, l3 = 0ull;
+  resize_mask_load(mask, mtotal, mb - ms, l0, l1);
+  if (ms) resize_mask_load(mask, mtotal, mb - ms + 16, l2, l3);
+  if (ms >= 8) { l0 = l1; l1 = l2; l2 = l3; }
+  const int bs = (ms & 7) * 8;
+  const unsigned long long lo = bs ? (l0 >> bs) | (l1 << (64 - bs)) : l0, hi = bs ? (l1 >> bs) | (l2 << (64 - bs)) : l1;
+  const unsigned long long klo = ~resize_mask_nonzero(lo), khi = ~resize_mask_nonzero(hi);
+  v.x &= (unsigned)klo; v.y &= (unsigned)(klo >> 32);
+  v.z &= (unsigned)khi; v.w &= (unsigned)(khi >> 32);
+  return v;
+}
+
+struct ResizeVideo {
+  const unsigned char* mask;   // [src_frames, mc, H, W] or null
+  long mtotal;                 // its bytes
+  const int* pick;             // [n] or null
+  int src_frames, mc;
+};
+
+// VIDEO: nothing (the plain form: no further parameter, and none of the video form's code) or one ResizeVideo
+template <int MODE, typename TA, typename... VIDEO>
 __global__ __launch_bounds__(256) void resize_frames_kernel(const unsigned char* __restrict__ frames, long total,
                                                             TA* __restrict__ out, int H, int W, int S, int TX, int tiles,
-                                                            int bands, int P, int Kp) {
+                                                            int bands, int P, int Kp, VIDEO... video) {
+  constexpr bool VID = sizeof...(VIDEO) != 0;
+  static_assert(sizeof...(VIDEO) <= 1, "at most one ResizeVideo");
+  ResizeVideo vd{nullptr, 0, nullptr, 0, 0};
+  if constexpr (VID) vd = (video, ...);
+  const unsigned char* __restrict__ mask = vd.mask;
   __shared__ __attribute__((aligned(16))) unsigned char src[RZ_HR * RZ_CWP];
   __shared__ float hrow[RZ_HR][RZ_TX];
   int wg = blockIdx.x;
@@ -142,7 +203,13 @@ __global__ __launch_bounds__(256) void resize_frames_kernel(const unsigned char*
     if (!active || r >= r1) vy[a].hi = vy[a].lo;   // no taps
     acc[a] = ws[a] = 0.f;
   }
-  const long plane = ((long)f * 3 + c) * H;   // first source row of this (frame, channel)
+  int fs = f;                                 // the source frame
+  if (VID) {
+    if (vd.pick) fs = vd.pick[f];
+    fs = fs < 0 ? 0 : fs < vd.src_frames ? fs : vd.src_frames - 1;
+  }
+  const long plane = ((long)fs * 3 + c) * H;   // first source row of this (frame, channel)
+  const long mplane = VID && mask ? ((long)fs * vd.mc + (vd.mc == 3 ? c : 0)) * H : 0;   // ... and of its mask plane
   constexpr int PCS = RZ_CWP / 16;            // 16-byte pieces per LDS row
 
   for (int j0 = rl; j0 < rh; j0 += RZ_HR) {
@@ -168,6 +235,7 @@ __global__ __launch_bounds__(256) void resize_frames_kernel(const unsigned char*
               if (b + e >= 0 && b + e < total) w4[e >> 2] |= (unsigned)frames[b + e] << (8 * (e & 3));
             v = make_uint4(w4[0], w4[1], w4[2], w4[3]);
           }
+          if (VID && mask) v = resize_mask_piece(v, mask, vd.mtotal, (mplane + j0 + row) * W + q0 - sh + pc * 16);
           *(uint4*)(src + row * RZ_CWP + pc * 16) = v;
         }
       }
@@ -246,6 +314,30 @@ hipError_t launch_resize_frames(const unsigned char* frames, int n, int H, int W
   if (mode == SAMAUDIO_RESIZE_NEAREST) return launch_resize_frames_m<SAMAUDIO_RESIZE_NEAREST>(frames, n, H, W, S, out, bf16, P, Kp, st);
   if (mode == SAMAUDIO_RESIZE_BILINEAR) return launch_resize_frames_m<SAMAUDIO_RESIZE_BILINEAR>(frames, n, H, W, S, out, bf16, P, Kp, st);
   if (mode == SAMAUDIO_RESIZE_BICUBIC) return launch_resize_frames_m<SAMAUDIO_RESIZE_BICUBIC>(frames, n, H, W, S, out, bf16, P, Kp, st);
+  return hipErrorInvalidValue;
+}
+
+template <int MODE>
+static hipError_t launch_resize_video_m(const unsigned char* frames, long src_frames, int H, int W, const unsigned char* mask, int mc,
+                                        const int* pick, int n, int S, void* out, bool bf16, int P, int Kp, hipStream_t st) {
+  const int tiles = (S + RZ_TX - 1) / RZ_TX, TX = (S + tiles - 1) / tiles, bands = (S + RZ_BAND - 1) / RZ_BAND;
+  const long wgs = (long)n * 3 * bands * tiles, total = src_frames * 3 * H * W, mtotal = mask ? src_frames * mc * H * W : 0;
+  if (wgs >= (1L << 24)) return hipErrorInvalidValue;
+  dim3 grid((unsigned)wgs), block(256);
+  const ResizeVideo vd{mask, mtotal, pick, (int)src_frames, mc};
+  if (bf16) hipLaunchKernelGGL((resize_frames_kernel<MODE, bf16_t, ResizeVideo>), grid, block, 0, st, frames, total, (bf16_t*)out, H, W, S, TX, tiles, bands, P, Kp, vd);
+  else hipLaunchKernelGGL((resize_frames_kernel<MODE, float, ResizeVideo>), grid, block, 0, st, frames, total, (float*)out, H, W, S, TX, tiles, bands, P, Kp, vd);
+  return hipGetLastError();
+}
+
+hipError_t launch_resize_video(const unsigned char* frames, long src_frames, int H, int W, const unsigned char* mask, int mc,
+                               const int* pick, int n, int S, int mode, void* out, bool bf16, int P, int Kp, hipStream_t st) {
+  if (n <= 0 || src_frames < 1 || src_frames > 0x7fffffffL || H < 1 || W < 1 || S < 1 || (mask && mc != 1 && mc != 3) ||
+      (!pick && n != src_frames) || (Kp && (P < 1 || S % P || Kp < 3 * P * P)))
+    return hipErrorInvalidValue;
+  if (mode == SAMAUDIO_RESIZE_NEAREST) return launch_resize_video_m<SAMAUDIO_RESIZE_NEAREST>(frames, src_frames, H, W, mask, mc, pick, n, S, out, bf16, P, Kp, st);
+  if (mode == SAMAUDIO_RESIZE_BILINEAR) return launch_resize_video_m<SAMAUDIO_RESIZE_BILINEAR>(frames, src_frames, H, W, mask, mc, pick, n, S, out, bf16, P, Kp, st);
+  if (mode == SAMAUDIO_RESIZE_BICUBIC) return launch_resize_video_m<SAMAUDIO_RESIZE_BICUBIC>(frames, src_frames, H, W, mask, mc, pick, n, S, out, bf16, P, Kp, st);
   return hipErrorInvalidValue;
 }
 

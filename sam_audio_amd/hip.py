@@ -362,6 +362,10 @@ _PROTOS = {
     "samaudio_vit_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "samaudio_vit_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
     "samaudio_op_resize_frames": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "samaudio_op_resize_video": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3
+                                 + [C.c_void_p, C.c_void_p]),
+    "samaudio_vit_encode_video": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+                                  + [C.c_int] * 3 + [C.c_void_p] * 3),
     "samaudio_resample_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "samaudio_op_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -893,7 +893,9 @@ class SAMAudio:
             warnings.warn(f"reranking_candidates={cand} but no applicable ranker is attached (model.text_ranker / "
                           "model.visual_ranker): candidate 0 is returned for every clip")
         if cand > 1 and batch.masked_video is not None and self.visual_ranker is not None:
-            scores = self.visual_ranker(extracted_audio=target_wavs, videos=batch.masked_video, sample_rate=sr)
+            # (a third-party callable that expects tensors: a MaskedVideo is materialised for it)
+            videos = [v.materialize() if hasattr(v, "materialize") else v for v in batch.masked_video]
+            scores = self.visual_ranker(extracted_audio=target_wavs, videos=videos, sample_rate=sr)
             return scores.argmax(dim=1)
         if cand > 1 and self.text_ranker is not None:
             input_audio = [audio[:, : int(size)].expand(cand, -1) for audio, size in zip(batch.audios, sizes)]

@@ -137,7 +137,7 @@ class Batch:
     def __init__(self, audios: torch.Tensor, sizes: torch.Tensor, wav_sizes: torch.Tensor,
                  descriptions: List[str], hop_length: int, audio_sampling_rate: int,
                  anchors: Optional[List[List[Anchor]]] = None, audio_pad_mask: Optional[torch.Tensor] = None,
-                 masked_video: Optional[List[torch.Tensor]] = None,
+                 masked_video: Optional[List] = None,
                  text_features: Optional[torch.Tensor] = None, text_mask: Optional[torch.Tensor] = None):
         assert audios.size(0) == len(descriptions), "one description per audio"
         self.audios = audios
@@ -227,19 +227,80 @@ class Batch:
         self._set_anchor_tensors(self._anchor_ids.to(device), self._anchor_alignment.to(device),
                                  getattr(self, "anchor_vocab_validated", 0))
         if self.masked_video is not None:
-            self.masked_video = [v.to(device) for v in self.masked_video]
+            self.masked_video = [v.to(device) for v in self.masked_video]   # (tensors and MaskedVideo items alike)
         return self
 
 
-def sample_video_frames(sizes: torch.Tensor, videos: Sequence[torch.Tensor]) -> List[torch.Tensor]:
-    """One frame per latent step, uniformly spread (reference processor.py:147-153, tensor branch)."""
+class MaskedVideo:
+    """A masked, sampled video that is described, not computed: `(frames * mask.eq(0))[index]` (reference processor.py:197-204 and
+    147-153) as its three operands.  `frames` uint8 [T, 3, H, W]; `mask` uint8 or bool [T, 1 | 3, H, W] (non-zero = the object that is
+    zeroed out) or None; `index` int64 on the host, the picked source frames in output order (repeats, any order), or None = all of
+    them.  `PerceptionEncoder(frame_transform="hip")` hands the three to the kernel that resizes the frames
+    (samaudio_vit_encode_video): the mask is applied and the frames are picked while they are read, and every distinct picked frame
+    is encoded once.  `materialize()` is the CPU statement of what it stands for."""
+
+    def __init__(self, frames: torch.Tensor, mask: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None):
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.size(1) != 3:
+            raise TypeError(f"MaskedVideo takes uint8 frames [T, 3, H, W], not {frames.dtype} {tuple(frames.shape)}")
+        if mask is not None:
+            if mask.dtype not in (torch.uint8, torch.bool):
+                raise TypeError(f"MaskedVideo takes a uint8 or bool mask, not {mask.dtype}")
+            if mask.dim() != 4 or mask.size(1) not in (1, 3) or (mask.size(0),) + tuple(mask.shape[2:]) != \
+                    (frames.size(0),) + tuple(frames.shape[2:]):
+                raise ValueError(f"mask {tuple(mask.shape)} does not fit frames {tuple(frames.shape)}: [T, 1 | 3, H, W]")
+        if index is not None:
+            index = torch.as_tensor(index, dtype=torch.long).cpu().reshape(-1)
+            if index.numel() and (int(index.min()) < -frames.size(0) or int(index.max()) >= frames.size(0)):
+                raise IndexError(f"frame index out of range for a video of {frames.size(0)} frames")
+            index = torch.where(index < 0, index + frames.size(0), index)
+        self.frames, self.mask, self.index = frames, mask, index
+
+    @property
+    def shape(self):
+        return torch.Size((len(self),) + tuple(self.frames.shape[1:]))
+
+    def __len__(self) -> int:
+        return self.frames.size(0) if self.index is None else self.index.numel()
+
+    def size(self, dim: Optional[int] = None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def select(self, idx: torch.Tensor) -> "MaskedVideo":
+        """The frames `idx` of this video, as `video[idx]` would pick them: composed with the index that is already there."""
+        idx = torch.as_tensor(idx, dtype=torch.long).cpu().reshape(-1)
+        if idx.numel() and (int(idx.min()) < -len(self) or int(idx.max()) >= len(self)):
+            raise IndexError(f"frame index out of range for a video of {len(self)} frames")
+        return MaskedVideo(self.frames, self.mask, idx if self.index is None else self.index[idx])
+
+    def materialize(self) -> torch.Tensor:
+        """`(frames * mask.eq(0))[index]` by torch ops, uint8 [len, 3, H, W] on the frames' device"""
+        video = self.frames if self.mask is None else self.frames * self.mask.eq(0)
+        return video if self.index is None else video[self.index.to(video.device)]
+
+    def to(self, device) -> "MaskedVideo":
+        """Frames and mask as they are on `device`, the index stays on the host: no float copy, no masked copy, no gather of the video.
+        Only where the index uses at most half of the source frames are the distinct picked frames gathered first (and the index
+        renumbered), so that the unused ones are not uploaded."""
+        frames, mask, index = self.frames, self.mask, self.index
+        if index is not None and torch.device(device) != frames.device:
+            uniq, inverse = index.unique(return_inverse=True)
+            if 2 * uniq.numel() <= frames.size(0):
+                frames, mask, index = frames[uniq], None if mask is None else mask[uniq], inverse
+        return MaskedVideo(frames.to(device), None if mask is None else mask.to(device), index)
+
+
+def sample_video_frames(sizes: torch.Tensor, videos: Sequence, lazy: bool = False) -> List:
+    """One frame per latent step, uniformly spread (reference processor.py:147-153, tensor branch).  A `MaskedVideo` records the
+    indices (composed with the ones it holds) instead of gathering; `lazy` wraps uint8 tensors into one first."""
     picked = []
     for size, video in zip(sizes, videos):
         if isinstance(video, str):
             raise ValueError("video file paths need torchcodec, which this build does not ship")
         assert video.size(1) == 3, f"expected NCHW video, found {video.size(1)} channels"
         idx = torch.linspace(0, video.size(0) - 1, int(size)).round().long()
-        picked.append(video[idx])
+        if lazy and torch.is_tensor(video) and video.dtype == torch.uint8 and video.dim() == 4:
+            video = MaskedVideo(video)
+        picked.append(video.select(idx) if isinstance(video, MaskedVideo) else video[idx])
     return picked
 
 
@@ -274,16 +335,27 @@ def batch_audio_hip(audios: Sequence, audio_sampling_rate: int, sampling_rates: 
 
 
 AUDIO_TRANSFORMS = ("torch", "hip")
+VIDEO_TRANSFORMS = ("torch", "hip")
 
 
 class SAMAudioProcessor:
-    def __init__(self, audio_hop_length: int, audio_sampling_rate: int, audio_transform: str = "torch", device=None):
+    def __init__(self, audio_hop_length: int, audio_sampling_rate: int, audio_transform: str = "torch", device=None,
+                 video_transform: str = "torch"):
         """`audio_transform`: who resamples, mixes down and pads the clips.
         "torch" (default): the CPU, `batch_audio`; the Batch lives on the CPU until `.to(device)`.
         "hip": one HIP kernel per clip on `device` (required), `batch_audio_hip`; `Batch.audios` is born on the device, everything
-        else on the CPU as before."""
+        else on the CPU as before.
+        `video_transform`: who masks the visual prompt and picks its frames.
+        "torch" (default): the CPU - `mask_videos` multiplies the whole video, `sample_video_frames` gathers one frame per latent step.
+        "hip": neither happens here.  `mask_videos` returns `MaskedVideo` descriptions of uint8 videos, `__call__` accepts them (and
+        plain uint8 tensors) as `masked_videos` and records the picked indices in them; `Batch.to(device)` uploads the raw video and
+        its mask, and `PerceptionEncoder(frame_transform="hip")` masks and picks inside the kernel that resizes the frames.  Videos
+        of any other dtype keep the "torch" behaviour."""
         if audio_transform not in AUDIO_TRANSFORMS:
             raise ValueError(f"audio_transform must be one of {AUDIO_TRANSFORMS}")
+        if video_transform not in VIDEO_TRANSFORMS:
+            raise ValueError(f"video_transform must be one of {VIDEO_TRANSFORMS}")
+        self.video_transform = video_transform
         if audio_transform == "hip" and device is None:
             raise ValueError('audio_transform="hip" needs a device')
         self.audio_hop_length = audio_hop_length
@@ -292,18 +364,22 @@ class SAMAudioProcessor:
         self.device = None if device is None else torch.device(device)
 
     @classmethod
-    def from_config(cls, cfg: SAMAudioConfig, audio_transform: str = "torch", device=None) -> "SAMAudioProcessor":
-        return cls(cfg.audio_codec.hop_length, cfg.audio_codec.sample_rate, audio_transform=audio_transform, device=device)
+    def from_config(cls, cfg: SAMAudioConfig, audio_transform: str = "torch", device=None,
+                    video_transform: str = "torch") -> "SAMAudioProcessor":
+        return cls(cfg.audio_codec.hop_length, cfg.audio_codec.sample_rate, audio_transform=audio_transform, device=device,
+                   video_transform=video_transform)
 
     @classmethod
-    def from_pretrained(cls, model_name_or_path: str, audio_transform: str = "torch", device=None) -> "SAMAudioProcessor":
+    def from_pretrained(cls, model_name_or_path: str, audio_transform: str = "torch", device=None,
+                        video_transform: str = "torch") -> "SAMAudioProcessor":
         """Local directory holding the reference's config.json (processor.py:165-185); hub ids need
         network access this build does not have."""
         path = os.path.join(model_name_or_path, "config.json")
         if not os.path.exists(path):
             raise FileNotFoundError(f"{path}: only local checkpoints are supported offline")
         with open(path) as fin:
-            return cls.from_config(SAMAudioConfig(**json.load(fin)), audio_transform=audio_transform, device=device)
+            return cls.from_config(SAMAudioConfig(**json.load(fin)), audio_transform=audio_transform, device=device,
+                                   video_transform=video_transform)
 
     def feature_to_wav_idx(self, feature_idx):
         return feature_idx * self.audio_hop_length
@@ -313,8 +389,13 @@ class SAMAudioProcessor:
             return torch.ceil(wav_idx / self.audio_hop_length)
         return math.ceil(wav_idx / self.audio_hop_length)
 
-    def mask_videos(self, videos: Sequence[torch.Tensor], masks: Sequence[torch.Tensor]) -> List[torch.Tensor]:
-        """Zero the masked object out of each frame (reference processor.py:197-204, tensor branch)."""
+    def mask_videos(self, videos: Sequence[torch.Tensor], masks: Sequence[torch.Tensor]) -> List:
+        """Zero the masked object out of each frame (reference processor.py:197-204, tensor branch).  `video_transform="hip"`: a
+        uint8 video with a uint8 / bool mask [T, 1 | 3, H, W] becomes a `MaskedVideo` - no arithmetic here."""
+        if self.video_transform == "hip":
+            lazy = lambda v, m: (v.dtype == torch.uint8 and v.dim() == 4 and v.size(1) == 3 and m.dim() == 4   # noqa: E731
+                                 and m.dtype in (torch.uint8, torch.bool))
+            return [MaskedVideo(v, m) if lazy(v, m) else v * m.eq(0) for v, m in zip(videos, masks)]
         return [v * m.eq(0) for v, m in zip(videos, masks)]
 
     def __call__(self, descriptions: List[str], audios: Sequence[torch.Tensor],
@@ -333,7 +414,7 @@ class SAMAudioProcessor:
             wavs, wav_sizes = batch_audio(audios, self.audio_sampling_rate, sampling_rates)
         sizes = self.wav_to_feature_idx(wav_sizes)
         pad_mask = mask_from_sizes(sizes)
-        video = None if masked_videos is None else sample_video_frames(sizes, masked_videos)
+        video = None if masked_videos is None else sample_video_frames(sizes, masked_videos, lazy=self.video_transform == "hip")
         return Batch(audios=wavs, sizes=sizes, wav_sizes=wav_sizes, descriptions=list(descriptions),
                      hop_length=self.audio_hop_length, audio_sampling_rate=self.audio_sampling_rate,
                      anchors=anchors, audio_pad_mask=pad_mask, masked_video=video,

@@ -29,7 +29,9 @@ class PerceptionEncoder:
         "hip": a uint8 video on a tower that has `encode_frames` (PEVisionTower) is chunked by `batch_size` AS uint8 and every chunk goes
         through `tower.encode_frames`, where one HIP kernel resizes, rounds, normalises and writes the patch embedding's operand: no
         float copy of the video exists, whatever its resolution; frames that already have the target size take the same path.  A
-        video of any other dtype, or an injected tower without `encode_frames`, takes the "torch" path."""
+        video of any other dtype, or an injected tower without `encode_frames`, takes the "torch" path.  A `processor.MaskedVideo`
+        item (`SAMAudioProcessor(video_transform="hip")`) is masked and picked by that kernel as well, each distinct frame encoded
+        once (`_encode_masked`); on the "torch" path it is materialised first."""
         if frame_transform not in FRAME_TRANSFORMS:
             raise ValueError(f"frame_transform must be one of {FRAME_TRANSFORMS}, not {frame_transform!r}")
         self.frame_transform = frame_transform
@@ -90,6 +92,11 @@ class PerceptionEncoder:
         result = []
         for video in videos:
             video = video.to(self.device) if self.device is not None else video
+            if hasattr(video, "materialize"):   # processor.MaskedVideo: frames, mask and index of `(frames * mask.eq(0))[index]`
+                if self.frame_transform == "hip" and hasattr(self.tower, "encode_frames"):
+                    result.append(self._encode_masked(video))
+                    continue
+                video = video.materialize()
             if self.frame_transform == "hip" and video.dtype == torch.uint8 and hasattr(self.tower, "encode_frames"):
                 encode = lambda v: self.tower.encode_frames(v, self.mode, normalize=self.normalize_feature)   # noqa: E731
             else:
@@ -100,5 +107,17 @@ class PerceptionEncoder:
             else:
                 result.append(encode(video))
         return torch.nn.utils.rnn.pad_sequence(result, batch_first=True, padding_value=0.0)
+
+    def _encode_masked(self, video) -> torch.Tensor:
+        """A MaskedVideo on the tower's kernel: every DISTINCT picked frame is encoded once, in chunks of `batch_size`, masked and
+        picked by the launch that resizes it (`tower.encode_frames(frames, masks=, index=)`); the features are then gathered into
+        the picked order - a video with fewer frames than the clip has latent steps does not go through the tower repeatedly."""
+        index = video.index if video.index is not None else torch.arange(video.frames.size(0))
+        uniq, inverse = index.unique(return_inverse=True)
+        step = self.batch_size if self.batch_size > 0 else uniq.numel()
+        parts = [self.tower.encode_frames(video.frames, self.mode, normalize=self.normalize_feature, masks=video.mask,
+                                          index=uniq[i: i + step]) for i in range(0, uniq.numel(), step)]
+        feats = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+        return feats[inverse.to(feats.device)]
 
     __call__ = forward

@@ -270,27 +270,36 @@ class PEVisionTower:
             self._side = (h, holder, torch.cuda.Stream(device=self.device))
         return self._side
 
-    def _encode_on(self, handle, owner, x, normalize, feats, tokens, mode=None):
+    def _encode_on(self, handle, owner, x, normalize, feats, tokens, mode=None, video=None):
         """One context's encode of the frames `x`: float [n,3,S,S] (samaudio_vit_encode), or - `mode` a hip.RESIZE_* code - raw uint8
-        [n,3,H,W] (samaudio_vit_encode_frames)."""
-        n = x.shape[0]
+        [n,3,H,W] (samaudio_vit_encode_frames), or - `video` = (mask or None, pick i32 [n] on the device or None) - the frames `pick` of
+        the uint8 video `x` under its mask (samaudio_vit_encode_video)."""
+        n = x.shape[0] if video is None or video[1] is None else video[1].shape[0]
         need = self._lib.samaudio_vit_workspace_bytes(handle, n)
         _ensure_ws(owner, need, lambda p, b: self._lib.samaudio_vit_set_workspace(handle, p, b))
         tail = (int(bool(normalize)), hip.ptr(feats), hip.ptr(tokens), hip.current_stream_ptr())
         if mode is None:
             hip.check(self._lib.samaudio_vit_encode(handle, hip.ptr(x), n, *tail))
+        elif video is not None:
+            mask, pick = video
+            hip.check(self._lib.samaudio_vit_encode_video(handle, hip.ptr(x), x.shape[0], x.shape[2], x.shape[3], hip.ptr(mask),
+                                                          1 if mask is None else mask.shape[1], hip.ptr(pick), n, mode, *tail))
         else:
             hip.check(self._lib.samaudio_vit_encode_frames(handle, hip.ptr(x), n, x.shape[2], x.shape[3], mode, *tail))
 
-    def _encode(self, x, normalize, return_tokens, mode=None):
-        """Workspace, outputs and the two-stream split of a frame batch `x` on the device (see _encode_on)."""
+    def _encode(self, x, normalize, return_tokens, mode=None, video=None):
+        """Workspace, outputs and the two-stream split of a frame batch `x` on the device (see _encode_on).  With `video` the split
+        slices the pick table, not the frames (no table: the identity table is made for it)."""
         cfg = self.cfg
-        n = x.shape[0]
+        n = x.shape[0] if video is None or video[1] is None else video[1].shape[0]
+        part = lambda lo, hi: (x[lo:hi], None) if video is None else (x, (video[0], video[1][lo:hi]))   # noqa: E731
         with torch.cuda.device(self.device):
             feats = torch.empty(n, cfg.output_dim, device=self.device, dtype=torch.float32)
             tokens = torch.empty(n, cfg.tokens, cfg.width, device=self.device, dtype=torch.float32) if return_tokens else None
             if self.streams == 2 and n >= 64:
                 import threading
+                if video is not None and video[1] is None:
+                    video = (video[0], torch.arange(n, device=self.device, dtype=torch.int32))
                 h2, holder, side = self._side_context()
                 k = n // 2
                 main = torch.cuda.current_stream(self.device)
@@ -300,18 +309,20 @@ class PEVisionTower:
                 def second():
                     try:
                         with torch.inference_mode(), torch.cuda.device(self.device), torch.cuda.stream(side):
-                            self._encode_on(h2, holder, x[k:], normalize, feats[k:], None if tokens is None else tokens[k:], mode)
+                            self._encode_on(h2, holder, part(k, n)[0], normalize, feats[k:], None if tokens is None else tokens[k:],
+                                            mode, part(k, n)[1])
                     except BaseException as exc:   # re-raised on the caller's thread
                         errors.append(exc)
                 th = threading.Thread(target=second)
                 th.start()
-                self._encode_on(self._h, self, x[:k], normalize, feats[:k], None if tokens is None else tokens[:k], mode)
+                self._encode_on(self._h, self, part(0, k)[0], normalize, feats[:k], None if tokens is None else tokens[:k], mode,
+                                part(0, k)[1])
                 th.join()
                 main.wait_stream(side)
                 if errors:
                     raise errors[0]
             else:
-                self._encode_on(self._h, self, x, normalize, feats, tokens, mode)
+                self._encode_on(self._h, self, x, normalize, feats, tokens, mode, video)
         return (feats, tokens) if return_tokens else feats
 
     @torch.inference_mode()
@@ -326,12 +337,17 @@ class PEVisionTower:
         return self._encode(x, normalize, return_tokens)
 
     @torch.inference_mode()
-    def encode_frames(self, frames_u8: torch.Tensor, mode: str = "bicubic", normalize: bool = False, return_tokens: bool = False):
+    def encode_frames(self, frames_u8: torch.Tensor, mode: str = "bicubic", normalize: bool = False, return_tokens: bool = False,
+                      masks: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None):
         """`encode_image` on raw uint8 frames [N, 3, H, W] of any size (H, W >= 1; frames of the target size included): the HIP library
         resizes (`mode`: "nearest" | "bilinear" | "bicubic", the last two antialiased - torch's F.interpolate(x.float(), (S, S), mode,
         antialias=True, align_corners=False)), rounds half to even, clamps to 0..255 and normalises (v / 255 - 0.5) / 0.5 in the launch
         that writes the patch embedding's operand (samaudio_vit_encode_frames).  No float copy of the frames is made: hand it slices
-        of the uint8 tensor.  Same workspace and two-stream split as encode_image."""
+        of the uint8 tensor.  Same workspace and two-stream split as encode_image.
+        `masks` (uint8 or bool [N, 1 | 3, H, W]: a source pixel under a non-zero byte counts as 0) and `index` (integers on the host:
+        the frames to encode, in output order, repeats allowed; range-checked here) make it the encode of
+        `(frames_u8 * masks.eq(0))[index]`, bit for bit, without either copy: the kernel masks and picks while it reads
+        (samaudio_vit_encode_video).  Both None: today's entry point, exactly as before."""
         if not self._loaded:
             raise hip.SamAudioHipError("PEVisionTower: no weights loaded")
         if mode not in hip.RESIZE_MODES:
@@ -341,7 +357,28 @@ class PEVisionTower:
         assert frames_u8.dim() == 4 and frames_u8.shape[1] == 3 and min(frames_u8.shape) >= 1, "frames must be [N, 3, H, W], N, H, W >= 1"
         with torch.cuda.device(self.device):
             x = frames_u8.to(self.device).contiguous()
-        return self._encode(x, normalize, return_tokens, hip.RESIZE_MODES[mode])
+        if masks is None and index is None:
+            return self._encode(x, normalize, return_tokens, hip.RESIZE_MODES[mode])
+        pick = None
+        if masks is not None:
+            if masks.dtype not in (torch.uint8, torch.bool):
+                raise TypeError(f"encode_frames takes a uint8 or bool mask, not {masks.dtype}")
+            if masks.dim() != 4 or masks.shape[1] not in (1, 3) or (masks.shape[0],) + tuple(masks.shape[2:]) != \
+                    (x.shape[0],) + tuple(x.shape[2:]):
+                raise ValueError(f"masks {tuple(masks.shape)} do not fit frames {tuple(x.shape)}: [N, 1 | 3, H, W]")
+            with torch.cuda.device(self.device):
+                masks = masks.to(self.device).contiguous()
+                masks = masks.view(torch.uint8) if masks.dtype == torch.bool else masks   # (bool storage: bytes 0 / 1)
+        if index is not None:
+            index = torch.as_tensor(index).cpu().reshape(-1).long()   # checked on the host: the kernel only clamps
+            if index.numel() < 1:
+                raise ValueError("index is empty")
+            if int(index.min()) < -x.shape[0] or int(index.max()) >= x.shape[0]:
+                raise IndexError(f"frame index out of range for {x.shape[0]} frames")
+            index = torch.where(index < 0, index + x.shape[0], index)
+            with torch.cuda.device(self.device):
+                pick = index.to(torch.int32).to(self.device)
+        return self._encode(x, normalize, return_tokens, hip.RESIZE_MODES[mode], (masks, pick))
 
     def __call__(self, frames: torch.Tensor, normalize: bool = False) -> torch.Tensor:
         return self.encode_image(frames, normalize=normalize)
