@@ -444,6 +444,43 @@ int samaudio_op_resample(const void* pcm, int fmt, int channels, int64_t samples
                          const float* taps, const int32_t* first, int phases, int step, int taps_per_phase, float* out,
                          int64_t out_capacity, samaudio_stream stream);
 
+/* ---- sound activity: silence detection and span overlap of `rows` mono waveforms -----------
+ * The reference's SoundActivityRanker (sam_audio/ranking/sound_activity.py): pydub.silence.detect_nonsilent on the separated
+ * waveform, then compute_iou_recall_precision against the prompt's spans.  The CPU statement is tests/activity_ref.py - pinned to
+ * CPython's audioop (what pydub calls), unpinned vs pydub / torchcodec.  All of it is integer arithmetic behind step 1:
+ *   1  s = clip(rint(fp64(x) 32768), -32768, 32767) as int16, round half to even, NaN -> 0
+ *   2  to 24 kHz as audioop.ratecv does: i = rate / g (`step`), o = 24000 / g (`phases`), g = gcd, M input samples,
+ *      N = floor(o (M - 1) / i) + 1;  m = ceil(i j / o), d = o m - i j,  y[j] = trunc(65536 (s[m-1] d + s[m] (o - d)) / o) >> 16,  s[-1] = 0
+ *   3  L = round(1000 N / 24000) ms, ties to even.  A slice [a, b) ms is frames [24 a, 24 b), frames at or beyond N count as zero
+ *   4  S(i) = sum of y^2 over the 6 000 frames of the window that starts at i ms;  rms(i) = floor(sqrt(S(i) / 6000))
+ *   5  L < 250: the nonsilent spans are [[0, L]]
+ *   6  peak = max rms(i), i in range(0, L - 250 + 1, 100)
+ *   7  thresh(peak): "rel_to_max" 10^((sil_threshold + 20 log10(peak / 32768)) / 20) 32768, "abs" 10^(sil_threshold / 20) 32768.  The
+ *      caller evaluates it on the host for every peak in [0, 32768] and hands over threshold_table[peak] = min(floor(thresh), 65535):
+ *      rms(i) <= thresh  <=>  S(i) < (T + 1)^2 6000.  No logarithm or power is evaluated on the device.
+ *   8  window starts range(0, L - 250 + 1, 10), plus L - 250 when (L - 250) % 10 != 0; a start is silent iff rms(i) <= thresh
+ *   9  silent ranges (detect_silence): walk the silent starts; close the range at prev + 250 when the next start is neither
+ *      prev + 10 nor <= prev + 250; close the last one
+ *  10  nonsilent ranges (detect_nonsilent): no silent range -> [[0, L]]; the gaps from 0 on, a final [prev_end, L] unless the last
+ *      silent range ends at L, a leading [0, 0] dropped; at most L / 250 + 1 of them.  In seconds: ms / 1000 in float64
+ *  11  score = iou | recall | precision (metric 0 | 1 | 2) of compute_iou_recall_precision(nonsilent spans, ref_spans), float64 in
+ *      the reference's order of operations (overlapping reference spans count twice, as there), rounded to float32
+ * wav: row r at wav + r * row_stride, contiguous in time.  The same ref_spans [n_ref][2] (seconds, f64, device) for every row. */
+/* L of step 3; -1 for an argument below 1 or phases not a divisor of 24 000 */
+int64_t samaudio_activity_length_ms(int64_t samples, int step, int phases);
+/* bytes of workspace samaudio_op_activity needs (rows x max(L, 1) int64, aligned to 8); -1 as above or for rows < 1 */
+int64_t samaudio_activity_workspace_bytes(int rows, int64_t samples, int step, int phases);
+/* scores [rows] f32; and, each where not NULL, spans [rows][max_spans][2] i32 = (start_ms, end_ms) of the first span_count [rows]
+ * nonsilent spans (the rest of a row is left as it was) and peak [rows] (0 when L < 250).  ref_spans NULL or n_ref = 0: spans only,
+ * scores 0.  Stateless, caller workspace, nothing is read back.  SAMAUDIO_ERR_ARG before any launch for a null wav /
+ * threshold_table / workspace / scores, rows / samples / step / phases < 1, phases not a divisor of 24 000, row_stride < samples, a
+ * metric outside 0..2, n_ref < 0 or n_ref > 0 with null ref_spans, a workspace that is too small or not aligned to 8 bytes, spans
+ * with max_spans < L / 250 + 1; SAMAUDIO_ERR_STATE in a build of the library without the kernels. */
+int samaudio_op_activity(const float* wav, int rows, int64_t row_stride, int64_t samples, int step, int phases,
+                         const int32_t* threshold_table /* [32769] */, const double* ref_spans /* [n_ref][2] s, or NULL */,
+                         int n_ref, int metric, void* workspace, int64_t workspace_bytes, float* scores, int32_t* spans,
+                         int max_spans, int32_t* span_count, int32_t* peak, samaudio_stream stream);
+
 /* ---- text-prompt encoder ---------------------------------------------------------
  * T5 encoder stack behind `T5TextEncoder.forward` (reference sam_audio/model/text_encoder.py:19-37:
  * `transformers.T5EncoderModel("t5-base")(input_ids, attention_mask)["last_hidden_state"]`).  Tokenisation stays with the

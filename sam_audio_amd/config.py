@@ -195,15 +195,34 @@ class JudgeRankerConfig:
     kind: str = "judge"
 
 
+@dataclass
+class SoundActivityRankerConfig:
+    """reference model/config.py:163-174.  The mode and the metric are checked here; the reference fails on them at the first call."""
+    threshold_mode: str = "rel_to_max"
+    sil_threshold: float = -40
+    metric: str = "iou"
+    kind: str = "sound_activity"
+
+    def __post_init__(self):
+        if self.threshold_mode not in ("abs", "rel_to_max"):
+            raise ValueError(f"SoundActivityRankerConfig: threshold_mode must be 'abs' or 'rel_to_max', got {self.threshold_mode!r}")
+        if self.metric not in ("iou", "recall", "precision"):
+            raise ValueError(f"SoundActivityRankerConfig: metric must be 'iou', 'recall' or 'precision', got {self.metric!r}")
+
+
 def parse_ranker_config(raw: Optional[Dict[str, Any]]):
-    """Only the Judge ranker is on this build's roadmap; CLAP / ImageBind are
-    third-party models that are out of scope, so their configs are kept as opaque dicts."""
+    """The Judge ranker and the sound-activity ranker are built here; CLAP / ImageBind
+    are third-party models that are out of scope, so their configs are kept as opaque dicts.  So is an ensemble's:
+    ranking.create_ranker parses its members with this function."""
     if raw is None:
         return None
     raw = dict(raw)
     if raw.get("kind") == "judge":
         raw.pop("kind")
         return JudgeRankerConfig(**raw)
+    if raw.get("kind") == "sound_activity":
+        raw.pop("kind")
+        return SoundActivityRankerConfig(**raw)
     return raw
 
 

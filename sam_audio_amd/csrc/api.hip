@@ -344,6 +344,55 @@ int samaudio_op_resample(const void* pcm, int fmt, int channels, int64_t samples
                  "resample");
 }
 
+// ---- sound activity --------------------------------------------------------------------------------------------
+// N = floor(phases (samples - 1) / step) + 1 frames at 24 kHz (audioop.ratecv's length); -1 for an argument it refuses
+static int64_t activity_frames(int64_t samples, int step, int phases) {
+  if (samples < 1 || step < 1 || phases < 1 || 24000 % phases) return -1;
+  const int64_t whole = (samples - 1) / step, rest = (samples - 1) % step;
+  if (whole > (INT64_MAX >> 32)) return -1;
+  return phases * whole + phases * rest / step + 1;
+}
+
+int64_t samaudio_activity_length_ms(int64_t samples, int step, int phases) {
+  const int64_t frames = activity_frames(samples, step, phases);
+  if (frames < 0) return -1;
+  const int64_t q = frames / 24, r = frames % 24;   // round(1000 N / 24000), ties to even
+  return q + ((r > 12 || (r == 12 && (q & 1))) ? 1 : 0);
+}
+
+int64_t samaudio_activity_workspace_bytes(int rows, int64_t samples, int step, int phases) {
+  const int64_t length = samaudio_activity_length_ms(samples, step, phases);
+  if (rows < 1 || length < 0) return -1;
+  return (int64_t)rows * (length > 0 ? length : 1) * (int64_t)sizeof(int64_t);
+}
+
+int samaudio_op_activity(const float* wav, int rows, int64_t row_stride, int64_t samples, int step, int phases,
+                         const int32_t* threshold_table, const double* ref_spans, int n_ref, int metric, void* workspace,
+                         int64_t workspace_bytes, float* scores, int32_t* spans, int max_spans, int32_t* span_count, int32_t* peak,
+                         samaudio_stream stream) {
+  if (!wav || !threshold_table || !workspace || !scores) return bad("activity: null wav / threshold_table / workspace / scores");
+  if (rows < 1 || samples < 1 || step < 1 || phases < 1) return bad("activity: rows, samples, step, phases < 1");
+  if (24000 % phases) return bad("activity: phases must divide 24000 (phases = 24000 / gcd(rate, 24000))");
+  if (row_stride < samples) return bad("activity: row_stride below samples");
+  if (metric < 0 || metric > 2) return bad("activity: metric must be 0 (iou), 1 (recall) or 2 (precision)");
+  if (n_ref < 0 || (n_ref > 0 && !ref_spans)) return bad("activity: n_ref < 0, or n_ref > 0 without ref_spans");
+  const int64_t frames = activity_frames(samples, step, phases);
+  const int64_t length = samaudio_activity_length_ms(samples, step, phases);
+  const int64_t need = samaudio_activity_workspace_bytes(rows, samples, step, phases);
+  if (frames < 0 || length < 0 || length > INT32_MAX) return bad("activity: clip too long");
+  if (need < 0 || workspace_bytes < need || (uintptr_t)workspace % sizeof(int64_t))
+    return bad("activity: workspace below samaudio_activity_workspace_bytes, or not aligned to 8 bytes");
+  if (spans && max_spans < length / 250 + 1) return bad("activity: max_spans below L / 250 + 1");
+  if (!sa::launch_activity) {
+    g_err = "activity: not in this build of the library";
+    return SAMAUDIO_ERR_STATE;
+  }
+  return hip_ret(sa::launch_activity(wav, rows, (long)row_stride, step, phases, (long)frames, (long)length, threshold_table, ref_spans,
+                                     n_ref, metric, (long long*)workspace, scores, spans, max_spans, span_count, peak,
+                                     (hipStream_t)stream),
+                 "activity");
+}
+
 int samaudio_op_split3(const float* x, int64_t x_ld, void* out, int64_t rows, int k, samaudio_stream stream) {
   if (!x || !out || rows <= 0 || k <= 0 || k % 8 || x_ld % 4) return bad("split3: k % 8, x_ld % 4");
   return hip_ret(sa::launch_split3(x, x_ld, out, rows, k, (hipStream_t)stream), "split3");

@@ -341,6 +341,16 @@ __attribute__((weak)) hipError_t launch_resample_mix(const void* pcm, bool s16, 
                                                      long s_stride, const float* taps, const int* first, int phases, int step, int K,
                                                      float* out, long out_len, long out_capacity, hipStream_t st);
 
+// ---- sound activity (kernels.hip) --------------------------------------------------------------------------------
+// `rows` mono fp32 waveforms (row r at wav + r * row_stride) -> int16 -> 24 kHz (`step` input samples per `phases` frames, phases a
+// divisor of 24 000; N frames, L ms: samaudio.h) -> cells [rows][L] i64 (the workspace: sums of y^2 per millisecond) -> per row the
+// nonsilent spans in ms (spans [rows][max_spans][2], span_count [rows], peak [rows]: each may be null) and scores [rows] = iou | recall | precision (metric 0 | 1 | 2) against ref_spans [n_ref][2] f64 seconds (null = none: score 0).
+// Two launches.  weak: the CPU emulation of the launchers (oracle/emu) does not define it - the hook then answers SAMAUDIO_ERR_STATE
+__attribute__((weak)) hipError_t launch_activity(const float* wav, int rows, long row_stride, int step, int phases, long N, long L,
+                                                 const int* table, const double* ref_spans, int n_ref, int metric, long long* cells,
+                                                 float* scores, int* spans, int max_spans, int* span_count, int* peak,
+                                                 hipStream_t st);
+
 // ---- PE-Core vision tower (vit_kernels.hip) ---------------------------------------------------------------------
 // im2col of the k = stride = P patch convolution: frames [n,3,S,S] f32 -> rows [n*(S/P)^2, Kp], column c*P*P + py*P + px
 hipError_t launch_patchify(const float* frames, void* out, bool bf16, int n, int S, int P, int Kp, hipStream_t st);

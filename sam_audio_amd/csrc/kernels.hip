@@ -1100,6 +1100,275 @@ hipError_t launch_resample_mix(const void* pcm, bool s16, int channels, long sam
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Sound activity (samaudio.h samaudio_op_activity; the statement is tests/activity_ref.py): silence detection
+// on `rows` mono waveforms and the overlap of the nonsilent spans with reference spans.  Everything behind the quantisation to
+// int16 is integer arithmetic, so no result depends on the launch geometry, on `rows` or on the other rows.
+//   activity_cells_kernel   waveform -> int16 -> 24 kHz by the closed form of audioop.ratecv -> cells[row][c] = sum of y^2 over the 24
+//                           frames of millisecond c.  A workgroup owns kActivityTileCells consecutive cells; consecutive lanes take
+//                           consecutive frames, so every input sample is fetched from memory once, in whole cache lines.
+//   activity_score_kernel   one workgroup per row: cells -> sums per 10 ms in LDS (a window sum is 25 of them), the peak rms by an LDS
+//                           max reduction, the silent flags of the window starts against the host's threshold table, then one thread
+//                           walks pydub's detect_silence / detect_nonsilent and the reference's
+//                           compute_iou_recall_precision in float64 with contraction off.
+// ------------------------------------------------------------------------------------------------
+constexpr int kActivityCellFrames = 24;       // frames per millisecond at 24 kHz
+constexpr int kActivityWindowMs = 250;        // min_sil_ms and the peak window
+constexpr int kActivitySeekMs = 10;           // seek_step
+constexpr int kActivityPeakHopMs = 100;       // get_peak_rms's hop
+constexpr int kActivityTileCells = 64;        // cells per workgroup of activity_cells_kernel: 1 536 frames, 6 per thread
+constexpr int kActivityTileFrames = kActivityTileCells * kActivityCellFrames;
+constexpr int kActivityDeca = kActivityWindowMs / kActivitySeekMs;   // decacells (10 ms) per window
+constexpr int kActivityStartChunk = 2000;     // regular window starts whose decacells and flags are in LDS at a time (a multiple of 10 and of 8)
+
+// clip(rint(x 32768), -32768, 32767), NaN -> 0.  The product with 2^15 is exact in fp32 (or overflows to an infinity, which the clip
+// takes), so this is the statement's float64 expression.
+__device__ __forceinline__ int activity_quantise(float x) {
+  float v = x * 32768.f;
+  if (!(v == v)) return 0;
+  v = rintf(v);
+  v = v < -32768.f ? -32768.f : (v > 32767.f ? 32767.f : v);
+  return (int)v;
+}
+
+__global__ __launch_bounds__(256) void activity_cells_kernel(const float* __restrict__ wav, long row_stride, int step, int phases,
+                                                             long N, long L, long tiles, long long* __restrict__ cells) {
+  __shared__ unsigned sq[kActivityTileFrames];
+  const int tid = threadIdx.x;
+  const long row = (long)blockIdx.x / tiles, tile = (long)blockIdx.x - row * tiles;
+  const float* x = wav + row * row_stride;
+  // frame j reads inputs m - 1 and m, m = ceil(step j / phases), with weights d = phases m - step j and phases - d.  step j is kept
+  // as qf phases + rf and advanced by 256 frames at a time: one division per thread.
+  const long inc = 256L * step, inc_q = inc / phases, inc_r = inc - inc_q * phases;
+  long j = tile * kActivityTileFrames + tid;
+  long qf = (long)step * j / phases, rf = (long)step * j - qf * phases;
+  for (int r = tid; r < kActivityTileFrames; r += 256, j += 256) {
+    unsigned v = 0;
+    if (j < N) {   // m <= samples - 1 for every j < N = floor(phases (samples - 1) / step) + 1
+      const long m = qf + (rf > 0 ? 1 : 0);
+      const int d = rf > 0 ? (int)(phases - rf) : 0;
+      const int a = d > 0 ? activity_quantise(x[m - 1]) : 0;   // (d > 0 implies m >= 1; x[-1] = 0 carries the weight 0 anyway)
+      const int b = activity_quantise(x[m]);
+      // trunc(65536 w / phases) >> 16 = floor(w / phases) for phases <= 65536: with w = q phases + t (truncated), the part below 2^16
+      // is trunc(65536 t / phases), which is zero only for t = 0 and has the sign of w.  |w| <= 32768 phases < 2^31.
+      const int w = a * d + b * (phases - d);
+      int y = w / phases;
+      if (w - y * phases < 0) --y;
+      v = (unsigned)(y * y);
+    }
+    sq[r] = v;
+    qf += inc_q;
+    rf += inc_r;
+    if (rf >= phases) {
+      rf -= phases;
+      ++qf;
+    }
+  }
+  __syncthreads();
+  if (tid < kActivityTileCells) {
+    const long c = tile * kActivityTileCells + tid;
+    if (c < L) {
+      long long s = 0;
+      for (int k = 0; k < kActivityCellFrames; ++k) s += sq[tid * kActivityCellFrames + k];
+      cells[row * L + c] = s;
+    }
+  }
+}
+
+__device__ __forceinline__ int activity_isqrt(long long v) {
+  long long r = (long long)sqrt((double)v);
+  while (r * r > v) --r;
+  while ((r + 1) * (r + 1) <= v) ++r;
+  return (int)r;
+}
+
+// what the one walking thread carries: pydub's detect_silence / detect_nonsilent state and the sums of compute_iou_recall_precision
+struct ActivityWalk {
+  const double* ref;
+  int n_ref;
+  int* spans;
+  int max_spans;
+  int count = 0;            // nonsilent spans so far
+  int silent_ranges = 0;
+  bool have = false;        // a silent range is open
+  long current = 0, prev = 0, prev_end = 0, last_end = 0;
+  double total_hyp = 0.0, inter = 0.0;
+
+  __device__ void emit(long a, long b) {   // one nonsilent span [a, b] ms
+#pragma clang fp contract(off)
+    if (spans && count < max_spans) {
+      spans[2 * count] = (int)a;
+      spans[2 * count + 1] = (int)b;
+    }
+    ++count;
+    const double h0 = (double)a / 1000.0, h1 = (double)b / 1000.0;   // = round(a / 1000, 3) for an integer a
+    total_hyp = total_hyp + (h1 - h0);
+    for (int r = 0; r < n_ref; ++r) {
+      const double r0 = ref[2 * r], r1 = ref[2 * r + 1];
+      const double lo = r0 > h0 ? r0 : h0, hi = r1 < h1 ? r1 : h1, v = hi - lo;
+      inter = inter + (v > 0.0 ? v : 0.0);
+    }
+  }
+  __device__ void close(long a, long b) {   // one silent range [a, b]: the nonsilent span in front of it, unless that is a leading [0, 0]
+    if (!(silent_ranges == 0 && a == 0)) emit(prev_end, a);
+    prev_end = b;
+    last_end = b;
+    ++silent_ranges;
+  }
+  __device__ void silent_start(long pos) {
+    if (!have) {
+      have = true;
+      current = pos;
+    } else if (pos != prev + kActivitySeekMs && pos > prev + kActivityWindowMs) {
+      close(current, prev + kActivityWindowMs);
+      current = pos;
+    }
+    prev = pos;
+  }
+  __device__ void finish(long L) {
+    if (!have) {
+      emit(0, L);
+      return;
+    }
+    close(current, prev + kActivityWindowMs);
+    if (last_end != L) emit(prev_end, L);
+  }
+  __device__ float score(int metric) const {
+#pragma clang fp contract(off)
+    double total_ref = 0.0, sum = total_hyp;   // the union's sum runs over the hypothesis spans, then the reference spans
+    for (int r = 0; r < n_ref; ++r) {
+      const double len = ref[2 * r + 1] - ref[2 * r];
+      total_ref = total_ref + len;
+      sum = sum + len;
+    }
+    const double uni = sum - inter;
+    const double den = metric == 0 ? uni : (metric == 1 ? total_ref : total_hyp);
+    return n_ref > 0 && den > 0.0 ? (float)(inter / den) : 0.f;
+  }
+};
+
+// the window starts range(0, last + 1, 10) are "regular": start 10 s sums the 25 decacells D[s .. s + 24], D[k] = cells[10 k .. 10 k + 9].
+// They pass through LDS kActivityStartChunk at a time, once for the peak and once for the flags (a clip of up to 20.2 s is one chunk
+// and is loaded once).  The start `last` itself, when it is no multiple of 10, sums its 250 cells on its own.
+__global__ __launch_bounds__(256) void activity_score_kernel(const long long* __restrict__ cells, long L, const int* __restrict__ table,
+                                                             const double* __restrict__ ref, int n_ref, int metric,
+                                                             float* __restrict__ scores, int* __restrict__ spans, int max_spans,
+                                                             int* __restrict__ span_count, int* __restrict__ peak_out) {
+  __shared__ long long deca[kActivityStartChunk + kActivityDeca - 1];
+  __shared__ long long part[256];
+  __shared__ int red[256];
+  __shared__ unsigned long long flagw[kActivityStartChunk / 8];
+  constexpr int kWindowFrames = kActivityWindowMs * kActivityCellFrames;
+  const int tid = threadIdx.x;
+  const long row = blockIdx.x;
+  const long long* P = cells + row * L;
+  ActivityWalk walk;
+  walk.ref = ref;
+  walk.n_ref = ref ? n_ref : 0;
+  walk.spans = spans ? spans + row * 2L * max_spans : nullptr;
+  walk.max_spans = max_spans;
+  int peak = 0;
+  if (L < kActivityWindowMs) {   // (uniform) shorter than one window: all of it is nonsilent
+    if (tid == 0) walk.emit(0, L);
+  } else {
+    const long last = L - kActivityWindowMs;
+    const long regular = last / kActivitySeekMs + 1;
+    const bool odd_last = last % kActivitySeekMs != 0;
+    // the decacells of the regular starts [s0, s0 + n): D[s0 .. s0 + n + 24); the last cell read is 10 (last / 10) + 249 <= L - 1
+    auto load = [&](long s0, int n) {
+      for (int k = tid; k < n + kActivityDeca - 1; k += 256) {
+        const long long* c = P + (s0 + k) * kActivitySeekMs;
+        long long d = 0;
+        for (int e = 0; e < kActivitySeekMs; ++e) d += c[e];
+        deca[k] = d;
+      }
+      __syncthreads();
+    };
+    auto window = [&](int s) {   // S(10 (s0 + s)): the sum of y^2 over the 6 000 frames of that window
+      long long S = 0;
+      for (int e = 0; e < kActivityDeca; ++e) S += deca[s + e];
+      return S;
+    };
+    long loaded = -1;
+    int mx = 0;
+    for (long s0 = 0; s0 < regular; s0 += kActivityStartChunk) {
+      const int n = regular - s0 < kActivityStartChunk ? (int)(regular - s0) : kActivityStartChunk;
+      if (loaded >= 0) __syncthreads();   // (every thread is done with the chunk before)
+      load(s0, n);
+      loaded = s0;
+      const int hop = kActivityPeakHopMs / kActivitySeekMs;
+      for (int s = tid * hop; s < n; s += 256 * hop) {   // (kActivityStartChunk is a multiple of hop: s0 + s is one too)
+        const int rms = activity_isqrt(window(s) / kWindowFrames);
+        mx = rms > mx ? rms : mx;
+      }
+    }
+    red[tid] = mx;
+    // the window that starts at `last`, where the regular starts do not reach it
+    part[tid] = odd_last && tid < kActivityWindowMs ? P[last + tid] : 0;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+      if (tid < h) {
+        red[tid] = red[tid + h] > red[tid] ? red[tid + h] : red[tid];
+        part[tid] += part[tid + h];
+      }
+      __syncthreads();
+    }
+    peak = red[0] > 32768 ? 32768 : red[0];
+    int T = table[peak];
+    T = T < 0 ? 0 : (T > 65535 ? 65535 : T);
+    const long long limit = (long long)(T + 1) * (T + 1) * kWindowFrames;   // rms <= thresh <=> S < limit
+    const bool last_silent = odd_last && part[0] < limit;
+    unsigned char* flags = (unsigned char*)flagw;
+    for (long s0 = 0; s0 < regular; s0 += kActivityStartChunk) {
+      const int n = regular - s0 < kActivityStartChunk ? (int)(regular - s0) : kActivityStartChunk;
+      if (loaded != s0) {
+        __syncthreads();
+        load(s0, n);
+        loaded = s0;
+      }
+      for (int s = tid; s < n; s += 256) flags[s] = window(s) < limit ? 1 : 0;
+      __syncthreads();
+      if (tid == 0) {
+        // eight starts at a time: a word of ones is one run (its first start may open or close a range, the others follow at + 10)
+        for (int s = 0; s < n; s += 8) {
+          const unsigned long long w = flagw[s >> 3];
+          const long pos = (s0 + s) * kActivitySeekMs;
+          if (s + 8 <= n && w == 0x0101010101010101ULL) {
+            walk.silent_start(pos);
+            walk.prev = pos + 7 * kActivitySeekMs;
+          } else if (s + 8 > n || w != 0) {
+            for (int e = 0; e < 8 && s + e < n; ++e)
+              if ((w >> (8 * e)) & 0xff) walk.silent_start(pos + e * kActivitySeekMs);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      if (last_silent) walk.silent_start(last);
+      walk.finish(L);
+    }
+  }
+  if (tid == 0) {
+    scores[row] = walk.score(metric);
+    if (span_count) span_count[row] = walk.count;
+    if (peak_out) peak_out[row] = peak;
+  }
+}
+
+hipError_t launch_activity(const float* wav, int rows, long row_stride, int step, int phases, long N, long L, const int* table,
+                           const double* ref_spans, int n_ref, int metric, long long* cells, float* scores, int* spans,
+                           int max_spans, int* span_count, int* peak, hipStream_t st) {
+  const long tiles = (L + kActivityTileCells - 1) / kActivityTileCells;
+  if (tiles * rows > 0x7fffffffL) return hipErrorInvalidValue;
+  if (tiles > 0)
+    hipLaunchKernelGGL(activity_cells_kernel, dim3((unsigned)(tiles * rows)), dim3(256), 0, st, wav, row_stride, step, phases, N, L,
+                       tiles, cells);
+  hipLaunchKernelGGL(activity_score_kernel, dim3((unsigned)rows), dim3(256), 0, st, cells, L, table, ref_spans, n_ref, metric, scores,
+                     spans, max_spans, span_count, peak);
+  return hipGetLastError();
+}
+
 // SAMAUDIO_OPT_SENTINEL (engine.hip): largest magnitude and number of non-finite values of a 16-bit (or fp32) tensor [rows, cols]
 // with row pitch ld, folded into a per-class slot {float absmax, float nonfinite count} - two launches on the launch stream, no
 // atomics (partials per workgroup, then one workgroup folds them into the slot; launches of a stream are ordered).  A debugging /

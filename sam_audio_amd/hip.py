@@ -157,6 +157,7 @@ DBG_ROLES_NONE, DBG_ROLES_PROD0, DBG_ROLES_PROD2 = 1, 2, 3
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1, 2   # samaudio.h SAMAUDIO_RESIZE_*
 RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR, "bicubic": RESIZE_BICUBIC}
 PCM_S16, PCM_F32 = 0, 1   # samaudio.h SAMAUDIO_PCM_*
+ACTIVITY_METRICS = {"iou": 0, "recall": 1, "precision": 2}   # samaudio.h samaudio_op_activity's metric
 
 ERR_ARG, ERR_WEIGHT, ERR_WORKSPACE, ERR_HIP, ERR_STATE = -1, -2, -3, -4, -5
 
@@ -369,6 +370,11 @@ _PROTOS = {
     "samaudio_resample_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "samaudio_op_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "samaudio_activity_length_ms": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "samaudio_activity_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "samaudio_op_activity": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -899,8 +899,14 @@ class SAMAudio:
             return scores.argmax(dim=1)
         if cand > 1 and self.text_ranker is not None:
             input_audio = [audio[:, : int(size)].expand(cand, -1) for audio, size in zip(batch.audios, sizes)]
+            more = {}
+            if getattr(self.text_ranker, "needs_spans", False):   # (ranking.SoundActivityRanker; after predict_spans the
+                if batch.anchors is None:                          # predicted spans are batch.anchors already)
+                    raise ValueError("the attached text ranker scores candidates against the prompt's spans: give the processor "
+                                     "anchors= or call separate(predict_spans=True) with a span predictor attached")
+                more["spans"] = batch.anchors
             scores = self.text_ranker(extracted_audio=target_wavs, input_audio=input_audio,
-                                      descriptions=batch.descriptions, sample_rate=sr)
+                                      descriptions=batch.descriptions, sample_rate=sr, **more)
             return scores.argmax(dim=1)
         return torch.zeros(B, dtype=torch.long, device=self.device)
 

@@ -1,7 +1,8 @@
 """Rerankers for `separate(reranking_candidates > 1)` - the reference's `sam_audio.ranking` surface
 (reference sam_audio/ranking/ranker.py:9-36, ranking/judge.py:11-42, ranking/__init__.py:15-30) for the rows this build
-covers: the Judge and ensembles of rankers.  CLAP / ImageBind rankers wrap third-party
-models that are not part of this build's environment: their configs are reported, not silently ignored.
+covers: the Judge, the sound-activity ranker (ranking/sound_activity.py)
+and ensembles of rankers.  CLAP / ImageBind rankers wrap third-party models that are not part of this build's environment: their
+configs are reported, not silently ignored.
 """
 from __future__ import annotations
 
@@ -9,7 +10,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from .config import JudgeRankerConfig
+from .config import JudgeRankerConfig, SoundActivityRankerConfig
 
 
 class Ranker:
@@ -28,6 +29,11 @@ class EnsembleRanker(Ranker):
     def __init__(self, rankers: Sequence[Ranker], weights: Sequence[float]):
         assert len(rankers) == len(weights)
         self.rankers, self.weights = list(rankers), list(weights)
+
+    @property
+    def needs_spans(self) -> bool:
+        """separate() hands `spans=` over when any member asks for them (the others take them as **kwargs)"""
+        return any(getattr(r, "needs_spans", False) for r in self.rankers)
 
     def forward(self, **kwargs) -> torch.Tensor:
         result = None
@@ -72,6 +78,43 @@ class JudgeRanker(Ranker):
             candidates=ncandidates, padding_mask=processed["padding_mask"]).view(bsz, ncandidates)
 
 
+class SoundActivityRanker(Ranker):
+    """reference ranking/sound_activity.py:96-129: how well a candidate's nonsilent spans (pydub's silence detection at 24 kHz)
+    overlap the prompt's spans - iou, recall or precision.  No weights.  The work is two HIP launches per clip on the
+    [candidates, n] view (sam_audio_amd/activity.py), nothing is read back.
+
+    Departure from the reference (like quirk Q13, the reference class cannot do what it is for): its forward hands `wav`
+    [candidates, n] to the encoder as the CHANNELS of one clip, returns one score per clip instead of [batch, candidates], and
+    SAMAudio.separate never passes it `spans` (dead code).  This class keeps its algorithm and its config and
+    gives it the `Ranker` contract: every candidate is scored as a mono clip, the result is [batch, candidates] (higher = better),
+    and `SAMAudio.separate` passes `spans=batch.anchors` to rankers with `needs_spans`.  Kept from the reference: the reference
+    spans are (start, end) of EVERY anchor of the clip, whatever its token ("+" or "-"), and overlapping ones count twice.
+    The statement it is held to is tests/activity_ref.py: pinned to CPython's audioop, unpinned vs pydub / torchcodec."""
+
+    needs_spans = True
+
+    def __init__(self, config: Optional[SoundActivityRankerConfig] = None):
+        self.config = config if config is not None else SoundActivityRankerConfig()
+
+    @torch.inference_mode()
+    def forward(self, extracted_audio: List[torch.Tensor], spans, sample_rate: int = 48_000, **kwargs) -> torch.Tensor:
+        from . import activity
+        if len(spans) != len(extracted_audio):
+            raise ValueError(f"{len(extracted_audio)} clips but spans for {len(spans)}")
+        device = extracted_audio[0].device
+        bsz, ncandidates = len(extracted_audio), len(extracted_audio[0])
+        # every clip's reference spans in one small float64 upload; a clip's rows of it are a view
+        flat = [[float(a[1]), float(a[2])] for clip in spans for a in clip]
+        ref = torch.tensor(flat, dtype=torch.float64).reshape(len(flat), 2).to(device) if flat else None
+        scores = torch.empty(bsz, ncandidates, dtype=torch.float32, device=device)
+        first = 0
+        for b, (wav, clip) in enumerate(zip(extracted_audio, spans)):
+            activity.activity(wav, sample_rate, ref[first: first + len(clip)] if clip else None, self.config.metric,
+                              self.config.sil_threshold, self.config.threshold_mode, out=scores[b])
+            first += len(clip)
+        return scores
+
+
 def create_ranker(config, **kwargs) -> Optional[Ranker]:
     """reference ranking/__init__.py:15-30."""
     if config is None:
@@ -80,6 +123,8 @@ def create_ranker(config, **kwargs) -> Optional[Ranker]:
         return config
     if isinstance(config, JudgeRankerConfig):
         return JudgeRanker(config, **kwargs)
+    if isinstance(config, SoundActivityRankerConfig):
+        return SoundActivityRanker(config)
     kind = config.get("kind") if isinstance(config, dict) else getattr(config, "kind", None)
     if kind == "ensemble":
         pairs = config["rankers"].values() if isinstance(config, dict) else config.rankers.values()
