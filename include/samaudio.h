@@ -586,6 +586,17 @@ int samaudio_profile_end(samaudio_ctx* ctx, samaudio_kernel_stat* out, int capac
 /* C[b] = epilogue(A(b) @ W^T): generalised GEMM / implicit conv, see sam_audio_amd/csrc/common.h GemmParams.
  * `params` points to a HOST copy of sa::GemmParams (size checked against params_bytes). */
 int samaudio_op_gemm(const void* params_host, size_t params_bytes, int precision, samaudio_stream stream);
+/* One DAC-VAE convolution the way an fp32 context with SAMAUDIO_OPT_X3_CLASSES bit CODEC runs it (csrc/host.h codec_x3_* - the
+ * functions the engine itself launches by).  `params_host`: the convolution's plain fp32 GemmParams, as for samaudio_op_gemm (fp32 A,
+ * fp32 outputs, W = the fp32 weight).  `w_twin`: the weight's registered twin - SAMAUDIO_CODEC_TWIN_FLY: "<name>.fly" (weights.py
+ * fly16_weight), SAMAUDIO_CODEC_TWIN_X3: "<name>.x3" with Cin-blocks of `cin` channels (weights.py convert_codec_x3), _NONE: no twin.
+ * With an x3 twin, `scratch` (>= 3 x 2 bytes per element of the halo buffers the launch reads) and a launch that qualifies, it runs
+ * as split3 + ONE 16-bit launch over K' = 3K + the elementwise activation pass; otherwise on operands split in registers.  `path`
+ * (may be null) receives the SAMAUDIO_CODEC_PATH_* taken. */
+enum { SAMAUDIO_CODEC_TWIN_NONE = 0, SAMAUDIO_CODEC_TWIN_FLY = 1, SAMAUDIO_CODEC_TWIN_X3 = 2 };
+enum { SAMAUDIO_CODEC_PATH_FLY = 0, SAMAUDIO_CODEC_PATH_X3_BLOCK = 1, SAMAUDIO_CODEC_PATH_X3 = 2 };
+int samaudio_op_codec_conv(const void* params_host, size_t params_bytes, const void* w_twin, int twin_kind, int cin, void* scratch,
+                           size_t scratch_bytes, int* path, samaudio_stream stream);
 /* One DAC residual unit as ONE kernel: the k7 convolution `conv7_params` and the k1 convolution `conv1_params` that reads
  * its output (two host GemmParams as for samaudio_op_gemm, 16-bit operands only).  The intermediate activation
  * (conv7_params.out_act == conv1_params.A) is never written; conv1_params.out_act must not be conv7_params.A.  Bitwise

@@ -178,6 +178,38 @@ int samaudio_op_gemm(const void* params_host, size_t params_bytes, int precision
   return hip_ret(sa::launch_gemm(p, bf16, (hipStream_t)stream), "gemm");
 }
 
+int samaudio_op_codec_conv(const void* params_host, size_t params_bytes, const void* w_twin, int twin_kind, int cin, void* scratch,
+                           size_t scratch_bytes, int* path, samaudio_stream stream) {
+  if (!params_host || params_bytes != sizeof(sa::GemmParams)) return bad("samaudio_op_codec_conv: GemmParams size mismatch");
+  if (twin_kind < SAMAUDIO_CODEC_TWIN_NONE || twin_kind > SAMAUDIO_CODEC_TWIN_X3 || (twin_kind != SAMAUDIO_CODEC_TWIN_NONE && !w_twin))
+    return bad("samaudio_op_codec_conv: twin_kind / w_twin");
+  sa::GemmParams p_in;
+  std::memcpy(&p_in, params_host, sizeof(p_in));
+  hipStream_t st = (hipStream_t)stream;
+  // what Engine::codec_gemm does in an fp32 context with class CODEC on compensated operands, by the same functions of host.h
+  const bool wide = twin_kind == SAMAUDIO_CODEC_TWIN_X3 && scratch && sa::codec_x3_eligible(p_in, cin, scratch_bytes);
+  if (!wide) {
+    sa::GemmParams p = sa::gemm_launch_params(p_in, 1, true, false, -1);
+    sa::codec_fly_operands(p, twin_kind == SAMAUDIO_CODEC_TWIN_FLY ? w_twin : nullptr);
+    if (path) *path = SAMAUDIO_CODEC_PATH_FLY;
+    if (const char* why = sa::gemm_check(p, false)) return bad(why);
+    return hip_ret(sa::launch_gemm(p, false, st), "codec_conv");
+  }
+  const bool whole_k = sa::codec_x3_whole_k(p_in, cin);
+  if (path) *path = whole_k ? SAMAUDIO_CODEC_PATH_X3 : SAMAUDIO_CODEC_PATH_X3_BLOCK;
+  if (hipError_t e = sa::launch_split3((const float*)p_in.A, cin, scratch, sa::codec_x3_split_rows(p_in, cin), cin, st); e != hipSuccess)
+    return hip_ret(e, "codec_conv: split3");
+  const sa::GemmParams p = sa::gemm_launch_params(sa::codec_x3_launch(p_in, scratch, w_twin), 1, true, false,
+                                                  whole_k ? SAMAUDIO_CLS_CODEC : -1);
+  if (const char* why = sa::gemm_check(p, true)) return bad(why);
+  if (hipError_t e = sa::launch_gemm(p, true, st); e != hipSuccess) return hip_ret(e, "codec_conv: gemm");
+  const sa::CodecActPass a = sa::codec_x3_act(p_in);
+  if (!a.run) return SAMAUDIO_OK;
+  if (!a.aligned) return bad("samaudio_op_codec_conv: window start is not a whole channel row");
+  return hip_ret(sa::launch_act_flat(a.in, a.in_bstride, a.out, a.out_bstride, a.items, a.count, a.chan, a.act, a.alpha, st),
+                 "codec_conv: act");
+}
+
 int samaudio_op_resunit(const void* conv7_params_host, const void* conv1_params_host, size_t params_bytes,
                         samaudio_stream stream) {
   if (!conv7_params_host || !conv1_params_host || params_bytes != sizeof(sa::GemmParams))

@@ -666,16 +666,10 @@ static int cls_slot(int cls) {   // the sentinel slot of a class
 
 // the tag and flags a launch of gemm() runs with (the OUT_SPLIT3 dry run of eval_field asks gemm_check about them)
 GemmParams Engine::launch_params(const GemmParams& p_in, int cls, GemmKind kind) const {
-  GemmParams p = p_in;
-  p.tag = phase_ == Phase::Codec ? 1 : 0;  // codec launches run under their own kernel symbols
-  // from the caller: alt-format output, K-tile-major W, split-form output; from the context: the tail split (gemm.hip gemm_tail_split) and
-  // the classes with operands in the alt format (SAMAUDIO_OPT_ALT16_CLASSES, mixed mode)
-  p.flags = (p_in.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split_ ? 0 : GEMM_FLAG_NO_TAIL_SPLIT) |
-            (alt16(cls) && kind != GemmKind::F32 ? GEMM_FLAG_OPND_ALT : 0);
-  // an x3 launch on K-concatenated split operands shares operand tiles wherever it qualifies (host.h x3_share); X3Block (the
-  // convolutions: every Cin-block of K' is its own [hi | lo | hi]) never does
-  if (kind == GemmKind::X3) p = x3_share(p, cls);
-  return p;
+  // codec launches run under their own kernel symbols; an x3 launch on K-concatenated split operands shares operand tiles wherever it
+  // qualifies (host.h x3_share); X3Block (the convolutions: every Cin-block of K' is its own [hi | lo | hi]) never does
+  return gemm_launch_params(p_in, phase_ == Phase::Codec ? 1 : 0, tail_split_, alt16(cls) && kind != GemmKind::F32,
+                            kind == GemmKind::X3 ? cls : -1);
 }
 
 Status Engine::gemm(const GemmParams& p, hipStream_t st, double alg_flops, int cls, GemmKind kind) {
@@ -698,16 +692,10 @@ Status Engine::scan_out(const GemmParams& p, int cls, GemmKind kind, hipStream_t
 }
 
 const Engine::X3CodecW* Engine::codec_x3_twin(const GemmParams& p) const {
-  if (p.N < 256 || !x3_codec_scratch_ || !x3(SAMAUDIO_CLS_CODEC)) return nullptr;
+  if (!x3_codec_scratch_ || !x3(SAMAUDIO_CLS_CODEC)) return nullptr;
   const auto it = x3_codec_.find(p.W);
   if (it == x3_codec_.end()) return nullptr;
-  const int c = it->second.cin;
-  const bool both = p.out_f32 && p.out_act;
-  const bool flat = !p.c_ld_rel ? (p.out_f32 ? p.f32_ld == p.N : p.act_ld == p.N) : true;
-  const bool ok = p.a_bstride > 0 && !p.w_bstride && !p.swiglu && !p.gate && !(p.kc % c) && !(p.lda % c) && !(p.a_off % c) &&
-                  !(p.a_bstride % c) && !(p.tap_stride % c) && !(p.K % c) && !((3L * p.K) % 64) && flat && (!both || !p.f32_act) &&
-                  (size_t)p.nbatch * (p.a_bstride / c) * 3 * c * 2 <= x3_codec_scratch_bytes_;
-  return ok ? &it->second : nullptr;
+  return codec_x3_eligible(p, it->second.cin, x3_codec_scratch_bytes_) ? &it->second : nullptr;
 }
 
 Status Engine::codec_gemm(const GemmParams& p_in, hipStream_t st, double alg_flops) {
@@ -716,9 +704,8 @@ Status Engine::codec_gemm(const GemmParams& p_in, hipStream_t st, double alg_flo
   } else {
     GemmParams p = launch_params(p_in, SAMAUDIO_CLS_CODEC, GemmKind::Native);
     if (x3(SAMAUDIO_CLS_CODEC)) {   // (fp32 contexts): the convolution multiplies on split operands, split in registers (gemm.hip)
-      p.flags |= GEMM_FLAG_X3_FLY;
-      const auto it = p.w_bstride ? fly_codec_.end() : fly_codec_.find(p.W);
-      if (it != fly_codec_.end()) { p.W = it->second; p.flags |= GEMM_FLAG_W_FLY16; }
+      const auto it = fly_codec_.find(p.W);
+      codec_fly_operands(p, it != fly_codec_.end() ? it->second : nullptr);
     }
     SA_TRY(launch(p, st, alg_flops, SAMAUDIO_CLS_CODEC, GemmKind::Native));
   }
@@ -792,29 +779,18 @@ Status Engine::linear(GemmParams p, const LinW& w, int cls, hipStream_t st, cons
 }
 
 Status Engine::gemm_codec_x3(const GemmParams& p_in, const X3CodecW& w, hipStream_t st, double alg_flops) {
+  // the geometry - the split, the restated launch, X3 / X3Block, the activation pass - is host.h's (codec_x3_*): here the launches
   const int c = w.cin;
-  const long rows = (long)p_in.nbatch * (p_in.a_bstride / c);   // every row of the halo buffers the launch reads (halo rows are zeros)
+  const long rows = codec_x3_split_rows(p_in, c);
   SA_TRY(op("split3", (double)rows * c * (4 + 6), 0, st, [&] { return launch_split3((const float*)p_in.A, c, x3_codec_scratch_, rows, c, st); }));
-  GemmParams p = p_in;
-  x3_block_operands(p, x3_codec_scratch_, w.w, false);   // ("one block": the whole K' is one [lo | hi | hi] x [W_hi | W_lo | W_hi], below)
-  // the 16-bit launch writes the RAW fp32 result (into the raw stream, or - a launch with an activated output only - into that
-  // buffer); the activation follows as an elementwise pass with the fp32 kernel's own expressions
-  const int act = p_in.act;
-  float* const raw = p_in.out_f32 ? p_in.out_f32 : (float*)p_in.out_act;
-  const long raw_off = p_in.out_f32 ? p_in.f32_off : p_in.act_off, raw_bs = p_in.out_f32 ? p_in.f32_bstride : p_in.act_bstride;
-  if (!p_in.out_f32) { p.out_f32 = raw; p.f32_ld = p_in.act_ld; p.f32_bstride = p_in.act_bstride; p.f32_off = p_in.act_off; }
-  p.out_act = nullptr; p.act_ld = p.act_bstride = p.act_off = 0; p.act = ACT_NONE; p.f32_act = 0;
   const double flops = alg_flops >= 0 ? alg_flops : 2.0 * p_in.M * (double)p_in.N * p_in.K * p_in.nbatch;
-  // one block: [lo | hi | hi] x [W_hi | W_lo | W_hi] over the whole K'
-  SA_TRY(gemm(p, st, flops, SAMAUDIO_CLS_CODEC, p_in.K == c && p_in.kc == c ? GemmKind::X3 : GemmKind::X3Block));
-  if (!p_in.out_act || (act == ACT_NONE && !p_in.out_f32)) return Status{};
-  // region the launch wrote, per item: [c_lo, c_hi) of the windowed (transposed) convolutions, else M rows of N
-  const long start = p_in.c_ld_rel ? p_in.c_lo : 0, count = p_in.c_ld_rel ? p_in.c_hi - p_in.c_lo : (long)p_in.M * p_in.N;
-  const int chan = p_in.chan_mod ? p_in.chan_mod : p_in.N;
-  if (start % chan) return fail(SAMAUDIO_ERR_ARG, "gemm_codec_x3: window start is not a whole channel row");
-  return op("codec_act", (double)count * p_in.nbatch * 8, 0, st, [&] {
-    return launch_act_flat(raw + raw_off + start, raw_bs, (float*)p_in.out_act + p_in.act_off + start, p_in.act_bstride, p_in.nbatch, count,
-                           chan, act, p_in.act_alpha, st);
+  SA_TRY(gemm(codec_x3_launch(p_in, x3_codec_scratch_, w.w), st, flops, SAMAUDIO_CLS_CODEC,
+              codec_x3_whole_k(p_in, c) ? GemmKind::X3 : GemmKind::X3Block));
+  const CodecActPass a = codec_x3_act(p_in);
+  if (!a.run) return Status{};
+  if (!a.aligned) return fail(SAMAUDIO_ERR_ARG, "gemm_codec_x3: window start is not a whole channel row");
+  return op("codec_act", (double)a.count * a.items * 8, 0, st, [&] {
+    return launch_act_flat(a.in, a.in_bstride, a.out, a.out_bstride, a.items, a.count, a.chan, a.act, a.alpha, st);
   });
 }
 

@@ -202,6 +202,77 @@ inline Status x3_linear(GemmParams p, const LinW& w, int cls, bool on, bool bf16
   return run_gemm(x3_share(p, cls), true, gemm_who, st);
 }
 
+// The tag / flags a context launches `p_in` with.  From the caller: alt-format output, K-tile-major W, split-form output; from the
+// context: the kernel symbols (`tag` 1: the codec's), the tail split (gemm.hip gemm_tail_split), operands in the alt format.
+// `share_cls` >= 0: an x3 launch on operands split over the whole K - it shares operand tiles wherever it qualifies (x3_share)
+inline GemmParams gemm_launch_params(const GemmParams& p_in, int tag, bool tail_split, bool opnd_alt, int share_cls) {
+  GemmParams p = p_in;
+  p.tag = tag;
+  p.flags = (p_in.flags & (GEMM_FLAG_OUT_ALT | GEMM_FLAG_W_KTM | GEMM_FLAG_OUT_SPLIT3)) | (tail_split ? 0 : GEMM_FLAG_NO_TAIL_SPLIT) |
+            (opnd_alt ? GEMM_FLAG_OPND_ALT : 0);
+  return share_cls >= 0 ? x3_share(p, share_cls) : p;
+}
+
+// ---- SAMAUDIO_OPT_X3_CLASSES bit CODEC: the geometry of one DAC-VAE convolution of an fp32 context ------------------------------
+// The engine (codec_gemm / gemm_codec_x3) and the test hook (api.hip samaudio_op_codec_conv) both launch by these functions: there
+// is no second statement of the strides anywhere.
+//
+// The narrow form: the fp32 kernel splits its operands in registers (GEMM_FLAG_X3_FLY); `fly` = the weight's "<name>.fly" twin
+// (already split, GEMM_FLAG_W_FLY16) or null.  `p` = the launch as launch_params left it
+inline void codec_fly_operands(GemmParams& p, const void* fly) {
+  p.flags |= GEMM_FLAG_X3_FLY;
+  if (fly && !p.w_bstride) { p.W = fly; p.flags |= GEMM_FLAG_W_FLY16; }
+}
+// The wide form (N >= 256, a "<name>.x3" twin with Cin-blocks of `c` channels): can `p` run on the buffer split row by row into a
+// scratch of `scratch_bytes`?  Every K-axis quantity must be whole input rows; the activation pass (codec_x3_act) walks ONE contiguous
+// region per item with the raw stream's geometry, so both outputs must be dense rows of N (a windowed launch: identical geometry)
+inline bool codec_x3_eligible(const GemmParams& p, int c, size_t scratch_bytes) {
+  if (p.N < 256 || c <= 0) return false;
+  const bool both = p.out_f32 && p.out_act;
+  const bool flat = (!p.out_f32 || p.f32_ld == p.N) && (!p.out_act || p.act_ld == p.N) && (!p.c_ld_rel || p.c_ld_rel == p.N);
+  return p.a_bstride > 0 && !p.w_bstride && !p.swiglu && !p.gate && !(p.kc % c) && !(p.lda % c) && !(p.a_off % c) &&
+         !(p.a_bstride % c) && !(p.tap_stride % c) && !(p.K % c) && !((3L * p.K) % 64) && flat && (!both || !p.f32_act) &&
+         (size_t)p.nbatch * (p.a_bstride / c) * 3 * c * 2 <= scratch_bytes;
+}
+// every row of the halo buffers the launch reads (halo rows are zeros): what launch_split3 splits into the scratch, `c` wide
+inline long codec_x3_split_rows(const GemmParams& p, int c) { return (long)p.nbatch * (p.a_bstride / c); }
+// whole-K (a k1 convolution on one block: operands split over the whole K, may share operand tiles) or per input block (a plain walk)
+inline bool codec_x3_whole_k(const GemmParams& p, int c) { return p.K == c && p.kc == c; }
+// The 16-bit launch over K' = 3K on the split buffer `a3` and the twin `w3`.  It writes the RAW fp32 result - into the raw stream, or
+// (a launch with an activated output only) into that buffer; the activation follows as an elementwise pass (codec_x3_act)
+inline GemmParams codec_x3_launch(const GemmParams& p_in, const void* a3, const void* w3) {
+  GemmParams p = p_in;
+  x3_block_operands(p, a3, w3, false);   // ("one block": the whole K' is one [lo | hi | hi] x [W_hi | W_lo | W_hi])
+  if (!p_in.out_f32) { p.out_f32 = (float*)p_in.out_act; p.f32_ld = p_in.act_ld; p.f32_bstride = p_in.act_bstride; p.f32_off = p_in.act_off; }
+  p.out_act = nullptr; p.act_ld = p.act_bstride = p.act_off = 0; p.act = ACT_NONE; p.f32_act = 0;
+  return p;
+}
+// The activation pass behind codec_x3_launch: act(raw) over the region the launch wrote, per item - [c_lo, c_hi) of the windowed
+// (transposed) convolutions, else M rows of N.  run = false: the launch needs none; aligned = false: the window does not start on a
+// whole channel row (refused - act_flat_kernel takes its channel from the index inside the region)
+struct CodecActPass {
+  bool run, aligned;
+  const float* in; long in_bstride;
+  float* out; long out_bstride;
+  int items; long count; int chan, act;
+  const float* alpha;
+};
+inline CodecActPass codec_x3_act(const GemmParams& p) {
+  CodecActPass a{};
+  a.run = p.out_act && !(p.act == ACT_NONE && !p.out_f32);
+  if (!a.run) return a;
+  const float* const raw = p.out_f32 ? p.out_f32 : (const float*)p.out_act;
+  const long raw_off = p.out_f32 ? p.f32_off : p.act_off;
+  const long start = p.c_ld_rel ? p.c_lo : 0;
+  a.count = p.c_ld_rel ? p.c_hi - p.c_lo : (long)p.M * p.N;
+  a.chan = p.chan_mod ? p.chan_mod : p.N;
+  a.aligned = start % a.chan == 0;
+  a.in = raw + raw_off + start; a.in_bstride = p.out_f32 ? p.f32_bstride : p.act_bstride;
+  a.out = (float*)p.out_act + p.act_off + start; a.out_bstride = p.act_bstride;
+  a.items = p.nbatch; a.act = p.act; a.alpha = p.act_alpha;
+  return a;
+}
+
 // Can the up-projection `up` (an x3 class's fp32 launch on the split operand a3, M rows) write the down-projection's split operand
 // [M, 3F] into `out3` itself?  The scratch holds it and gemm_check takes the launch that `finish` makes of it - the caller's own way
 // of launching (the engine: launch_params(.., GemmKind::X3); the towers: x3_share).  Otherwise the down-projection splits the fp32

@@ -159,6 +159,9 @@ RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR, "bicubic
 PCM_S16, PCM_F32 = 0, 1   # samaudio.h SAMAUDIO_PCM_*
 ACTIVITY_METRICS = {"iou": 0, "recall": 1, "precision": 2}   # samaudio.h samaudio_op_activity's metric
 
+CODEC_TWIN_NONE, CODEC_TWIN_FLY, CODEC_TWIN_X3 = 0, 1, 2       # samaudio.h samaudio_op_codec_conv's twin_kind ...
+CODEC_PATH_FLY, CODEC_PATH_X3_BLOCK, CODEC_PATH_X3 = 0, 1, 2    # ... and the path it reports
+
 ERR_ARG, ERR_WEIGHT, ERR_WORKSPACE, ERR_HIP, ERR_STATE = -1, -2, -3, -4, -5
 
 
@@ -295,6 +298,8 @@ _PROTOS = {
     "samaudio_debug_poison_lds": (C.c_int, [C.c_void_p]),
     "samaudio_profile_end": (C.c_int, [C.c_void_p, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),
     "samaudio_op_gemm": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "samaudio_op_codec_conv": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_int), C.c_void_p]),
     "samaudio_op_resunit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "samaudio_op_rmsnorm_mod": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                              C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
