@@ -230,6 +230,24 @@ int samaudio_ode_solve(samaudio_ctx* ctx, float* state, int method, const float*
 size_t samaudio_ode_stage_bytes(samaudio_ctx* ctx, int method, int rows, int frames);
 int samaudio_set_ode_stages(samaudio_ctx* ctx, void* stages, size_t bytes);
 
+/* Windowed solve of clips longer than one window (SAMAudio.separate(window_seconds=...)).  The prepared rows
+ * are windows of `frames` frames cut from longer clips with a stride of frames - overlap_frames; next_row_device [rows] i32 ON THE
+ * DEVICE names for every row the row that holds the clip's next window, or -1.  While a table is set, every field evaluation
+ * (samaudio_forward, every stage of every samaudio_ode_solve method) ends with one launch of window_blend_kernel on its output: for a
+ * row r with successor s, frame j < overlap_frames of the overlap becomes v = p + a_j (q - p), p = out[r, frames - overlap + j],
+ * q = out[s, j], a_j = (j + 1) / (overlap + 1), written to BOTH places - so rows whose overlapping frames start equal stay equal, bit
+ * for bit, through the whole solve.  Call it after samaudio_prepare / samaudio_prepare_latent: rows must be the prepared row count and
+ * 1 <= overlap_frames <= frames / 2 (SAMAUDIO_ERR_ARG otherwise; SAMAUDIO_ERR_STATE before any prepare).  The table is borrowed until
+ * it is replaced; its contents are the caller's responsibility (the host cannot read them without a blocking copy) - an entry outside
+ * [0, rows) or equal to its own index counts as -1, two rows naming the same successor is undefined.  next_row_device = NULL switches
+ * windows off, and so does every later samaudio_prepare / samaudio_prepare_latent: a stale table never meets a new batch.  A library
+ * built without the kernel (the CPU launcher emulation) answers SAMAUDIO_ERR_STATE. */
+int samaudio_set_windows(samaudio_ctx* ctx, const int32_t* next_row_device, int rows, int overlap_frames);
+/* kernel-level hook: the blend above on out [rows, frames, channels] f32 in place.  SAMAUDIO_ERR_ARG before any launch for a null
+ * pointer, rows < 1, frames < 2, overlap outside [1, frames / 2], channels % 4 != 0, out not aligned to 16 bytes. */
+int samaudio_op_window_blend(float* out, const int32_t* next_row, int rows, int frames, int overlap, int channels,
+                             samaudio_stream stream);
+
 /* DAC-VAE.  encode (codec.py:65-70): wav [items, samples] f32, samples % hop == 0 -> mean latent
  * [items, samples/hop, codec_dim] f32 (channels-last).  decode (codec.py:86-89):
  * latent [items, frames, codec_dim] f32 (channels-last) -> wav [items, frames*hop] f32. */

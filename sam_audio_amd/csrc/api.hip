@@ -115,6 +115,10 @@ int samaudio_set_ode_stages(samaudio_ctx* ctx, void* stages, size_t bytes) {
   return SA_ENTRY(ctx, "null context", ctx->engine->set_ode_stages(stages, bytes));
 }
 
+int samaudio_set_windows(samaudio_ctx* ctx, const int32_t* next_row_device, int rows, int overlap_frames) {
+  return SA_ENTRY(ctx, "null context", ctx->engine->set_windows(next_row_device, rows, overlap_frames));
+}
+
 int samaudio_codec_encode(samaudio_ctx* ctx, const float* wav, int items, int64_t samples, float* latent,
                           samaudio_stream stream) {
   return SA_ENTRY(ctx, "null context", ctx->engine->codec_encode(wav, items, samples, latent, (hipStream_t)stream));
@@ -423,6 +427,19 @@ int samaudio_op_activity(const float* wav, int rows, int64_t row_stride, int64_t
                                      n_ref, metric, (long long*)workspace, scores, spans, max_spans, span_count, peak,
                                      (hipStream_t)stream),
                  "activity");
+}
+
+int samaudio_op_window_blend(float* out, const int32_t* next_row, int rows, int frames, int overlap, int channels,
+                             samaudio_stream stream) {
+  if (!out || !next_row || rows < 1 || frames < 2) return bad("window_blend: null out / next_row, rows < 1 or frames < 2");
+  if (overlap < 1 || overlap > frames / 2) return bad("window_blend: overlap must be in [1, frames / 2]");
+  if (channels < 4 || channels % 4) return bad("window_blend: channels % 4 != 0");
+  if (((uintptr_t)out & 15) || ((uintptr_t)next_row & 3)) return bad("window_blend: out must be aligned to 16 bytes, next_row to 4");
+  if (!sa::launch_window_blend) {
+    g_err = "window_blend: not in this build of the library";
+    return SAMAUDIO_ERR_STATE;
+  }
+  return hip_ret(sa::launch_window_blend(out, next_row, rows, frames, overlap, channels, (hipStream_t)stream), "window_blend");
 }
 
 int samaudio_op_split3(const float* x, int64_t x_ld, void* out, int64_t rows, int k, samaudio_stream stream) {

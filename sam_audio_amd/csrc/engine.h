@@ -28,6 +28,9 @@ class Engine {
   struct RkTableau;   // engine.hip: rk4 / heun3
   size_t ode_stage_bytes(int method, int rows, int frames) const;
   Status set_ode_stages(void* p, size_t bytes);
+  // windowed solve (samaudio_set_windows): while a successor table is set, every field evaluation ends with window_blend_kernel on its
+  // output.  next_row: device i32 [rows], borrowed; null switches windows off, and so does every prepare
+  Status set_windows(const int32_t* next_row, int rows, int overlap);
   Status codec_encode(const float* wav, int items, int64_t samples, float* latent, hipStream_t st);
   // `pairs`: latent is the ODE state [items / 2, frames, 2 * codec_dim] - item 2b = the first codec_dim channels of row b (target),
   // 2b + 1 the second (residual): reference model.py:291-295 without the transposed copy
@@ -132,6 +135,8 @@ class Engine {
   Status solve_rk(float* y, const RkTableau& tab, const float* grid, int n_grid, hipStream_t st);   // ... of rk4 / heun3
   float* stages_ = nullptr;   // samaudio_set_ode_stages
   size_t stages_bytes_ = 0;
+  const int32_t* win_next_ = nullptr;   // samaudio_set_windows: the successor table of the prepared rows (null: no windows)
+  int win_overlap_ = 0;
   bool sentinel_on_ = false;   // SAMAUDIO_OPT_SENTINEL
   float* sentinel_dev_ = nullptr;   // [SAMAUDIO_SENTINEL_SLOTS][2] slots + [kSentinelPartials][2] partials (debug_device_alloc)
   // fold the scan of a tensor into `slot` (no-op unless the sentinel is on); fmt as launch_sentinel

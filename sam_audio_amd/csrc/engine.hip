@@ -907,6 +907,8 @@ static void with_res(GemmParams& p, const float* r, long ld) { p.res = r; p.res_
 Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float* text, const uint8_t* text_mask,
                        const float* video, const int64_t* anchor_ids, int n_ids, const int64_t* anchor_alignment,
                        const uint8_t* pad_mask, hipStream_t st, int cand, bool latent_feats) {
+  win_next_ = nullptr;   // a successor table (samaudio_set_windows) belongs to the rows it was set for: it never meets a new batch
+  win_overlap_ = 0;
   if (!dit_ready_) return fail(SAMAUDIO_ERR_STATE, "prepare: DiT weights not finalized");
   if (rows <= 0 || T <= 0 || !feats) return fail(SAMAUDIO_ERR_ARG, "prepare: bad shape");
   if (cand < 1 || rows % cand) return fail(SAMAUDIO_ERR_ARG, "prepare: rows must be a multiple of candidates");
@@ -1020,6 +1022,8 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
                           hipStream_t st) {
   if (!prepared_) return fail(SAMAUDIO_ERR_STATE, "forward: call samaudio_prepare first");
   if (nt != 1 && nt != rows_) return fail(SAMAUDIO_ERR_ARG, "forward: n_time must be 1 or rows");
+  if (win_next_ && !launch_window_blend)
+    return fail(SAMAUDIO_ERR_STATE, "forward: windows are set, but this build has no window_blend_kernel");
   const int D = cfg_.dim, F = cfg_.ffn_hidden, C2 = cfg_.latent_channels, H = cfg_.n_heads, T = frames_,
             Lt = text_len_, Tp = frames_pad_, rows = rows_;
   const long M = (long)rows * T, Mt = (long)rows * Lt;
@@ -1331,7 +1335,28 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
     out_f32(p, out, C2);
     SA_TRY(gemm(p, st, -1.0, SAMAUDIO_CLS_OUT, f32_if(f)));
   }
+  // windowed solve: the overlapping frames of neighbouring window rows leave every evaluation with the same value (out = res + alpha *
+  // field is linear in the field and res is equal in both rows, so blending `out` blends the field: DESIGN.md section 10.7).  Bytes: two
+  // reads and two writes per pair if every row had a successor (the table lives on the device: an upper bound)
+  if (win_next_)
+    SA_TRY(op("window_blend", 16.0 * rows * win_overlap_ * C2, 3.0 * rows * win_overlap_ * C2, st,
+              [&] { return launch_window_blend(out, win_next_, rows, T, win_overlap_, C2, st); }));
   hash_stage("field out", out, (size_t)M * C2 * 4, st);
+  return Status{};
+}
+
+Status Engine::set_windows(const int32_t* next_row, int rows, int overlap) {
+  win_next_ = nullptr;
+  win_overlap_ = 0;
+  if (!next_row) return Status{};
+  if (!prepared_) return fail(SAMAUDIO_ERR_STATE, "set_windows: call samaudio_prepare first");
+  if (rows != rows_) return fail(SAMAUDIO_ERR_ARG, "set_windows: rows is not the prepared row count");
+  if (overlap < 1 || overlap > frames_ / 2) return fail(SAMAUDIO_ERR_ARG, "set_windows: overlap must be in [1, frames / 2]");
+  if (cfg_.latent_channels % 4) return fail(SAMAUDIO_ERR_ARG, "set_windows: latent_channels % 4 != 0");
+  if (reinterpret_cast<uintptr_t>(next_row) & 3) return fail(SAMAUDIO_ERR_ARG, "set_windows: the table must be aligned to 4 bytes");
+  if (!launch_window_blend) return fail(SAMAUDIO_ERR_STATE, "set_windows: this build has no window_blend_kernel");
+  win_next_ = next_row;
+  win_overlap_ = overlap;
   return Status{};
 }
 

@@ -273,6 +273,14 @@ struct OdeStageArgs {
 __attribute__((weak)) hipError_t launch_ode_stage(const float* y0, const OdeStageArgs& a, float scale, float* out, long n,
                                                   hipStream_t st);
 
+// windowed solve of long clips (engine.hip eval_field): out [rows, W, C2] fp32 in place.  For every row r with
+// next_row[r] = s in [0, rows), s != r (device i32 [rows]; anything else = no successor), every j < O and channel c:
+//   p = out[r, W - O + j, c], q = out[s, j, c], v = p + a_j (q - p) with a_j = (j + 1) / (O + 1); v is written to both places.
+// One lane owns both elements of a pair; 1 <= O <= W / 2 keeps the head and the tail of a row apart; C2 % 4 == 0 (float4 per lane).
+// weak: the CPU emulation of the launchers (oracle/emu) does not define it - eval_field then refuses a windowed evaluation and the hook
+// answers SAMAUDIO_ERR_STATE (api.hip)
+__attribute__((weak)) hipError_t launch_window_blend(float* out, const int* next_row, int rows, int W, int O, int C2, hipStream_t st);
+
 // out[r,:] = AT(x[r,:] + vec[(r / rows_per_b) * vec_ld + :])
 hipError_t launch_add_rowvec(const float* x, const float* vec, long vec_ld, void* out, bool bf16, int rows, int D,
                              int rows_per_b, hipStream_t st);

@@ -797,6 +797,43 @@ hipError_t launch_ode_stage(const float* y0, const OdeStageArgs& a, float scale,
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// windowed solve of long clips (engine.hip eval_field): the last O frames of a window row and the first O frames
+// of its successor row describe the same frames of the clip; after every field evaluation both are replaced by their cross-fade
+// v = p + a_j (q - p), a_j = (j + 1) / (O + 1), in place, float4 per lane.  One lane reads both elements of a pair and writes the same
+// value to both, so no two lanes touch the same address: the tail of a row is frames [W - O, W), the head [0, O), disjoint because
+// O <= W / 2, and a row is the successor of at most one row (the table is the caller's; an entry outside [0, rows) or equal to its own
+// index is treated as "no successor", so a bad table blends wrong rows but never reaches outside the tensor).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void window_blend_kernel(float* out, const int* __restrict__ next_row, const int rows, const int W,
+                                                           const int O, const int n4, const long total) {
+  const float den = (float)(O + 1);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int c4 = (int)(i % n4);
+    const long t = i / n4;
+    const int j = (int)(t % O), r = (int)(t / O);
+    const int s = next_row[r];
+    if (s < 0 || s >= rows || s == r) continue;
+    float4* const pp = (float4*)out + ((long)r * W + (W - O) + j) * n4 + c4;
+    float4* const pq = (float4*)out + ((long)s * W + j) * n4 + c4;
+    const float4 p = *pp, q = *pq;
+    const float a = (float)(j + 1) / den;   // the fp32 weight (a divide per float4 pair is free next to the four memory accesses)
+    const float4 v = make_float4(fmaf(a, q.x - p.x, p.x), fmaf(a, q.y - p.y, p.y), fmaf(a, q.z - p.z, p.z), fmaf(a, q.w - p.w, p.w));
+    *pp = v;
+    *pq = v;
+  }
+}
+
+hipError_t launch_window_blend(float* out, const int* next_row, int rows, int W, int O, int C2, hipStream_t st) {
+  if (!out || !next_row || rows < 1 || O < 1 || O > W / 2 || C2 < 4 || C2 % 4) return hipErrorInvalidValue;
+  const int n4 = C2 / 4;
+  const long total = (long)rows * O * n4;
+  long gx = (total + 255) / 256;
+  if (gx > 2048) gx = 2048;
+  hipLaunchKernelGGL(window_blend_kernel, dim3((unsigned)gx), dim3(256), 0, st, out, next_row, rows, W, O, n4, total);
+  return hipGetLastError();
+}
+
 hipError_t launch_time_features(const float* t, int nt, const float* freqs, int fdim, const float* inv_freq, int D,
                                 void* temb, float* tsin, bool bf16, hipStream_t st) {
   if (bf16)

@@ -289,6 +289,8 @@ _PROTOS = {
     "samaudio_ode_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     "samaudio_ode_stage_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "samaudio_set_ode_stages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "samaudio_set_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "samaudio_op_window_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "samaudio_codec_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "samaudio_codec_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_profile_begin": (C.c_int, [C.c_void_p]),

@@ -800,15 +800,32 @@ class SAMAudio:
     @torch.inference_mode()
     def separate(self, batch: Batch, noise: Optional[torch.Tensor] = None,
                  ode_opt: Dict[str, Any] = DFLT_ODE_OPT, reranking_candidates: int = 1,
-                 predict_spans: bool = False, output_sampling_rate: Optional[int] = None) -> SeparationResult:
+                 predict_spans: bool = False, output_sampling_rate: Optional[int] = None,
+                 window_seconds: Optional[float] = None, window_overlap_seconds: Optional[float] = None) -> SeparationResult:
         """Reference model.py:247-338.  `reranking_candidates > 1` draws that many ODE solutions per clip and lets
         `visual_ranker` / `text_ranker` pick one (model.py:306-330); `predict_spans` runs `span_predictor` first
         (model.py:259-268; mind quirk Q13 below).  `output_sampling_rate`: when set and different from the codec's rate, the chosen
         target and residual of every clip are resampled to it on the device (sam_audio_amd/audio.py resample: what the reference's
-        evaluation does with torchaudio behind separate()); None leaves the results as the codec wrote them."""
+        evaluation does with torchaudio behind separate()); None leaves the results as the codec wrote them.
+        `window_seconds` / `window_overlap_seconds` (both or neither; this build's own definition): clips longer
+        than the window are solved as overlapping windows of that length - rows of ONE batch whose overlapping frames are cross-faded
+        after every evaluation of the vector field, so they hold the same bits through the whole solve; the latent is stitched by index
+        and decoded once over its whole length.  Encoder, text, visual features, span predictor and rerankers see whole clips.  All
+        windows of a batch are solved together (no splitting when they do not fit in memory), on the model's own context: `streams` > 1
+        is ignored for a windowed solve.  `last_latent` is the stitched latent, `last_window_latent` the window rows,
+        `last_window_plan` the longform.WindowPlan.  A clip that fits one window is one row without a successor: the plain path."""
         if not (self._has_dit and self._has_codec):
             raise RuntimeError("load_state_dict() first")
-        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans)
+        if (window_seconds is None) != (window_overlap_seconds is None):
+            raise ValueError("window_seconds and window_overlap_seconds go together: give both or neither")
+        window = None
+        if window_seconds is not None:
+            from . import longform
+            c = self.cfg.audio_codec
+            window = (longform.seconds_to_frames(window_seconds, c.sample_rate, c.hop_length),
+                      longform.seconds_to_frames(window_overlap_seconds, c.sample_rate, c.hop_length))
+            longform.check_window(*window, self.cfg.transformer.max_positions)
+        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans, window)
         if output_sampling_rate is None or int(output_sampling_rate) == self.sample_rate:
             return res
         from . import audio
@@ -818,7 +835,7 @@ class SAMAudio:
                                     noise=res.noise)
 
     def _separate(self, batch: Batch, noise: Optional[torch.Tensor], ode_opt: Dict[str, Any], reranking_candidates: int,
-                  predict_spans: bool) -> SeparationResult:
+                  predict_spans: bool, window: Optional[tuple] = None) -> SeparationResult:
         cand = int(reranking_candidates)
         with torch.cuda.device(self.device):
             # Nothing of torch's own arithmetic runs between the first and the last kernel of a step: the noise is drawn first
@@ -857,7 +874,9 @@ class SAMAudio:
             cond = [z, text, text_mask, video, anchor_ids, anchor_alignment, batch.audio_pad_mask]   # per clip: B items each
             groups = min(self.streams, B)
             wavs = None
-            if groups > 1:
+            if window is not None:   # (window, overlap) in frames: all windows of the batch as rows of one solve on the main context
+                latent = self._solve_windowed(batch, noise, cond, window, cand, validated, ode_opt)
+            elif groups > 1:
                 cond = [None if c is None else c.to(self.device) for c in cond]
                 # each group also decodes its own rows on its stream: the codec's HBM-bound convolutions of one group run
                 # beside the other group's kernels instead of after both solves
@@ -883,6 +902,65 @@ class SAMAudio:
                 target=[w[i] for w, i in zip(target, idxs)],
                 residual=[w[i] for w, i in zip(residual, idxs)],
                 noise=noise)
+
+    def _solve_windowed(self, batch: Batch, noise: torch.Tensor, cond: List[Optional[torch.Tensor]], window: tuple, cand: int,
+                        validated: bool, ode_opt: Dict[str, Any]) -> torch.Tensor:
+        """The ODE solve of separate() over overlapping windows.  `cond` holds the whole clips' conditioning
+        (B items each), `noise` is [B * cand, T, C2] over the whole clips.  Everything here is index plumbing: gathers into window rows,
+        one prepare, the successor table, one solve, the stitch.  Returns the stitched latent [B * cand, T, C2]."""
+        from . import longform
+        z, text, text_mask, video, anchor_ids, anchor_alignment, pad = cond
+        dev = self.device
+        B, T = z.shape[:2]
+        lengths = getattr(batch, "sizes_host", None) or [int(v) for v in batch.sizes.tolist()]
+        plan = longform.plan_windows(lengths, window[0], window[1], cand, batch_frames=T,
+                                     max_positions=self.cfg.transformer.max_positions)
+        clip_of, frame_of, inside = plan.gather_index()
+        clip = torch.tensor(clip_of, device=dev)
+        frame = torch.tensor(frame_of, device=dev)                                # [window rows, L]: whole-clip frame of a row's frame
+        hole = ~torch.tensor(inside, device=dev) if not all(map(all, inside)) else None   # row frames past the padded batch
+
+        def rows_of(x: Optional[torch.Tensor], row, frames, holes, fill=0):       # [.., T, ...] -> [rows, L, ...]
+            if x is None:
+                return None
+            out = x.to(dev)[row[:, None], frames]
+            if holes is not None:
+                out.masked_fill_(holes.view(holes.shape + (1,) * (out.dim() - 2)), fill)
+            return out
+
+        if pad is None:
+            pad = torch.arange(T)[None, :] < torch.tensor(lengths)[:, None]
+
+        def per_row(x: Optional[torch.Tensor]):                                   # text, text mask, anchor ids: repeated per window
+            return None if x is None else x.to(dev)[clip]
+
+        cond_rows = [rows_of(z, clip, frame, hole), per_row(text), per_row(text_mask),
+                     None if video is None else rows_of(video.transpose(1, 2), clip, frame, hole).transpose(1, 2),
+                     per_row(anchor_ids),
+                     None if anchor_ids is None else rows_of(anchor_alignment, clip, frame, hole, fill=1),   # 1 = the <pad> slot
+                     rows_of(pad, clip, frame, hole, fill=False)]
+        # the noise of engine row (window row g, candidate c) = the frames of whole-clip noise row clip(g) * cand + c: overlapping frames
+        # of neighbouring windows start identical
+        nrow = (clip[:, None] * cand + torch.arange(cand, device=dev)[None, :]).reshape(-1)
+        wnoise = rows_of(noise.to(dev, torch.float32), nrow, frame.repeat_interleave(cand, dim=0),
+                         None if hole is None else hole.repeat_interleave(cand, dim=0))
+        self._apply_options(1)
+        self._prepare(*cond_rows, anchors_validated=validated, candidates=cand, latent=True)
+        linked = any(s >= 0 for s in plan.next_row)   # clips that all fit one window: plain rows, no table, no extra launch
+        table = torch.tensor(plan.next_row, dtype=torch.int32, device=dev) if linked else None
+        try:
+            if linked:
+                hip.check(self._lib.samaudio_set_windows(self._ctx, hip.ptr(table), plan.rows, plan.overlap))
+            rows = self.solve(wnoise, ode_opt)
+        finally:
+            if linked:   # the table is this call's: the context does not keep the pointer
+                hip.check(self._lib.samaudio_set_windows(self._ctx, None, 0, 0))
+        srow, soff, have = plan.stitch_index()
+        latent = rows[torch.tensor(srow, device=dev), torch.tensor(soff, device=dev)]   # frame t from window min(t // S, n - 1)
+        if not all(map(all, have)):   # padding frames behind the last window's row: zero
+            latent.masked_fill_(~torch.tensor(have, device=dev)[:, :, None], 0)
+        self.last_window_latent, self.last_window_plan = rows, plan
+        return latent
 
     def _rerank(self, batch: Batch, target_wavs: List[torch.Tensor], sizes: List[int], cand: int) -> torch.Tensor:
         """Candidate selection, reference model.py:306-330: visual ranker if a masked video came with the batch, else
