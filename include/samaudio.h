@@ -499,6 +499,95 @@ int samaudio_op_activity(const float* wav, int rows, int64_t row_stride, int64_t
                          int n_ref, int metric, void* workspace, int64_t workspace_bytes, float* scores, int32_t* spans,
                          int max_spans, int32_t* span_count, int32_t* peak, samaudio_stream stream);
 
+/* ---- CLAP log-mel front end: `rows` mono waveforms -> [rows][frames][n_mels] dB features -----
+ * What `transformers.ClapFeatureExtractor(truncation="rand_trunc", padding="repeatpad")` computes for one clip, with the reference
+ * ranker's int16 round trip in front (sam_audio/ranking/clap.py:50-52), as one kernel; nothing but the features is stored.  The CPU
+ * statement is tests/clap_ref.py - pinned to ClapFeatureExtractor, unpinned vs laion_clap.  Per row, with n = lengths[r],
+ * L = max_length, N = fft_size:
+ *   1  quantise != 0: x = float(trunc(clamp(x, -1, 1) * SAMAUDIO_CLAP_INT16_SCALE)) / SAMAUDIO_CLAP_INT16_SCALE, each operation
+ *      rounded to fp32 as torch does it
+ *   2  n < L ("repeatpad"): y[i] = x[i % n] for i < (L / n) n, 0 behind;  n == L: y = x;  n > L: y[i] = x[offsets[r] + i], i < L
+ *      (the extractor draws that offset at random; the caller decides here)
+ *   3  frames = 1 + L / hop centred frames: frame f is y[f hop - N / 2 + j], j < N, reflected at both ends (y[-i] = y[i],
+ *      y[L - 1 + i] = y[L - 1 - i]), times window[j] (the caller's; the extractor's is the periodic Hann window)
+ *   4  X = the real DFT of the frame (a complex FFT of N / 2 points in LDS and one untangling pass), P[k] = |X[k]|^2, k <= N / 2
+ *   5  mel[m] = sum_k bank[k][m] P[k] (bank [N / 2 + 1][n_mels] f32, the caller's: any of the extractor's filter banks)
+ *   6  dB = 10 log10(max(mel, 1e-10)), exactly -100 at and below the floor;  out = dB * bn_scale[m] + bn_shift[m] where both are
+ *      given (the audio tower's eval-mode BatchNorm2d over the mel bins, folded by the caller)
+ * tables [2 N] f32 (device): window [N], then (cos, -sin)(2 pi t / N) interleaved for t < N / 2 - evaluated by the caller in
+ * float64 (sam_audio_amd/clap.py logmel_tables).  lengths / offsets are HOST arrays [rows] (offsets NULL = 0; it is read for rows
+ * longer than L only); consecutive rows of equal length and offset share a launch.  A frame's value does not depend on the other
+ * frames, the other rows or the launch geometry. */
+#define SAMAUDIO_CLAP_INT16_SCALE 32767.0f   /* laion_clap's float32_to_int16 / int16_to_float32 constant: unpinned (laion_clap is absent) */
+/* 1 + max_length / hop; -1 for an argument below 1 */
+int64_t samaudio_logmel_frames(int64_t max_length, int hop);
+/* out [rows][frames][n_mels] f32.  Stateless, no workspace, nothing is read back.  SAMAUDIO_ERR_ARG before any launch for a null
+ * wav / lengths / tables / bank / out, only one of bn_scale / bn_shift, rows / hop / n_mels < 1, fft_size not a power of two in
+ * [64, 2048], max_length <= fft_size / 2 (no reflection) or >= 2^30, a length < 1 or > row_stride (rows > 1), an offset outside
+ * [0, n - max_length]; SAMAUDIO_ERR_STATE in a build of the library without the kernel. */
+int samaudio_op_logmel(const float* wav, int rows, int64_t row_stride, const int64_t* lengths, const int64_t* offsets,
+                       int64_t max_length, int quantise, int fft_size, int hop, int n_mels, const float* tables,
+                       const float* bank, const float* bn_scale, const float* bn_shift, float* out, samaudio_stream stream);
+
+/* ---- CLAP ranker towers ---------------------------------------------------------------------
+ * `transformers.ClapModel` without feature fusion: get_audio_features (the log-mel front end above with the BatchNorm folded in,
+ * the HTSAT audio tower - mel-to-image patch embedding, stages of shifted-window attention blocks, patch merging - the final
+ * LayerNorm, the mean over all tokens, audio_projection, L2 normalisation) and get_text_features (the RoBERTa text tower, its
+ * pooler, text_projection, L2 normalisation).  fp32 only; the towers own no device memory: borrowed weights, one caller workspace.
+ * Engine tensor names: sam_audio_amd/clap.py documents the mapping from ClapModel's state_dict keys. */
+typedef struct {
+  /* front end */
+  int32_t fft_size, hop, max_length;          /* 1024, 480, 480000 */
+  /* audio tower */
+  int32_t spec_size, num_mel_bins;            /* 256, 64: spec_size % num_mel_bins == 0 (freq_ratio), frames <= spec_size * freq_ratio */
+  int32_t patch_size, patch_stride;           /* 4, 4 */
+  int32_t embed_dim;                          /* patch_embeds_hidden_size, 96; stage s is embed_dim << s wide */
+  int32_t num_stages;                         /* 4 (<= 4) */
+  int32_t depths[4], heads[4];                /* {2, 2, 6, 2}, {4, 8, 16, 32}: head width 24 or 32 */
+  int32_t window_size;                        /* 8 (window_size^2 <= 64) */
+  int32_t mlp_ratio;                          /* 4 */
+  int32_t patch_norm;                         /* enable_patch_layer_norm */
+  int32_t enable_fusion;                      /* must be 0: refused at create */
+  float audio_ln_eps;                         /* layer_norm_eps of the blocks, 1e-5 (the patch, merge and final norms are 1e-5 as nn.LayerNorm) */
+  /* text tower */
+  int32_t text_vocab, text_hidden, text_heads, text_layers, text_intermediate;   /* 50265, 768, 12, 12, 3072 */
+  int32_t text_max_positions, text_pad_id;    /* 514 (<= 514), 1 */
+  float text_ln_eps;                          /* 1e-12 */
+  int32_t projection_dim;                     /* 512 */
+} samaudio_clap_config;
+typedef struct samaudio_clap samaudio_clap;
+int samaudio_clap_create(const samaudio_clap_config* cfg, samaudio_clap** out);
+void samaudio_clap_destroy(samaudio_clap* t);
+int samaudio_clap_set_tensor(samaudio_clap* t, const char* name, const void* data, int dtype, int ndim, const int64_t* shape);
+/* resolves the weights; SAMAUDIO_ERR_ARG when a GEMM's K (a stage width, its MLP width, 4 x a merged width, text_hidden,
+ * text_intermediate) is no multiple of 32, a resolution is no multiple of its window or odd before a merge, a head width is neither 24
+ * nor 32; SAMAUDIO_ERR_WEIGHT for a missing or misshapen tensor */
+int samaudio_clap_finalize(samaudio_clap* t);
+/* bytes for audio_rows clips and text_rows x tokens tokens (either may be 0); the two towers share the workspace */
+size_t samaudio_clap_workspace_bytes(samaudio_clap* t, int audio_rows, int text_rows, int tokens);
+int samaudio_clap_set_workspace(samaudio_clap* t, void* workspace, size_t bytes);
+/* out [rows][projection_dim] f32, unit norm: waveforms as samaudio_op_logmel takes them (lengths / offsets are host arrays).
+ * SAMAUDIO_ERR_ARG for a clip of length < 1 (and what samaudio_op_logmel refuses), SAMAUDIO_ERR_WORKSPACE for a workspace that is
+ * missing or too small */
+int samaudio_clap_audio_embed(samaudio_clap* t, const float* wav, int rows, int64_t row_stride, const int64_t* lengths,
+                              const int64_t* offsets, int quantise, float* out, samaudio_stream stream);
+/* out [rows][projection_dim] f32, unit norm: input_ids [rows][tokens] i64 and attention_mask [rows][tokens] u8 (device).
+ * SAMAUDIO_ERR_ARG for tokens + text_pad_id + 1 > text_max_positions (the position table) */
+int samaudio_clap_text_embed(samaudio_clap* t, const int64_t* input_ids, const unsigned char* attention_mask, int rows, int tokens,
+                             float* out, samaudio_stream stream);
+/* scores [clips][candidates] = <audio [clips * candidates][dim], text [clips][dim]>: the reference's [B, cand, E] @ [B, E, 1] */
+int samaudio_clap_score(const float* audio, const float* text, int clips, int candidates, int dim, float* scores,
+                        samaudio_stream stream);
+/* the tower's new kernels alone, for tests (csrc/kernels.h launch_clap_patch_embed / launch_swin_window_attn /
+ * launch_swin_patch_merge say what they compute); SAMAUDIO_ERR_ARG for what a launcher's comment excludes */
+int samaudio_op_clap_patch_embed(const float* feat, int n, int frames, int n_mels, int spec_size, int patch_size, int patch_stride,
+                                 int dim, const float* w, const float* bias, const float* ln_w, const float* ln_b, float eps,
+                                 float* tokens, samaudio_stream stream);
+int samaudio_op_swin_window_attn(const float* qkv, const float* table, float* out, int n, int height, int width, int heads,
+                                 int head_dim, int window, int shift, samaudio_stream stream);
+int samaudio_op_swin_patch_merge(const float* x, const float* ln_w, const float* ln_b, float eps, float* out, int n, int height,
+                                 int width, int dim, samaudio_stream stream);
+
 /* ---- text-prompt encoder ---------------------------------------------------------
  * T5 encoder stack behind `T5TextEncoder.forward` (reference sam_audio/model/text_encoder.py:19-37:
  * `transformers.T5EncoderModel("t5-base")(input_ids, attention_mask)["last_hidden_state"]`).  Tokenisation stays with the

@@ -3,7 +3,7 @@
 Public surface mirrors `sam_audio` (reference sam_audio/__init__.py:3-4) for that path:
 SAMAudio, SAMAudioProcessor, Batch, SeparationResult.
 """
-from .config import SAMAudioConfig, SoundActivityRankerConfig, preset_config  # noqa: F401
+from .config import ClapRankerConfig, SAMAudioConfig, SoundActivityRankerConfig, preset_config  # noqa: F401
 from .processor import Batch, MaskedVideo, SAMAudioJudgeProcessor, SAMAudioProcessor  # noqa: F401
 
 
@@ -16,11 +16,15 @@ def __getattr__(name):
     if name in ("SAMAudioJudgeModel", "SAMAudioJudgeOutput", "PEAudioFrame"):
         from . import judge
         return getattr(judge, name)
-    if name == "SoundActivityRanker":
+    if name in ("SoundActivityRanker", "ClapRanker"):
         from . import ranking
-        return ranking.SoundActivityRanker
+        return getattr(ranking, name)
+    if name == "ClapTower":
+        from . import clap
+        return clap.ClapTower
     raise AttributeError(name)
 
 
 __all__ = ["SAMAudio", "SAMAudioProcessor", "SAMAudioJudgeProcessor", "SAMAudioJudgeModel", "Batch", "SeparationResult",
-           "SAMAudioConfig", "preset_config", "MaskedVideo", "SoundActivityRanker", "SoundActivityRankerConfig"]
+           "SAMAudioConfig", "preset_config", "MaskedVideo", "SoundActivityRanker", "SoundActivityRankerConfig",
+           "ClapRanker", "ClapRankerConfig", "ClapTower"]

@@ -210,10 +210,19 @@ class SoundActivityRankerConfig:
             raise ValueError(f"SoundActivityRankerConfig: metric must be 'iou', 'recall' or 'precision', got {self.metric!r}")
 
 
+@dataclass
+class ClapRankerConfig:
+    """reference model/config.py ClapRankerConfig.  `checkpoint`: a local `ClapModel.save_pretrained` directory (Hugging Face key
+    names).  None is what the reference resolves by downloading lukewys/laion_clap's 630k-best.pt from the hub: impossible offline,
+    and laion's own key names cannot be checked here - ranking.create_ranker refuses it."""
+    checkpoint: Optional[str] = None
+    kind: str = "clap"
+
+
 def parse_ranker_config(raw: Optional[Dict[str, Any]]):
-    """The Judge ranker and the sound-activity ranker are built here; CLAP / ImageBind
-    are third-party models that are out of scope, so their configs are kept as opaque dicts.  So is an ensemble's:
-    ranking.create_ranker parses its members with this function."""
+    """The Judge ranker, the sound-activity ranker and the CLAP ranker (section 10.8) are
+    built here; ImageBind is a third-party model without a statement in this environment, so its config is kept as an opaque dict.
+    So is an ensemble's: ranking.create_ranker parses its members with this function."""
     if raw is None:
         return None
     raw = dict(raw)
@@ -223,6 +232,9 @@ def parse_ranker_config(raw: Optional[Dict[str, Any]]):
     if raw.get("kind") == "sound_activity":
         raw.pop("kind")
         return SoundActivityRankerConfig(**raw)
+    if raw.get("kind") == "clap":
+        raw.pop("kind")
+        return ClapRankerConfig(**raw)
     return raw
 
 

@@ -429,6 +429,47 @@ int samaudio_op_activity(const float* wav, int rows, int64_t row_stride, int64_t
                  "activity");
 }
 
+// ---- CLAP log-mel front end ------------------------------------------------------------------------------------------
+int64_t samaudio_logmel_frames(int64_t max_length, int hop) {
+  if (max_length < 1 || hop < 1) return -1;
+  return 1 + max_length / hop;
+}
+
+int samaudio_op_logmel(const float* wav, int rows, int64_t row_stride, const int64_t* lengths, const int64_t* offsets,
+                       int64_t max_length, int quantise, int fft_size, int hop, int n_mels, const float* tables, const float* bank,
+                       const float* bn_scale, const float* bn_shift, float* out, samaudio_stream stream) {
+  if (!wav || !lengths || !tables || !bank || !out) return bad("logmel: null wav / lengths / tables / bank / out");
+  if ((bn_scale == nullptr) != (bn_shift == nullptr)) return bad("logmel: bn_scale and bn_shift go together");
+  if (rows < 1 || rows > 65535 || hop < 1 || n_mels < 1) return bad("logmel: rows outside [1, 65535], hop or n_mels < 1");
+  int log2n = 0;
+  while ((1 << log2n) < fft_size && log2n < 12) ++log2n;
+  if (fft_size < 64 || fft_size > 2048 || (1 << log2n) != fft_size) return bad("logmel: fft_size must be a power of two in [64, 2048]");
+  if (max_length <= fft_size / 2 || max_length >= (1LL << 30))
+    return bad("logmel: max_length must be above fft_size / 2 (the reflection) and below 2^30");
+  for (int r = 0; r < rows; ++r) {
+    if (lengths[r] < 1) return bad("logmel: a clip of length < 1");
+    if (rows > 1 && lengths[r] > row_stride) return bad("logmel: a clip longer than row_stride");
+    if (lengths[r] > max_length && offsets && (offsets[r] < 0 || offsets[r] > lengths[r] - max_length))
+      return bad("logmel: a crop offset outside [0, length - max_length]");
+  }
+  if (!sa::launch_clap_logmel) {
+    g_err = "logmel: not in this build of the library";
+    return SAMAUDIO_ERR_STATE;
+  }
+  const int frames = (int)samaudio_logmel_frames(max_length, hop);
+  const auto offset_of = [&](int r) { return lengths[r] > max_length && offsets ? offsets[r] : (int64_t)0; };
+  for (int r0 = 0; r0 < rows;) {   // consecutive rows of one length and offset share a launch
+    int r1 = r0 + 1;
+    while (r1 < rows && lengths[r1] == lengths[r0] && offset_of(r1) == offset_of(r0)) ++r1;
+    const hipError_t e = sa::launch_clap_logmel(wav + (int64_t)r0 * row_stride, r1 - r0, (long)row_stride, (long)lengths[r0],
+                                                (long)offset_of(r0), (int)max_length, quantise != 0, log2n, hop, n_mels, frames, tables,
+                                                bank, bn_scale, bn_shift, out + (int64_t)r0 * frames * n_mels, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_ret(e, "logmel");
+    r0 = r1;
+  }
+  return SAMAUDIO_OK;
+}
+
 int samaudio_op_window_blend(float* out, const int32_t* next_row, int rows, int frames, int overlap, int channels,
                              samaudio_stream stream) {
   if (!out || !next_row || rows < 1 || frames < 2) return bad("window_blend: null out / next_row, rows < 1 or frames < 2");

@@ -359,6 +359,40 @@ __attribute__((weak)) hipError_t launch_activity(const float* wav, int rows, lon
                                                  float* scores, int* spans, int max_spans, int* span_count, int* peak,
                                                  hipStream_t st);
 
+// ---- CLAP log-mel front end (kernels.hip) -------------------------------------------------------------------------
+// `rows` mono fp32 waveforms of one length n (row r at wav + r * row_stride) -> out [rows][frames][n_mels] dB features: the int16 round
+// trip (quantise), repeatpad to L / the crop [offset, offset + L), centred reflect-padded frames of N = 1 << log2n samples at `hop`,
+// window, real FFT in LDS, |X|^2, the mel bank [N / 2 + 1][n_mels], 10 log10(max(., 1e-10)), the per-mel scale and shift (null = none):
+// samaudio.h samaudio_op_logmel.  tables = window [N] | (cos, -sin)(2 pi t / N) [N / 2][2].  One launch.  weak: the CPU emulation of
+// the launchers (oracle/emu) does not define it - the hook then answers SAMAUDIO_ERR_STATE
+__attribute__((weak)) hipError_t launch_clap_logmel(const float* wav, int rows, long row_stride, long n, long offset, int L, bool quantise,
+                                                    int log2n, int hop, int n_mels, int frames, const float* tables, const float* bank,
+                                                    const float* bn_scale, const float* bn_shift, float* out, hipStream_t st);
+
+// ---- CLAP towers (clap_kernels.hip; samaudio.h "CLAP ranker towers").  fp32 only.  weak: the CPU builds of the launchers under oracle/
+// do not define them - the hooks and the tower then answer SAMAUDIO_ERR_STATE ----------------------------------------
+// feat [n][frames][F] (normalised log-mel) -> tokens [n][G * G][C], G = spec / stride: bicubic align_corners time interpolation to
+// spec * (spec / F) frames where frames is below that, the mel-to-image fold (image row r F + f, column x = frame r spec + x), the
+// P x P stride-S convolution (w [C][P * P], padding (P - S) / 2, bias), LayerNorm(C) (ln_w null = none).  C <= 1024, P * P <= 64
+__attribute__((weak)) hipError_t launch_clap_patch_embed(const float* feat, int n, int frames, int F, int spec, int P, int S, int C,
+                                                         const float* w, const float* bias, const float* ln_w, const float* ln_b,
+                                                         float eps, float* tokens, hipStream_t st);
+// shifted-window attention on q|k|v rows [n * H * W][3 * heads * hd]: per (clip, window, head) the ws x ws tokens at the rolled,
+// window-partitioned positions, softmax(q k^T / sqrt(hd) + table[rel(i, j)][head] + region mask (-100, shift > 0 only)) v, written to
+// out [n * H * W][heads * hd] at the un-rolled positions.  hd 24 | 32, ws * ws <= 64, H % ws == W % ws == 0, table [(2 ws - 1)^2][heads]
+__attribute__((weak)) hipError_t launch_swin_window_attn(const float* qkv, const float* table, float* out, int n, int H, int W,
+                                                         int heads, int hd, int ws, int shift, hipStream_t st);
+// x [n][H * W][C] -> out [n][H/2 * W/2][4 C] = LayerNorm(4 C) of (x(2y, 2x) | x(2y + 1, 2x) | x(2y, 2x + 1) | x(2y + 1, 2x + 1))
+__attribute__((weak)) hipError_t launch_swin_patch_merge(const float* x, const float* ln_w, const float* ln_b, float eps, float* out,
+                                                         int n, int H, int W, int C, hipStream_t st);
+// RoBERTa embeddings before their LayerNorm: out[r][t] = word[ids] + pos[position] + type[0], position = pad + (number of non-pad ids
+// in row r up to and including t) for a non-pad id, pad for a pad id (modeling_clap.py:1010).  T <= 1024
+__attribute__((weak)) hipError_t launch_clap_text_embed(const long long* ids, const float* word, const float* pos, const float* type,
+                                                        float* out, int rows, int T, int D, int vocab, int pad, hipStream_t st);
+// scores[b][c] = <audio[b * cand + c][:], text[b][:]> (one wave per score, a fixed summation order)
+__attribute__((weak)) hipError_t launch_clap_score(const float* audio, const float* text, float* scores, int clips, int cand, int dim,
+                                                   hipStream_t st);
+
 // ---- PE-Core vision tower (vit_kernels.hip) ---------------------------------------------------------------------
 // im2col of the k = stride = P patch convolution: frames [n,3,S,S] f32 -> rows [n*(S/P)^2, Kp], column c*P*P + py*P + px
 hipError_t launch_patchify(const float* frames, void* out, bool bf16, int n, int S, int P, int Kp, hipStream_t st);

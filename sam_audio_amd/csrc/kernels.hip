@@ -1406,6 +1406,122 @@ hipError_t launch_activity(const float* wav, int rows, long row_stride, int step
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// CLAP log-mel front end (samaudio.h samaudio_op_logmel; the statement is tests/clap_ref.py): waveform rows ->
+// [frames, n_mels] dB features in one kernel.  A workgroup owns `fb` consecutive frames of one row (fb M <= kLogmelPoints complex
+// points, M = N / 2) and keeps everything between the waveform and the features in LDS:
+//   load      sample 2t | 2t + 1 of a frame -> the int16 round trip, repeatpad / crop and the reflection as index arithmetic on the
+//             load, times the window -> z[bitrev(t)] = (even, odd): the real frame packed as M complex points
+//   fft       log2 M radix-2 decimation-in-time passes in place, twiddles from the caller's float64-evaluated table
+//   untangle  X[k] = E[k] + w^k O[k], E / O from Z[k] and conj Z[M - k], k <= M; P[k] = |X[k]|^2.  A frame of zeros gives exact zeros
+//             (no frame shares a transform with another one)
+//   mel       16 features per wave at a time, each summed by 4 lanes over k = j, j + 4, ... and folded by two xor shuffles (a fixed
+//             order: the result does not depend on the launch geometry); 10 log10, the floor, the per-mel scale and shift
+// ------------------------------------------------------------------------------------------------
+constexpr int kLogmelPoints = 2048;      // complex points of z: fb = min(kLogmelMaxFrames, kLogmelPoints / M) frames per workgroup
+constexpr int kLogmelMaxFrames = 8;
+constexpr float kClapInt16Scale = 32767.0f;   // samaudio.h SAMAUDIO_CLAP_INT16_SCALE
+
+// laion_clap's int16_to_float32_torch(float32_to_int16_torch(x)): clamp, x 32767 rounded to fp32, truncated toward zero, / 32767
+// rounded to fp32 (nothing can be contracted into the product: the truncation stands between it and the division)
+__device__ __forceinline__ float clap_quantise(float x) {
+  x = x < -1.f ? -1.f : (x > 1.f ? 1.f : x);
+  return truncf(x * kClapInt16Scale) / kClapInt16Scale;
+}
+
+// sample p of the padded clip, p in [-N / 2, L + N / 2): reflected into [0, L) (N / 2 < L), then the crop x[offset + p] of a longer
+// clip, or x[p % n] below rep_end = (L / n) n and zero behind
+__device__ __forceinline__ float clap_sample(const float* __restrict__ x, unsigned n, long offset, int L, unsigned rep_end, bool longer,
+                                             bool quantise, int p) {
+  if (p < 0) p = -p;
+  if (p >= L) p = 2 * (L - 1) - p;
+  float v;
+  if (longer) v = x[offset + p];
+  else if ((unsigned)p < rep_end) v = x[(unsigned)p % n];
+  else return 0.f;
+  return quantise ? clap_quantise(v) : v;
+}
+
+__global__ __launch_bounds__(256) void clap_logmel_kernel(const float* __restrict__ wav, long row_stride, unsigned n, long offset, int L,
+                                                          unsigned rep_end, int longer, int quantise, int log2n, int hop, int n_mels,
+                                                          int frames, int fb, const float* __restrict__ tables,
+                                                          const float* __restrict__ bank, const float* __restrict__ bn_scale,
+                                                          const float* __restrict__ bn_shift, float* __restrict__ out) {
+  __shared__ float2 z[kLogmelPoints];
+  __shared__ float2 tw[kLogmelPoints / 2];
+  __shared__ float win[kLogmelPoints];
+  __shared__ float pw[kLogmelPoints + kLogmelMaxFrames];
+  const int tid = threadIdx.x, N = 1 << log2n, M = N >> 1, logm = log2n - 1, nb = M + 1;
+  const int row = blockIdx.y, f0 = (int)blockIdx.x * fb, nf = frames - f0 < fb ? frames - f0 : fb;
+  const float* x = wav + (long)row * row_stride;
+  for (int i = tid; i < N; i += 256) win[i] = tables[i];
+  for (int i = tid; i < M; i += 256) tw[i] = make_float2(tables[N + 2 * i], tables[N + 2 * i + 1]);
+  __syncthreads();
+  for (int i = tid; i < nf * M; i += 256) {
+    const int f = i >> logm, t = i & (M - 1), p = (f0 + f) * hop - M + 2 * t;
+    const float a = clap_sample(x, n, offset, L, rep_end, longer != 0, quantise != 0, p) * win[2 * t];
+    const float b = clap_sample(x, n, offset, L, rep_end, longer != 0, quantise != 0, p + 1) * win[2 * t + 1];
+    z[(f << logm) + (int)(__builtin_bitreverse32((unsigned)t) >> (32 - logm))] = make_float2(a, b);
+  }
+  __syncthreads();
+  for (int s = 0; s < logm; ++s) {
+    const int half = 1 << s;
+    for (int i = tid; i < nf * (M >> 1); i += 256) {
+      const int f = i >> (logm - 1), b = i & ((M >> 1) - 1), pos = b & (half - 1);
+      const int i0 = (f << logm) + ((b >> s) << (s + 1)) + pos, i1 = i0 + half;
+      const float2 w = tw[pos << (logm - s)];   // exp(-2 pi i pos / (2 half)) = entry pos N / (2 half) of the table over N
+      const float2 u = z[i0], v = z[i1];
+      const float tr = v.x * w.x - v.y * w.y, ti = v.x * w.y + v.y * w.x;
+      z[i0] = make_float2(u.x + tr, u.y + ti);
+      z[i1] = make_float2(u.x - tr, u.y - ti);
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < nf * nb; i += 256) {
+    const int f = i / nb, k = i - f * nb;
+    const float2 a = z[(f << logm) + (k & (M - 1))], b = z[(f << logm) + ((M - k) & (M - 1))];
+    const float er = 0.5f * (a.x + b.x), ei = 0.5f * (a.y - b.y);     // E = (Z[k] + conj Z[M - k]) / 2
+    const float qr = 0.5f * (a.y + b.y), qi = -0.5f * (a.x - b.x);    // O = (Z[k] - conj Z[M - k]) / 2i
+    const float2 w = k < M ? tw[k] : make_float2(-1.f, 0.f);
+    const float xr = er + (qr * w.x - qi * w.y), xi = ei + (qr * w.y + qi * w.x);
+    pw[i] = xr * xr + xi * xi;
+  }
+  __syncthreads();
+  const int lane = tid & 63, wave = tid >> 6, j = lane >> 4, total = nf * n_mels;
+  for (int base = 0; base < total; base += 64) {
+    const int o = base + wave * 16 + (lane & 15);
+    int f = 0, m = 0;
+    float s = 0.f;
+    if (o < total) {
+      f = o / n_mels;
+      m = o - f * n_mels;
+      const float* pf = pw + f * nb;
+      for (int k = j; k < nb; k += 4) s = fmaf(bank[(long)k * n_mels + m], pf[k], s);
+    }
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    if (o < total && j == 0) {
+      float d = s > 1e-10f ? 10.f * log10f(s) : -100.f;
+      if (bn_scale) d = d * bn_scale[m] + bn_shift[m];
+      out[((long)row * frames + f0 + f) * n_mels + m] = d;
+    }
+  }
+}
+
+hipError_t launch_clap_logmel(const float* wav, int rows, long row_stride, long n, long offset, int L, bool quantise, int log2n, int hop,
+                              int n_mels, int frames, const float* tables, const float* bank, const float* bn_scale,
+                              const float* bn_shift, float* out, hipStream_t st) {
+  const int M = 1 << (log2n - 1);
+  if (log2n < 6 || M > kLogmelPoints / 2 || rows < 1 || rows > 65535 || n < 1 || frames < 1) return hipErrorInvalidValue;
+  const int fb = kLogmelPoints / M < kLogmelMaxFrames ? kLogmelPoints / M : kLogmelMaxFrames;
+  const bool longer = n > L;
+  const unsigned nn = longer ? 0u : (unsigned)n, rep_end = longer ? 0u : (unsigned)((L / n) * n);
+  hipLaunchKernelGGL(clap_logmel_kernel, dim3((unsigned)((frames + fb - 1) / fb), (unsigned)rows), dim3(256), 0, st, wav, row_stride, nn,
+                     longer ? offset : 0L, L, rep_end, longer ? 1 : 0, quantise ? 1 : 0, log2n, hop, n_mels, frames, fb, tables, bank,
+                     bn_scale, bn_shift, out);
+  return hipGetLastError();
+}
+
 // SAMAUDIO_OPT_SENTINEL (engine.hip): largest magnitude and number of non-finite values of a 16-bit (or fp32) tensor [rows, cols]
 // with row pitch ld, folded into a per-class slot {float absmax, float nonfinite count} - two launches on the launch stream, no
 // atomics (partials per workgroup, then one workgroup folds them into the slot; launches of a stream are ordered).  A debugging /

@@ -240,6 +240,18 @@ class MBertConfig(C.Structure):
                 ("max_len", C.c_int32), ("ln_eps", C.c_float)]
 
 
+class ClapConfig(C.Structure):
+    """Mirror of `samaudio_clap_config`."""
+    _fields_ = [("fft_size", C.c_int32), ("hop", C.c_int32), ("max_length", C.c_int32),
+                ("spec_size", C.c_int32), ("num_mel_bins", C.c_int32), ("patch_size", C.c_int32), ("patch_stride", C.c_int32),
+                ("embed_dim", C.c_int32), ("num_stages", C.c_int32), ("depths", C.c_int32 * 4), ("heads", C.c_int32 * 4),
+                ("window_size", C.c_int32), ("mlp_ratio", C.c_int32), ("patch_norm", C.c_int32), ("enable_fusion", C.c_int32),
+                ("audio_ln_eps", C.c_float),
+                ("text_vocab", C.c_int32), ("text_hidden", C.c_int32), ("text_heads", C.c_int32), ("text_layers", C.c_int32),
+                ("text_intermediate", C.c_int32), ("text_max_positions", C.c_int32), ("text_pad_id", C.c_int32),
+                ("text_ln_eps", C.c_float), ("projection_dim", C.c_int32)]
+
+
 class KernelStat(C.Structure):
     """Mirror of `samaudio_kernel_stat`."""
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("flops", C.c_double), ("bytes", C.c_double),
@@ -382,9 +394,45 @@ _PROTOS = {
     "samaudio_op_activity": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "samaudio_logmel_frames": (C.c_int64, [C.c_int64, C.c_int]),
+    "samaudio_op_logmel": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_int,
+                                     C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
 }
 
-EXPORTED_SYMBOLS = tuple(_PROTOS)
+# The CLAP towers (csrc/clap.hip): exported by the product libraries only - the CPU builds of the library that the tests' dry runs
+# bind by _PROTOS (oracle/) are built from a fixed list of sources without them - so they are a table of their own, bound by lib() on
+# the product libraries and by clap_lib() on whatever library is in use.
+_CLAP_PROTOS = {
+    "samaudio_clap_create": (C.c_int, [C.POINTER(ClapConfig), C.POINTER(C.c_void_p)]),
+    "samaudio_clap_destroy": (None, [C.c_void_p]),
+    "samaudio_clap_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "samaudio_clap_finalize": (C.c_int, [C.c_void_p]),
+    "samaudio_clap_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "samaudio_clap_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "samaudio_clap_audio_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                            C.c_int, C.c_void_p, C.c_void_p]),
+    "samaudio_clap_text_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "samaudio_clap_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "samaudio_op_clap_patch_embed": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p]),
+    "samaudio_op_swin_window_attn": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p]),
+    "samaudio_op_swin_patch_merge": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+}
+
+EXPORTED_SYMBOLS = tuple(_PROTOS) + tuple(_CLAP_PROTOS)
+
+
+def _bind(cdll, protos) -> None:
+    for name, (res, args) in protos.items():
+        fn = getattr(cdll, name)  # AttributeError if the .so does not export it
+        fn.restype = res
+        fn.argtypes = args
+
+
+def clap_lib():
+    """lib() with the CLAP towers' entry points bound; AttributeError for a library built without them"""
+    handle = lib()
+    _bind(getattr(handle, "_cdll", handle), _CLAP_PROTOS)
+    return handle
 
 
 def lib(operands: str = "bf16"):
@@ -402,10 +450,8 @@ def lib(operands: str = "bf16"):
             f"{path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or sam_audio_amd/csrc/build.sh.  There is no CPU fallback for the separate() hot path.")
     cdll = C.CDLL(path)
-    for name, (res, args) in _PROTOS.items():
-        fn = getattr(cdll, name)  # AttributeError if the .so does not export it
-        fn.restype = res
-        fn.argtypes = args
+    _bind(cdll, _PROTOS)
+    _bind(cdll, _CLAP_PROTOS)
     handle = _Handle(cdll)
     _libs[operands] = handle
     if operands == "bf16":

@@ -1,8 +1,10 @@
 """Rerankers for `separate(reranking_candidates > 1)` - the reference's `sam_audio.ranking` surface
 (reference sam_audio/ranking/ranker.py:9-36, ranking/judge.py:11-42, ranking/__init__.py:15-30) for the rows this build
-covers: the Judge, the sound-activity ranker (ranking/sound_activity.py)
-and ensembles of rankers.  CLAP / ImageBind rankers wrap third-party models that are not part of this build's environment: their
-configs are reported, not silently ignored.
+covers: the Judge, the sound-activity ranker (ranking/sound_activity.py),
+the CLAP ranker (ranking/clap.py; DESIGN.md section 10.8: the model is transformers' ClapModel on the HIP towers of
+sam_audio_amd/clap.py, from a local checkpoint directory) and ensembles of rankers.  The ImageBind ranker wraps a third-party model
+that is not part of this build's environment, and so does a CLAP config without a local checkpoint (the reference downloads
+laion_clap's): those configs are reported, not silently ignored.
 """
 from __future__ import annotations
 
@@ -10,7 +12,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from .config import JudgeRankerConfig, SoundActivityRankerConfig
+from .config import ClapRankerConfig, JudgeRankerConfig, SoundActivityRankerConfig
 
 
 class Ranker:
@@ -115,6 +117,69 @@ class SoundActivityRanker(Ranker):
         return scores
 
 
+class ClapRanker(Ranker):
+    """reference ranking/clap.py:33-86: the cosine of CLAP's audio embedding of every candidate and its text embedding of the clip's
+    description, [batch, candidates] fp32 on the device (higher = better).  `model` is a loaded `clap.ClapTower`, `tokenizer` the
+    checkpoint's (RoBERTa's); from a config both are loaded from the local checkpoint directory.  Every clip's [candidates, n] view
+    goes to the tower as it is; nothing is read back.
+
+    Pinned to transformers' ClapModel / ClapFeatureExtractor, unpinned vs laion_clap (absent here): the int16 round trip's constant
+    and laion's `fmin` are taken on trust.  A candidate longer than 10 s is cropped at the head (`truncation="head"`, deterministic:
+    this build's default); the reference crops at a random offset - `truncation="rand_trunc"` draws one per candidate from
+    `generator` (a torch.Generator; None = torch's global one).  The towers are fp32 only: a `precision=` is accepted and ignored."""
+
+    def __init__(self, config: Optional[ClapRankerConfig] = None, model=None, tokenizer=None, truncation: str = "head",
+                 generator: Optional[torch.Generator] = None, device=None, **_ignored):
+        if truncation not in ("head", "rand_trunc"):
+            raise ValueError(f"truncation must be 'head' or 'rand_trunc', got {truncation!r}")
+        self.config, self.truncation, self.generator = config, truncation, generator
+        if model is None or tokenizer is None:
+            path = getattr(config, "checkpoint", None)
+            if path is None:
+                raise NotImplementedError(_CLAP_NEEDS_A_DIRECTORY)
+            if model is None:
+                from .clap import ClapTower
+                model = ClapTower.from_pretrained(path, device=device)
+            if tokenizer is None:
+                from transformers import AutoTokenizer
+                tokenizer = AutoTokenizer.from_pretrained(path)
+        self.model, self.tokenizer = model, tokenizer
+
+    def _offsets(self, samples: int, sample_rate: int, candidates: int) -> Optional[List[int]]:
+        """crop offsets of one clip's candidates, at the tower's rate; None = the head"""
+        if self.truncation == "head":
+            return None
+        from .audio import resample_length
+        n = resample_length(samples, sample_rate, self.model.sample_rate) if sample_rate != self.model.sample_rate else samples
+        overflow = n - int(self.model.cfg.max_length)
+        if overflow <= 0:
+            return None
+        return torch.randint(0, overflow + 1, (candidates,), generator=self.generator).tolist()
+
+    @torch.inference_mode()
+    def forward(self, extracted_audio: List[torch.Tensor], descriptions: List[str], sample_rate: int = 48_000, **kwargs) -> torch.Tensor:
+        bsz, ncandidates = len(extracted_audio), len(extracted_audio[0])
+        if len(descriptions) != bsz:
+            raise ValueError(f"{bsz} clips but {len(descriptions)} descriptions")
+        device = extracted_audio[0].device
+        audio = torch.empty(bsz * ncandidates, self.model.dim, dtype=torch.float32, device=device)
+        for b, wav in enumerate(extracted_audio):
+            if wav.dim() != 2 or wav.shape[0] != ncandidates:
+                raise ValueError("every clip must be [candidates, samples] with the same number of candidates")
+            self.model.audio_embed(wav, int(sample_rate), offsets=self._offsets(wav.shape[1], int(sample_rate), ncandidates),
+                                   out=audio[b * ncandidates: (b + 1) * ncandidates])
+        limit = min(77, int(self.model.cfg.text_max_positions) - int(self.model.cfg.text_pad_id) - 1)   # (77: laion_clap's tokenizer call)
+        tokens = self.tokenizer(list(descriptions), padding=True, truncation=True, max_length=limit, return_tensors="pt")
+        text = self.model.text_embed(tokens["input_ids"], tokens.get("attention_mask"))
+        return self.model.score(audio, text, ncandidates)
+
+
+_CLAP_NEEDS_A_DIRECTORY = (
+    "ranker kind 'clap' without a checkpoint wraps a third-party model: the reference downloads laion_clap's 630k-best.pt from the "
+    "hub, which this build cannot do.  Pass {'kind': 'clap', 'checkpoint': <local ClapModel.save_pretrained directory>}, or attach "
+    "a callable ranker to model.text_ranker")
+
+
 def create_ranker(config, **kwargs) -> Optional[Ranker]:
     """reference ranking/__init__.py:15-30."""
     if config is None:
@@ -125,6 +190,11 @@ def create_ranker(config, **kwargs) -> Optional[Ranker]:
         return JudgeRanker(config, **kwargs)
     if isinstance(config, SoundActivityRankerConfig):
         return SoundActivityRanker(config)
+    if isinstance(config, dict) and config.get("kind") == "clap":
+        from .config import parse_ranker_config
+        config = parse_ranker_config(config)
+    if isinstance(config, ClapRankerConfig):
+        return ClapRanker(config, **kwargs)   # (NotImplementedError without a checkpoint directory: nothing can be downloaded)
     kind = config.get("kind") if isinstance(config, dict) else getattr(config, "kind", None)
     if kind == "ensemble":
         pairs = config["rankers"].values() if isinstance(config, dict) else config.rankers.values()
@@ -132,5 +202,5 @@ def create_ranker(config, **kwargs) -> Optional[Ranker]:
         cfgs, weights = zip(*[(parse_ranker_config(c) if isinstance(c, dict) else c, w) for c, w in pairs])
         return EnsembleRanker([create_ranker(c, **kwargs) for c in cfgs], list(weights))
     raise NotImplementedError(
-        f"ranker kind {kind!r} wraps a third-party model (CLAP / ImageBind / ...) that this build does not ship; "
+        f"ranker kind {kind!r} wraps a third-party model (ImageBind / ...) that this build does not ship; "
         "attach a callable ranker to model.text_ranker / model.visual_ranker instead")

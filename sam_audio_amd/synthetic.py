@@ -460,3 +460,47 @@ def make_hostile_vision(sd: Dict[str, torch.Tensor], cfg, seed: int = 0, outlier
         for name in ("ln_1.weight", "ln_2.weight"):
             out[p + name] = out[p + name] * torch.exp(torch.randn(W, generator=g) * norm_std).to(dev)
     return out
+
+
+# ---- CLAP (sam_audio_amd/clap.py) ---------------------------------------------------------------------------
+
+CLAP_MINI_FRONTEND = dict(feature_size=16, sampling_rate=48_000, hop_length=8, fft_window_size=64, nb_max_samples=2_000,
+                          frequency_min=0.0, frequency_max=14_000.0)
+
+
+def clap_config(name: str = "mini"):
+    """`transformers.ClapConfig` of the test sizes: "mini" (HTSAT 16 -> 8 -> 4 tokens a side, window 4, head width 24; RoBERTa hidden
+    64) or "real" (HTSAT-tiny / RoBERTa-base, the dims of laion/clap-htsat-unfused)."""
+    from transformers import ClapConfig
+    if name == "mini":
+        audio = dict(spec_size=64, num_mel_bins=16, patch_size=4, patch_stride=[4, 4], patch_embeds_hidden_size=96, depths=[2, 2, 2],
+                     num_attention_heads=[4, 8, 16], window_size=4, hidden_size=384, enable_fusion=False)
+        text = dict(hidden_size=64, num_attention_heads=2, num_hidden_layers=2, intermediate_size=128, vocab_size=100,
+                    max_position_embeddings=40, pad_token_id=1, bos_token_id=0, eos_token_id=2)
+        return ClapConfig(audio_config=audio, text_config=text, projection_dim=64)
+    if name == "real":
+        return ClapConfig(audio_config=dict(enable_fusion=False), text_config={}, projection_dim=512)
+    raise ValueError(f"unknown CLAP test config {name!r}")
+
+
+def init_clap_model(config, seed: int = 0):
+    """A seeded random `transformers.ClapModel` in eval mode whose every term counts: the relative-position bias tables (zeros at
+    initialisation), the BatchNorm running statistics and affine, and all LayerNorm weights and biases get non-trivial values."""
+    from transformers import ClapModel
+    torch.manual_seed(seed)
+    model = ClapModel(config).eval()
+    g = torch.Generator().manual_seed(seed + 1)
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if name.endswith("relative_position_bias_table"):
+                p.copy_(torch.randn(p.shape, generator=g))
+            elif "norm" in name.lower() and name.endswith(".weight"):
+                p.copy_(1.0 + 0.2 * torch.randn(p.shape, generator=g))
+            elif "norm" in name.lower() and name.endswith(".bias"):
+                p.copy_(0.2 * torch.randn(p.shape, generator=g))
+            elif name.endswith(".bias"):
+                p.copy_(0.1 * torch.randn(p.shape, generator=g))
+        bn = model.audio_model.audio_encoder.batch_norm
+        bn.running_mean.copy_(-30.0 + 5.0 * torch.randn(bn.running_mean.shape, generator=g))
+        bn.running_var.copy_(400.0 * (0.5 + torch.rand(bn.running_var.shape, generator=g)))
+    return model
