@@ -795,6 +795,58 @@ int samaudio_op_cross_attn_probs3(const float* q, const float* q_w, const float*
 int samaudio_op_cross_attn_fold3(const float* wo, const float* kv, int64_t kv_ld, void* ut3, int kp, int batch, int text_len,
                                  int ltp, int heads, samaudio_stream stream);
 
+/* ---- the kernels only the towers launch, one hook each (tests/test_tower_kernels_gpu.py) ------------------
+ * T5 prompt encoder, ModernBERT and CLAP text towers (t5_kernels.hip), PE-Core vision tower (vit_kernels.hip), Judge and span
+ * predictor (peav_kernels.hip).  Each hook refuses with SAMAUDIO_ERR_ARG, before any launch, what its kernel cannot do - the limits the
+ * towers' host code otherwise guarantees - and adds no arithmetic.  `precision` is the storage type of the tensors marked "act"
+ * (SAMAUDIO_F32 | SAMAUDIO_BF16 = the library's 16-bit format).  SAMAUDIO_ERR_STATE ("not in this build of the library") in a build
+ * without t5_kernels.hip / vit_kernels.hip (the CPU emulation of the launchers). */
+
+/* t5_attention_kernel: out [batch * tokens, heads * head_dim] act = softmax(scale * q k^T + bias[h][k - q] + key mask) v on q|k|v rows
+ * qkv [batch * tokens, 3 * heads * head_dim] act.  mask [batch, tokens] bytes (non-zero = key allowed); bias [heads, 2 * max_len - 1]
+ * f32 with the distance k - q at column k - q + max_len - 1, or NULL; window > 0: only keys with |k - q| <= window.  The softmax runs
+ * over the allowed keys; a row without one attends uniformly over all `tokens` keys; every query row is written, masked ones too.
+ * Refused: tokens outside [1, 512], head_dim outside [1, 128], a bias with max_len < tokens, null qkv / mask / out. */
+int samaudio_op_tower_attention(const void* qkv, const uint8_t* mask, const float* bias, void* out, int precision, int batch,
+                                int tokens, int heads, int head_dim, int max_len, float scale, int window, samaudio_stream stream);
+/* mbert_rope_kernel, in place: x' = x * cos + rotate_half(x) * sin on the q and k segments of qkv [rows, 3 * heads * head_dim] act,
+ * row m at position m % tokens of rope_cos / rope_sin [>= tokens, head_dim] f32; the v segment is not touched.  Refused: odd head_dim. */
+int samaudio_op_mbert_rope(void* qkv, const float* rope_cos, const float* rope_sin, int precision, int64_t rows, int tokens, int heads,
+                           int head_dim, samaudio_stream stream);
+/* geglu_kernel: out [rows, features] act = gelu(x[:, :features]) * x[:, features:] (erf form) of x [rows, 2 * features] act */
+int samaudio_op_geglu(const void* x, void* out, int precision, int64_t rows, int features, samaudio_stream stream);
+/* rope2d_split_kernel (fp32) / rope2d_split_bf16_kernel (16-bit): q|k|v rows qkv [n * tokens, 3 * heads * head_dim] act -> q, k
+ * [n, heads, tokens_padded, head_dim] with (x0, x1) -> (x0 c - x1 s, x0 s + x1 c) on adjacent pairs, c / s = rope_cos / rope_sin
+ * [tokens, head_dim / 2] f32 (both NULL: a copy), and vt [n, heads, head_dim, tokens_padded] = V^T; rows / columns tokens ..
+ * tokens_padded are written as zeros.  Refused: head_dim other than 64 | 128, tokens_padded % 64, tokens_padded < tokens, one table
+ * without the other, 16-bit: a pointer that is not aligned to 16 bytes. */
+int samaudio_op_rope2d_split(const void* qkv, const float* rope_cos, const float* rope_sin, void* q, void* k, void* vt, int precision,
+                             int n, int tokens, int tokens_padded, int heads, int head_dim, samaudio_stream stream);
+/* pool_attention_kernel: out [n, heads * head_dim] act = softmax_t(q_h . k[f, t, h] * head_dim^-0.5) . v[f, t, h] for one query
+ * q [heads * head_dim] f32 over kv [n * tokens, 2 * heads * head_dim] act = (k | v).  Refused: head_dim other than 64 | 128, tokens < 1. */
+int samaudio_op_pool_attention(const float* q, const void* kv, void* out, int precision, int n, int tokens, int heads, int head_dim,
+                               samaudio_stream stream);
+/* l2_normalize_kernel, in place: x[r, :] /= max(||x[r, :]||, 1e-12) on x [rows, dim] f32 */
+int samaudio_op_l2_normalize(float* x, int rows, int dim, samaudio_stream stream);
+/* token_mean_kernel: mean over the `tokens` rows of each item of x [n * tokens, x_ld] f32 (columns [0, dim)) -> out_f32 [n, dim] f32
+ * and / or out_act [n, dim] act (the same fp32 value, rounded).  Refused: both outputs NULL, x_ld < dim. */
+int samaudio_op_token_mean(const float* x, int64_t x_ld, float* out_f32, void* out_act, int precision, int n, int tokens, int dim,
+                           samaudio_stream stream);
+/* peav_cls_mask_kernel: h [batch, frames + 1, dim] f32: row 0 of every item = cls [dim], the other rows are not touched;
+ * mask_s [batch, frames + 1] bytes: mask_s[b][0] = pad[b][0] != 0, mask_s[b][1 + t] = pad[b][t] != 0 (pad [batch, frames] bytes; NULL:
+ * all 1).  Refused: dim % 4, h or cls not aligned to 16 bytes. */
+int samaudio_op_peav_cls_mask(float* h, const float* cls, const uint8_t* pad, uint8_t* mask_s, int batch, int frames, int dim,
+                              samaudio_stream stream);
+/* judge_pool_head_kernel: out [batch, 4] f32 = (mean over the frames t with mask_s[b][1 + t] != 0 of hidden[b][1 + t][:]) . head_w[j][:]
+ * * std[j] + mean[j]; hidden [batch, frames + 1, dim] f32 (row 0, the class token, and mask_s[b][0] are not read), head_w [4, dim];
+ * an item without a valid frame yields mean.  Refused: dim > 4096. */
+int samaudio_op_judge_pool_head(const float* hidden, const uint8_t* mask_s, const float* head_w, const float* mean, const float* std_,
+                                float* out, int batch, int frames, int dim, samaudio_stream stream);
+/* frame_logits_kernel: out [batch, frames] f32 = <audio[a_off + b * a_bstride + t * embed_dim + :], text[b][:]> * scale[0] + bias[0]
+ * (scale, bias: device scalars).  Refused: embed_dim % 4, a_off % 4, a_bstride % 4, audio or text not aligned to 16 bytes. */
+int samaudio_op_frame_logits(const float* audio, int64_t a_bstride, int64_t a_off, const float* text, const float* scale,
+                             const float* bias, float* out, int batch, int frames, int embed_dim, samaudio_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

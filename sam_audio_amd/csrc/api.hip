@@ -595,6 +595,125 @@ int samaudio_op_cross_attn_fold3(const float* wo, const float* kv, int64_t kv_ld
                  "cross_attn_fold3");
 }
 
+// ---- hooks of the kernels only the towers launch (tests/test_tower_kernels_gpu.py) --------------------------
+// Each refuses what its kernel cannot do - limits that otherwise live in t5.hip, mbert.hip, clap.hip, vit.hip and peav.hip - and calls
+// the launcher; no arithmetic here.  The launchers of t5_kernels.hip / vit_kernels.hip are weak (kernels.h).
+namespace {
+int not_built(const char* what) {
+  g_err = std::string(what) + ": not in this build of the library";
+  return SAMAUDIO_ERR_STATE;
+}
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+constexpr int kMaxGridYZ = 65535;
+}  // namespace
+
+int samaudio_op_tower_attention(const void* qkv, const uint8_t* mask, const float* bias, void* out, int precision, int batch,
+                                int tokens, int heads, int head_dim, int max_len, float scale, int window, samaudio_stream stream) {
+  if (!qkv || !mask || !out) return bad("tower_attention: null qkv / mask / out");
+  if (precision != SAMAUDIO_F32 && precision != SAMAUDIO_BF16) return bad("tower_attention: precision");
+  if (tokens < 1 || tokens > 512) return bad("tower_attention: tokens outside [1, 512]");
+  if (head_dim < 1 || head_dim > 128) return bad("tower_attention: head_dim outside [1, 128]");
+  if (batch < 1 || batch > kMaxGridYZ || heads < 1 || heads > kMaxGridYZ) return bad("tower_attention: batch / heads");
+  if (bias && max_len < tokens) return bad("tower_attention: a bias table of max_len < tokens");
+  if (!sa::launch_t5_attention) return not_built("tower_attention");
+  return hip_ret(sa::launch_t5_attention(qkv, mask, bias, out, precision == SAMAUDIO_BF16, batch, tokens, heads, head_dim, max_len,
+                                         scale, window, (hipStream_t)stream), "tower_attention");
+}
+
+int samaudio_op_mbert_rope(void* qkv, const float* rope_cos, const float* rope_sin, int precision, int64_t rows, int tokens, int heads,
+                           int head_dim, samaudio_stream stream) {
+  if (!qkv || !rope_cos || !rope_sin) return bad("mbert_rope: null argument");
+  if (precision != SAMAUDIO_F32 && precision != SAMAUDIO_BF16) return bad("mbert_rope: precision");
+  if (head_dim < 2 || head_dim % 2) return bad("mbert_rope: odd head_dim");
+  if (rows < 1 || rows > INT32_MAX || tokens < 1 || heads < 1) return bad("mbert_rope: rows / tokens / heads");
+  if (!sa::launch_mbert_rope) return not_built("mbert_rope");
+  return hip_ret(sa::launch_mbert_rope(qkv, rope_cos, rope_sin, precision == SAMAUDIO_BF16, (long)rows, tokens, heads, head_dim,
+                                       (hipStream_t)stream), "mbert_rope");
+}
+
+int samaudio_op_geglu(const void* x, void* out, int precision, int64_t rows, int features, samaudio_stream stream) {
+  if (!x || !out) return bad("geglu: null argument");
+  if (precision != SAMAUDIO_F32 && precision != SAMAUDIO_BF16) return bad("geglu: precision");
+  if (rows < 1 || features < 1) return bad("geglu: rows / features");
+  if (!sa::launch_geglu) return not_built("geglu");
+  return hip_ret(sa::launch_geglu(x, out, precision == SAMAUDIO_BF16, (long)rows, features, (hipStream_t)stream), "geglu");
+}
+
+int samaudio_op_rope2d_split(const void* qkv, const float* rope_cos, const float* rope_sin, void* q, void* k, void* vt, int precision,
+                             int n, int tokens, int tokens_padded, int heads, int head_dim, samaudio_stream stream) {
+  if (!qkv || !q || !k || !vt) return bad("rope2d_split: null argument");
+  if ((rope_cos == nullptr) != (rope_sin == nullptr)) return bad("rope2d_split: rope_cos and rope_sin go together");
+  if (precision != SAMAUDIO_F32 && precision != SAMAUDIO_BF16) return bad("rope2d_split: precision");
+  if (head_dim != 64 && head_dim != 128) return bad("rope2d_split: head_dim");
+  if (tokens < 1 || tokens_padded % 64 || tokens_padded < tokens) return bad("rope2d_split: tokens_padded");
+  if (n < 1 || n > kMaxGridYZ || heads < 1 || heads > kMaxGridYZ) return bad("rope2d_split: n / heads");
+  if (precision == SAMAUDIO_BF16 && !(aligned16(qkv) && aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(rope_cos) &&
+                                      aligned16(rope_sin)))
+    return bad("rope2d_split: the 16-bit kernel moves 16 bytes per lane - every pointer must be aligned to 16 bytes");
+  if (precision == SAMAUDIO_F32 && (((uintptr_t)qkv | (uintptr_t)q | (uintptr_t)k) & 7))
+    return bad("rope2d_split: qkv, q and k must be aligned to 8 bytes");
+  if (!sa::launch_rope2d_split) return not_built("rope2d_split");
+  return hip_ret(sa::launch_rope2d_split(qkv, rope_cos, rope_sin, q, k, vt, precision == SAMAUDIO_BF16, n, tokens, tokens_padded, heads,
+                                         head_dim, (hipStream_t)stream), "rope2d_split");
+}
+
+int samaudio_op_pool_attention(const float* q, const void* kv, void* out, int precision, int n, int tokens, int heads, int head_dim,
+                               samaudio_stream stream) {
+  if (!q || !kv || !out) return bad("pool_attention: null argument");
+  if (precision != SAMAUDIO_F32 && precision != SAMAUDIO_BF16) return bad("pool_attention: precision");
+  if (head_dim != 64 && head_dim != 128) return bad("pool_attention: head_dim");
+  if (tokens < 1) return bad("pool_attention: tokens < 1");
+  if (n < 1 || n > kMaxGridYZ || heads < 1) return bad("pool_attention: n / heads");
+  if (!sa::launch_pool_attention) return not_built("pool_attention");
+  return hip_ret(sa::launch_pool_attention(q, kv, out, precision == SAMAUDIO_BF16, n, tokens, heads, head_dim, (hipStream_t)stream),
+                 "pool_attention");
+}
+
+int samaudio_op_l2_normalize(float* x, int rows, int dim, samaudio_stream stream) {
+  if (!x || rows < 1 || dim < 1) return bad("l2_normalize: null x / rows, dim < 1");
+  if (!sa::launch_l2_normalize) return not_built("l2_normalize");
+  return hip_ret(sa::launch_l2_normalize(x, rows, dim, (hipStream_t)stream), "l2_normalize");
+}
+
+int samaudio_op_token_mean(const float* x, int64_t x_ld, float* out_f32, void* out_act, int precision, int n, int tokens, int dim,
+                           samaudio_stream stream) {
+  if (!x) return bad("token_mean: null x");
+  if (!out_f32 && !out_act) return bad("token_mean: both outputs null");
+  if (precision != SAMAUDIO_F32 && precision != SAMAUDIO_BF16) return bad("token_mean: precision");
+  if (n < 1 || tokens < 1 || dim < 1 || x_ld < dim) return bad("token_mean: n, tokens, dim < 1 or x_ld < dim");
+  if (!sa::launch_token_mean) return not_built("token_mean");
+  return hip_ret(sa::launch_token_mean(x, (long)x_ld, out_f32, out_act, precision == SAMAUDIO_BF16, n, tokens, dim, (hipStream_t)stream),
+                 "token_mean");
+}
+
+int samaudio_op_peav_cls_mask(float* h, const float* cls, const uint8_t* pad, uint8_t* mask_s, int batch, int frames, int dim,
+                              samaudio_stream stream) {
+  if (!h || !cls || !mask_s) return bad("peav_cls_mask: null h / cls / mask_s");
+  if (batch < 1 || frames < 1 || dim < 4 || dim % 4) return bad("peav_cls_mask: batch, frames < 1 or dim % 4");
+  if (!aligned16(h) || !aligned16(cls)) return bad("peav_cls_mask: h and cls must be aligned to 16 bytes");
+  return hip_ret(sa::launch_peav_cls_mask(h, cls, pad, mask_s, batch, frames, dim, (hipStream_t)stream), "peav_cls_mask");
+}
+
+int samaudio_op_judge_pool_head(const float* hidden, const uint8_t* mask_s, const float* head_w, const float* mean, const float* std_,
+                                float* out, int batch, int frames, int dim, samaudio_stream stream) {
+  if (!hidden || !mask_s || !head_w || !mean || !std_ || !out) return bad("judge_pool_head: null argument");
+  if (dim < 1 || dim > 4096) return bad("judge_pool_head: dim outside [1, 4096] (the pooled row lives in LDS)");
+  if (batch < 1 || frames < 1) return bad("judge_pool_head: batch / frames");
+  return hip_ret(sa::launch_judge_pool_head(hidden, mask_s, head_w, mean, std_, out, batch, frames, dim, (hipStream_t)stream),
+                 "judge_pool_head");
+}
+
+int samaudio_op_frame_logits(const float* audio, int64_t a_bstride, int64_t a_off, const float* text, const float* scale,
+                             const float* bias, float* out, int batch, int frames, int embed_dim, samaudio_stream stream) {
+  if (!audio || !text || !scale || !bias || !out) return bad("frame_logits: null argument");
+  if (embed_dim < 4 || embed_dim % 4) return bad("frame_logits: embed_dim % 4");
+  if (a_off < 0 || a_off % 4 || a_bstride < 0 || a_bstride % 4) return bad("frame_logits: a_off % 4 / a_bstride % 4");
+  if (batch < 1 || frames < 1) return bad("frame_logits: batch / frames");
+  if (!aligned16(audio) || !aligned16(text)) return bad("frame_logits: audio and text must be aligned to 16 bytes");
+  return hip_ret(sa::launch_frame_logits(audio, (long)a_bstride, (long)a_off, text, scale, bias, out, batch, frames, embed_dim,
+                                         (hipStream_t)stream), "frame_logits");
+}
+
 // ---- Judge reranker ----------------------------------------------------------------------------------
 int samaudio_judge_create(const samaudio_judge_config* cfg, samaudio_judge** out) {
   if (!cfg || !out) return bad("samaudio_judge_create: null argument");

@@ -409,25 +409,30 @@ __attribute__((weak)) hipError_t launch_resize_video(const unsigned char* frames
                                                      const unsigned char* mask, int mc, const int* pick, int n, int S, int mode,
                                                      void* out, bool bf16, int P, int Kp, hipStream_t st);
 // q|k|v rows [n*T, 3*H*hd] -> Q, K [n,H,Tp,hd] (adjacent-pair rotation by rc / rs [T, hd/2]; null = none), V^T [n,H,hd,Tp]
-hipError_t launch_rope2d_split(const void* qkv, const float* rc, const float* rs, void* Q, void* K, void* Vt, bool bf16,
-                               int n, int T, int Tp, int H, int head_dim, hipStream_t st);
+// (the four below are weak: the CPU emulation of the launchers - oracle/emu - links api.hip without vit_kernels.hip, and their parity
+// hooks then answer SAMAUDIO_ERR_STATE)
+__attribute__((weak)) hipError_t launch_rope2d_split(const void* qkv, const float* rc, const float* rs, void* Q, void* K, void* Vt,
+                                                     bool bf16, int n, int T, int Tp, int H, int head_dim, hipStream_t st);
 // one query per head over all tokens: q [H*hd] f32, kv rows [n*T, 2*H*hd] = (k | v) -> out [n, H*hd]
-hipError_t launch_pool_attention(const float* q, const void* kv, void* out, bool bf16, int n, int T, int H, int head_dim,
-                                 hipStream_t st);
-hipError_t launch_l2_normalize(float* x, int rows, int D, hipStream_t st);
+__attribute__((weak)) hipError_t launch_pool_attention(const float* q, const void* kv, void* out, bool bf16, int n, int T, int H,
+                                                       int head_dim, hipStream_t st);
+__attribute__((weak)) hipError_t launch_l2_normalize(float* x, int rows, int D, hipStream_t st);
 // out[f, :] = mean over the T tokens of x[f, t, :]
-hipError_t launch_token_mean(const float* x, long x_ld, float* out_f32, void* out_act, bool bf16, int n, int T, int D,
-                             hipStream_t st);
+__attribute__((weak)) hipError_t launch_token_mean(const float* x, long x_ld, float* out_f32, void* out_act, bool bf16, int n, int T,
+                                                   int D, hipStream_t st);
 
 // ---- T5 prompt encoder (t5_kernels.hip) ------------------------------------------------------------
 hipError_t launch_t5_embed(const long long* ids, const float* table, float* out, long M, int D, int vocab, hipStream_t st);
 // softmax(q k^T + bias[h][k - q] + key mask) v per (item, head, query row); qkv [B*Lt, 3*H*dkv]; Lt <= 512, dkv <= 128
 // (bias nullable; scale multiplies q k^T; window > 0: only keys within +-window tokens)
-hipError_t launch_t5_attention(const void* qkv, const unsigned char* mask, const float* bias, void* out, bool bf16, int B,
-                               int Lt, int H, int dkv, int max_len, float scale, int window, hipStream_t st);
+// (this one and the two below are weak: oracle/emu links api.hip without t5_kernels.hip; their parity hooks then answer
+// SAMAUDIO_ERR_STATE)
+__attribute__((weak)) hipError_t launch_t5_attention(const void* qkv, const unsigned char* mask, const float* bias, void* out, bool bf16,
+                                                     int B, int Lt, int H, int dkv, int max_len, float scale, int window,
+                                                     hipStream_t st);
 // ModernBERT text tower (mbert.hip): rotate-half RoPE of the q / k segments of q|k|v rows in place; gated GELU
-hipError_t launch_mbert_rope(void* qkv, const float* cs, const float* sn, bool bf16, long M, int Lt, int H, int hd,
-                             hipStream_t st);
-hipError_t launch_geglu(const void* x, void* out, bool bf16, long M, int F, hipStream_t st);
+__attribute__((weak)) hipError_t launch_mbert_rope(void* qkv, const float* cs, const float* sn, bool bf16, long M, int Lt, int H, int hd,
+                                                   hipStream_t st);
+__attribute__((weak)) hipError_t launch_geglu(const void* x, void* out, bool bf16, long M, int F, hipStream_t st);
 
 }  // namespace sa

@@ -338,6 +338,17 @@ _PROTOS = {
     "samaudio_op_cross_attn_probs": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
     "samaudio_op_cross_attn_probs3": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
     "samaudio_op_cross_attn_fold3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    # the kernels only the towers launch (tests/test_tower_kernels_gpu.py)
+    "samaudio_op_tower_attention": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p]),
+    "samaudio_op_mbert_rope": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "samaudio_op_geglu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    "samaudio_op_rope2d_split": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p]),
+    "samaudio_op_pool_attention": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "samaudio_op_l2_normalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "samaudio_op_token_mean": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "samaudio_op_peav_cls_mask": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+    "samaudio_op_judge_pool_head": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]),
+    "samaudio_op_frame_logits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
     "samaudio_judge_create": (C.c_int, [C.POINTER(JudgeConfig), C.POINTER(C.c_void_p)]),
     "samaudio_judge_destroy": (None, [C.c_void_p]),
     "samaudio_judge_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),

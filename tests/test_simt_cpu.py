@@ -129,3 +129,14 @@ def test_layer_kernels_on_the_simulator_plain_and_with_poisoned_lds():
     for extra in ({}, {"SAMAUDIO_SIMT_POISON": "1"}):
         out = _run(subset, 600, **extra)
         assert "141 passed" in out and "failed" not in out and "skipped" not in out, out
+
+
+def test_tower_kernels_on_the_simulator_plain_and_with_poisoned_lds():
+    """All of tests/test_tower_kernels_gpu.py (the kernels only the towers launch, each against float64 through its own hook; bfloat16
+    library, so every case but the fp16 ones - Lt = 512 and the 129 x 8200 GEGLU included: nothing is left out) - once plain and once with
+    every LDS array full of NaN patterns before each workgroup: the pooling kernel's waves without a token (T < 4) and the attention
+    rows without an allowed key are where a kernel could consume LDS it never wrote.  125 tests; measured 10 s plain and 30 s poisoned
+    on an 8-core host."""
+    for extra in ({}, {"SAMAUDIO_SIMT_POISON": "1"}):
+        out = _run(["tests/test_tower_kernels_gpu.py"], 600, **extra)
+        assert "125 passed" in out and "failed" not in out and "skipped" not in out, out
