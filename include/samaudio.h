@@ -126,7 +126,8 @@ int samaudio_set_workspace(samaudio_ctx* ctx, void* workspace, size_t bytes);
 /*   SAMAUDIO_OPT_SENTINEL (default 0; validation aid, never on in timed runs): value 1 makes the context scan every 16-bit tensor a
  *   GEMM of the hot path writes (and the RMSNorm / attention outputs that feed GEMMs) for its largest magnitude and for
  *   non-finite values, per GEMM class, on the launch stream - an IEEE-fp16 operand that overflowed (|x| > 65504 -> inf) is then
- *   REPORTED by samaudio_sentinel_read with the class it came from instead of propagating silently.  Allocates 4 KiB of device
+ *   REPORTED by samaudio_sentinel_read with the class it came from instead of propagating silently.  Non-finite = NaN and +-Inf,
+ *   nothing else: every finite value, however large, goes into the magnitude (samaudio_op_sentinel).  Allocates 4 KiB of device
  *   memory on first use (the only allocation of the library besides the checksum trace). */
 #define SAMAUDIO_OPT_SENTINEL 7
 /* (option 8 was SAMAUDIO_OPT_ODE_GRAPH, rounds 5: a solve's launches replayed as one HIP graph.  Bitwise equal and measured at
@@ -846,6 +847,70 @@ int samaudio_op_judge_pool_head(const float* hidden, const uint8_t* mask_s, cons
  * (scale, bias: device scalars).  Refused: embed_dim % 4, a_off % 4, a_bstride % 4, audio or text not aligned to 16 bytes. */
 int samaudio_op_frame_logits(const float* audio, int64_t a_bstride, int64_t a_off, const float* text, const float* scale,
                              const float* bias, float* out, int batch, int frames, int embed_dim, samaudio_stream stream);
+
+/* ---- the glue kernels between those, one hook each (tests/test_glue_kernels_gpu.py) ------------------------
+ * kernels.hip, peav_kernels.hip, t5_kernels.hip, clap_kernels.hip.  Each hook refuses with SAMAUDIO_ERR_ARG, before any launch, null
+ * pointers, sizes < 1 and what its kernel cannot do, then calls the launcher the engine and the towers call; no arithmetic here.
+ * `precision` as above (the storage type of the tensors marked "act").  SAMAUDIO_ERR_STATE ("not in this build of the library") where
+ * the launcher is missing (the CPU emulation of the launchers: ode_stage, embed_rows, clap_text_embed, sentinel). */
+
+/* time_features_kernel: temb [n_time, freq_dim] act = (cos | sin)(t[j] * freqs[i]), i < freq_dim / 2, and tsin [n_time, dim] f32 =
+ * (cos | sin)(t[j] * inv_freq[i]), i < dim / 2; t, freqs [freq_dim / 2], inv_freq [dim / 2] f32.  Refused: odd freq_dim / dim. */
+int samaudio_op_time_features(const float* t, int n_time, const float* freqs, int freq_dim, const float* inv_freq, int dim, void* temb,
+                              float* tsin, int precision, samaudio_stream stream);
+/* add_rowvec_kernel: out [rows, dim] act = x [rows, dim] f32 + vec[(r / rows_per_batch) * vec_ld + :] (vec_ld = 0: one vector for
+ * every row).  Refused: dim % 4, vec_ld % 4, x or vec not aligned to 16 bytes, out not aligned to 16 (f32) / 8 (16-bit) bytes. */
+int samaudio_op_add_rowvec(const float* x, const float* vec, int64_t vec_ld, void* out, int precision, int rows, int dim,
+                           int rows_per_batch, samaudio_stream stream);
+/* headnorm_layers_kernel, in place: per (row, layer, head) RMSNorm over head_dim of the K half of kv_all [rows, layers * 2 * heads *
+ * head_dim] act (layer l's block = (k | v), the v half is not touched), times w_all[l][:] (w_all [layers, head_dim] f32).
+ * Refused: head_dim other than 64 | 128, kv_all not aligned to 8 (f32) / 4 (16-bit) bytes. */
+int samaudio_op_headnorm_layers(void* kv_all, const float* w_all, int precision, int rows, int layers, int heads, int head_dim,
+                                float eps, samaudio_stream stream);
+/* to_act_kernel: out[b][halo + t][c] act = c < c_in ? in[b * in_bstride + in_col0 + t * in_ld + c] : 0 for t < frames, c < c_out
+ * (in f32; item b of out at b * out_bstride elements, 0 = dense (frames + 2 halo) * c_out; halo rows are not touched; the cast rounds
+ * to nearest even).  Refused: c_in > c_out, negative strides / offsets / halo. */
+int samaudio_op_to_act(const float* in, int64_t in_bstride, int64_t in_ld, int in_col0, void* out, int64_t out_bstride, int precision,
+                       int batch, int64_t frames, int c_in, int c_out, int halo, samaudio_stream stream);
+/* zero_halo_kernel: rows [0, halo) and [halo + frames, frames + 2 halo) of every item of buf [batch][frames + 2 halo][channels] act
+ * = +0; the other rows are not touched.  Refused: halo < 1. */
+int samaudio_op_zero_halo(void* buf, int precision, int batch, int64_t frames, int channels, int halo, samaudio_stream stream);
+/* anchor_gather_kernel: out [batch * frames, embed_dim] act = emb[ids[b][align[b][t]]][:] (emb [vocab, embed_dim] f32, ids [batch,
+ * n_ids] i64, align [batch, frames] i64); a slot outside [0, n_ids) and a token outside [0, vocab) are clamped into range. */
+int samaudio_op_anchor_gather(const float* emb, const int64_t* ids, int n_ids, const int64_t* align, void* out, int precision,
+                              int batch, int frames, int embed_dim, int vocab, samaudio_stream stream);
+/* set_floats_kernel: dst[0 .. n) (device) = host_values[0 .. n) (HOST), handed over as kernel arguments, 64 per launch */
+int samaudio_op_set_floats(float* dst, const float* host_values, int n, samaudio_stream stream);
+/* ode_stage_kernel: out[i] = y0[i] + scale * sum_{j < n_src} coef[j] * k[j][i] for i < n, f32; k, coef: HOST arrays of FOUR device
+ * pointers / floats, of which the kernel reads the first n_src (the rest are handed to it as they are and never used: the engine
+ * leaves out the sources whose tableau coefficient is 0); out may be y0.  Refused: n_src outside [1, 4], n % 4, a pointer in use
+ * that is not aligned to 16 bytes. */
+int samaudio_op_ode_stage(const float* y0, const float* const* k, const float* coef, int n_src, float scale, float* out, int64_t n,
+                          samaudio_stream stream);
+/* repeat_rows_u8_kernel: dst [rows * rep, width] bytes, dst[b * rep + c][:] = src[b][:] */
+int samaudio_op_repeat_rows(const uint8_t* src, uint8_t* dst, int rows, int rep, int width, samaudio_stream stream);
+/* repeat_items_f32_kernel: the same for items of `elems` f32 values.  Refused: elems % 4, src or dst not aligned to 16 bytes. */
+int samaudio_op_repeat_items(const float* src, float* dst, int items, int rep, int64_t elems, samaudio_stream stream);
+/* t5_embed_kernel (T5 and ModernBERT towers): out [rows, dim] f32 = table[ids[m]][:] (table [vocab, dim] f32, ids i64; an id outside
+ * [0, vocab) is clamped into range).  Refused: dim % 4, table or out not aligned to 16 bytes. */
+int samaudio_op_embed_rows(const int64_t* ids, const float* table, float* out, int64_t rows, int dim, int vocab,
+                           samaudio_stream stream);
+/* clap_text_embed_kernel: out [rows, tokens, dim] f32 = word[ids] + pos[position] + type[0], position = pad_id + (number of ids !=
+ * pad_id in the row up to and including the token) for an id != pad_id, pad_id otherwise (transformers'
+ * create_position_ids_from_input_ids); word [vocab, dim], pos [max_positions, dim], type [>= 1, dim] f32; ids outside [0, vocab) are
+ * clamped.  Refused: tokens > 1024, max_positions < pad_id + tokens + 1, pad_id < 0. */
+int samaudio_op_clap_text_embed(const int64_t* ids, const float* word, const float* pos, const float* type, float* out, int rows,
+                                int tokens, int dim, int vocab, int pad_id, int max_positions, samaudio_stream stream);
+/* sentinel_scan_kernel + sentinel_fold_kernel (SAMAUDIO_OPT_SENTINEL): scans x [rows, cols] with row pitch ld >= cols elements (the
+ * pitch gap is not read) and folds into the caller's slot: slot[0] = max(slot[0], largest finite |x|), slot[1] += number of NaN and
+ * +-Inf elements - every finite value counts as finite, the largest ones of bfloat16 and fp32 included.  format 0: f32, 1: the
+ * library's 16-bit format, 2: the alt 16-bit format (bfloat16).  scratch: 2 * 256 floats, written by the launch (as many partials as
+ * it has workgroups).  Refused: format outside 0..2, ld < cols. */
+int samaudio_op_sentinel(const void* x, int format, int64_t rows, int cols, int64_t ld, float* scratch, float* slot,
+                         samaudio_stream stream);
+/* hash_items_kernel (SAMAUDIO_TRACE_HASH): out[b] u64 = sum_i (x[b][i] ^ (u32)(i * 0x9E3779B1)) * (2 i + 1) mod 2^64 over the
+ * `words` u32 words of item b */
+int samaudio_op_hash_items(const uint32_t* x, int64_t words, int items, uint64_t* out, samaudio_stream stream);
 
 #ifdef __cplusplus
 }

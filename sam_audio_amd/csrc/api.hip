@@ -714,6 +714,153 @@ int samaudio_op_frame_logits(const float* audio, int64_t a_bstride, int64_t a_of
                                          (hipStream_t)stream), "frame_logits");
 }
 
+// ---- hooks of the glue kernels between those (tests/test_glue_kernels_gpu.py) -------------------------------
+// The same rule: argument checks, then the launcher the engine / the towers call, unchanged.  launch_ode_stage, launch_t5_embed and
+// launch_clap_text_embed are weak (kernels.h); so is sa::sentinel_built, defined beside the real launch_sentinel only (the emulation's is a stub).
+namespace {
+bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+bool storage(int precision) { return precision == SAMAUDIO_F32 || precision == SAMAUDIO_BF16; }
+}  // namespace
+
+int samaudio_op_time_features(const float* t, int n_time, const float* freqs, int freq_dim, const float* inv_freq, int dim, void* temb,
+                              float* tsin, int precision, samaudio_stream stream) {
+  if (!t || !freqs || !inv_freq || !temb || !tsin) return bad("time_features: null argument");
+  if (!storage(precision)) return bad("time_features: precision");
+  if (n_time < 1) return bad("time_features: n_time < 1");
+  if (freq_dim < 2 || freq_dim % 2) return bad("time_features: odd freq_dim");
+  if (dim < 2 || dim % 2) return bad("time_features: odd dim");
+  return hip_ret(sa::launch_time_features(t, n_time, freqs, freq_dim, inv_freq, dim, temb, tsin, precision == SAMAUDIO_BF16,
+                                          (hipStream_t)stream), "time_features");
+}
+
+int samaudio_op_add_rowvec(const float* x, const float* vec, int64_t vec_ld, void* out, int precision, int rows, int dim,
+                           int rows_per_batch, samaudio_stream stream) {
+  if (!x || !vec || !out) return bad("add_rowvec: null argument");
+  if (!storage(precision)) return bad("add_rowvec: precision");
+  if (rows < 1 || rows_per_batch < 1) return bad("add_rowvec: rows / rows_per_batch < 1");
+  if (dim < 4 || dim % 4) return bad("add_rowvec: dim % 4");
+  if (vec_ld < 0 || vec_ld % 4) return bad("add_rowvec: vec_ld % 4");
+  if (!aligned16(x) || !aligned16(vec) || !aligned_to(out, precision == SAMAUDIO_BF16 ? 8 : 16))
+    return bad("add_rowvec: x and vec must be aligned to 16 bytes, out to 16 (fp32) / 8 (16-bit)");
+  return hip_ret(sa::launch_add_rowvec(x, vec, (long)vec_ld, out, precision == SAMAUDIO_BF16, rows, dim, rows_per_batch,
+                                       (hipStream_t)stream), "add_rowvec");
+}
+
+int samaudio_op_headnorm_layers(void* kv_all, const float* w_all, int precision, int rows, int layers, int heads, int head_dim,
+                                float eps, samaudio_stream stream) {
+  if (!kv_all || !w_all) return bad("headnorm_layers: null argument");
+  if (!storage(precision)) return bad("headnorm_layers: precision");
+  if (head_dim != 64 && head_dim != 128) return bad("headnorm_layers: head_dim");
+  if (rows < 1 || layers < 1 || heads < 1) return bad("headnorm_layers: rows / layers / heads < 1");
+  if (!aligned_to(kv_all, precision == SAMAUDIO_BF16 ? 4 : 8)) return bad("headnorm_layers: kv_all must be aligned to 8 (fp32) / 4 (16-bit) bytes");
+  return hip_ret(sa::launch_headnorm_layers(kv_all, w_all, precision == SAMAUDIO_BF16, rows, layers, heads, eps, (hipStream_t)stream,
+                                            head_dim), "headnorm_layers");
+}
+
+int samaudio_op_to_act(const float* in, int64_t in_bstride, int64_t in_ld, int in_col0, void* out, int64_t out_bstride, int precision,
+                       int batch, int64_t frames, int c_in, int c_out, int halo, samaudio_stream stream) {
+  if (!in || !out) return bad("to_act: null argument");
+  if (!storage(precision)) return bad("to_act: precision");
+  if (batch < 1 || batch > kMaxGridYZ || frames < 1 || c_in < 1 || c_out < 1) return bad("to_act: batch, frames, c_in, c_out < 1");
+  if (c_in > c_out) return bad("to_act: c_in > c_out");
+  if (in_bstride < 0 || in_ld < 0 || in_col0 < 0 || out_bstride < 0 || halo < 0) return bad("to_act: a negative stride / offset / halo");
+  return hip_ret(sa::launch_to_act(in, (long)in_bstride, (long)in_ld, in_col0, out, (long)out_bstride, precision == SAMAUDIO_BF16, batch,
+                                   (long)frames, c_in, c_out, halo, (hipStream_t)stream), "to_act");
+}
+
+int samaudio_op_zero_halo(void* buf, int precision, int batch, int64_t frames, int channels, int halo, samaudio_stream stream) {
+  if (!buf) return bad("zero_halo: null buf");
+  if (!storage(precision)) return bad("zero_halo: precision");
+  if (batch < 1 || batch > kMaxGridYZ || frames < 1 || channels < 1 || halo < 1) return bad("zero_halo: batch, frames, channels, halo < 1");
+  return hip_ret(sa::launch_zero_halo(buf, precision == SAMAUDIO_BF16, batch, (long)frames, channels, halo, (hipStream_t)stream),
+                 "zero_halo");
+}
+
+int samaudio_op_anchor_gather(const float* emb, const int64_t* ids, int n_ids, const int64_t* align, void* out, int precision,
+                              int batch, int frames, int embed_dim, int vocab, samaudio_stream stream) {
+  if (!emb || !ids || !align || !out) return bad("anchor_gather: null argument");
+  if (!storage(precision)) return bad("anchor_gather: precision");
+  if (n_ids < 1 || batch < 1 || frames < 1 || embed_dim < 1 || vocab < 1) return bad("anchor_gather: n_ids, batch, frames, embed_dim, vocab < 1");
+  if (!aligned_to(ids, 8) || !aligned_to(align, 8)) return bad("anchor_gather: ids and align must be aligned to 8 bytes");
+  return hip_ret(sa::launch_anchor_gather(emb, (const long*)ids, n_ids, (const long*)align, out, precision == SAMAUDIO_BF16, batch,
+                                          frames, embed_dim, vocab, (hipStream_t)stream), "anchor_gather");
+}
+
+int samaudio_op_set_floats(float* dst, const float* host_values, int n, samaudio_stream stream) {
+  if (!dst || !host_values || n < 1) return bad("set_floats: null argument or n < 1");
+  return hip_ret(sa::launch_set_floats(dst, host_values, n, (hipStream_t)stream), "set_floats");
+}
+
+int samaudio_op_ode_stage(const float* y0, const float* const* k, const float* coef, int n_src, float scale, float* out, int64_t n,
+                          samaudio_stream stream) {
+  if (!y0 || !k || !coef || !out) return bad("ode_stage: null argument");
+  if (n_src < 1 || n_src > 4) return bad("ode_stage: n_src outside [1, 4]");
+  if (n < 4 || n % 4) return bad("ode_stage: n % 4");
+  if (!aligned16(y0) || !aligned16(out)) return bad("ode_stage: every pointer must be aligned to 16 bytes");
+  sa::OdeStageArgs a{};
+  a.n_src = n_src;
+  for (int j = 0; j < 4; ++j) {   // entries n_src .. 3 travel as they are: the kernel must not look at them
+    if (j < n_src && !k[j]) return bad("ode_stage: null argument");
+    if (j < n_src && !aligned16(k[j])) return bad("ode_stage: every pointer must be aligned to 16 bytes");
+    a.k[j] = k[j];
+    a.coef[j] = coef[j];
+  }
+  if (!sa::launch_ode_stage) return not_built("ode_stage");
+  return hip_ret(sa::launch_ode_stage(y0, a, scale, out, (long)n, (hipStream_t)stream), "ode_stage");
+}
+
+int samaudio_op_repeat_rows(const uint8_t* src, uint8_t* dst, int rows, int rep, int width, samaudio_stream stream) {
+  if (!src || !dst || rows < 1 || rep < 1 || width < 1) return bad("repeat_rows: null argument or rows, rep, width < 1");
+  return hip_ret(sa::launch_repeat_rows_u8(src, dst, rows, rep, width, (hipStream_t)stream), "repeat_rows");
+}
+
+int samaudio_op_repeat_items(const float* src, float* dst, int items, int rep, int64_t elems, samaudio_stream stream) {
+  if (!src || !dst || items < 1 || rep < 1) return bad("repeat_items: null argument or items, rep < 1");
+  if (elems < 4 || elems % 4) return bad("repeat_items: elems % 4");
+  if (!aligned16(src) || !aligned16(dst)) return bad("repeat_items: src and dst must be aligned to 16 bytes");
+  return hip_ret(sa::launch_repeat_items_f32(src, dst, items, rep, (long)elems, (hipStream_t)stream), "repeat_items");
+}
+
+int samaudio_op_embed_rows(const int64_t* ids, const float* table, float* out, int64_t rows, int dim, int vocab,
+                           samaudio_stream stream) {
+  if (!ids || !table || !out) return bad("embed_rows: null argument");
+  if (rows < 1 || rows > INT32_MAX || vocab < 1) return bad("embed_rows: rows / vocab < 1");
+  if (dim < 4 || dim % 4) return bad("embed_rows: dim % 4");
+  if (!aligned16(table) || !aligned16(out) || !aligned_to(ids, 8)) return bad("embed_rows: table and out must be aligned to 16 bytes, ids to 8");
+  if (!sa::launch_t5_embed) return not_built("embed_rows");
+  return hip_ret(sa::launch_t5_embed((const long long*)ids, table, out, (long)rows, dim, vocab, (hipStream_t)stream), "embed_rows");
+}
+
+int samaudio_op_clap_text_embed(const int64_t* ids, const float* word, const float* pos, const float* type, float* out, int rows,
+                                int tokens, int dim, int vocab, int pad_id, int max_positions, samaudio_stream stream) {
+  if (!ids || !word || !pos || !type || !out) return bad("clap_text_embed: null argument");
+  if (rows < 1 || tokens < 1 || dim < 1 || vocab < 1 || pad_id < 0) return bad("clap_text_embed: rows, tokens, dim, vocab < 1 or pad_id < 0");
+  if (tokens > 1024) return bad("clap_text_embed: tokens > 1024 (the position ids of a row live in LDS)");
+  if ((int64_t)pad_id + tokens + 1 > max_positions)
+    return bad("clap_text_embed: the position table has fewer than pad_id + tokens + 1 rows");
+  if (!aligned_to(ids, 8)) return bad("clap_text_embed: ids must be aligned to 8 bytes");
+  if (!sa::launch_clap_text_embed) return not_built("clap_text_embed");
+  return hip_ret(sa::launch_clap_text_embed((const long long*)ids, word, pos, type, out, rows, tokens, dim, vocab, pad_id,
+                                            (hipStream_t)stream), "clap_text_embed");
+}
+
+int samaudio_op_sentinel(const void* x, int format, int64_t rows, int cols, int64_t ld, float* scratch, float* slot,
+                         samaudio_stream stream) {
+  if (!x || !scratch || !slot) return bad("sentinel: null argument");
+  if (format < 0 || format > 2) return bad("sentinel: format outside 0..2");
+  if (rows < 1 || cols < 1) return bad("sentinel: rows / cols < 1");
+  if (ld < cols) return bad("sentinel: ld < cols");
+  if (!aligned_to(x, format == 0 ? 4 : 2)) return bad("sentinel: x is not aligned to its element size");
+  if (!sa::sentinel_built) return not_built("sentinel");
+  return hip_ret(sa::launch_sentinel(x, format, (long)rows, cols, (long)ld, scratch, slot, (hipStream_t)stream), "sentinel");
+}
+
+int samaudio_op_hash_items(const uint32_t* x, int64_t words, int items, uint64_t* out, samaudio_stream stream) {
+  if (!x || !out || words < 1 || items < 1) return bad("hash_items: null argument or words, items < 1");
+  return hip_ret(sa::launch_hash_items((const unsigned*)x, (size_t)words, items, (unsigned long long*)out, (hipStream_t)stream),
+                 "hash_items");
+}
+
 // ---- Judge reranker ----------------------------------------------------------------------------------
 int samaudio_judge_create(const samaudio_judge_config* cfg, samaudio_judge** out) {
   if (!cfg || !out) return bad("samaudio_judge_create: null argument");

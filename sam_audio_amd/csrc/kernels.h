@@ -63,6 +63,10 @@ hipError_t launch_hash_items(const unsigned* x, size_t words_per_item, int items
 // SAMAUDIO_OPT_SENTINEL: absmax / non-finite scan of a tensor folded into slot[0..1] (kernels.hip)
 constexpr int kSentinelPartials = 256;
 hipError_t launch_sentinel(const void* x, int fmt, long rows, int cols, long ld, float* partial, float* slot, hipStream_t st);
+// defined (returning true) beside the real launch_sentinel only.  weak: the CPU emulation of the launchers (oracle/emu) has an empty
+// launch_sentinel and no definition of this - samaudio_op_sentinel then answers SAMAUDIO_ERR_STATE instead of reporting success with
+// an untouched slot, and the emulation itself stays as it is
+__attribute__((weak)) bool sentinel_built();
 void* debug_device_alloc(size_t bytes);
 void debug_device_free(void* p);
 int debug_flag(int flag);
@@ -422,7 +426,10 @@ __attribute__((weak)) hipError_t launch_token_mean(const float* x, long x_ld, fl
                                                    int D, hipStream_t st);
 
 // ---- T5 prompt encoder (t5_kernels.hip) ------------------------------------------------------------
-hipError_t launch_t5_embed(const long long* ids, const float* table, float* out, long M, int D, int vocab, hipStream_t st);
+// out[m, :] = table[ids[m], :], ids clamped into [0, vocab); D % 4 == 0.  weak: oracle/emu links api.hip without t5_kernels.hip; the
+// parity hook samaudio_op_embed_rows then answers SAMAUDIO_ERR_STATE
+__attribute__((weak)) hipError_t launch_t5_embed(const long long* ids, const float* table, float* out, long M, int D, int vocab,
+                                                 hipStream_t st);
 // softmax(q k^T + bias[h][k - q] + key mask) v per (item, head, query row); qkv [B*Lt, 3*H*dkv]; Lt <= 512, dkv <= 128
 // (bias nullable; scale multiplies q k^T; window > 0: only keys within +-window tokens)
 // (this one and the two below are weak: oracle/emu links api.hip without t5_kernels.hip; their parity hooks then answer

@@ -1536,7 +1536,9 @@ __global__ __launch_bounds__(256) void sentinel_scan_kernel(const T* __restrict_
   const long total = rows * cols;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const float v = SentinelLoad<T>::ld(x + (i / cols) * ld + (i % cols));
-    if (v != v || fabsf(v) > 3.0e38f) bad += 1.f;
+    // NaN and +-Inf only (exponent bits all set): the finite values above 3.0e38 - bfloat16's 0x7f62 .. 0x7f7f, fp32's top - are
+    // magnitudes, as samaudio.h says "non-finite" (before, `fabsf(v) > 3.0e38f` counted them as non-finite)
+    if ((__float_as_uint(v) & 0x7f800000u) == 0x7f800000u) bad += 1.f;
     else mx = fmaxf(mx, fabsf(v));
   }
   __shared__ float smx[256], sbad[256];
@@ -1596,6 +1598,7 @@ hipError_t launch_hash_items(const unsigned* x, size_t words_per_item, int items
   hipLaunchKernelGGL(hash_items_kernel, dim3(items), dim3(256), 0, st, x, words_per_item, out);
   return hipGetLastError();
 }
+bool sentinel_built() { return true; }
 void* debug_device_alloc(size_t bytes) {   // debugging aids only: the product path never allocates device memory
   void* p = nullptr;
   return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;

@@ -349,6 +349,24 @@ _PROTOS = {
     "samaudio_op_peav_cls_mask": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
     "samaudio_op_judge_pool_head": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]),
     "samaudio_op_frame_logits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+    # the glue kernels between those (tests/test_glue_kernels_gpu.py)
+    "samaudio_op_time_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_int, C.c_void_p]),
+    "samaudio_op_add_rowvec": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "samaudio_op_headnorm_layers": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "samaudio_op_to_act": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64,
+                                     C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "samaudio_op_zero_halo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "samaudio_op_anchor_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "samaudio_op_set_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "samaudio_op_ode_stage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_void_p,
+                                        C.c_int64, C.c_void_p]),
+    "samaudio_op_repeat_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "samaudio_op_repeat_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "samaudio_op_embed_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "samaudio_op_clap_text_embed": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
+    "samaudio_op_sentinel": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "samaudio_op_hash_items": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_judge_create": (C.c_int, [C.POINTER(JudgeConfig), C.POINTER(C.c_void_p)]),
     "samaudio_judge_destroy": (None, [C.c_void_p]),
     "samaudio_judge_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),

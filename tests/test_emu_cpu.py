@@ -320,3 +320,14 @@ def test_f32_class_copies_and_their_checks_on_the_emulation(emu):
     added by set_f32_classes; a class switched on without its copy is refused by finalize / set_option, naming the copy."""
     out = _dryrun(["tests/test_precision_gpu.py", "-k", "option_validation or f32_copies"], 900)
     assert "2 passed" in out
+
+
+def test_glue_launchers_of_the_emulation_against_float64(emu):
+    """tests/test_glue_kernels_gpu.py on the emulation's own C++ versions of the glue launchers (time_features, add_rowvec,
+    headnorm_layers, to_act, zero_halo, anchor_gather, set_floats, repeat_rows / repeat_items, hash_items): the float64 statements and
+    bit comparisons that hold the HIP kernels hold them too, so the engine-logic tests above stand on the same ground.  What the
+    emulation lacks (ode_stage, embed_rows, the sentinel, head_dim 64) skips with "not in this build of the library"."""
+    out = _dryrun(["tests/test_glue_kernels_gpu.py", "-rs"], 600)
+    assert "160 passed, 46 skipped" in out and "failed" not in out, out
+    skips = [line for line in out.splitlines() if line.startswith("SKIPPED")]
+    assert skips and all("not in this build of the library" in line for line in skips), out
