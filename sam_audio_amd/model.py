@@ -167,7 +167,9 @@ class SAMAudio:
         (exact-fp32 MFMA) | "bf16x3".
         `weight_layout` (16-bit precisions): "ktm" stores the weights of the five big GEMM classes of the DiT layers
         K-tile-major (weights.ktm_layout; a launch then streams its weights front to back), "rows" keeps them row-major;
-        "auto" = DEFAULT_WEIGHT_LAYOUT.  `prefetch_rows`: evaluations of at most this many rows (batch x frames) let the CUs a
+        "auto" = DEFAULT_WEIGHT_LAYOUT.  In the x3 precisions it is the layout of the 16-bit ".x3" twins of the compensated classes (the
+        fp32 weights stay row-major; `prefetch_rows` has no effect there: an fp32 context never prefetches).
+        `prefetch_rows`: evaluations of at most this many rows (batch x frames) let the CUs a
         GEMM launch leaves idle read the next GEMM's weights (samaudio.h SAMAUDIO_OPT_PREFETCH_ROWS; None =
         DEFAULT_PREFETCH_ROWS, 0 = off).  Both are scheduling / layout choices: results are bitwise the same.
         `f32_classes` (16-bit precisions): the GEMM classes that run on exact-fp32 operands inside the 16-bit engine
@@ -213,6 +215,9 @@ class SAMAudio:
         if weight_layout not in ("ktm", "rows"):
             raise ValueError("weight_layout must be 'auto', 'ktm' or 'rows'")
         self.weight_layout = "rows" if precision == "fp32" else weight_layout
+        # x3 precisions: the fp32 weights stay row-major; the layout is that of their 16-bit "<name>.x3" twins, the operands the big
+        # GEMMs of the layers actually stream (weights.convert_dit_x3; the engine takes either form of a twin)
+        self.x3_weight_layout = weight_layout if hip.is_x3(self.precision) else None
         if prefetch_rows is None:
             prefetch_rows = int(os.environ.get("SAMAUDIO_PREFETCH_ROWS", DEFAULT_PREFETCH_ROWS))
         self.prefetch_rows = 0 if precision == "fp32" else int(prefetch_rows)
@@ -365,7 +370,7 @@ class SAMAudio:
                 self._register(dit)
                 if self.x3_classes:
                     self._register(convert_dit_x3(dit, self.cfg.transformer.n_layers, hip.half_dtype(self.precision),
-                                                  self.x3_classes))
+                                                  self.x3_classes, ktm=self.x3_weight_layout == "ktm"))
                 # fp32 operand copies exist for the classes that run in fp32 now; set_f32_classes adds a class's later
                 # from these references to the checkpoint entries (no copy is made here)
                 self._f32_have = self.f32_classes
