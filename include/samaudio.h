@@ -31,8 +31,10 @@ enum { SAMAUDIO_DT_F32 = 0, SAMAUDIO_DT_BF16 = 1, SAMAUDIO_DT_I64 = 2, SAMAUDIO_
 /* ODE methods of samaudio_ode_solve, torchdiffeq's fixed-grid solvers.  EULER and MIDPOINT fold each
  * step into the output GEMM's epilogue; RK4 (torchdiffeq's "rk4": the 3/8-rule variant, 4 evaluations per step, the last at the grid
  * point t1) and HEUN3 (Heun's third-order method, 3 evaluations) write every stage's field into a stage buffer of their own
- * (samaudio_set_ode_stages) and combine them in ode_stage_kernel. */
-enum { SAMAUDIO_ODE_EULER = 0, SAMAUDIO_ODE_MIDPOINT = 1, SAMAUDIO_ODE_RK4 = 2, SAMAUDIO_ODE_HEUN3 = 3 };
+ * (samaudio_set_ode_stages) and combine them in ode_stage_kernel.  DOPRI5 and BOSH3 are the adaptive embedded pairs of
+ * samaudio_ode_solve_adaptive (below); samaudio_ode_solve answers them with SAMAUDIO_ERR_ARG. */
+enum { SAMAUDIO_ODE_EULER = 0, SAMAUDIO_ODE_MIDPOINT = 1, SAMAUDIO_ODE_RK4 = 2, SAMAUDIO_ODE_HEUN3 = 3, SAMAUDIO_ODE_DOPRI5 = 4,
+       SAMAUDIO_ODE_BOSH3 = 5 };
 
 enum {
   SAMAUDIO_OK = 0,
@@ -230,6 +232,40 @@ int samaudio_ode_solve(samaudio_ctx* ctx, float* state, int method, const float*
  * the workspace or the state, and each context of a process needs its own. */
 size_t samaudio_ode_stage_bytes(samaudio_ctx* ctx, int method, int rows, int frames);
 int samaudio_set_ode_stages(samaudio_ctx* ctx, void* stages, size_t bytes);
+
+/* Adaptive ODE solve with PER-ROW step control (tests/ode_adaptive_ref.py is the statement).  method
+ * SAMAUDIO_ODE_DOPRI5 (Dormand-Prince 5(4): 6 evaluations per trial step) | SAMAUDIO_ODE_BOSH3 (Bogacki-Shampine 3(2): 3), both FSAL.
+ * Every row of state [rows, frames, 256] f32 integrates from t0 to t1 on its own: its time, its step, its error norm - the root mean
+ * square of h K^T E / (atol + rtol max(|y|, |y_new|)) over the row's valid frames (the audio_pad_mask of samaudio_prepare) and all
+ * channels - and its accept / reject decision live on the device, so a row's result does not depend on which rows share the call.
+ * Tableaux, controller and initial step are those of scipy.integrate's RK45 / RK23 (max_step = inf) in fp32; pinned to scipy,
+ * unpinned vs torchdiffeq, from which it departs in that the norm and the step are per row, the last step is clipped to end at t1
+ * exactly, and the accept factor is capped at 1 after a rejection within the same step.
+ * UNLIKE samaudio_ode_solve THIS CALL SYNCHRONISES THE STREAM, once per trial step: the host has to learn whether a row is still
+ * running.  Rows that have ended ride along, untouched, until the last one ends.
+ * The context's stage buffers (samaudio_ode_stage_bytes answers for these methods: the K rows, the candidate state, the per-row
+ * control block, the per-stage time table and the norm partials) are the caller's as for rk4: missing or too small or overlapping =
+ * SAMAUDIO_ERR_WORKSPACE with the state untouched; a library built without the kernels (the CPU launcher emulation) = SAMAUDIO_ERR_STATE;
+ * a window table set (samaudio_set_windows) = SAMAUDIO_ERR_STATE.  stats_host: HOST array, one entry per row.  A row that fails (status
+ * 2: a rejection drove its step below 10 ulp(t); 3: max_num_steps trial steps) stops where it is while the other rows go on; the call
+ * still returns SAMAUDIO_OK and the caller reads the status. */
+typedef struct {
+  float rtol, atol;         /* > 0 */
+  float first_step;         /* <= 0: scipy's select_initial_step (one more field evaluation) */
+  float safety;             /* 0.9  */
+  float ifactor;            /* 10: the largest growth of a step  */
+  float dfactor;            /* 0.2: the largest shrink after a rejection */
+  int32_t max_num_steps;    /* trial steps (accepted + rejected) a row may take */
+} samaudio_ode_adaptive;
+enum { SAMAUDIO_ODE_ROW_RUNNING = 0, SAMAUDIO_ODE_ROW_FINISHED = 1, SAMAUDIO_ODE_ROW_STEP_UNDERFLOW = 2, SAMAUDIO_ODE_ROW_MAX_STEPS = 3 };
+typedef struct {
+  int32_t accepted, rejected;   /* steps of this row */
+  int32_t status;               /* SAMAUDIO_ODE_ROW_* */
+  int32_t evaluations;          /* field launches of the whole solve (the same in every entry) */
+  float t, last_h;              /* where the row stands (t1 exactly when finished), its last accepted step */
+} samaudio_ode_row_stats;
+int samaudio_ode_solve_adaptive(samaudio_ctx* ctx, float* state, int method, float t0, float t1, const samaudio_ode_adaptive* opt,
+                                samaudio_ode_row_stats* stats_host, samaudio_stream stream);
 
 /* Windowed solve of clips longer than one window (SAMAudio.separate(window_seconds=...)).  The prepared rows
  * are windows of `frames` frames cut from longer clips with a stride of frames - overlap_frames; next_row_device [rows] i32 ON THE
@@ -887,6 +923,31 @@ int samaudio_op_set_floats(float* dst, const float* host_values, int n, samaudio
  * that is not aligned to 16 bytes. */
 int samaudio_op_ode_stage(const float* y0, const float* const* k, const float* coef, int n_src, float scale, float* out, int64_t n,
                           samaudio_stream stream);
+/* The kernels of samaudio_ode_solve_adaptive (kernels.hip; tests/test_ode_adaptive_gpu.py).  ctl [rows] is the per-row control block,
+ * 16 words of 4 bytes each: f32 t, h (the trial step in flight), t_new, h_abs, h_prev, err, d1, h0; i32 status (SAMAUDIO_ODE_ROW_*),
+ * accepted, rejected, step_rejected, accepted_now, n_valid (elements in the row's norms); two spare.  k, coef: HOST arrays of SEVEN
+ * device pointers / floats of which the first n_src are read.  All device pointers aligned to 16 bytes, row_elems % 4 == 0.
+ * ode_stage_rows_kernel: out[r, i] = y[r, i] + ctl[r].h * sum_j coef[j] k[j][r, i] for running rows; a row whose status is not RUNNING
+ *   is copied through without its K being read.  out may be y, never a k. */
+int samaudio_op_ode_stage_rows(const float* y, const float* const* k, const float* coef, int n_src, const void* ctl, float* out,
+                               int rows, int64_t row_elems, samaudio_stream stream);
+/* ode_error_kernel: partials [rows, chunks] f32, chunks = ceil(frames * channels / 4096): partials[r, c] = the sum over the valid
+ *   elements of [4096 c, 4096 (c + 1)) of row r of (m sum_j coef[j] k[j] / (atol + rtol max(|y|, |ynew|)))^2, m = ctl[r].h if use_h else
+ *   1, ynew null: |y| alone; lane-ordered adds and a fixed tree, no atomics; 0 for rows that are not running.  mask [rows, frames] u8
+ *   (null: every frame valid). */
+int samaudio_op_ode_error(const float* y, const float* ynew, const float* const* k, const float* coef, int n_src, const void* ctl,
+                          const uint8_t* mask, float rtol, float atol, int use_h, float* partials, int rows, int frames, int channels,
+                          samaudio_stream stream);
+/* ode_control_kernel, one lane per row; mode 0 reset (t = t0, counters 0, n_valid from the mask; first_step > 0: the first trial),
+ *   1 / 2 the two halves of the initial-step rule (1 reads partials = d0 and partials_b = d1, 2 reads partials = d2 h0), 3 the
+ *   accept / reject decision on partials and the next trial.  times [stages + 1, rows] f32: the next trial's t + c_i h;
+ *   *active (device i32) = rows running afterwards. */
+int samaudio_op_ode_control(void* ctl, int mode, int method, float t0, float t1, const samaudio_ode_adaptive* opt, const float* partials,
+                            const float* partials_b, int chunks, const uint8_t* mask, int frames, int channels, float* times,
+                            int32_t* active, int rows, samaudio_stream stream);
+/* ode_commit_kernel: rows with accepted_now: y <- ynew, k_first <- k_last */
+int samaudio_op_ode_commit(float* y, const float* ynew, float* k_first, const float* k_last, const void* ctl, int rows,
+                           int64_t row_elems, samaudio_stream stream);
 /* repeat_rows_u8_kernel: dst [rows * rep, width] bytes, dst[b * rep + c][:] = src[b][:] */
 int samaudio_op_repeat_rows(const uint8_t* src, uint8_t* dst, int rows, int rep, int width, samaudio_stream stream);
 /* repeat_items_f32_kernel: the same for items of `elems` f32 values.  Refused: elems % 4, src or dst not aligned to 16 bytes. */

@@ -106,6 +106,11 @@ int samaudio_ode_solve(samaudio_ctx* ctx, float* state, int method, const float*
   return SA_ENTRY(ctx, "null context", ctx->engine->ode_solve(state, method, grid_host, n_grid, (hipStream_t)stream));
 }
 
+int samaudio_ode_solve_adaptive(samaudio_ctx* ctx, float* state, int method, float t0, float t1, const samaudio_ode_adaptive* opt,
+                                samaudio_ode_row_stats* stats_host, samaudio_stream stream) {
+  return SA_ENTRY(ctx, "null context", ctx->engine->ode_solve_adaptive(state, method, t0, t1, opt, stats_host, (hipStream_t)stream));
+}
+
 size_t samaudio_ode_stage_bytes(samaudio_ctx* ctx, int method, int rows, int frames) {
   if (!ctx) return 0;
   return ctx->engine->ode_stage_bytes(method, rows, frames);
@@ -807,6 +812,82 @@ int samaudio_op_ode_stage(const float* y0, const float* const* k, const float* c
   }
   if (!sa::launch_ode_stage) return not_built("ode_stage");
   return hip_ret(sa::launch_ode_stage(y0, a, scale, out, (long)n, (hipStream_t)stream), "ode_stage");
+}
+
+// the kernels of the adaptive solve: k / coef are host arrays of kOdeMaxSrc entries, ctl the device control blocks
+namespace {
+static_assert(sizeof(sa::OdeRowCtl) == 64, "samaudio.h documents the control block as 16 words");
+const char* ode_sources(const float* const* k, const float* coef, int n_src, sa::OdeSrcArgs& a) {
+  if (!k || !coef) return "null argument";
+  if (n_src < 1 || n_src > sa::kOdeMaxSrc) return "n_src outside [1, 7]";
+  a = sa::OdeSrcArgs{};
+  a.n_src = n_src;
+  for (int j = 0; j < sa::kOdeMaxSrc; ++j) {
+    if (j < n_src && (!k[j] || !aligned16(k[j]))) return "a source is null or not aligned to 16 bytes";
+    a.k[j] = k[j];
+    a.coef[j] = coef[j];
+  }
+  return nullptr;
+}
+}  // namespace
+
+int samaudio_op_ode_stage_rows(const float* y, const float* const* k, const float* coef, int n_src, const void* ctl, float* out,
+                               int rows, int64_t row_elems, samaudio_stream stream) {
+  if (!y || !ctl || !out) return bad("ode_stage_rows: null argument");
+  sa::OdeSrcArgs a;
+  if (const char* why = ode_sources(k, coef, n_src, a)) return bad((std::string("ode_stage_rows: ") + why).c_str());
+  if (rows < 1 || rows > kMaxGridYZ) return bad("ode_stage_rows: rows");
+  if (row_elems < 4 || row_elems % 4) return bad("ode_stage_rows: row_elems % 4");
+  if (!aligned16(y) || !aligned16(out) || !aligned_to(ctl, 4)) return bad("ode_stage_rows: y and out must be aligned to 16 bytes");
+  for (int j = 0; j < n_src; ++j)
+    if (k[j] == out) return bad("ode_stage_rows: out must not be a source");
+  if (!sa::launch_ode_stage_rows) return not_built("ode_stage_rows");
+  return hip_ret(sa::launch_ode_stage_rows(y, a, (const sa::OdeRowCtl*)ctl, out, rows, (long)row_elems, (hipStream_t)stream),
+                 "ode_stage_rows");
+}
+
+int samaudio_op_ode_error(const float* y, const float* ynew, const float* const* k, const float* coef, int n_src, const void* ctl,
+                          const uint8_t* mask, float rtol, float atol, int use_h, float* partials, int rows, int frames, int channels,
+                          samaudio_stream stream) {
+  if (!y || !ctl || !partials) return bad("ode_error: null argument");
+  sa::OdeSrcArgs a;
+  if (const char* why = ode_sources(k, coef, n_src, a)) return bad((std::string("ode_error: ") + why).c_str());
+  if (rows < 1 || rows > kMaxGridYZ || frames < 1) return bad("ode_error: rows / frames");
+  if (channels < 4 || channels % 4) return bad("ode_error: channels % 4");
+  if (!(rtol >= 0.f) || !(atol > 0.f)) return bad("ode_error: rtol >= 0 and atol > 0");
+  if (!aligned16(y) || (ynew && !aligned16(ynew)) || !aligned_to(ctl, 4) || !aligned_to(partials, 4))
+    return bad("ode_error: y and ynew must be aligned to 16 bytes");
+  if (!sa::launch_ode_error) return not_built("ode_error");
+  return hip_ret(sa::launch_ode_error(y, ynew, a, (const sa::OdeRowCtl*)ctl, mask, rtol, atol, use_h, partials, rows, frames, channels,
+                                      (hipStream_t)stream), "ode_error");
+}
+
+int samaudio_op_ode_control(void* ctl, int mode, int method, float t0, float t1, const samaudio_ode_adaptive* opt, const float* partials,
+                            const float* partials_b, int chunks, const uint8_t* mask, int frames, int channels, float* times,
+                            int32_t* active, int rows, samaudio_stream stream) {
+  if (!ctl || !opt || !times || !active) return bad("ode_control: null argument");
+  sa::OdeControlArgs a;
+  if (!sa::ode_control_args(method, t0, t1, *opt, a)) return bad("ode_control: the method must be dopri5 or bosh3");
+  if (mode < sa::ODE_CTL_RESET || mode > sa::ODE_CTL_STEP) return bad("ode_control: mode");
+  if (rows < 1 || frames < 1 || channels < 1) return bad("ode_control: rows, frames, channels < 1");
+  if (mode != sa::ODE_CTL_RESET && (!partials || chunks < 1)) return bad("ode_control: partials");
+  if (mode == sa::ODE_CTL_INIT1 && !partials_b) return bad("ode_control: the initial-step rule reads two sets of partials");
+  if (!aligned_to(ctl, 4) || !aligned_to(times, 4) || !aligned_to(active, 4)) return bad("ode_control: alignment");
+  if (!sa::launch_ode_control) return not_built("ode_control");
+  return hip_ret(sa::launch_ode_control((sa::OdeRowCtl*)ctl, mode, a, partials, partials_b, chunks, mask, frames, channels, times,
+                                        (int*)active, rows, (hipStream_t)stream), "ode_control");
+}
+
+int samaudio_op_ode_commit(float* y, const float* ynew, float* k_first, const float* k_last, const void* ctl, int rows,
+                           int64_t row_elems, samaudio_stream stream) {
+  if (!y || !ynew || !k_first || !k_last || !ctl) return bad("ode_commit: null argument");
+  if (rows < 1 || rows > kMaxGridYZ) return bad("ode_commit: rows");
+  if (row_elems < 4 || row_elems % 4) return bad("ode_commit: row_elems % 4");
+  if (!aligned16(y) || !aligned16(ynew) || !aligned16(k_first) || !aligned16(k_last) || !aligned_to(ctl, 4))
+    return bad("ode_commit: every array must be aligned to 16 bytes");
+  if (!sa::launch_ode_commit) return not_built("ode_commit");
+  return hip_ret(sa::launch_ode_commit(y, ynew, k_first, k_last, (const sa::OdeRowCtl*)ctl, rows, (long)row_elems, (hipStream_t)stream),
+                 "ode_commit");
 }
 
 int samaudio_op_repeat_rows(const uint8_t* src, uint8_t* dst, int rows, int rep, int width, samaudio_stream stream) {

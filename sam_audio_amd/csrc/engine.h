@@ -6,6 +6,9 @@ namespace sa {
 
 constexpr int HALO = 40;  // zero rows either side of codec activations (>= 4 * max dilation 9)
 
+// the controller arguments of an adaptive method (its nodes and estimator order, the caller's options); false: not an adaptive method
+bool ode_control_args(int method, float t0, float t1, const samaudio_ode_adaptive& opt, OdeControlArgs& out);
+
 class Engine {
  public:
   explicit Engine(const samaudio_config& c);
@@ -24,8 +27,13 @@ class Engine {
                  const uint8_t* pad_mask, hipStream_t st, int candidates = 1, bool latent_feats = false);
   Status forward(const float* noisy, const float* time, int n_time, float* out, hipStream_t st);
   Status ode_solve(float* state, int method, const float* grid_host, int n_grid, hipStream_t st);
+  // dopri5 / bosh3 with per-row step control; synchronises `st`; stats: host, one entry per row
+  Status ode_solve_adaptive(float* state, int method, float t0, float t1, const samaudio_ode_adaptive* opt,
+                            samaudio_ode_row_stats* stats, hipStream_t st);
   // stage buffers of the Runge-Kutta methods (samaudio_set_ode_stages): borrowed, apart from the workspace
   struct RkTableau;   // engine.hip: rk4 / heun3
+  struct AdaptiveTableau;   // engine.hip: dopri5 / bosh3
+  struct AdaptiveBufs;
   size_t ode_stage_bytes(int method, int rows, int frames) const;
   Status set_ode_stages(void* p, size_t bytes);
   // windowed solve (samaudio_set_windows): while a successor table is set, every field evaluation ends with window_blend_kernel on its
@@ -133,6 +141,7 @@ class Engine {
   int x3_classes_ = 0;      // SAMAUDIO_OPT_X3_CLASSES (fp32 contexts)
   Status solve_launches(float* y, int method, const float* grid, int n_grid, hipStream_t st);   // the launches of one solve
   Status solve_rk(float* y, const RkTableau& tab, const float* grid, int n_grid, hipStream_t st);   // ... of rk4 / heun3
+  AdaptiveBufs adaptive_carve(const AdaptiveTableau& tab, int rows, int frames) const;   // the stage buffer of an adaptive solve
   float* stages_ = nullptr;   // samaudio_set_ode_stages
   size_t stages_bytes_ = 0;
   const int32_t* win_next_ = nullptr;   // samaudio_set_windows: the successor table of the prepared rows (null: no windows)

@@ -1386,7 +1386,67 @@ static const Engine::RkTableau* rk_tableau(int method) {
 }
 static size_t stage_stride(int rows, int frames, int C2) { return ((size_t)rows * frames * C2 * 4 + 255) & ~size_t(255); }
 
+// The embedded pairs of the adaptive methods: scipy.integrate's RK45 (Dormand-Prince 5(4)) and RK23
+// (Bogacki-Shampine 3(2)) tableaux, rounded to fp32.  Both are FSAL: row `stages` of `a` is `b`, its evaluation at the candidate
+// is K[stages], the last term of the error estimate and the next step's K[0].
+struct Engine::AdaptiveTableau {
+  int stages, order;               // evaluations per trial step; order of the error estimator
+  float c[kOdeMaxSrc];             // c[stages] = 1
+  float a[kOdeMaxSrc][kOdeMaxSrc];
+  float e[kOdeMaxSrc];
+};
+#define Q(n, d) (float)((double)(n) / (double)(d))
+static const Engine::AdaptiveTableau* adaptive_tableau(int method) {
+  static const Engine::AdaptiveTableau dopri5 = {
+      6, 4, {0.f, Q(1, 5), Q(3, 10), Q(4, 5), Q(8, 9), 1.f, 1.f},
+      {{},
+       {Q(1, 5)},
+       {Q(3, 40), Q(9, 40)},
+       {Q(44, 45), Q(-56, 15), Q(32, 9)},
+       {Q(19372, 6561), Q(-25360, 2187), Q(64448, 6561), Q(-212, 729)},
+       {Q(9017, 3168), Q(-355, 33), Q(46732, 5247), Q(49, 176), Q(-5103, 18656)},
+       {Q(35, 384), 0.f, Q(500, 1113), Q(125, 192), Q(-2187, 6784), Q(11, 84)}},
+      {Q(-71, 57600), 0.f, Q(71, 16695), Q(-71, 1920), Q(17253, 339200), Q(-22, 525), Q(1, 40)}};
+  static const Engine::AdaptiveTableau bosh3 = {
+      3, 2, {0.f, Q(1, 2), Q(3, 4), 1.f},
+      {{}, {Q(1, 2)}, {0.f, Q(3, 4)}, {Q(2, 9), Q(1, 3), Q(4, 9)}},
+      {Q(5, 72), Q(-1, 12), Q(-1, 9), Q(1, 8)}};
+  return method == SAMAUDIO_ODE_DOPRI5 ? &dopri5 : method == SAMAUDIO_ODE_BOSH3 ? &bosh3 : nullptr;
+}
+#undef Q
+static size_t pad256(size_t n) { return (n + 255) & ~size_t(255); }
+static int ode_chunks(int frames, int C2) { return (int)(((long)frames * C2 + kOdeChunk - 1) / kOdeChunk); }
+
+// the caller's stage buffer of an adaptive solve, carved: K[0 .. stages], the candidate, one control block per row, the time table
+// [stages + 1][rows], two sets of norm partials [rows][chunks] and the word the host reads after every trial step
+struct Engine::AdaptiveBufs {
+  float* k[kOdeMaxSrc];
+  float *ynew, *times, *part, *part_b;
+  OdeRowCtl* ctl;
+  int* active;
+  size_t bytes;
+};
+Engine::AdaptiveBufs Engine::adaptive_carve(const AdaptiveTableau& tab, int rows, int frames) const {
+  AdaptiveBufs b{};
+  char* p = (char*)stages_;
+  size_t off = 0;
+  auto take = [&](size_t n) { char* q = p + off; off += pad256(n); return q; };
+  const size_t state = (size_t)rows * frames * cfg_.latent_channels * 4;
+  for (int i = 0; i <= tab.stages; ++i) b.k[i] = (float*)take(state);
+  b.ynew = (float*)take(state);
+  b.ctl = (OdeRowCtl*)take((size_t)rows * sizeof(OdeRowCtl));
+  b.times = (float*)take((size_t)(tab.stages + 1) * rows * 4);
+  const size_t part = (size_t)rows * ode_chunks(frames, cfg_.latent_channels) * 4;
+  b.part = (float*)take(part);
+  b.part_b = (float*)take(part);
+  b.active = (int*)take(4);
+  b.bytes = off;
+  return b;
+}
+
 size_t Engine::ode_stage_bytes(int method, int rows, int frames) const {
+  if (const AdaptiveTableau* ad = adaptive_tableau(method))
+    return rows <= 0 || frames <= 0 ? 0 : adaptive_carve(*ad, rows, frames).bytes;
   const RkTableau* tab = rk_tableau(method);
   if (!tab || rows <= 0 || frames <= 0) return 0;
   return (size_t)tab->stages * stage_stride(rows, frames, cfg_.latent_channels);
@@ -1457,6 +1517,132 @@ Status Engine::solve_rk(float* y, const RkTableau& tab, const float* grid, int n
       SA_TRY(op("ode_stage", (a.n_src + 2.0) * n * 4, 2.0 * (a.n_src + 1) * n, st,
                 [&] { return launch_ode_stage(y, a, scale, out, n, st); }));
     }
+  }
+  if (hash_on()) hash_flush((HashTrace*)hash_, this, st);
+  return Status{};
+}
+
+bool ode_control_args(int method, float t0, float t1, const samaudio_ode_adaptive& opt, OdeControlArgs& ca) {
+  const Engine::AdaptiveTableau* tab = adaptive_tableau(method);
+  if (!tab) return false;
+  ca = OdeControlArgs{};
+  ca.t0 = t0; ca.t1 = t1; ca.first_step = opt.first_step;
+  ca.safety = opt.safety; ca.ifactor = opt.ifactor; ca.dfactor = opt.dfactor;
+  ca.order = tab->order; ca.max_num_steps = opt.max_num_steps; ca.n_times = tab->stages + 1;
+  for (int i = 0; i <= tab->stages; ++i) ca.c[i] = tab->c[i];
+  return true;
+}
+
+// Adaptive solve: every row integrates from t0 to t1 with its own time, step and accept / reject decision, all
+// of them on the device.  One trial step = the stage evaluations of all rows (per-row times: eval_field with n_time = rows), the error
+// norms, the controller, the commit, then ONE host read: the number of rows still running.  Rows that have ended ride along - the stage
+// kernel hands their state through, the field evaluates it at their own time, and nothing of theirs is written - until the last row ends.
+Status Engine::ode_solve_adaptive(float* y, int method, float t0, float t1, const samaudio_ode_adaptive* opt,
+                                  samaudio_ode_row_stats* stats, hipStream_t st) {
+  if (!prepared_) return fail(SAMAUDIO_ERR_STATE, "ode_solve_adaptive: call samaudio_prepare first");
+  const AdaptiveTableau* tab = adaptive_tableau(method);
+  if (!tab) return fail(SAMAUDIO_ERR_ARG, "ode_solve_adaptive: the method must be SAMAUDIO_ODE_DOPRI5 or SAMAUDIO_ODE_BOSH3");
+  if (!y || !opt || !stats) return fail(SAMAUDIO_ERR_ARG, "ode_solve_adaptive: null pointer");
+  if (!(t1 > t0)) return fail(SAMAUDIO_ERR_ARG, "ode_solve_adaptive: t1 must lie behind t0");
+  if (!(opt->rtol > 0.f) || !(opt->atol > 0.f)) return fail(SAMAUDIO_ERR_ARG, "ode_solve_adaptive: rtol and atol must be positive");
+  if (!(opt->safety > 0.f) || !(opt->ifactor >= 1.f) || !(opt->dfactor > 0.f) || !(opt->dfactor < 1.f) || opt->max_num_steps < 1 ||
+      opt->first_step != opt->first_step)
+    return fail(SAMAUDIO_ERR_ARG, "ode_solve_adaptive: safety > 0, ifactor >= 1, 0 < dfactor < 1, max_num_steps >= 1");
+  if (cfg_.latent_channels % 4) return fail(SAMAUDIO_ERR_ARG, "ode_solve_adaptive: latent_channels % 4 != 0");
+  if (win_next_) return fail(SAMAUDIO_ERR_STATE, "ode_solve_adaptive: windows are set (rows of one clip must share their times)");
+  if (!launch_ode_stage_rows || !launch_ode_error || !launch_ode_control || !launch_ode_commit)
+    return fail(SAMAUDIO_ERR_STATE, "ode_solve_adaptive: dopri5 / bosh3 are not available in this build (no ode_*_rows kernels)");
+  const int rows = rows_, T = frames_, C2 = cfg_.latent_channels, S = tab->stages;
+  const size_t need = ode_stage_bytes(method, rows, T);
+  if (!stages_ || stages_bytes_ < need)
+    return fail(SAMAUDIO_ERR_WORKSPACE,
+                "ode_solve_adaptive: dopri5 / bosh3 need samaudio_ode_stage_bytes() of stage buffers (samaudio_set_ode_stages)");
+  if (overlaps(stages_, need, ws_, ws_bytes_) || overlaps(stages_, need, y, (size_t)rows * T * C2 * 4))
+    return fail(SAMAUDIO_ERR_WORKSPACE, "ode_solve_adaptive: the stage buffers overlap the workspace or the state");
+  const AdaptiveBufs b = adaptive_carve(*tab, rows, T);
+  phase_ = Phase::Dit;   // (the profile label of the launches ahead of the first evaluation)
+  const long row_elems = (long)T * C2;
+  const double n = (double)rows * row_elems;
+  const int chunks = ode_chunks(T, C2);
+  OdeControlArgs ca{};
+  ode_control_args(method, t0, t1, *opt, ca);
+
+  auto control = [&](int mode) {
+    return op("ode_control", (2.0 * sizeof(OdeRowCtl) + 4.0 * chunks) * rows, 0, st, [&] {
+      return launch_ode_control(b.ctl, mode, ca, b.part, b.part_b, chunks, d_.pad_mask, T, C2, b.times, b.active, rows, st);
+    });
+  };
+  // sources = the K rows with a non-zero weight among w[0 .. count)
+  auto sources = [&](const float* w, int count) {
+    OdeSrcArgs a{};
+    for (int j = 0; j < count; ++j)
+      if (w[j] != 0.f) {
+        a.k[a.n_src] = b.k[j];
+        a.coef[a.n_src++] = w[j];
+      }
+    return a;
+  };
+  auto combine = [&](const OdeSrcArgs& a, float* out) {
+    return op("ode_stage_rows", (a.n_src + 2.0) * n * 4, 2.0 * (a.n_src + 1) * n, st,
+              [&] { return launch_ode_stage_rows(y, a, b.ctl, out, rows, row_elems, st); });
+  };
+  auto norm = [&](const OdeSrcArgs& a, const float* ynew, int use_h, float* part) {
+    return op("ode_error", (a.n_src + (ynew ? 2.0 : 1.0)) * n * 4, 2.0 * (a.n_src + 4) * n, st, [&] {
+      return launch_ode_error(y, ynew, a, b.ctl, d_.pad_mask, opt->rtol, opt->atol, use_h, part, rows, T, C2, st);
+    });
+  };
+  auto field = [&](const float* in, int slot, float* out) {
+    return eval_field(in, b.times + (size_t)slot * rows, rows, out, nullptr, 1.f, st);
+  };
+  int evaluations = 0, active = rows;
+  auto read_active = [&]() -> Status {
+    SA_HIP(hipMemcpyAsync(&active, b.active, sizeof(int), hipMemcpyDeviceToHost, st));
+    SA_HIP(hipStreamSynchronize(st));
+    return Status{};
+  };
+
+  SA_TRY(control(ODE_CTL_RESET));
+  SA_TRY(field(y, 0, b.k[0]));   // K[0] = f(t0, y0)
+  ++evaluations;
+  if (!(opt->first_step > 0.f)) {   // scipy's select_initial_step, with the row's own norms
+    const float one[2] = {1.f, -1.f};
+    OdeSrcArgs self{};
+    self.k[0] = y; self.coef[0] = 1.f; self.n_src = 1;
+    SA_TRY(norm(self, nullptr, 0, b.part));                  // d0 = |y0 / scale|
+    SA_TRY(norm(sources(one, 1), nullptr, 0, b.part_b));     // d1 = |f0 / scale|
+    SA_TRY(control(ODE_CTL_INIT1));                          // h0
+    SA_TRY(combine(sources(one, 1), d_.ymid));               // y1 = y0 + h0 f0
+    SA_TRY(field(d_.ymid, 1, b.k[1]));                       // f1 = f(t0 + h0, y1)
+    ++evaluations;
+    OdeSrcArgs diff{};
+    diff.k[0] = b.k[1]; diff.k[1] = b.k[0]; diff.coef[0] = 1.f; diff.coef[1] = -1.f; diff.n_src = 2;
+    SA_TRY(norm(diff, nullptr, 0, b.part));                  // d2 h0 = |(f1 - f0) / scale|
+    SA_TRY(control(ODE_CTL_INIT2));
+  }
+  SA_TRY(read_active());
+  while (active > 0) {
+    for (int i = 1; i < S; ++i) {
+      SA_TRY(combine(sources(tab->a[i], i), d_.ymid));
+      SA_TRY(field(d_.ymid, i, b.k[i]));
+    }
+    SA_TRY(combine(sources(tab->a[S], S), b.ynew));          // the candidate: row S of `a` is b
+    SA_TRY(field(b.ynew, S, b.k[S]));
+    evaluations += S;
+    SA_TRY(norm(sources(tab->e, S + 1), b.ynew, 1, b.part));
+    SA_TRY(control(ODE_CTL_STEP));
+    SA_TRY(op("ode_commit", 4.0 * n * 4, 0, st, [&] { return launch_ode_commit(y, b.ynew, b.k[0], b.k[S], b.ctl, rows, row_elems, st); }));
+    SA_TRY(read_active());
+  }
+  std::vector<OdeRowCtl> host(rows);
+  SA_HIP(hipMemcpyAsync(host.data(), b.ctl, (size_t)rows * sizeof(OdeRowCtl), hipMemcpyDeviceToHost, st));
+  SA_HIP(hipStreamSynchronize(st));
+  for (int r = 0; r < rows; ++r) {
+    stats[r].accepted = host[r].accepted;
+    stats[r].rejected = host[r].rejected;
+    stats[r].status = host[r].status;
+    stats[r].evaluations = evaluations;
+    stats[r].t = host[r].t;
+    stats[r].last_h = host[r].h_prev;
   }
   if (hash_on()) hash_flush((HashTrace*)hash_, this, st);
   return Status{};

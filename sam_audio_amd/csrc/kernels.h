@@ -277,6 +277,60 @@ struct OdeStageArgs {
 __attribute__((weak)) hipError_t launch_ode_stage(const float* y0, const OdeStageArgs& a, float scale, float* out, long n,
                                                   hipStream_t st);
 
+// Adaptive solve with per-row step control (engine.hip Engine::ode_solve_adaptive).  Every row carries its own time, step
+// and accept / reject decision in one OdeRowCtl on the device; all launchers below read it and only launch_ode_control writes it.
+constexpr int kOdeMaxSrc = 7;      // dopri5's error estimate reads K0 .. K6
+constexpr int kOdeChunk = 4096;    // elements of a row that one block of ode_error_kernel sums (a fixed tree, then one partial)
+enum { ODE_ROW_RUNNING = 0, ODE_ROW_FINISHED = 1, ODE_ROW_STEP_UNDERFLOW = 2, ODE_ROW_MAX_STEPS = 3 };
+struct OdeRowCtl {      // 64 bytes
+  float t;              // the row's time (end of its last accepted step)
+  float h;              // the trial step in flight, clipped to t1 (the stage kernels' multiplier)
+  float t_new;          // t + h, or t1 exactly where the step was clipped
+  float h_abs;          // the controller's proposal behind h (scipy's h_abs)
+  float h_prev;         // the last accepted step
+  float err;            // the last trial's error norm
+  float d1, h0;         // initial-step rule: |f0 / scale|, the explicit-Euler probe step
+  int status;           // ODE_ROW_*
+  int accepted, rejected;
+  int step_rejected;    // a trial of the current step was rejected already (caps the accept factor at 1)
+  int accepted_now;     // the last decision (ode_commit_kernel's predicate)
+  int n_valid;          // elements in the row's norms: valid frames * channels
+  int pad[2];
+};
+struct OdeSrcArgs {     // up to kOdeMaxSrc device arrays [rows, row_elems] fp32 and their weights
+  const float* k[kOdeMaxSrc];
+  float coef[kOdeMaxSrc];
+  int n_src;
+};
+enum { ODE_CTL_RESET = 0, ODE_CTL_INIT1 = 1, ODE_CTL_INIT2 = 2, ODE_CTL_STEP = 3 };
+struct OdeControlArgs {
+  float t0, t1, first_step;             // first_step <= 0: the initial-step rule (RESET leaves h = 0, INIT1 / INIT2 follow)
+  float safety, ifactor, dfactor;
+  int order;                            // of the error estimator (4 | 2): exponent -1 / (order + 1)
+  int max_num_steps;
+  int n_times;                          // rows of the time table: stages + 1
+  float c[kOdeMaxSrc];                  // the table's nodes (c[0] = 0, c[n_times - 1] = 1)
+};
+// weak, as launch_ode_stage: the CPU emulation of the launchers has none of them and ode_solve_adaptive then answers SAMAUDIO_ERR_STATE.
+// out[r, i] = y[r, i] + ctl[r].h * sum_j coef[j] k[j][r, i] for running rows, y[r, i] (no K read) for finished / failed ones;
+// row_elems % 4 == 0, 16-byte aligned, out distinct from every k
+__attribute__((weak)) hipError_t launch_ode_stage_rows(const float* y, const OdeSrcArgs& a, const OdeRowCtl* ctl, float* out, int rows,
+                                                       long row_elems, hipStream_t st);
+// partials[r, c] = sum over the valid elements i of chunk c of row r of (m * sum_j coef[j] k[j][r, i] / scale)^2 with
+// scale = atol + rtol * max(|y|, |ynew|) (ynew null: |y|), m = ctl[r].h if use_h else 1; 0 for rows that are not running.  An element
+// is valid iff mask[r, i / channels] != 0 (mask null: all).  partials [rows, chunks], chunks = ceil(frames * channels / kOdeChunk)
+__attribute__((weak)) hipError_t launch_ode_error(const float* y, const float* ynew, const OdeSrcArgs& a, const OdeRowCtl* ctl,
+                                                  const unsigned char* mask, float rtol, float atol, int use_h, float* partials, int rows,
+                                                  int frames, int channels, hipStream_t st);
+// one thread per row: `mode` ODE_CTL_*; sums partials (and partials_b: INIT1's second norm) in chunk order; times [n_times, rows];
+// *active = rows still running afterwards
+__attribute__((weak)) hipError_t launch_ode_control(OdeRowCtl* ctl, int mode, const OdeControlArgs& a, const float* partials,
+                                                    const float* partials_b, int chunks, const unsigned char* mask, int frames,
+                                                    int channels, float* times, int* active, int rows, hipStream_t st);
+// rows with accepted_now: y <- ynew, k_first <- k_last
+__attribute__((weak)) hipError_t launch_ode_commit(float* y, const float* ynew, float* k_first, const float* k_last, const OdeRowCtl* ctl,
+                                                   int rows, long row_elems, hipStream_t st);
+
 // windowed solve of long clips (engine.hip eval_field): out [rows, W, C2] fp32 in place.  For every row r with
 // next_row[r] = s in [0, rows), s != r (device i32 [rows]; anything else = no successor), every j < O and channel c:
 //   p = out[r, W - O + j, c], q = out[s, j, c], v = p + a_j (q - p) with a_j = (j + 1) / (O + 1); v is written to both places.

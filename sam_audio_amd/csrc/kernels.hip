@@ -798,6 +798,253 @@ hipError_t launch_ode_stage(const float* y0, const OdeStageArgs& a, float scale,
 }
 
 // ------------------------------------------------------------------------------------------------
+// adaptive solve with per-row step control (engine.hip Engine::ode_solve_adaptive).  blockIdx.y is the row everywhere, so a
+// row's status and step are uniform over a block: the branches on them are scalar.
+// ------------------------------------------------------------------------------------------------
+// out = y + h[r] * sum_j coef[j] k[j] for running rows; a finished or failed row is copied through WITHOUT reading its K (which may hold
+// anything, NaN included: a predicate, not a multiplication by zero).  out may be y itself, never a k.
+__global__ __launch_bounds__(256) void ode_stage_rows_kernel(const float4* y, const OdeSrcArgs a, const OdeRowCtl* __restrict__ ctl,
+                                                             float4* out, const long row4) {
+  const int r = blockIdx.y;
+  const bool run = ctl[r].status == ODE_ROW_RUNNING;
+  const float h = ctl[r].h;
+  const long base = (long)r * row4;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < row4; i += (long)gridDim.x * 256) {
+    const float4 v = y[base + i];
+    if (!run) {
+      out[base + i] = v;
+      continue;
+    }
+    float4 k[kOdeMaxSrc];
+#pragma unroll
+    for (int j = 0; j < kOdeMaxSrc; ++j)
+      if (j < a.n_src) k[j] = ((const float4*)a.k[j])[base + i];
+    float4 s = make_float4(a.coef[0] * k[0].x, a.coef[0] * k[0].y, a.coef[0] * k[0].z, a.coef[0] * k[0].w);
+#pragma unroll
+    for (int j = 1; j < kOdeMaxSrc; ++j)
+      if (j < a.n_src) {
+        s.x += a.coef[j] * k[j].x;
+        s.y += a.coef[j] * k[j].y;
+        s.z += a.coef[j] * k[j].z;
+        s.w += a.coef[j] * k[j].w;
+      }
+    out[base + i] = make_float4(v.x + h * s.x, v.y + h * s.y, v.z + h * s.z, v.w + h * s.w);
+  }
+}
+
+hipError_t launch_ode_stage_rows(const float* y, const OdeSrcArgs& a, const OdeRowCtl* ctl, float* out, int rows, long row_elems,
+                                 hipStream_t st) {
+  if (a.n_src < 1 || a.n_src > kOdeMaxSrc || rows < 1 || rows > 65535 || row_elems < 4 || row_elems % 4) return hipErrorInvalidValue;
+  const long row4 = row_elems / 4;
+  long gx = (row4 + 255) / 256;
+  if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(ode_stage_rows_kernel, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, st, (const float4*)y, a, ctl, (float4*)out,
+                     row4);
+  return hipGetLastError();
+}
+
+// The sum of squares of one chunk of one row's scaled error, in an order that depends on nothing but the element's place in the row:
+// block (c, r) owns elements [c * kOdeChunk, (c + 1) * kOdeChunk) of row r, lane l adds its 16 elements in index order (float4 number
+// l, l + 256, l + 512, l + 768 of the chunk), the 256 lane sums meet in a fixed binary tree in LDS, and the chunk's sum is written to
+// partials[r, c] for ode_control_kernel to add in chunk order.  No atomics.  An element of a padding frame adds nothing (a predicate),
+// so chunks behind a row's valid prefix hold +0 and a larger padded frame count only appends zeros to a sum of non-negative terms:
+// the row's norm has the same bits alone, among other rows and in a longer batch.
+__global__ __launch_bounds__(256) void ode_error_kernel(const float4* __restrict__ y, const float4* __restrict__ ynew, const OdeSrcArgs a,
+                                                        const OdeRowCtl* __restrict__ ctl, const unsigned char* __restrict__ mask,
+                                                        const float rtol, const float atol, const int use_h,
+                                                        float* __restrict__ partials, const int frames, const int chan4) {
+  __shared__ float red[256];
+  const int r = blockIdx.y, c = blockIdx.x, l = threadIdx.x;
+  const long row4 = (long)frames * chan4;
+  float sum = 0.f;
+  if (ctl[r].status == ODE_ROW_RUNNING) {
+    const float m = use_h ? ctl[r].h : 1.f;
+    const long base = (long)r * row4;
+#pragma unroll
+    for (int it = 0; it < kOdeChunk / 1024; ++it) {
+      const long i = (long)c * (kOdeChunk / 4) + it * 256 + l;
+      if (i >= row4) continue;
+      if (mask && !mask[(long)r * frames + i / chan4]) continue;
+      float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int j = 0; j < kOdeMaxSrc; ++j)
+        if (j < a.n_src) {
+          const float4 k = ((const float4*)a.k[j])[base + i];
+          e.x += a.coef[j] * k.x;
+          e.y += a.coef[j] * k.y;
+          e.z += a.coef[j] * k.z;
+          e.w += a.coef[j] * k.w;
+        }
+      const float4 v = y[base + i];
+      float4 w = v;
+      if (ynew) w = ynew[base + i];
+      const float qx = m * e.x / (atol + rtol * fmaxf(fabsf(v.x), fabsf(w.x)));
+      const float qy = m * e.y / (atol + rtol * fmaxf(fabsf(v.y), fabsf(w.y)));
+      const float qz = m * e.z / (atol + rtol * fmaxf(fabsf(v.z), fabsf(w.z)));
+      const float qw = m * e.w / (atol + rtol * fmaxf(fabsf(v.w), fabsf(w.w)));
+      sum += qx * qx;
+      sum += qy * qy;
+      sum += qz * qz;
+      sum += qw * qw;
+    }
+  }
+  red[l] = sum;
+  for (int o = 128; o > 0; o >>= 1) {
+    __syncthreads();
+    if (l < o) red[l] += red[l + o];
+  }
+  if (l == 0) partials[(long)r * gridDim.x + c] = red[0];
+}
+
+hipError_t launch_ode_error(const float* y, const float* ynew, const OdeSrcArgs& a, const OdeRowCtl* ctl, const unsigned char* mask,
+                            float rtol, float atol, int use_h, float* partials, int rows, int frames, int channels, hipStream_t st) {
+  if (a.n_src < 1 || a.n_src > kOdeMaxSrc || rows < 1 || rows > 65535 || frames < 1 || channels < 4 || channels % 4)
+    return hipErrorInvalidValue;
+  const long chunks = ((long)frames * channels + kOdeChunk - 1) / kOdeChunk;
+  hipLaunchKernelGGL(ode_error_kernel, dim3((unsigned)chunks, (unsigned)rows), dim3(256), 0, st, (const float4*)y, (const float4*)ynew, a,
+                     ctl, mask, rtol, atol, use_h, partials, frames, channels / 4);
+  return hipGetLastError();
+}
+
+// The controller: scipy's RungeKutta._step_impl (max_step = inf) and select_initial_step, one lane per row, fp32 throughout.
+// Contraction is off in the bookkeeping: t, h and the stage times are the separately rounded products and sums that a float32
+// restatement computes; powf is the one operation that may differ from it in the last place.
+__device__ inline void ode_row_begin_trial(OdeRowCtl& c, const OdeControlArgs& a, float* times, const int rows, const int r) {
+#pragma clang fp contract(off)
+  if (c.accepted + c.rejected >= a.max_num_steps) {
+    c.status = ODE_ROW_MAX_STEPS;
+    return;
+  }
+  const float min_step = 10.f * (nextafterf(c.t, INFINITY) - c.t);
+  if (!c.step_rejected) {
+    if (c.h_abs < min_step) c.h_abs = min_step;
+  } else if (c.h_abs < min_step) {
+    c.status = ODE_ROW_STEP_UNDERFLOW;
+    return;
+  }
+  float t_new = c.t + c.h_abs;
+  if (t_new - a.t1 > 0.f) t_new = a.t1;
+  c.t_new = t_new;
+  c.h = t_new - c.t;
+  for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = c.t + a.c[i] * c.h;
+}
+
+__global__ __launch_bounds__(256) void ode_control_kernel(OdeRowCtl* ctl, const int mode, const OdeControlArgs a,
+                                                          const float* __restrict__ partials, const float* __restrict__ partials_b,
+                                                          const int chunks, const unsigned char* __restrict__ mask, const int frames,
+                                                          const int channels, float* times, int* active, const int rows) {
+#pragma clang fp contract(off)
+  __shared__ int running[256];
+  int mine = 0;
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    OdeRowCtl c = ctl[r];
+    if (mode == ODE_CTL_RESET) {
+      c = OdeRowCtl{};
+      c.t = c.t_new = a.t0;
+      int valid = frames;
+      if (mask) {
+        valid = 0;
+        for (int f = 0; f < frames; ++f) valid += mask[(long)r * frames + f] != 0;
+      }
+      c.n_valid = valid * channels;
+      for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = a.t0;
+      if (a.first_step > 0.f) {
+        c.h_abs = a.first_step;
+        ode_row_begin_trial(c, a, times, rows, r);
+      }
+    } else if (c.status == ODE_ROW_RUNNING) {
+      float ss = 0.f, ss_b = 0.f;
+      for (int k = 0; k < chunks; ++k) ss += partials[(long)r * chunks + k];
+      const float n = (float)(c.n_valid > 0 ? c.n_valid : 1);
+      const float norm = sqrtf(ss / n);
+      if (mode == ODE_CTL_INIT1) {   // d0 = |y0 / scale|, d1 = |f0 / scale|: the explicit-Euler probe step h0
+        for (int k = 0; k < chunks; ++k) ss_b += partials_b[(long)r * chunks + k];
+        const float d0 = norm, d1 = sqrtf(ss_b / n);
+        float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+        h0 = fminf(h0, a.t1 - a.t0);
+        c.d1 = d1;
+        c.h0 = c.h = h0;
+        times[rows + r] = a.t0 + h0;
+      } else if (mode == ODE_CTL_INIT2) {   // d2 = |(f1 - f0) / scale| / h0
+        const float d2 = norm / c.h0;
+        const float h1 = (c.d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, c.h0 * 1e-3f)
+                                                          : powf(0.01f / fmaxf(c.d1, d2), 1.f / (float)(a.order + 1));
+        c.h_abs = fminf(fminf(100.f * c.h0, h1), a.t1 - a.t0);
+        ode_row_begin_trial(c, a, times, rows, r);
+      } else {
+        const float expo = -1.f / (float)(a.order + 1);
+        c.err = norm;
+        c.h_abs = c.h;
+        if (norm < 1.f) {
+          float factor = norm == 0.f ? a.ifactor : fminf(a.ifactor, a.safety * powf(norm, expo));
+          if (c.step_rejected) factor = fminf(1.f, factor);
+          c.h_abs *= factor;
+          c.h_prev = c.h;
+          c.t = c.t_new;
+          c.accepted += 1;
+          c.accepted_now = 1;
+          c.step_rejected = 0;
+          if (c.t - a.t1 >= 0.f) c.status = ODE_ROW_FINISHED;
+        } else {   // (a NaN norm lands here: fmaxf drops it and the step shrinks by dfactor until it underflows)
+          c.h_abs *= fmaxf(a.dfactor, a.safety * powf(norm, expo));
+          c.rejected += 1;
+          c.accepted_now = 0;
+          c.step_rejected = 1;
+        }
+        if (c.status == ODE_ROW_RUNNING) ode_row_begin_trial(c, a, times, rows, r);
+      }
+      if (c.status != ODE_ROW_RUNNING)   // a row that stops rides along at its own time
+        for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = c.t;
+    } else {
+      c.accepted_now = 0;
+    }
+    ctl[r] = c;
+    mine += c.status == ODE_ROW_RUNNING;
+  }
+  running[threadIdx.x] = mine;
+  for (int o = 128; o > 0; o >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < o) running[threadIdx.x] += running[threadIdx.x + o];
+  }
+  if (threadIdx.x == 0) *active = running[0];
+}
+
+hipError_t launch_ode_control(OdeRowCtl* ctl, int mode, const OdeControlArgs& a, const float* partials, const float* partials_b,
+                              int chunks, const unsigned char* mask, int frames, int channels, float* times, int* active, int rows,
+                              hipStream_t st) {
+  if (rows < 1 || mode < ODE_CTL_RESET || mode > ODE_CTL_STEP || a.n_times < 2 || a.n_times > kOdeMaxSrc) return hipErrorInvalidValue;
+  if (mode != ODE_CTL_RESET && (!partials || chunks < 1)) return hipErrorInvalidValue;
+  if (mode == ODE_CTL_INIT1 && !partials_b) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ode_control_kernel, dim3(1), dim3(256), 0, st, ctl, mode, a, partials, partials_b, chunks, mask, frames, channels,
+                     times, active, rows);
+  return hipGetLastError();
+}
+
+// accepted rows: y <- y_new and (first same as last) K[0] <- K[last]; the other rows keep both
+__global__ __launch_bounds__(256) void ode_commit_kernel(float4* __restrict__ y, const float4* __restrict__ ynew,
+                                                         float4* __restrict__ k_first, const float4* __restrict__ k_last,
+                                                         const OdeRowCtl* __restrict__ ctl, const long row4) {
+  const int r = blockIdx.y;
+  if (!ctl[r].accepted_now) return;
+  const long base = (long)r * row4;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < row4; i += (long)gridDim.x * 256) {
+    y[base + i] = ynew[base + i];
+    k_first[base + i] = k_last[base + i];
+  }
+}
+
+hipError_t launch_ode_commit(float* y, const float* ynew, float* k_first, const float* k_last, const OdeRowCtl* ctl, int rows,
+                             long row_elems, hipStream_t st) {
+  if (rows < 1 || rows > 65535 || row_elems < 4 || row_elems % 4) return hipErrorInvalidValue;
+  const long row4 = row_elems / 4;
+  long gx = (row4 + 255) / 256;
+  if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(ode_commit_kernel, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, st, (float4*)y, (const float4*)ynew,
+                     (float4*)k_first, (const float4*)k_last, ctl, row4);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // windowed solve of long clips (engine.hip eval_field): the last O frames of a window row and the first O frames
 // of its successor row describe the same frames of the clip; after every field evaluation both are replaced by their cross-fade
 // v = p + a_j (q - p), a_j = (j + 1) / (O + 1), in place, float4 per lane.  One lane reads both elements of a pair and writes the same

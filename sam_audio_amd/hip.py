@@ -80,7 +80,10 @@ def dtype_code(dtype, operands: Optional[str] = None, alt_ok: bool = False) -> i
         if dtype != want:
             raise TypeError(f"{dtype} tensor handed to the {operands}-operand build of libsamaudio_hip")
     return {torch.float32: DT_F32, torch.bfloat16: DT_BF16, torch.float16: DT_BF16}[dtype]
-ODE_EULER, ODE_MIDPOINT, ODE_RK4, ODE_HEUN3 = 0, 1, 2, 3
+ODE_EULER, ODE_MIDPOINT, ODE_RK4, ODE_HEUN3, ODE_DOPRI5, ODE_BOSH3 = 0, 1, 2, 3, 4, 5
+ODE_ADAPTIVE_STAGES = {ODE_DOPRI5: 6, ODE_BOSH3: 3}   # field evaluations per trial step of samaudio_ode_solve_adaptive's methods
+ODE_ROW_STATUS = ("running", "finished", "step_underflow", "max_num_steps")   # samaudio.h SAMAUDIO_ODE_ROW_*
+ODE_CTL_WORDS = 16   # 4-byte words of a row's control block (samaudio.h, the ode_* kernel hooks)
 ODE_STAGES = {ODE_RK4: 4, ODE_HEUN3: 3}   # field evaluations per step of the methods that keep stage buffers
 ODE_TIME_SLOTS = 4096                     # the engine's table of evaluation times (samaudio.h samaudio_ode_solve)
 OPT_TAIL_SPLIT, OPT_F32_CLASSES, OPT_QUANT_CLASSES, OPT_QUANT_FORMAT, OPT_ALT16_CLASSES, OPT_PREFETCH_ROWS, OPT_SENTINEL = 1, 2, 3, 4, 5, 6, 7
@@ -258,6 +261,18 @@ class KernelStat(C.Structure):
                 ("ms", C.c_double)]
 
 
+class OdeAdaptive(C.Structure):
+    """Mirror of `samaudio_ode_adaptive`."""
+    _fields_ = [("rtol", C.c_float), ("atol", C.c_float), ("first_step", C.c_float), ("safety", C.c_float), ("ifactor", C.c_float),
+                ("dfactor", C.c_float), ("max_num_steps", C.c_int32)]
+
+
+class OdeRowStats(C.Structure):
+    """Mirror of `samaudio_ode_row_stats`."""
+    _fields_ = [("accepted", C.c_int32), ("rejected", C.c_int32), ("status", C.c_int32), ("evaluations", C.c_int32),
+                ("t", C.c_float), ("last_h", C.c_float)]
+
+
 _lib = None     # the default (bf16-operand) library; tests/conftest.py swaps it for its CPU dry-run builds
 _libs = {}      # operand format -> loaded library
 # library of this THREAD's most recent call: check() reads samaudio_last_error() (itself a thread-local string of the
@@ -299,6 +314,8 @@ _PROTOS = {
     "samaudio_codec_decode_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_ode_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "samaudio_ode_solve_adaptive": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.POINTER(OdeAdaptive),
+                                              C.POINTER(OdeRowStats), C.c_void_p]),
     "samaudio_ode_stage_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "samaudio_set_ode_stages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_set_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
@@ -361,6 +378,14 @@ _PROTOS = {
     "samaudio_op_set_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     "samaudio_op_ode_stage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_void_p,
                                         C.c_int64, C.c_void_p]),
+    "samaudio_op_ode_stage_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int64, C.c_void_p]),
+    "samaudio_op_ode_error": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "samaudio_op_ode_control": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(OdeAdaptive), C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p]),
+    "samaudio_op_ode_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "samaudio_op_repeat_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "samaudio_op_repeat_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "samaudio_op_embed_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),

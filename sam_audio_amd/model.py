@@ -38,10 +38,58 @@ class SeparationResult:  # reference model.py:68-72
     noise: torch.Tensor
 
 
-# torchdiffeq's fixed-grid solvers the engine runs (samaudio.h SAMAUDIO_ODE_*).  Its adaptive solvers size every step from the error
-# norm of the whole batch, so a row's result would depend on which rows share the call (sharding, streams=2 and the candidate repeat rely
-# on rows being independent), and the Adams family's warm-up cannot be restated without its source: DESIGN.md section 1 row a6.
+# torchdiffeq's fixed-grid solvers the engine runs (samaudio.h SAMAUDIO_ODE_*), and the two adaptive pairs.  torchdiffeq's adaptive
+# solvers size every step from the error norm of the whole batch, so a row's result would depend on which rows share the call
+# (sharding, streams=2 and the candidate repeat rely on rows being independent); here every row carries its own time, step and error
+# norm on the device instead (`ode_adaptive` below): pinned to scipy's RK45 / RK23, unpinned vs torchdiffeq.
+# The other adaptive methods and the Adams family cannot be restated without their source: DESIGN.md section 1 row a6.
 ODE_METHODS = {"euler": hip.ODE_EULER, "midpoint": hip.ODE_MIDPOINT, "rk4": hip.ODE_RK4, "heun3": hip.ODE_HEUN3}
+ODE_ADAPTIVE_METHODS = {"dopri5": hip.ODE_DOPRI5, "bosh3": hip.ODE_BOSH3}
+# options of the adaptive methods (torchdiffeq's names) and their defaults: scipy's SAFETY / MAX_FACTOR / MIN_FACTOR
+ODE_ADAPTIVE_OPTIONS = {"first_step": None, "safety": 0.9, "ifactor": 10.0, "dfactor": 0.2, "max_num_steps": 2 ** 31 - 1}
+
+
+def is_adaptive(ode_opt: Dict[str, Any]) -> bool:
+    return ode_opt.get("method", "midpoint") in ODE_ADAPTIVE_METHODS
+
+
+def ode_adaptive(ode_opt: Dict[str, Any], windowed: bool = False):
+    """(method id, hip.OdeAdaptive) for `ode_opt` = {"method": "dopri5" | "bosh3", "rtol": r, "atol": a, "options": {...}}, the shape
+    torchdiffeq.odeint takes (reference model.py:285-290).  The solver is this build's own: embedded Runge-Kutta pairs with PER-ROW step
+    control, pinned to scipy's RK45 / RK23 (tableaux, controller, initial step) and unpinned vs torchdiffeq, from which it differs in
+    three known ways - the error norm and the step are per row, not per call (identical for one row); the last step is clipped to
+    t1 instead of stepping past it and interpolating back; the accept factor is capped at 1 after a rejection within the same step -
+    so the two agree to O(tolerance), no closer.
+    rtol, atol: required, positive.  options: first_step (default: scipy's select_initial_step, one more field evaluation), safety
+    (0.9), ifactor (10), dfactor (0.2), max_num_steps (trial steps per row).  Everything else - other keys, missing tolerances, a
+    windowed solve - is a ValueError."""
+    method = ode_opt.get("method", "midpoint")
+    if method not in ODE_ADAPTIVE_METHODS:
+        raise ValueError(f"ode method {method!r} is not an adaptive method of the HIP path ({' | '.join(ODE_ADAPTIVE_METHODS)})")
+    if windowed:
+        raise ValueError(f"window_seconds= with the adaptive method {method!r}: the rows of one clip share their blended frames and "
+                         "must share their times, which per-row step control does not give them; use a fixed-grid method")
+    unknown = sorted(set(ode_opt) - {"method", "rtol", "atol", "options"})
+    if unknown:
+        raise ValueError(f"ode_opt: unsupported {unknown} for {method!r} (method | rtol | atol | options)")
+    if ode_opt.get("rtol") is None or ode_opt.get("atol") is None:
+        raise ValueError(f"ode method {method!r} needs ode_opt['rtol'] and ode_opt['atol']: torchdiffeq's defaults (1e-7 / 1e-9) lie "
+                         "below what an fp32 vector field resolves, so there is no default here; 1e-3 .. 1e-5 are sensible")
+    rtol, atol = float(ode_opt["rtol"]), float(ode_opt["atol"])
+    if not (rtol > 0 and atol > 0 and math.isfinite(rtol) and math.isfinite(atol)):
+        raise ValueError(f"ode_opt: rtol and atol must be positive floats (got {ode_opt['rtol']!r}, {ode_opt['atol']!r})")
+    options = dict(ode_opt.get("options") or {})
+    unknown = sorted(set(options) - set(ODE_ADAPTIVE_OPTIONS))
+    if unknown:
+        raise ValueError(f"ode_opt['options']: unsupported {unknown} for {method!r} ({' | '.join(ODE_ADAPTIVE_OPTIONS)})")
+    o = {k: (v if options.get(k) is None else options[k]) for k, v in ODE_ADAPTIVE_OPTIONS.items()}
+    first = 0.0 if o["first_step"] is None else float(o["first_step"])
+    if o["first_step"] is not None and not (0 < first <= 1.0):
+        raise ValueError(f"ode_opt['options']['first_step'] must lie in (0, 1] (got {o['first_step']!r})")
+    safety, ifactor, dfactor, steps = float(o["safety"]), float(o["ifactor"]), float(o["dfactor"]), int(o["max_num_steps"])
+    if not (safety > 0 and ifactor >= 1 and 0 < dfactor < 1 and steps >= 1):
+        raise ValueError("ode_opt['options']: safety > 0, ifactor >= 1, 0 < dfactor < 1 and max_num_steps >= 1 are required")
+    return ODE_ADAPTIVE_METHODS[method], hip.OdeAdaptive(rtol, atol, first, safety, ifactor, dfactor, min(steps, 2 ** 31 - 1))
 
 
 def _field_stand_in(t, y):
@@ -56,11 +104,13 @@ def ode_grid(ode_opt: Dict[str, Any], t0: float = 0.0, t1: float = 1.0, y0: Opti
       {"grid_constructor": g} g(func, y0, t) with t = tensor([t0, t1]) on y0's device and `func` a stand-in that raises if called;
                               1-D, strictly increasing (also as float32, what the engine integrates over), from t0 to t1 exactly;
       none / {}               one step over [t0, t1].
-    Everything else - other methods, other keys, step_size together with grid_constructor - is a ValueError."""
+    Everything else - other methods (dopri5 | bosh3 are ode_adaptive's), other keys, step_size together with grid_constructor - is a
+    ValueError."""
     method = ode_opt.get("method", "midpoint")
     if method not in ODE_METHODS:
-        raise ValueError(f"ode method {method!r} is not supported by the HIP path ({' | '.join(ODE_METHODS)}; the adaptive and "
-                         "Adams solvers are not: DESIGN.md section 1 row a6)")
+        raise ValueError(f"ode method {method!r} is not a fixed-grid method of the HIP path ({' | '.join(ODE_METHODS)}; "
+                         f"{' | '.join(ODE_ADAPTIVE_METHODS)} go through ode_adaptive; the other adaptive and the Adams solvers are "
+                         "not supported: DESIGN.md section 1 row a6)")
     options = dict(ode_opt.get("options") or {})
     step = options.pop("step_size", None)
     constructor = options.pop("grid_constructor", None)
@@ -699,6 +749,12 @@ class SAMAudio:
     def solve(self, noise: torch.Tensor, ode_opt: Dict[str, Any] = DFLT_ODE_OPT) -> torch.Tensor:
         """Integrate the flow ODE from `noise` with the conditioning of the last `_prepare` call."""
         state = noise.to(self.device, torch.float32).clone().contiguous()
+        if is_adaptive(ode_opt):
+            method, params = ode_adaptive(ode_opt)
+            with torch.cuda.device(self.device):
+                rows = self._solve_adaptive(None, state, method, params)
+            self._set_ode_stats([rows], state)
+            return state
         method, grid = ode_grid(ode_opt, y0=state)
         g = (C.c_float * len(grid))(*grid)
         with torch.cuda.device(self.device):
@@ -706,6 +762,37 @@ class SAMAudio:
             hip.check(self._lib.samaudio_ode_solve(self._ctx, hip.ptr(state), method, g, len(grid),
                                                    hip.current_stream_ptr()))
         return state
+
+    def _solve_adaptive(self, lane: Optional[_Lane], state: torch.Tensor, method: int, params: "hip.OdeAdaptive") -> List[dict]:
+        """samaudio_ode_solve_adaptive on `state` (rows of the context's last prepare), in place, from t = 0 to 1; the call synchronises
+        the current stream once per trial step.  Returns the rows' statistics."""
+        ctx = self._ctx if lane is None else lane._ctx
+        rows, frames = state.size(0), state.size(1)
+        self._ensure_stages(method, rows, frames, lane)
+        stats = (hip.OdeRowStats * rows)()
+        hip.check(self._lib.samaudio_ode_solve_adaptive(ctx, hip.ptr(state), method, 0.0, 1.0, C.byref(params), stats,
+                                                        hip.current_stream_ptr()))
+        return [dict(accepted=s.accepted, rejected=s.rejected, t=s.t, last_h=s.last_h, status=hip.ODE_ROW_STATUS[s.status],
+                     evaluations=s.evaluations) for s in stats]
+
+    def _set_ode_stats(self, groups: List[List[dict]], state: torch.Tensor) -> None:
+        """`last_ode_stats` of an adaptive solve: per row accepted / rejected / t / last_h / status, and `evaluations`, the field
+        launches of the solve (summed over the row groups of a streams > 1 solve).  A row that failed raises RuntimeError; nothing of
+        the solve is rolled back, and the state as the solve left it is kept in `last_latent` before raising: finished rows are
+        complete there, a failed row holds its state at the `t` of its statistics."""
+        self.last_latent = state
+        rows = [dict(r) for g in groups for r in g]
+        evaluations = sum(g[0]["evaluations"] for g in groups if g)
+        for r in rows:
+            del r["evaluations"]
+        self.last_ode_stats = {"rows": rows, "evaluations": evaluations}
+        for i, r in enumerate(rows):
+            if r["status"] != "finished":
+                why = ("its step fell below 10 ulp(t)" if r["status"] == "step_underflow"
+                       else "it used up options['max_num_steps'] trial steps")
+                raise RuntimeError(f"adaptive ODE solve: row {i} stopped at t = {r['t']:.6g} after {r['accepted']} accepted and "
+                                   f"{r['rejected']} rejected steps ({why}); try a looser rtol / atol (the state every row "
+                                   "reached is in model.last_latent, the statistics in model.last_ode_stats)")
 
     def _apply_options(self, groups: int) -> None:
         split = int(self.tail_split if self.tail_split is not None else groups == 1)
@@ -722,8 +809,13 @@ class SAMAudio:
         import threading
         from .dist import shard_range
         state = noise.to(self.device, torch.float32).clone().contiguous()
-        method, grid = ode_grid(ode_opt, y0=state)   # one grid for the whole batch (a grid_constructor sees all rows)
-        g = (C.c_float * len(grid))(*grid)
+        adaptive = is_adaptive(ode_opt)   # rows are independent there as well: each lane loops on its own context and stream
+        if adaptive:
+            method, params = ode_adaptive(ode_opt)
+            group_stats: List[List[dict]] = [[] for _ in range(groups)]
+        else:
+            method, grid = ode_grid(ode_opt, y0=state)   # one grid for the whole batch (a grid_constructor sees all rows)
+            g = (C.c_float * len(grid))(*grid)
         rows, frames, C2 = state.shape
         wavs = (torch.empty(rows * 2, frames * self.cfg.audio_codec.hop_length, device=self.device)
                 if decode else None)
@@ -758,9 +850,12 @@ class SAMAudio:
                 with torch.inference_mode(), torch.cuda.device(self.device), torch.cuda.stream(stream):
                     self._prepare(*part, lane=lane, anchors_validated=anchors_validated, candidates=candidates, latent=latent)
                     ctx = self._ctx if lane is None else lane._ctx
-                    self._ensure_stages(method, len(rr), frames, lane)
-                    hip.check(self._lib.samaudio_ode_solve(ctx, hip.ptr(state[sl]), method, g, len(grid),
-                                                           hip.current_stream_ptr()))
+                    if adaptive:
+                        group_stats[i] = self._solve_adaptive(lane, state[sl], method, params)
+                    else:
+                        self._ensure_stages(method, len(rr), frames, lane)
+                        hip.check(self._lib.samaudio_ode_solve(ctx, hip.ptr(state[sl]), method, g, len(grid),
+                                                               hip.current_stream_ptr()))
                     if decode:   # waveforms (2b, 2b+1) = (target, residual) of row b, gathered from the state inside the engine
                         self.decode_audio(state[sl], lane=lane, out=wavs[2 * rr.start: 2 * rr.stop], pairs=True)
             except BaseException as exc:  # re-raised on the caller's thread
@@ -781,6 +876,8 @@ class SAMAudio:
                 main.wait_stream(lane.stream)
         if errors:
             raise errors[0]
+        if adaptive:
+            self._set_ode_stats(group_stats, state)
         return (state, wavs.view(rows, 2, -1)) if decode else state
 
     # ------------------------------------------------------------------ separate()
@@ -812,6 +909,10 @@ class SAMAudio:
         (model.py:259-268; mind quirk Q13 below).  `output_sampling_rate`: when set and different from the codec's rate, the chosen
         target and residual of every clip are resampled to it on the device (sam_audio_amd/audio.py resample: what the reference's
         evaluation does with torchaudio behind separate()); None leaves the results as the codec wrote them.
+        `ode_opt`: torchdiffeq's shape.  The fixed-grid methods (`ode_grid`) or {"method": "dopri5" | "bosh3", "rtol": r, "atol": a,
+        "options": {...}} (`ode_adaptive`): embedded pairs with per-row step control, pinned to scipy's RK45 / RK23 and unpinned vs
+        torchdiffeq.  An adaptive solve leaves `last_ode_stats` and raises RuntimeError when a row fails (the
+        state every row reached is then in `last_latent`); it does not combine with `window_seconds`.
         `window_seconds` / `window_overlap_seconds` (both or neither; this build's own definition): clips longer
         than the window are solved as overlapping windows of that length - rows of ONE batch whose overlapping frames are cross-faded
         after every evaluation of the vector field, so they hold the same bits through the whole solve; the latent is stitched by index
@@ -819,6 +920,8 @@ class SAMAudio:
         windows of a batch are solved together (no splitting when they do not fit in memory), on the model's own context: `streams` > 1
         is ignored for a windowed solve.  `last_latent` is the stitched latent, `last_window_latent` the window rows,
         `last_window_plan` the longform.WindowPlan.  A clip that fits one window is one row without a successor: the plain path."""
+        if is_adaptive(ode_opt):   # before anything runs: the tolerances, the options, and no windows
+            ode_adaptive(ode_opt, windowed=window_seconds is not None)
         if not (self._has_dit and self._has_codec):
             raise RuntimeError("load_state_dict() first")
         if (window_seconds is None) != (window_overlap_seconds is None):
