@@ -747,9 +747,18 @@ int samaudio_op_codec_conv(const void* params_host, size_t params_bytes, const v
  * equal to the two samaudio_op_gemm launches; ERR_ARG when the pair is not one the fused kernel covers. */
 int samaudio_op_resunit(const void* conv7_params_host, const void* conv1_params_host, size_t params_bytes,
                         samaudio_stream stream);
+/* ---- the norm kernels (tests/test_norm_kernels_gpu.py).  Each hook refuses, as SAMAUDIO_ERR_ARG with a message naming the argument,
+ * what its kernels assume - null required pointers; rows / batch / frames / dim (channels) <= 0, halo < 0, rows_per_batch <= 0;
+ * dim % 4; fp32 base pointers off 16 bytes (a 16-bit output: 8; partials_f64: 8) - and launches nothing then. */
+/* out[r] = rms_norm(x[r]) * w, and with a time vector ... * (1 + scale_tab + tvec[r / rows_per_batch][scale_off ..]) + shift_tab +
+ * tvec[..][shift_off ..]: x [rows, dim] f32, out [rows, dim] in `precision`'s storage type, tvec rows tvec_ld floats apart (0: one
+ * row for all).  shift_tab, scale_tab and tvec are given together or all null (plain RMSNorm); tvec_ld, shift_off, scale_off % 4. */
 int samaudio_op_rmsnorm_mod(const float* x, const float* w, const float* shift_tab, const float* scale_tab,
                             const float* tvec, int64_t tvec_ld, int shift_off, int scale_off, void* out,
                             int precision, int rows, int dim, int rows_per_batch, float eps, samaudio_stream stream);
+/* GroupNorm(1 group) + SiLU, channels-last: x [batch, frames, channels] f32, statistics per item over all its entries,
+ * partials_f64: batch*64*2 doubles of scratch (every one written before it is read), out [batch][halo + frames + halo][channels]
+ * (halo rows untouched) */
 int samaudio_op_groupnorm_silu(const float* x, const float* w, const float* b, void* partials_f64, void* out,
                                int precision, int batch, int frames, int channels, int halo, float eps,
                                samaudio_stream stream);
@@ -766,6 +775,7 @@ int samaudio_op_cross_attention(const void* q, const float* q_w, void* kv, const
  * the per-batch operand of the folded cross-attention output projection. */
 int samaudio_op_cross_attn_fold(const void* wo, const void* kv, int64_t kv_ld, void* ut, int kp, int batch, int text_len,
                                 int ltp, int heads, samaudio_stream stream);
+/* acc[r] += tanh(gate[0]) * (LayerNorm(x[r]) * w + b), in place: x, acc [rows, dim] f32, gate one float on the device */
 int samaudio_op_layernorm_accum(const float* x, const float* w, const float* b, const float* gate, float* acc,
                                 int rows, int dim, float eps, samaudio_stream stream);
 /* masked GroupNorm(1) + SiLU of the PE-AV patch embedder: x [batch, frames, channels] f32, mask [batch, frames] u8,
@@ -778,6 +788,8 @@ int samaudio_op_masked_groupnorm_silu(const float* x, const float* w, const floa
 int samaudio_op_masked_groupnorm_silu_split3(const float* x, const float* w, const float* b, const uint8_t* mask,
                                              void* partials_f64, void* out3, int batch, int frames, int channels, int halo,
                                              float eps, samaudio_stream stream);
+/* LayerNorm(x[r]) * w + b: x rows x_ld floats apart (x_ld % 4, x_ld >= dim), out_f32 [rows, dim] and / or out_act [rows, dim] in
+ * `precision`'s storage type (the fp32 value rounded to nearest even); either may be null, not both */
 int samaudio_op_layernorm_rows(const float* x, int64_t x_ld, const float* w, const float* b, float* out_f32,
                                void* out_act, int precision, int64_t rows, int dim, float eps, samaudio_stream stream);
 /* the same with the output as a compensated GEMM operand (SAMAUDIO_OPT_X3_CLASSES; the PE-Core vision tower's LayerNorms in front of

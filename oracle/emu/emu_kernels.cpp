@@ -156,9 +156,11 @@ static void rmsnorm_mod_t(const float* x, const float* w, const float* shift_tab
                           int rows_per_b, float eps) {
   for (int row = 0; row < M; ++row) {
     const float* xr = x + (long)row * D;
-    float ss = 0.f;
-    for (int i = 0; i < D; ++i) ss += xr[i] * xr[i];
-    const float inv = 1.0f / std::sqrt(ss / (float)D + eps);
+    // (summed in double, as launch_rmsnorm_gs below: a serial float sum over 3072 and more squares drifts by more than the 8 x
+    // float32-statement bound of tests/test_norm_kernels_gpu.py allows - the kernel's 64 lanes + wave tree do not)
+    double ss = 0;
+    for (int i = 0; i < D; ++i) ss += (double)xr[i] * xr[i];
+    const float inv = 1.0f / std::sqrt((float)(ss / D) + eps);
     const float* trow = tvec ? tvec + (long)(row / rows_per_b) * tvec_ld : nullptr;
     for (int i = 0; i < D; ++i) {
       float o = xr[i] * inv * w[i];

@@ -232,10 +232,28 @@ int samaudio_op_resunit(const void* conv7_params_host, const void* conv1_params_
   return hip_ret(sa::launch_resunit(p, q, (hipStream_t)stream), "resunit");
 }
 
+// ---- the norm hooks (tests/test_norm_kernels_gpu.py): they refuse what their kernels assume, then call the launcher unchanged ----
+namespace {
+bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+bool al_out(const void* p, int precision) { return ((uintptr_t)p & (precision == SAMAUDIO_BF16 ? 7 : 15)) == 0; }
+}  // namespace
+
 int samaudio_op_rmsnorm_mod(const float* x, const float* w, const float* shift_tab, const float* scale_tab,
                             const float* tvec, int64_t tvec_ld, int shift_off, int scale_off, void* out,
                             int precision, int rows, int dim, int rows_per_batch, float eps, samaudio_stream stream) {
-  if (dim % 4) return bad("rmsnorm_mod: dim % 4");
+  if (!x || !w || !out) return bad("rmsnorm_mod: null x / w / out");
+  if (rows <= 0) return bad("rmsnorm_mod: rows <= 0");
+  if (dim <= 0 || dim % 4) return bad("rmsnorm_mod: dim % 4 (and dim > 0)");
+  if (rows_per_batch <= 0) return bad("rmsnorm_mod: rows_per_batch <= 0");
+  const int given = (shift_tab ? 1 : 0) + (scale_tab ? 1 : 0) + (tvec ? 1 : 0);
+  if (given != 0 && given != 3) return bad("rmsnorm_mod: shift_tab, scale_tab and tvec are given together or not at all");
+  if (tvec) {
+    if (tvec_ld < 0 || tvec_ld % 4) return bad("rmsnorm_mod: tvec_ld % 4");
+    if (shift_off < 0 || shift_off % 4) return bad("rmsnorm_mod: shift_off % 4");
+    if (scale_off < 0 || scale_off % 4) return bad("rmsnorm_mod: scale_off % 4");
+  }
+  if (!al16(x) || !al16(w) || !al16(shift_tab) || !al16(scale_tab) || !al16(tvec) || !al_out(out, precision))
+    return bad("rmsnorm_mod: x, w, shift_tab, scale_tab and tvec must be aligned to 16 bytes, out to 16 (fp32) / 8 (16-bit)");
   return hip_ret(sa::launch_rmsnorm_mod(x, w, shift_tab, scale_tab, tvec, tvec_ld, shift_off, scale_off, out,
                                         precision == SAMAUDIO_BF16, rows, dim, rows_per_batch, eps,
                                         (hipStream_t)stream), "rmsnorm_mod");
@@ -244,7 +262,13 @@ int samaudio_op_rmsnorm_mod(const float* x, const float* w, const float* shift_t
 int samaudio_op_groupnorm_silu(const float* x, const float* w, const float* b, void* partials_f64, void* out,
                                int precision, int batch, int frames, int channels, int halo, float eps,
                                samaudio_stream stream) {
-  if (channels % 4) return bad("groupnorm: channels % 4");
+  if (!x || !w || !b || !partials_f64 || !out) return bad("groupnorm: null x / w / b / partials_f64 / out");
+  if (batch <= 0) return bad("groupnorm: batch <= 0");
+  if (frames <= 0) return bad("groupnorm: frames <= 0");
+  if (channels <= 0 || channels % 4) return bad("groupnorm: channels % 4 (and channels > 0)");
+  if (halo < 0) return bad("groupnorm: halo < 0");
+  if (!al16(x) || !al16(w) || !al16(b) || ((uintptr_t)partials_f64 & 7) || !al_out(out, precision))
+    return bad("groupnorm: x, w and b must be aligned to 16 bytes, partials_f64 to 8, out to 16 (fp32) / 8 (16-bit)");
   return hip_ret(sa::launch_groupnorm_silu(x, w, b, (double*)partials_f64, out, precision == SAMAUDIO_BF16, batch,
                                            frames, channels, halo, eps, (hipStream_t)stream), "groupnorm_silu");
 }
@@ -288,6 +312,10 @@ int samaudio_op_cross_attn_fold(const void* wo, const void* kv, int64_t kv_ld, v
 
 int samaudio_op_layernorm_accum(const float* x, const float* w, const float* b, const float* gate, float* acc,
                                 int rows, int dim, float eps, samaudio_stream stream) {
+  if (!x || !w || !b || !gate || !acc) return bad("layernorm_accum: null x / w / b / gate / acc");
+  if (rows <= 0) return bad("layernorm_accum: rows <= 0");
+  if (dim <= 0 || dim % 4) return bad("layernorm_accum: dim % 4 (and dim > 0)");
+  if (!al16(x) || !al16(w) || !al16(b) || !al16(acc)) return bad("layernorm_accum: x, w, b and acc must be aligned to 16 bytes");
   return hip_ret(sa::launch_layernorm_accum(x, w, b, gate, acc, rows, dim, eps, (hipStream_t)stream),
                  "layernorm_accum");
 }
@@ -295,7 +323,13 @@ int samaudio_op_layernorm_accum(const float* x, const float* w, const float* b, 
 int samaudio_op_masked_groupnorm_silu(const float* x, const float* w, const float* b, const uint8_t* mask,
                                       void* partials_f64, void* out, int precision, int batch, int frames,
                                       int channels, int halo, float eps, samaudio_stream stream) {
-  if (channels % 4 || !mask) return bad("masked_groupnorm: channels % 4 / null mask");
+  if (!x || !w || !b || !mask || !partials_f64 || !out) return bad("masked_groupnorm: null x / w / b / mask / partials_f64 / out");
+  if (batch <= 0) return bad("masked_groupnorm: batch <= 0");
+  if (frames <= 0) return bad("masked_groupnorm: frames <= 0");
+  if (channels <= 0 || channels % 4) return bad("masked_groupnorm: channels % 4 (and channels > 0)");
+  if (halo < 0) return bad("masked_groupnorm: halo < 0");
+  if (!al16(x) || !al16(w) || !al16(b) || ((uintptr_t)partials_f64 & 7) || !al_out(out, precision))
+    return bad("masked_groupnorm: x, w and b must be aligned to 16 bytes, partials_f64 to 8, out to 16 (fp32) / 8 (16-bit)");
   return hip_ret(sa::launch_masked_groupnorm_silu(x, w, b, mask, (double*)partials_f64, out, precision == SAMAUDIO_BF16,
                                                   batch, frames, channels, halo, eps, (hipStream_t)stream),
                  "masked_groupnorm_silu");
@@ -314,7 +348,14 @@ int samaudio_op_masked_groupnorm_silu_split3(const float* x, const float* w, con
 
 int samaudio_op_layernorm_rows(const float* x, int64_t x_ld, const float* w, const float* b, float* out_f32,
                                void* out_act, int precision, int64_t rows, int dim, float eps, samaudio_stream stream) {
-  if (dim % 4 || x_ld % 4) return bad("layernorm_rows: dim % 4");
+  if (!x || !w || !b) return bad("layernorm_rows: null x / w / b");
+  if (!out_f32 && !out_act) return bad("layernorm_rows: out_f32 and out_act are both null");
+  if (rows <= 0) return bad("layernorm_rows: rows <= 0");
+  if (dim <= 0 || dim % 4) return bad("layernorm_rows: dim % 4 (and dim > 0)");
+  if (x_ld % 4) return bad("layernorm_rows: x_ld % 4");
+  if (x_ld < dim) return bad("layernorm_rows: x_ld < dim");
+  if (!al16(x) || !al16(w) || !al16(b) || !al16(out_f32) || !al_out(out_act, precision))
+    return bad("layernorm_rows: x, w, b and out_f32 must be aligned to 16 bytes, out_act to 16 (fp32) / 8 (16-bit)");
   return hip_ret(sa::launch_layernorm_rows(x, x_ld, w, b, out_f32, out_act, precision == SAMAUDIO_BF16, rows, dim, eps,
                                            (hipStream_t)stream), "layernorm_rows");
 }

@@ -331,3 +331,14 @@ def test_glue_launchers_of_the_emulation_against_float64(emu):
     assert "160 passed, 46 skipped" in out and "failed" not in out, out
     skips = [line for line in out.splitlines() if line.startswith("SKIPPED")]
     assert skips and all("not in this build of the library" in line for line in skips), out
+
+
+def test_norm_launchers_of_the_emulation_against_float64(emu):
+    """tests/test_norm_kernels_gpu.py on the emulation's own C++ versions of launch_rmsnorm_mod, launch_layernorm_rows,
+    launch_layernorm_accum, launch_groupnorm_silu and launch_masked_groupnorm_silu (and of rmsnorm_gs, headnorm_layers and qkv_prep for
+    the eps-visible cases): the engine-logic tests above stand on them, and they meet the same float64 statements, eps in reach, as the
+    HIP kernels.  Head width 64 is "not in this build of the library" there: 4 skips."""
+    out = _dryrun(["tests/test_norm_kernels_gpu.py", "-rs"], 600)
+    assert "196 passed, 4 skipped" in out and "failed" not in out, out
+    skips = [line for line in out.splitlines() if line.startswith("SKIPPED")]
+    assert skips and all("not in this build of the library" in line or "no 64-wide heads" in line for line in skips), out

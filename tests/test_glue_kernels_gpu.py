@@ -136,10 +136,10 @@ def test_add_rowvec_above_the_grid_cap(gpu, prec):
 # ---------------------------------------------------------------------------------------------------------------------
 # headnorm_layers
 # ---------------------------------------------------------------------------------------------------------------------
-def _headnorm_stmt(k, w, dtype):
+def _headnorm_stmt(k, w, dtype, eps=EPS):
     """k [rows, L, H, hd], w [L, hd]"""
     k, w = k.to(dtype), w.to(dtype)
-    return k * torch.rsqrt((k * k).mean(-1, keepdim=True) + EPS) * w[None, :, None, :]
+    return k * torch.rsqrt((k * k).mean(-1, keepdim=True) + eps) * w[None, :, None, :]
 
 
 @pytest.mark.parametrize("prec", STORAGE)

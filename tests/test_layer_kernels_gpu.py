@@ -97,9 +97,9 @@ def _ulp16(x, dtype):
     return torch.pow(2.0, e - mant)
 
 
-def _rms64(x, w):
+def _rms64(x, w, eps=EPS):
     x = x.double()
-    return x * torch.rsqrt((x * x).mean(-1, keepdim=True) + EPS) * w.double()
+    return x * torch.rsqrt((x * x).mean(-1, keepdim=True) + eps) * w.double()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -142,10 +142,10 @@ def _gs_ref(D, w, tabs, tvec, n):
     return w[n].double()[None] * (1 + scale), shift, scale
 
 
-def _norm_want(D, x, w, tabs, tvec):
+def _norm_want(D, x, w, tabs, tvec, eps=EPS):
     _, shift, scale = _gs_ref(D, w, tabs, tvec, USED)
     rep = lambda z: z.expand(B_N, -1).repeat_interleave(T_N, 0)
-    return _rms64(x, w[USED]) * (1 + rep(scale)) + rep(shift)
+    return _rms64(x, w[USED], eps) * (1 + rep(scale)) + rep(shift)
 
 
 @pytest.mark.parametrize("lib", S16)
@@ -260,12 +260,12 @@ def test_hooks_refuse_what_the_kernels_do_not_cover(gpu):
 # ---------------------------------------------------------------------------------------------------------------------
 # qkv_prep
 # ---------------------------------------------------------------------------------------------------------------------
-def _qkv_want(x, B, T, H, hd, qw, kw, cos, sin):
+def _qkv_want(x, B, T, H, hd, qw, kw, cos, sin, eps=EPS):
     """x float64 [B, T, 3 D] (head-major columns) -> Q, K [B, H, T, hd] and V^T [B, H, hd, T]"""
     D = H * hd
     heads = lambda z: z.reshape(B, T, H, hd).permute(0, 2, 1, 3)
-    q = O.apply_rope(_rms64(heads(x[..., :D]), qw), cos.double(), sin.double())
-    k = O.apply_rope(_rms64(heads(x[..., D:2 * D]), kw), cos.double(), sin.double())
+    q = O.apply_rope(_rms64(heads(x[..., :D]), qw, eps), cos.double(), sin.double())
+    k = O.apply_rope(_rms64(heads(x[..., D:2 * D]), kw, eps), cos.double(), sin.double())
     return q, k, heads(x[..., 2 * D:]).transpose(2, 3)
 
 
