@@ -929,6 +929,19 @@ int samaudio_op_anchor_gather(const float* emb, const int64_t* ids, int n_ids, c
                               int batch, int frames, int embed_dim, int vocab, samaudio_stream stream);
 /* set_floats_kernel: dst[0 .. n) (device) = host_values[0 .. n) (HOST), handed over as kernel arguments, 64 per launch */
 int samaudio_op_set_floats(float* dst, const float* host_values, int n, samaudio_stream stream);
+/* noise_rows_kernel: the seeded start state of SAMAudio.separate(seed=...) (tests/noise_ref.py is the
+ * statement, this build's own: pinned to Random123's Philox4x32-10 known answers and to the float64 statement, unpinned vs torch's
+ * randn).  out [clips * candidates, frames, channels] f32 contiguous, row b * candidates + c = candidate c of clip b.  The value at
+ * (seed, clip id, candidate, frame t, channel ch): Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (t * channels / 4 + ch / 4, candidate, id & 0xffffffff, id >> 32) yields x0..x3 for channels 4q..4q+3; (x0, x1) and (x2, x3) each
+ * give r = sqrt(-2 ln(((xa >> 8) + 1) 2^-24)), th = 2 pi (xb >> 8) 2^-24, (r cos th, r sin th), |z| <= sqrt(48 ln 2).  Nothing else
+ * enters: not frames, clips, candidates or the place in the batch.  clip_ids_host: HOST array [clips] of ids in [0, 2^63), handed to
+ * the kernel as kernel arguments, 64 clips per launch: no upload, no synchronisation.  SAMAUDIO_ERR_ARG before any launch: null out /
+ * clip_ids_host, out not aligned to 16 bytes, clips / candidates / frames < 1, channels < 4 or channels % 4 != 0,
+ * frames * channels / 4 > 2^32 (counter word 0), a negative clip id.  SAMAUDIO_ERR_STATE ("not available in this build") where the
+ * launcher is missing (the CPU emulation of the launchers). */
+int samaudio_op_noise(float* out, int clips, int candidates, int frames, int channels, uint64_t seed, const int64_t* clip_ids_host,
+                      samaudio_stream stream);
 /* ode_stage_kernel: out[i] = y0[i] + scale * sum_{j < n_src} coef[j] * k[j][i] for i < n, f32; k, coef: HOST arrays of FOUR device
  * pointers / floats, of which the kernel reads the first n_src (the rest are handed to it as they are and never used: the engine
  * leaves out the sources whose tableau coefficient is 0); out may be y0.  Refused: n_src outside [1, 4], n % 4, a pointer in use

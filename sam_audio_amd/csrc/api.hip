@@ -837,6 +837,25 @@ int samaudio_op_set_floats(float* dst, const float* host_values, int n, samaudio
   return hip_ret(sa::launch_set_floats(dst, host_values, n, (hipStream_t)stream), "set_floats");
 }
 
+int samaudio_op_noise(float* out, int clips, int candidates, int frames, int channels, uint64_t seed, const int64_t* clip_ids_host,
+                      samaudio_stream stream) {
+  if (!out || !clip_ids_host) return bad("noise: null out / clip_ids_host");
+  if (!aligned16(out)) return bad("noise: out must be aligned to 16 bytes");
+  if (clips < 1 || candidates < 1 || frames < 1) return bad("noise: clips, candidates, frames < 1");
+  if (channels < 4 || channels % 4) return bad("noise: channels % 4 != 0");
+  if ((uint64_t)frames * (uint64_t)(channels / 4) > (1ull << 32))
+    return bad("noise: frames * channels / 4 above 2^32 (the counter's first word)");
+  for (int b = 0; b < clips; ++b)
+    if (clip_ids_host[b] < 0) return bad("noise: a negative clip id");
+  if (!sa::launch_noise_rows) {
+    g_err = "noise: not available in this build of the library";
+    return SAMAUDIO_ERR_STATE;
+  }
+  static_assert(sizeof(long long) == sizeof(int64_t), "the launcher takes the ids as long long");
+  return hip_ret(sa::launch_noise_rows(out, clips, candidates, frames, channels, (unsigned long long)seed,
+                                       (const long long*)clip_ids_host, (hipStream_t)stream), "noise");
+}
+
 int samaudio_op_ode_stage(const float* y0, const float* const* k, const float* coef, int n_src, float scale, float* out, int64_t n,
                           samaudio_stream stream) {
   if (!y0 || !k || !coef || !out) return bad("ode_stage: null argument");

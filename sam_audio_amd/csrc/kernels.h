@@ -339,6 +339,21 @@ __attribute__((weak)) hipError_t launch_ode_commit(float* y, const float* ynew, 
 // answers SAMAUDIO_ERR_STATE (api.hip)
 __attribute__((weak)) hipError_t launch_window_blend(float* out, const int* next_row, int rows, int W, int O, int C2, hipStream_t st);
 
+// seeded noise of separate(seed=...) (tests/noise_ref.py is the statement): out [clips * candidates, frames,
+// channels] fp32, row b * candidates + c = stream (clip_ids[b], candidate c).  Quad q of frame t of a stream = one Philox4x32-10 call
+// with key (seed lo, seed hi) and counter (t * channels / 4 + q, c, id lo, id hi), its four words two Box-Muller pairs: a value knows
+// nothing of frames, clips, candidates or its place in the batch.  clip_ids is a HOST array: the ids travel as kernel arguments,
+// NoiseClipPack::N clips per launch (values are per element, so the partition changes no bit).  channels % 4 == 0, out 16-byte
+// aligned, frames * channels / 4 <= 2^32, ids >= 0: the caller's checks (api.hip).  weak: the CPU emulation of the launchers
+// (oracle/emu) does not define it - the hook then answers SAMAUDIO_ERR_STATE
+struct NoiseClipPack {
+  static constexpr int N = 64;
+  long long v[N];
+};
+constexpr int kNoiseGridCap = 2048;   // blocks of 256 lanes per launch; a lane walks further quads in grid strides
+__attribute__((weak)) hipError_t launch_noise_rows(float* out, int clips, int candidates, int frames, int channels,
+                                                   unsigned long long seed, const long long* clip_ids, hipStream_t st);
+
 // out[r,:] = AT(x[r,:] + vec[(r / rows_per_b) * vec_ld + :])
 hipError_t launch_add_rowvec(const float* x, const float* vec, long vec_ld, void* out, bool bf16, int rows, int D,
                              int rows_per_b, hipStream_t st);

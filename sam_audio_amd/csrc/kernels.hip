@@ -1081,6 +1081,67 @@ hipError_t launch_window_blend(float* out, const int* next_row, int rows, int W,
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// seeded noise of separate(seed=...) (tests/noise_ref.py is the statement).  One lane per quad of four
+// channels: one Philox4x32-10 call (Random123's constants; the high product as a 64-bit multiply), two Box-Muller pairs in plain fp32,
+// one float4 store - consecutive lanes write consecutive 16 bytes of a row.  The counter is (t * Q + q, candidate, clip id lo, hi), the
+// key the seed: a value depends on nothing else, so padding, batch composition, candidate count and the split into launches leave
+// every bit alone.  Both uniforms are exact in fp32: u_a = ((x >> 8) + 1) 2^-24 in (0, 1] (the logarithm's; 1 gives r = 0),
+// u_b = (x >> 8) 2^-24 in [0, 1) (the angle's).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x, p1 = (unsigned long long)0xCD9E8D57u * c.z;
+    c = make_uint4((unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c;
+}
+
+__device__ __forceinline__ float2 box_muller(unsigned xa, unsigned xb) {
+  const float ua = (float)((xa >> 8) + 1u) * 0x1p-24f, ub = (float)(xb >> 8) * 0x1p-24f;   // 24-bit integers: both exact
+  const float r = sqrtf(-2.f * logf(ua));
+  const float th = 6.28318530717958647692f * ub;
+  return make_float2(r * cosf(th), r * sinf(th));
+}
+
+// per_stream = frames * Q quads of one (clip, candidate) row, <= 2^32: the quad's index inside its row is counter word 0
+__global__ __launch_bounds__(256) void noise_rows_kernel(float4* __restrict__ out, const NoiseClipPack ids, const int candidates,
+                                                         const unsigned long long per_stream, const long total, const unsigned k0,
+                                                         const unsigned k1) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const unsigned long long row = (unsigned long long)i / per_stream;   // b * candidates + c of this launch's clips
+    const unsigned w0 = (unsigned)((unsigned long long)i - row * per_stream);
+    const unsigned b = (unsigned)(row / (unsigned)candidates), c = (unsigned)(row % (unsigned)candidates);
+    const unsigned long long id = (unsigned long long)ids.v[b];
+    const uint4 x = philox4x32_10(make_uint4(w0, c, (unsigned)id, (unsigned)(id >> 32)), k0, k1);
+    const float2 z01 = box_muller(x.x, x.y), z23 = box_muller(x.z, x.w);
+    out[i] = make_float4(z01.x, z01.y, z23.x, z23.y);
+  }
+}
+
+hipError_t launch_noise_rows(float* out, int clips, int candidates, int frames, int channels, unsigned long long seed,
+                             const long long* clip_ids, hipStream_t st) {
+  if (!out || !clip_ids || clips < 1 || candidates < 1 || frames < 1 || channels < 4 || channels % 4) return hipErrorInvalidValue;
+  const unsigned long long per_stream = (unsigned long long)frames * (unsigned)(channels / 4);
+  // counter word 0 holds the quad index of a row; 64 clips of a launch stay far inside a signed 64-bit index
+  if (per_stream > (1ull << 32) || (unsigned long long)candidates * per_stream > (1ull << 56)) return hipErrorInvalidValue;
+  for (int off = 0; off < clips; off += NoiseClipPack::N) {
+    NoiseClipPack ids;
+    const int m = clips - off < NoiseClipPack::N ? clips - off : NoiseClipPack::N;
+    for (int i = 0; i < NoiseClipPack::N; ++i) ids.v[i] = i < m ? clip_ids[off + i] : 0;
+    const long total = (long)((unsigned long long)m * candidates * per_stream);
+    long gx = (total + 255) / 256;
+    if (gx > kNoiseGridCap) gx = kNoiseGridCap;
+    hipLaunchKernelGGL(noise_rows_kernel, dim3((unsigned)gx), dim3(256), 0, st,
+                       (float4*)out + (unsigned long long)off * candidates * per_stream, ids, candidates, per_stream, total,
+                       (unsigned)seed, (unsigned)(seed >> 32));
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_time_features(const float* t, int nt, const float* freqs, int fdim, const float* inv_freq, int D,
                                 void* temb, float* tsin, bool bf16, hipStream_t st) {
   if (bf16)

@@ -66,6 +66,10 @@ def shard_batch(batch: Batch, rank: int, world: int) -> Batch:
     out.anchors = None if batch.anchors is None else [batch.anchors[i] for i in rows]
     host = getattr(batch, "sizes_host", None)
     out.sizes_host = [host[i] for i in rows] if host is not None else [int(v) for v in sizes.tolist()]
+    # the owned clips keep their ids - their rows in the whole batch where it has none - so that separate(shard, seed=s) draws
+    # exactly the rows of the unsharded call (noise.seeded_noise: a stream per (seed, clip id, candidate))
+    ids = getattr(batch, "clip_ids", None)
+    out.clip_ids = rows if ids is None else [ids[i] for i in rows]
     return out
 
 

@@ -86,6 +86,7 @@ ODE_ROW_STATUS = ("running", "finished", "step_underflow", "max_num_steps")   # 
 ODE_CTL_WORDS = 16   # 4-byte words of a row's control block (samaudio.h, the ode_* kernel hooks)
 ODE_STAGES = {ODE_RK4: 4, ODE_HEUN3: 3}   # field evaluations per step of the methods that keep stage buffers
 ODE_TIME_SLOTS = 4096                     # the engine's table of evaluation times (samaudio.h samaudio_ode_solve)
+NOISE_PACK_CLIPS, NOISE_GRID_CAP = 64, 2048   # kernels.h NoiseClipPack::N (clip ids per launch of samaudio_op_noise) and kNoiseGridCap
 OPT_TAIL_SPLIT, OPT_F32_CLASSES, OPT_QUANT_CLASSES, OPT_QUANT_FORMAT, OPT_ALT16_CLASSES, OPT_PREFETCH_ROWS, OPT_SENTINEL = 1, 2, 3, 4, 5, 6, 7
 OPT_X3_CLASSES = 9
 SENTINEL_SLOTS = 16
@@ -376,6 +377,7 @@ _PROTOS = {
     "samaudio_op_zero_halo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "samaudio_op_anchor_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "samaudio_op_set_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "samaudio_op_noise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_int64), C.c_void_p]),
     "samaudio_op_ode_stage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_float, C.c_void_p,
                                         C.c_int64, C.c_void_p]),
     "samaudio_op_ode_stage_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p,

@@ -903,7 +903,8 @@ class SAMAudio:
     def separate(self, batch: Batch, noise: Optional[torch.Tensor] = None,
                  ode_opt: Dict[str, Any] = DFLT_ODE_OPT, reranking_candidates: int = 1,
                  predict_spans: bool = False, output_sampling_rate: Optional[int] = None,
-                 window_seconds: Optional[float] = None, window_overlap_seconds: Optional[float] = None) -> SeparationResult:
+                 window_seconds: Optional[float] = None, window_overlap_seconds: Optional[float] = None,
+                 seed: Optional[int] = None) -> SeparationResult:
         """Reference model.py:247-338.  `reranking_candidates > 1` draws that many ODE solutions per clip and lets
         `visual_ranker` / `text_ranker` pick one (model.py:306-330); `predict_spans` runs `span_predictor` first
         (model.py:259-268; mind quirk Q13 below).  `output_sampling_rate`: when set and different from the codec's rate, the chosen
@@ -919,7 +920,18 @@ class SAMAudio:
         and decoded once over its whole length.  Encoder, text, visual features, span predictor and rerankers see whole clips.  All
         windows of a batch are solved together (no splitting when they do not fit in memory), on the model's own context: `streams` > 1
         is ignored for a windowed solve.  `last_latent` is the stitched latent, `last_window_latent` the window rows,
-        `last_window_plan` the longform.WindowPlan.  A clip that fits one window is one row without a successor: the plain path."""
+        `last_window_plan` the longform.WindowPlan.  A clip that fits one window is one row without a successor: the plain path.
+        `seed` (an int in [0, 2**64); not together with `noise`; this build's own definition): the start state
+        is `noise.seeded_noise(seed, ids, candidates, T, 256)` instead of a `torch.randn` draw - one counter-based stream per (seed,
+        clip id, candidate), ids = `batch.clip_ids` (SAMAudioProcessor(..., clip_ids=...); `dist.shard_batch` keeps each clip's) or
+        range(B).  What a clip starts from then depends on nothing but those three: not on the batch around it, its padded length,
+        the number of candidates, earlier draws or the rank that owns it.  The tensor comes back in `SeparationResult.noise`, and every
+        path takes it as it takes a caller's.  None (default): `torch.randn`, as the reference draws."""
+        if seed is not None:   # before anything runs
+            if noise is not None:
+                raise ValueError("seed and noise are mutually exclusive: a seed stands for the noise it generates")
+            from .noise import check_seed
+            seed = check_seed(seed)
         if is_adaptive(ode_opt):   # before anything runs: the tolerances, the options, and no windows
             ode_adaptive(ode_opt, windowed=window_seconds is not None)
         if not (self._has_dit and self._has_codec):
@@ -933,7 +945,7 @@ class SAMAudio:
             window = (longform.seconds_to_frames(window_seconds, c.sample_rate, c.hop_length),
                       longform.seconds_to_frames(window_overlap_seconds, c.sample_rate, c.hop_length))
             longform.check_window(*window, self.cfg.transformer.max_positions)
-        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans, window)
+        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans, window, seed)
         if output_sampling_rate is None or int(output_sampling_rate) == self.sample_rate:
             return res
         from . import audio
@@ -943,7 +955,7 @@ class SAMAudio:
                                     noise=res.noise)
 
     def _separate(self, batch: Batch, noise: Optional[torch.Tensor], ode_opt: Dict[str, Any], reranking_candidates: int,
-                  predict_spans: bool, window: Optional[tuple] = None) -> SeparationResult:
+                  predict_spans: bool, window: Optional[tuple] = None, seed: Optional[int] = None) -> SeparationResult:
         cand = int(reranking_candidates)
         with torch.cuda.device(self.device):
             # Nothing of torch's own arithmetic runs between the first and the last kernel of a step: the noise is drawn first
@@ -953,6 +965,10 @@ class SAMAudio:
             hop = self.cfg.audio_codec.hop_length
             B, T = batch.audios.size(0), -(-batch.audios.size(-1) // hop)
             C2 = self.cfg.transformer.out_channels
+            if seed is not None:   # one stream per (seed, clip id, candidate): noise_rows_kernel
+                from .noise import check_clip_ids, seeded_noise
+                ids = getattr(batch, "clip_ids", None)
+                noise = seeded_noise(seed, range(B) if ids is None else check_clip_ids(ids, B, distinct=True), cand, T, C2, self.device)
             if noise is None:
                 noise = torch.randn(B * cand, T, C2, device=self.device)         # model.py:274-275
             assert tuple(noise.shape) == (B * cand, T, C2), "noise must be [B*candidates, T, 256]"

@@ -129,16 +129,23 @@ def batch_audio(audios: Sequence[torch.Tensor], audio_sampling_rate: int = 48_00
     return out, sizes
 
 
+def _check_clip_ids(clip_ids: Sequence[int], n: int) -> List[int]:
+    """one id per clip, distinct, in [0, 2**63) (ValueError otherwise): the host list Batch.clip_ids holds"""
+    from .noise import check_clip_ids   # (the rule lives beside the generator; no library is loaded by the import)
+    return check_clip_ids(clip_ids, n, distinct=True)
+
+
 class Batch:
-    """Same fields as the reference Batch (processor.py:39-64) plus two optional ones,
-    ``text_features`` / ``text_mask``, for callers that bring pre-computed T5 features (the t5-base
-    tokenizer cannot be fetched offline)."""
+    """Same fields as the reference Batch (processor.py:39-64) plus optional ones: ``text_features`` / ``text_mask`` for callers
+    that bring pre-computed T5 features (the t5-base tokenizer cannot be fetched offline), and ``clip_ids``, a host list of one
+    integer id per clip for ``SAMAudio.separate(seed=...)``."""
 
     def __init__(self, audios: torch.Tensor, sizes: torch.Tensor, wav_sizes: torch.Tensor,
                  descriptions: List[str], hop_length: int, audio_sampling_rate: int,
                  anchors: Optional[List[List[Anchor]]] = None, audio_pad_mask: Optional[torch.Tensor] = None,
                  masked_video: Optional[List] = None,
-                 text_features: Optional[torch.Tensor] = None, text_mask: Optional[torch.Tensor] = None):
+                 text_features: Optional[torch.Tensor] = None, text_mask: Optional[torch.Tensor] = None,
+                 clip_ids: Optional[Sequence[int]] = None):
         assert audios.size(0) == len(descriptions), "one description per audio"
         self.audios = audios
         self.sizes = sizes
@@ -153,6 +160,9 @@ class Batch:
         # host copy of the frame counts (one read at construction, where the processor's tensors still live on the CPU): what
         # SAMAudio.separate() slices its outputs with - no device -> host read inside the timed path
         self.sizes_host: List[int] = [int(v) for v in sizes.tolist()]
+        # optional host list of one id per clip (distinct, in [0, 2**63)): what SAMAudio.separate(seed=...) names a clip's noise
+        # stream by instead of its row in the batch - dist.shard_batch hands every rank its clips' ids
+        self.clip_ids: Optional[List[int]] = None if clip_ids is None else _check_clip_ids(clip_ids, len(descriptions))
         self.process_anchors(anchors)
 
     def _frame_of(self, seconds: float) -> int:
@@ -228,6 +238,7 @@ class Batch:
                                  getattr(self, "anchor_vocab_validated", 0))
         if self.masked_video is not None:
             self.masked_video = [v.to(device) for v in self.masked_video]   # (tensors and MaskedVideo items alike)
+        self.clip_ids = getattr(self, "clip_ids", None)   # a host list: it stays where it is and travels with the batch
         return self
 
 
@@ -403,9 +414,15 @@ class SAMAudioProcessor:
                  masked_videos: Optional[Sequence[torch.Tensor]] = None,
                  text_features: Optional[torch.Tensor] = None,
                  text_mask: Optional[torch.Tensor] = None,
-                 sampling_rates: Optional[Sequence[Optional[int]]] = None) -> Batch:
-        """`sampling_rates`: one source rate per clip for tensor clips (None = the model's rate); a WAV file keeps its own."""
+                 sampling_rates: Optional[Sequence[Optional[int]]] = None,
+                 clip_ids: Optional[Sequence[int]] = None) -> Batch:
+        """`sampling_rates`: one source rate per clip for tensor clips (None = the model's rate); a WAV file keeps its own.
+        `clip_ids`: one integer id per clip, distinct and in [0, 2**63) (ValueError otherwise) - `SAMAudio.separate(seed=...)` draws
+        a clip's noise from (seed, id, candidate) instead of (seed, row in the batch, candidate), so a clip keeps its noise whatever
+        batch it is in."""
         assert len(descriptions) == len(audios)
+        if clip_ids is not None:   # before any audio work
+            clip_ids = _check_clip_ids(clip_ids, len(descriptions))
         assert anchors is None or len(descriptions) == len(anchors)
         assert masked_videos is None or len(descriptions) == len(masked_videos)
         if self.audio_transform == "hip":
@@ -418,7 +435,7 @@ class SAMAudioProcessor:
         return Batch(audios=wavs, sizes=sizes, wav_sizes=wav_sizes, descriptions=list(descriptions),
                      hop_length=self.audio_hop_length, audio_sampling_rate=self.audio_sampling_rate,
                      anchors=anchors, audio_pad_mask=pad_mask, masked_video=video,
-                     text_features=text_features, text_mask=text_mask)
+                     text_features=text_features, text_mask=text_mask, clip_ids=clip_ids)
 
 
 class JudgeBatch(dict):
