@@ -21,7 +21,6 @@ import torch  # noqa: E402
 
 import tests.conftest  # noqa: E402,F401  (binds sam_audio_amd.hip to oracle/_simt/libsamaudio_simt.so of `root`)
 from sam_audio_amd import hip  # noqa: E402
-from sam_audio_amd.judge import _register  # noqa: E402
 from sam_audio_amd.mbert_encoder import MBertDims, ModernBertHIP  # noqa: E402
 from sam_audio_amd.t5_encoder import T5Dims, T5EncoderHIP  # noqa: E402
 from sam_audio_amd.vision_tower import PEVisionTower, convert_vision  # noqa: E402
@@ -77,7 +76,7 @@ rc("null handle: set_option", lib.samaudio_vit_set_option(None, hip.OPT_X3_CLASS
 rc("null handle: finalize", lib.samaudio_vit_finalize(None))
 rc("null handle: set_workspace", lib.samaudio_vit_set_workspace(None, None, 0))
 rc("w2 on", lib.samaudio_vit_set_option(t32._h, hip.OPT_X3_CLASSES, hip.CLS["w2"]))
-_register(lib.samaudio_vit_set_tensor, t32._h, t32._tensors, convert_vision(sd, cfg, torch.float32, dev))
+t32.register(convert_vision(sd, cfg, torch.float32, dev))
 rc("finalize without L0.w2.x3", lib.samaudio_vit_finalize(t32._h))
 rc("qkv on", lib.samaudio_vit_set_option(t32._h, hip.OPT_X3_CLASSES, hip.CLS["qkv"]))
 rc("finalize without L0.wqkv.x3", lib.samaudio_vit_finalize(t32._h))

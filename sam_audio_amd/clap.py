@@ -21,6 +21,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import hip
+from .context import Context
 
 SAMPLE_RATE = 48_000
 MAX_LENGTH = 480_000       # 10 s
@@ -307,7 +308,7 @@ def load_checkpoint(path: str):
     return config, frontend, sd
 
 
-class ClapTower:
+class ClapTower(Context):
     """The two CLAP towers on the HIP library: `audio_embed(wavs, sample_rate) -> [rows, projection_dim]`,
     `text_embed(input_ids, attention_mask) -> [rows, projection_dim]` (both unit norm, fp32, on the device), `logmel(wavs)` - the
     front end alone with this checkpoint's BatchNorm folded in - and `score(audio, text, candidates)`.  Owns its workspace."""
@@ -316,17 +317,7 @@ class ClapTower:
         self.frontend = dict(frontend or {})
         self.cfg = tower_config(config, self.frontend)
         self.device = torch.device(device) if device is not None else None
-        self._lib = hip.clap_lib()
-        self._h = C.c_void_p()
-        self._tensors: Dict[str, torch.Tensor] = {}
-        self._workspace: Optional[torch.Tensor] = None
-        self._loaded = False
-        hip.check(self._lib.samaudio_clap_create(C.byref(self.cfg), C.byref(self._h)))
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.samaudio_clap_destroy(self._h)
-            self._h = None
+        super().__init__(hip.clap_lib(), "samaudio_clap", self.cfg, device=self.device)
 
     @property
     def sample_rate(self) -> int:
@@ -354,21 +345,15 @@ class ClapTower:
         if self.device is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         hip.require_gpu(self.device, "ClapTower")
-        from .judge_util import register
         with torch.cuda.device(self.device):
-            register(self._lib.samaudio_clap_set_tensor, self._h, self._tensors,
-                     convert_clap(state_dict, self.cfg, self.frontend, self.device))
-            hip.check(self._lib.samaudio_clap_finalize(self._h))
-        self._loaded = True
+            self.register(convert_clap(state_dict, self.cfg, self.frontend, self.device))
+            self.finalize()
+
+    _ensure = Context.ensure_workspace   # (audio rows, text rows, tokens)
 
     def _ready(self) -> None:
         if not self._loaded:
             raise hip.SamAudioHipError("ClapTower: no weights loaded")
-
-    def _ensure(self, audio_rows: int, text_rows: int, tokens: int) -> None:
-        from .judge_util import ensure_ws
-        need = self._lib.samaudio_clap_workspace_bytes(self._h, audio_rows, text_rows, tokens)
-        ensure_ws(self, need, lambda p, b: self._lib.samaudio_clap_set_workspace(self._h, p, b))
 
     def _at_rate(self, wavs: torch.Tensor, sample_rate: int) -> torch.Tensor:
         if int(sample_rate) == self.sample_rate:

@@ -298,16 +298,32 @@ class _Handle:
         return call
 
 
+def _lifecycle(abi: str, config, workspace_args, has_option: bool) -> dict:
+    """The prototypes every kind of context shares (context.Context calls them by `abi`): create / destroy / set_tensor / finalize /
+    workspace_bytes(handle, *workspace_args) / set_workspace and, where the kind takes options, set_option."""
+    protos = {
+        f"{abi}_create": (C.c_int, [C.POINTER(config), C.POINTER(C.c_void_p)]),
+        f"{abi}_destroy": (None, [C.c_void_p]),
+        f"{abi}_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+        f"{abi}_finalize": (C.c_int, [C.c_void_p]),
+        f"{abi}_workspace_bytes": (C.c_size_t, [C.c_void_p] + workspace_args),
+        f"{abi}_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    }
+    if has_option:
+        protos[f"{abi}_set_option"] = (C.c_int, [C.c_void_p, C.c_int, C.c_int])
+    return protos
+
+
 _PROTOS = {
     "samaudio_last_error": (C.c_char_p, []),
     "samaudio_version": (C.c_char_p, []),
-    "samaudio_create": (C.c_int, [C.POINTER(Config), C.POINTER(C.c_void_p)]),
-    "samaudio_destroy": (None, [C.c_void_p]),
-    "samaudio_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    "samaudio_finalize": (C.c_int, [C.c_void_p, C.c_int]),
-    "samaudio_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
-    "samaudio_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
-    "samaudio_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    **_lifecycle("samaudio", Config, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64], True),   # (rows, frames, text_len, codec items, samples)
+    "samaudio_finalize": (C.c_int, [C.c_void_p, C.c_int]),   # the engine alone finalizes by weight set
+    **_lifecycle("samaudio_judge", JudgeConfig, [C.c_int] * 3, True),
+    **_lifecycle("samaudio_frame", FrameConfig, [C.c_int] * 2, True),
+    **_lifecycle("samaudio_mbert", MBertConfig, [C.c_int] * 2, False),
+    **_lifecycle("samaudio_t5", T5Config, [C.c_int] * 2, False),
+    **_lifecycle("samaudio_vit", VitConfig, [C.c_int], True),
     "samaudio_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "samaudio_prepare_latent": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -394,47 +410,14 @@ _PROTOS = {
     "samaudio_op_clap_text_embed": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
     "samaudio_op_sentinel": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "samaudio_op_hash_items": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
-    "samaudio_judge_create": (C.c_int, [C.POINTER(JudgeConfig), C.POINTER(C.c_void_p)]),
-    "samaudio_judge_destroy": (None, [C.c_void_p]),
-    "samaudio_judge_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    "samaudio_judge_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
-    "samaudio_judge_finalize": (C.c_int, [C.c_void_p]),
-    "samaudio_judge_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "samaudio_judge_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_judge_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "samaudio_judge_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p]),
-    "samaudio_frame_create": (C.c_int, [C.POINTER(FrameConfig), C.POINTER(C.c_void_p)]),
-    "samaudio_frame_destroy": (None, [C.c_void_p]),
-    "samaudio_frame_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    "samaudio_frame_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
-    "samaudio_frame_finalize": (C.c_int, [C.c_void_p]),
-    "samaudio_frame_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "samaudio_frame_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_frame_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p]),
-    "samaudio_mbert_create": (C.c_int, [C.POINTER(MBertConfig), C.POINTER(C.c_void_p)]),
-    "samaudio_mbert_destroy": (None, [C.c_void_p]),
-    "samaudio_mbert_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    "samaudio_mbert_finalize": (C.c_int, [C.c_void_p]),
-    "samaudio_mbert_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "samaudio_mbert_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_mbert_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "samaudio_t5_create": (C.c_int, [C.POINTER(T5Config), C.POINTER(C.c_void_p)]),
-    "samaudio_t5_destroy": (None, [C.c_void_p]),
-    "samaudio_t5_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    "samaudio_t5_finalize": (C.c_int, [C.c_void_p]),
-    "samaudio_t5_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
-    "samaudio_t5_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_t5_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "samaudio_vit_create": (C.c_int, [C.POINTER(VitConfig), C.POINTER(C.c_void_p)]),
-    "samaudio_vit_destroy": (None, [C.c_void_p]),
-    "samaudio_vit_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    "samaudio_vit_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
-    "samaudio_vit_finalize": (C.c_int, [C.c_void_p]),
-    "samaudio_vit_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
-    "samaudio_vit_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_vit_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "samaudio_vit_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
     "samaudio_op_resize_frames": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
@@ -459,12 +442,7 @@ _PROTOS = {
 # bind by _PROTOS (oracle/) are built from a fixed list of sources without them - so they are a table of their own, bound by lib() on
 # the product libraries and by clap_lib() on whatever library is in use.
 _CLAP_PROTOS = {
-    "samaudio_clap_create": (C.c_int, [C.POINTER(ClapConfig), C.POINTER(C.c_void_p)]),
-    "samaudio_clap_destroy": (None, [C.c_void_p]),
-    "samaudio_clap_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
-    "samaudio_clap_finalize": (C.c_int, [C.c_void_p]),
-    "samaudio_clap_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "samaudio_clap_set_workspace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    **_lifecycle("samaudio_clap", ClapConfig, [C.c_int] * 3, False),
     "samaudio_clap_audio_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                             C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_clap_text_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

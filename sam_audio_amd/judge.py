@@ -28,7 +28,7 @@ import torch
 
 from . import hip
 from .config import PEAudioFrameConfig, PEAVTransformerConfig, SAMAudioJudgeConfig
-from .judge_util import ensure_ws as _ensure_ws, register as _register
+from .context import Context, check_keys
 from .weights import _interleave16, convert_codec, convert_codec_fly16, convert_codec_x3, convert_peav_x3, x3_tower_weight
 
 
@@ -144,29 +144,21 @@ def convert_judge_x3(tensors: Dict[str, torch.Tensor], cfg: SAMAudioJudgeConfig,
     return out
 
 
-class _CodecEncoder:
+class _CodecEncoder(Context):
     """Codec-only engine context: the DACVAEEncoder of reference codec.py:42-78 on the separate() path's kernels."""
+    _ctx = property(lambda self: self._h)
 
     def __init__(self, codec_cfg, precision: str, device: torch.device):
-        self.cfg, self.device = codec_cfg, device
-        self._lib = hip.lib(hip.operands_for(precision))
-        self._ctx = C.c_void_p()
+        self.cfg = codec_cfg
         hc = hip.Config(
             precision=hip.precision_code(precision), dim=256, n_heads=2, n_layers=0, ffn_hidden=64,
             latent_channels=2 * codec_cfg.codebook_dim, text_dim=64, video_dim=64, freq_dim=64, anchor_dim=64,
             anchor_vocab=4, max_positions=64, norm_eps=1e-5, codec_dim=codec_cfg.codebook_dim,
             codec_latent=codec_cfg.latent_dim, enc_dim=codec_cfg.encoder_dim, dec_dim=codec_cfg.decoder_dim,
             enc_rates=(C.c_int32 * 4)(*codec_cfg.encoder_rates), dec_rates=(C.c_int32 * 4)(*codec_cfg.decoder_rates))
-        hip.check(self._lib.samaudio_create(C.byref(hc), C.byref(self._ctx)))
-        self._tensors: Dict[str, torch.Tensor] = {}
-        self._workspace: Optional[torch.Tensor] = None
+        super().__init__(hip.lib(hip.operands_for(precision)), "samaudio", hc, device=device)
         self._x3 = hip.is_x3(precision)
         self._half = hip.half_dtype(precision)
-
-    def __del__(self):
-        if getattr(self, "_ctx", None):
-            self._lib.samaudio_destroy(self._ctx)
-            self._ctx = None
 
     def load(self, tensors: Dict[str, torch.Tensor]) -> None:
         if self._x3:   # the codec's x3 class with its twins, exactly as SAMAudio sets them up for an x3 precision
@@ -174,15 +166,9 @@ class _CodecEncoder:
             codec = {k: v for k, v in tensors.items() if k.startswith(("enc.", "dec."))}
             tensors.update(convert_codec_x3(codec, self._half))
             tensors.update(convert_codec_fly16(codec, self._half))
-            hip.check(self._lib.samaudio_set_option(self._ctx, hip.OPT_X3_CLASSES, hip.CLS["codec"]))
-        for name, t in tensors.items():
-            dt = hip.dtype_code(t.dtype)
-            if t.data_ptr() % 16:
-                t = t.clone()
-            self._tensors[name] = t
-            hip.check(self._lib.samaudio_set_tensor(self._ctx, name.encode(), hip.ptr(t), dt, t.dim(),
-                                                    hip.shape_array(t.shape)))
-        hip.check(self._lib.samaudio_finalize(self._ctx, 2))
+            self.set_option(hip.OPT_X3_CLASSES, hip.CLS["codec"])
+        self.register(tensors)
+        self.finalize(2)
 
     def encode(self, audios: torch.Tensor) -> torch.Tensor:
         """[N, 1, Tw] -> mean latents, channels-last [N, T, codebook_dim] (right reflect-pad to the hop, codec.py:72-78)."""
@@ -195,8 +181,7 @@ class _CodecEncoder:
         items, samples = wav.shape
         z = torch.empty(items, samples // hop, self.cfg.codebook_dim, device=self.device)
         chunk = min(items, int(os.environ.get("SAMAUDIO_CODEC_CHUNK", "16")))
-        need = self._lib.samaudio_workspace_bytes(self._ctx, 0, 0, 1, chunk, samples)
-        _ensure_ws(self, need, lambda p, n: self._lib.samaudio_set_workspace(self._ctx, p, n))
+        self.ensure_workspace(0, 0, 1, chunk, samples)
         hip.check(self._lib.samaudio_codec_encode(self._ctx, hip.ptr(wav), items, samples, hip.ptr(z),
                                                   hip.current_stream_ptr()))
         return z
@@ -238,7 +223,7 @@ def _text_tower(text_cfg: Dict[str, Any]):
 # --------------------------------------------------------------------------------------------------------------
 # Judge
 # --------------------------------------------------------------------------------------------------------------
-class SAMAudioJudgeModel:
+class SAMAudioJudgeModel(Context):
     config_cls = SAMAudioJudgeConfig
 
     def __init__(self, config: SAMAudioJudgeConfig, precision: str = "bf16", device: Optional[str] = None,
@@ -250,26 +235,16 @@ class SAMAudioJudgeModel:
         self.device = torch.device(device) if device is not None else None
         self.text_model = text_model if text_model is not None else _text_tower(config.text_model)  # judge.py:48
         self._text = _TextTower(self.text_model)
-        self._lib = hip.lib(hip.operands_for(precision))
-        self._h = C.c_void_p()
-        self._tensors: Dict[str, torch.Tensor] = {}
-        self._workspace: Optional[torch.Tensor] = None
         self._codec: Optional[_CodecEncoder] = None
-        self._loaded = False
         jc = hip.JudgeConfig(
             precision=hip.precision_code(precision),
             transformer=peav_dims(config.transformer, config.audio_codec.codebook_dim),
             finetune_transformer=peav_dims(config.finetune_transformer, config.bottleneck_dim),
             codec_dim=config.audio_codec.codebook_dim, text_hidden=config.text_hidden,
             bottleneck_dim=config.bottleneck_dim)
-        hip.check(self._lib.samaudio_judge_create(C.byref(jc), C.byref(self._h)))
+        super().__init__(hip.lib(hip.operands_for(precision)), "samaudio_judge", jc, device=self.device)
         if hip.is_x3(precision):   # fp32 storage, the towers' big contractions on compensated 16-bit operands
-            hip.check(self._lib.samaudio_judge_set_option(self._h, hip.OPT_X3_CLASSES, hip.CLS_X3_TOWER))
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.samaudio_judge_destroy(self._h)
-            self._h = None
+            self.set_option(hip.OPT_X3_CLASSES, hip.CLS_X3_TOWER)
 
     @property
     def act_dtype(self) -> torch.dtype:
@@ -322,15 +297,13 @@ class SAMAudioJudgeModel:
         hip.require_gpu(self.device, "SAMAudioJudgeModel")
         import re
         canon = lambda k: re.sub(r"\.(weight_g|weight_v|parametrizations\.weight\.original[01])$", ".weight", k)  # noqa: E731
-        have = {canon(k) for k in state_dict}
         want = set(self.expected_keys())
         # the reference DACVAEEncoder keeps the WHOLE quantizer of the dacvae model (codec.py:62-63: in_proj, out_proj, ...),
         # and a checkpoint saved from a full DACVAE also carries the decoder: present in a genuine checkpoint, unused here
         unused = re.compile(r"^audio_codec\.(quantizer\.(?!in_proj\.)|decoder\.)")
-        missing = sorted(want - have)
-        unexpected = sorted(k for k in state_dict if canon(k) not in want and not unused.search(k))
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Missing keys: {missing}, unexpected_keys: {unexpected}")
+        # a wanted key counts under its canonical name, any other under its own (that is how it is reported) unless it is unused
+        have = {canon(k) if canon(k) in want else k for k in state_dict if canon(k) in want or not unused.search(k)}
+        missing, unexpected = check_keys(want, have, strict)
         text_sd = {k[len("text_model."):]: v for k, v in state_dict.items() if k.startswith("text_model.")}
         if text_sd:
             self.text_model.load_state_dict(text_sd, strict=False)
@@ -341,9 +314,8 @@ class SAMAudioJudgeModel:
                 tensors = convert_judge(state_dict, self.config, self.act_dtype, self.device)
                 if hip.is_x3(self.precision):
                     tensors.update(convert_judge_x3(tensors, self.config, hip.half_dtype(self.precision)))
-                _register(self._lib.samaudio_judge_set_tensor, self._h, self._tensors, tensors)
-                hip.check(self._lib.samaudio_judge_finalize(self._h))
-                self._loaded = True
+                self.register(tensors)
+                self.finalize()
             if not any(k for k in missing if k.startswith("audio_codec.")):
                 self._codec = _CodecEncoder(self.config.audio_codec, self.precision, self.device)
                 self._codec.load(convert_codec(state_dict, self.config, self.act_dtype, self.device, with_decoder=False))
@@ -364,8 +336,7 @@ class SAMAudioJudgeModel:
         pooled = pooled.to(self.device, torch.float32).contiguous()
         mask = None if frame_mask is None else frame_mask.to(self.device).to(torch.uint8).contiguous()
         scores = torch.empty(inputs * cand, 4, device=self.device)
-        need = self._lib.samaudio_judge_workspace_bytes(self._h, inputs, cand, frames)
-        _ensure_ws(self, need, lambda p, n: self._lib.samaudio_judge_set_workspace(self._h, p, n))
+        self.ensure_workspace(inputs, cand, frames)
         hip.check(self._lib.samaudio_judge_score(self._h, hip.ptr(in_lat), hip.ptr(sep_lat), inputs, cand, frames,
                                                  hip.ptr(pooled), hip.ptr(mask), hip.ptr(scores),
                                                  hip.current_stream_ptr()))
@@ -470,7 +441,7 @@ class PEAudioFrameOutput:
     spans: Optional[List[List[List[float]]]]  # per row: [[start_s, end_s], ...]
 
 
-class PEAudioFrame:
+class PEAudioFrame(Context):
     """Span predictor with the call shape of reference model.py:234-243:
     `predictor(input_features=[B, T, 128], padding_mask=[B, T], return_spans=True, input_ids=..., attention_mask=...)`."""
 
@@ -483,22 +454,12 @@ class PEAudioFrame:
         self.hop_length, self.sample_rate = hop_length, sample_rate
         self.text_model = text_model if text_model is not None else _text_tower(config.text_model)
         self._text = _TextTower(self.text_model)
-        self._lib = hip.lib(hip.operands_for(precision))
-        self._h = C.c_void_p()
-        self._tensors: Dict[str, torch.Tensor] = {}
-        self._workspace: Optional[torch.Tensor] = None
-        self._loaded = False
         fc = hip.FrameConfig(precision=hip.precision_code(precision),
                              audio=peav_dims(config.audio, config.codebook_dim), codec_dim=config.codebook_dim,
                              embed_dim=config.text_hidden)
-        hip.check(self._lib.samaudio_frame_create(C.byref(fc), C.byref(self._h)))
+        super().__init__(hip.lib(hip.operands_for(precision)), "samaudio_frame", fc, device=self.device)
         if hip.is_x3(precision):
-            hip.check(self._lib.samaudio_frame_set_option(self._h, hip.OPT_X3_CLASSES, hip.CLS_X3_TOWER))
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.samaudio_frame_destroy(self._h)
-            self._h = None
+            self.set_option(hip.OPT_X3_CLASSES, hip.CLS_X3_TOWER)
 
     @property
     def act_dtype(self) -> torch.dtype:
@@ -518,9 +479,8 @@ class PEAudioFrame:
             if hip.is_x3(self.precision):
                 tensors.update(convert_peav_x3(tensors, "a.", self.config.audio.num_hidden_layers,
                                                hip.half_dtype(self.precision), hip.CLS_X3_TOWER))
-            _register(self._lib.samaudio_frame_set_tensor, self._h, self._tensors, tensors)
-            hip.check(self._lib.samaudio_frame_finalize(self._h))
-        self._loaded = True
+            self.register(tensors)
+            self.finalize()
 
     @torch.inference_mode()
     def frame_logits(self, input_features: torch.Tensor, text_pooled: torch.Tensor,
@@ -535,8 +495,7 @@ class PEAudioFrame:
         mask = None if padding_mask is None else padding_mask.to(self.device).to(torch.uint8).contiguous()
         logits = torch.empty(rows, frames, device=self.device)
         with torch.cuda.device(self.device):
-            need = self._lib.samaudio_frame_workspace_bytes(self._h, rows, frames)
-            _ensure_ws(self, need, lambda p, n: self._lib.samaudio_frame_set_workspace(self._h, p, n))
+            self.ensure_workspace(rows, frames)
             hip.check(self._lib.samaudio_frame_logits(self._h, hip.ptr(feats), hip.ptr(pooled), hip.ptr(mask), rows,
                                                       frames, hip.ptr(logits), hip.current_stream_ptr()))
         return logits

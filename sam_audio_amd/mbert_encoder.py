@@ -20,14 +20,13 @@ ModernBertModel key                               engine tensor
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
 
 import torch
 
 from . import hip
-from .judge_util import ensure_ws, register
+from .context import Context, check_keys
 
 
 @dataclass
@@ -117,7 +116,7 @@ def convert_mbert(sd: Dict[str, torch.Tensor], dims: MBertDims, act_dtype: torch
     return out
 
 
-class ModernBertHIP:
+class ModernBertHIP(Context):
     """`tower(input_ids [B, Lt], attention_mask [B, Lt] | None, nth=None) -> [B, Lt, hidden] float32`:
     nth None = last_hidden_state, otherwise transformers' `hidden_states[nth]`."""
 
@@ -126,21 +125,11 @@ class ModernBertHIP:
         dims.check_supported()
         self.dims, self.precision = dims, precision
         self.device = torch.device(device) if device is not None else None
-        self._lib = hip.lib(hip.operands_for(precision))
-        self._h = C.c_void_p()
-        self._tensors: Dict[str, torch.Tensor] = {}
-        self._workspace: Optional[torch.Tensor] = None
-        self._loaded = False
         mc = hip.MBertConfig(precision=hip.precision_code(precision), vocab=dims.vocab_size, hidden=dims.hidden_size,
                              heads=dims.num_attention_heads, intermediate=dims.intermediate_size,
                              layers=dims.num_hidden_layers, global_every=dims.global_attn_every_n_layers,
                              window=dims.local_attention // 2, max_len=dims.max_len, ln_eps=dims.norm_eps)
-        hip.check(self._lib.samaudio_mbert_create(C.byref(mc), C.byref(self._h)))
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.samaudio_mbert_destroy(self._h)
-            self._h = None
+        super().__init__(hip.lib(hip.operands_for(precision)), "samaudio_mbert", mc, device=self.device)
 
     @classmethod
     def from_module(cls, module, device, precision: str = "fp32") -> "ModernBertHIP":
@@ -154,16 +143,11 @@ class ModernBertHIP:
             self.device = torch.device("cuda", torch.cuda.current_device())
         hip.require_gpu(self.device, "ModernBertHIP")
         sd = {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in state_dict.items()}
-        want = set(expected_keys(self.dims))
-        missing, unexpected = sorted(want - set(sd)), sorted(set(sd) - want)
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Missing keys: {missing}, unexpected_keys: {unexpected}")
+        missing, unexpected = check_keys(expected_keys(self.dims), sd, strict)
         if not missing:
             with torch.cuda.device(self.device):
-                register(self._lib.samaudio_mbert_set_tensor, self._h, self._tensors,
-                         convert_mbert(sd, self.dims, hip.act_dtype(self.precision), self.device))
-                hip.check(self._lib.samaudio_mbert_finalize(self._h))
-            self._loaded = True
+                self.register(convert_mbert(sd, self.dims, hip.act_dtype(self.precision), self.device))
+                self.finalize()
         return missing, unexpected
 
     @torch.inference_mode()
@@ -190,8 +174,7 @@ class ModernBertHIP:
             out = torch.empty(rows, tokens, self.dims.hidden_size, device=self.device, dtype=torch.float32)
             if rows == 0 or tokens == 0:
                 return out
-            need = self._lib.samaudio_mbert_workspace_bytes(self._h, rows, tokens)
-            ensure_ws(self, need, lambda p, b: self._lib.samaudio_mbert_set_workspace(self._h, p, b))
+            self.ensure_workspace(rows, tokens)
             hip.check(self._lib.samaudio_mbert_encode(self._h, hip.ptr(ids), hip.ptr(mask), rows, tokens,
                                                       -1 if nth is None or (nth == self.dims.num_hidden_layers and not last_prenorm)
                                                       else int(nth), hip.ptr(out), hip.current_stream_ptr()))

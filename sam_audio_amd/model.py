@@ -8,6 +8,7 @@ hand-written HIP kernels behind the C ABI of include/samaudio.h.  No eager/CPU f
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import json
 import math
 import os
@@ -19,6 +20,7 @@ import torch
 
 from . import hip
 from .config import SAMAudioConfig
+from .context import Context, scratch
 from .processor import Batch
 from .weights import (F32_SOURCE_KEYS, convert_codec, convert_codec_fly16, convert_codec_x3, convert_dit, convert_dit_f32, convert_dit_x3,
                       split_missing_unexpected)
@@ -148,59 +150,51 @@ def _constructed_grid(constructor: Callable, y0: Optional[torch.Tensor], t0: flo
     return g32.tolist()
 
 
-class _Codec16:
+def _alt16_weight(alt16_classes: int, name: str) -> bool:
+    """engine tensor `name` is the weight of a class that reads alt-format (bfloat16) operands in a model with these alt16 classes"""
+    leaf = name.rsplit(".", 1)[-1]
+    return name.startswith("L") and leaf in hip.ALT16_WEIGHTS and bool(alt16_classes & hip.CLS[hip.ALT16_WEIGHTS[leaf]])
+
+
+class _Codec16(Context):
     """A codec-only engine context on plain 16-bit operands beside an fp32-storage model (precision "fp16x3", `codec_decode="16"`):
     SAMAudio.decode_audio runs on it.  It borrows the model's 16-bit copies of the codec weights and whatever workspace its owner
     (the model or a stream lane) holds at the time of the call."""
 
+    _ctx = property(lambda self: self._h)
+
     def __init__(self, model: "SAMAudio"):
-        self.lib = model._lib
-        self._ctx = C.c_void_p()
         hc = hip.Config.from_buffer_copy(model._hc)
         hc.precision = hip.BF16   # "the library's 16-bit operand format"
-        hip.check(self.lib.samaudio_create(C.byref(hc), C.byref(self._ctx)))
-        for name, t in model._codec16_tensors.items():
-            dt = hip.dtype_code(t.dtype, hip.operands_for(model.precision))
-            hip.check(self.lib.samaudio_set_tensor(self._ctx, name.encode(), hip.ptr(t), dt, t.dim(), hip.shape_array(t.shape)))
-        hip.check(self.lib.samaudio_finalize(self._ctx, 1))
-
-    def __del__(self):
-        if getattr(self, "_ctx", None):
-            self.lib.samaudio_destroy(self._ctx)
-            self._ctx = None
+        super().__init__(model._lib, "samaudio", hc, device=model.device, operands=hip.operands_for(model.precision))
+        self.register(model._codec16_tensors, borrowed=True)
+        self.finalize(1)
 
 
-class _Lane:
+class _Lane(Context):
     """An extra engine context bound to its own HIP stream.  It borrows the model's weight tensors (no copy) and
     owns only a workspace; `SAMAudio(streams=S)` solves S contiguous row groups of a batch concurrently so that one
     group's GEMM tails / epilogues / launch gaps are filled by the other group's workgroups."""
 
+    _ctx = property(lambda self: self._h)
+
     def __init__(self, model: "SAMAudio"):
-        self.lib = model._lib
-        self._ctx = C.c_void_p()
-        hip.check(self.lib.samaudio_create(C.byref(model._hc), C.byref(self._ctx)))
-        for name, t in model._tensors.items():
-            dt = hip.dtype_code(t.dtype, hip.operands_for(model.precision), alt_ok=model._alt16_weight(name))
-            hip.check(self.lib.samaudio_set_tensor(self._ctx, name.encode(), hip.ptr(t), dt, t.dim(),
-                                                   hip.shape_array(t.shape)))
-        hip.check(self.lib.samaudio_finalize(self._ctx, 0))
+        super().__init__(model._lib, "samaudio", model._hc, device=model.device, operands=model._operands, alt16=model._alt16)
+        self.register(model._tensors, borrowed=True)
+        self.finalize(0)
         model._set_precision_options(self._ctx)
         if model._has_codec:   # the lane also decodes its own row group (SAMAudio._solve_concurrent)
-            hip.check(self.lib.samaudio_finalize(self._ctx, 1))
-        self._workspace: Optional[torch.Tensor] = None
+            self.finalize(1)
         self._stages: Optional[torch.Tensor] = None   # rk4 / heun3 stage buffers of this context (SAMAudio._ensure_stages)
         self._live = None
         self._codec16: Optional[_Codec16] = None
         self.stream = torch.cuda.Stream(device=model.device)
 
-    def __del__(self):
-        if getattr(self, "_ctx", None):
-            self.lib.samaudio_destroy(self._ctx)
-            self._ctx = None
 
-
-class SAMAudio:
+class SAMAudio(Context):
     config_cls = SAMAudioConfig
+    _ctx = property(lambda self: self._h)
+    _register = Context.register   # (the name tests register extra tensors by)
 
     def __init__(self, cfg: SAMAudioConfig, precision: str = "fp16x3", device: Optional[str] = None,
                  text_encoder: Optional[Callable] = None, streams: int = 1, f32_classes="auto",
@@ -284,10 +278,6 @@ class SAMAudio:
         self.span_predictor_transform = None
         self.vision_encoder = None            # callable: list of [T,3,H,W] videos -> [B, T, vision_encoder.dim]
         self.fix_span_order = False           # quirk Q13, see separate()
-        self._lib = hip.lib(hip.operands_for(self.precision))   # raises if the HIP library is not built
-        self._ctx = C.c_void_p()
-        self._tensors: Dict[str, torch.Tensor] = {}
-        self._workspace: Optional[torch.Tensor] = None
         self._stages: Optional[torch.Tensor] = None
         self._has_dit = self._has_codec = False
         if int(streams) not in (1, 2) and not os.environ.get("SAMAUDIO_ALLOW_STREAMS"):
@@ -314,14 +304,10 @@ class SAMAudio:
             dec_dim=c.decoder_dim, enc_rates=(C.c_int32 * 4)(*c.encoder_rates),
             dec_rates=(C.c_int32 * 4)(*c.decoder_rates))
         self._hc = hc
-        hip.check(self._lib.samaudio_create(C.byref(hc), C.byref(self._ctx)))
+        operands = hip.operands_for(self.precision)
+        super().__init__(hip.lib(operands), "samaudio", hc, device=self.device, operands=operands,   # (raises if the HIP library is not built)
+                         alt16=functools.partial(_alt16_weight, self.alt16_classes))
         self._set_precision_options(self._ctx)
-
-    def __del__(self):
-        ctx = getattr(self, "_ctx", None)
-        if ctx:
-            self._lib.samaudio_destroy(ctx)
-            self._ctx = None
 
     # ------------------------------------------------------------------ nn.Module-ish surface
     @property
@@ -417,9 +403,9 @@ class SAMAudio:
                 alt = [leaf for leaf, c in hip.ALT16_WEIGHTS.items() if self.alt16_classes & hip.CLS[c]]
                 dit = convert_dit(state_dict, self.cfg, self.act_dtype, self.device, alt16_leaves=alt,
                                   f32_classes=self.f32_classes, ktm=self.weight_layout == "ktm")
-                self._register(dit)
+                self.register(dit)
                 if self.x3_classes:
-                    self._register(convert_dit_x3(dit, self.cfg.transformer.n_layers, hip.half_dtype(self.precision),
+                    self.register(convert_dit_x3(dit, self.cfg.transformer.n_layers, hip.half_dtype(self.precision),
                                                   self.x3_classes, ktm=self.x3_weight_layout == "ktm"))
                 # fp32 operand copies exist for the classes that run in fp32 now; set_f32_classes adds a class's later
                 # from these references to the checkpoint entries (no copy is made here)
@@ -428,11 +414,11 @@ class SAMAudio:
                 self._has_dit = True
             if not codec_missing:
                 codec = convert_codec(state_dict, self.cfg, self.act_dtype, self.device)
-                self._register(codec)
+                self.register(codec)
                 if self.x3_classes & hip.CLS["codec"]:   # the wide convolutions' split twins (8-phase 16-bit launches over K' = 3K)
-                    self._register(convert_codec_x3(codec, hip.half_dtype(self.precision)))
+                    self.register(convert_codec_x3(codec, hip.half_dtype(self.precision)))
                     # ... and the narrow ones' weights split once, for the fp32 kernel that splits its activations on the fly
-                    self._register(convert_codec_fly16(codec, hip.half_dtype(self.precision)))
+                    self.register(convert_codec_fly16(codec, hip.half_dtype(self.precision)))
                 self._has_codec = True
                 if self.codec_decode == "16":
                     self._codec16_tensors = convert_codec(state_dict, self.cfg, hip.half_dtype(self.precision), self.device)
@@ -440,9 +426,9 @@ class SAMAudio:
                     for lane in self._lanes:
                         lane._codec16 = None
             if self._has_dit and not (dit_missing and codec_missing):
-                hip.check(self._lib.samaudio_finalize(self._ctx, 0))
+                self.finalize(0)
             if self._has_codec and not (dit_missing and codec_missing):
-                hip.check(self._lib.samaudio_finalize(self._ctx, 1))
+                self.finalize(1)
         return missing, unexpected
 
     def _covers_vision_tower(self, vis: Dict[str, torch.Tensor]) -> bool:
@@ -468,15 +454,15 @@ class SAMAudio:
         need = self.f32_classes & ~self._f32_have
         if need and self._has_dit:   # the classes switched on for the first time: their "<name>.f32" operand copies
             with torch.cuda.device(self.device):
-                self._register(convert_dit_f32(self._f32_sd, self.cfg, self.device, need))
+                self.register(convert_dit_f32(self._f32_sd, self.cfg, self.device, need))
                 self._f32_have |= need
                 self._lanes = []   # stream lanes borrow the registered tensors: rebuilt on demand
                 # binds the new names.  Registering a name the engine already holds (the copies of an earlier checkpoint that
                 # a later load_state_dict left behind) marks EVERY weight set as not finalized: each set the model has is
                 # finalized again (the codec set was not, and the next separate() failed in the codec)
-                hip.check(self._lib.samaudio_finalize(self._ctx, 0))
+                self.finalize(0)
                 if self._has_codec:
-                    hip.check(self._lib.samaudio_finalize(self._ctx, 1))
+                    self.finalize(1)
         for ctx in [self._ctx] + [lane._ctx for lane in self._lanes]:
             self._set_precision_options(ctx)
 
@@ -488,20 +474,6 @@ class SAMAudio:
         self.quant_classes, self.quant_format = hip.class_mask(classes), hip.QUANT_FORMATS[fmt]
         for ctx in [self._ctx] + [lane._ctx for lane in self._lanes]:
             self._set_precision_options(ctx)
-
-    def _alt16_weight(self, name: str) -> bool:
-        """engine tensor `name` is the weight of a class that reads alt-format (bfloat16) operands in this model"""
-        leaf = name.rsplit(".", 1)[-1]
-        return name.startswith("L") and leaf in hip.ALT16_WEIGHTS and bool(self.alt16_classes & hip.CLS[hip.ALT16_WEIGHTS[leaf]])
-
-    def _register(self, tensors: Dict[str, torch.Tensor]) -> None:
-        for name, t in tensors.items():
-            dt = hip.dtype_code(t.dtype, hip.operands_for(self.precision), alt_ok=self._alt16_weight(name))
-            if t.data_ptr() % 16:   # a view into a larger buffer: the library needs 16-byte aligned pointers
-                t = t.clone()
-            self._tensors[name] = t  # keep alive: the library borrows the pointer
-            hip.check(self._lib.samaudio_set_tensor(self._ctx, name.encode(), hip.ptr(t), dt, t.dim(),
-                                                    hip.shape_array(t.shape)))
 
     def engine_tensors(self) -> Dict[str, torch.Tensor]:
         return self._tensors
@@ -570,16 +542,7 @@ class SAMAudio:
     def _ensure_workspace(self, rows: int, frames: int, text_len: int, codec_items: int, samples: int,
                           lane: Optional[_Lane] = None) -> None:
         own = lane if lane is not None else self   # whoever owns the context owns its workspace
-        need = self._lib.samaudio_workspace_bytes(own._ctx, rows, frames, max(1, text_len), codec_items, samples)
-        if own._workspace is None or own._workspace.numel() < need:
-            own._workspace = None
-            if os.environ.get("SAMAUDIO_POISON"):
-                # test aid: every byte 0xFF = NaN in fp32 and bf16, so a kernel that reads scratch nobody wrote shows up
-                # as NaN deterministically instead of depending on what the allocator handed out
-                fill = int(os.environ.get("SAMAUDIO_POISON_BYTE", "255"), 0)   # a finite pattern (e.g. 0x3F) shows reads
-                own._workspace = torch.full((need + 256,), fill, dtype=torch.uint8, device=self.device)  # that NaN-ignoring ops hide
-            else:
-                own._workspace = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        own.ensure_workspace(rows, frames, max(1, text_len), codec_items, samples)
         base = own._workspace.data_ptr()
         # contexts never share scratch: the workspaces of the model and of its stream lanes are pairwise disjoint
         for other in [self] + list(self._lanes):
@@ -588,27 +551,14 @@ class SAMAudio:
                 lo, hi = ws.data_ptr(), ws.data_ptr() + ws.numel()
                 if base < hi and lo < base + own._workspace.numel():
                     raise RuntimeError("engine contexts were handed overlapping workspaces")
-        aligned = (base + 255) // 256 * 256
-        hip.check(self._lib.samaudio_set_workspace(own._ctx, C.c_void_p(aligned),
-                                                   own._workspace.numel() - (aligned - base)))
 
     def _ensure_stages(self, method: int, rows: int, frames: int, lane: Optional[_Lane] = None) -> None:
         """Stage buffers of a Runge-Kutta solve (samaudio_set_ode_stages), owned per engine context like the workspace and apart from
         it; euler and midpoint need none and allocate nothing."""
         own = lane if lane is not None else self
         need = self._lib.samaudio_ode_stage_bytes(own._ctx, method, rows, frames)
-        if need == 0:
-            return
-        if own._stages is None or own._stages.numel() < need + 256:
-            own._stages = None
-            if os.environ.get("SAMAUDIO_POISON"):   # as the workspace: a stage read before it was written shows up as NaN
-                fill = int(os.environ.get("SAMAUDIO_POISON_BYTE", "255"), 0)
-                own._stages = torch.full((need + 256,), fill, dtype=torch.uint8, device=self.device)
-            else:
-                own._stages = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-        base = own._stages.data_ptr()
-        aligned = (base + 255) // 256 * 256
-        hip.check(self._lib.samaudio_set_ode_stages(own._ctx, C.c_void_p(aligned), own._stages.numel() - (aligned - base)))
+        if need:   # (poisoned as the workspace is: a stage read before it was written shows up as NaN)
+            hip.check(self._lib.samaudio_set_ode_stages(own._ctx, *scratch(own, "_stages", need, self.device)))
 
     def _codec_chunk(self, items: int) -> int:
         return min(items, int(os.environ.get("SAMAUDIO_CODEC_CHUNK", "16")))
@@ -661,11 +611,7 @@ class SAMAudio:
                 if own._codec16 is None:
                     own._codec16 = _Codec16(self)
                 ctx = own._codec16._ctx
-                base = own._workspace.data_ptr()
-                aligned = (base + 255) // 256 * 256
-                need = self._lib.samaudio_workspace_bytes(ctx, 0, 0, 1, self._codec_chunk(items), samples)
-                assert own._workspace.numel() - (aligned - base) >= need
-                hip.check(self._lib.samaudio_set_workspace(ctx, C.c_void_p(aligned), own._workspace.numel() - (aligned - base)))
+                own.lend_workspace(own._codec16, 0, 0, 1, self._codec_chunk(items), samples)
             if pairs:
                 hip.check(self._lib.samaudio_codec_decode_pairs(ctx, hip.ptr(lat), items // 2, frames, hip.ptr(wav),
                                                                 hip.current_stream_ptr()))

@@ -21,7 +21,6 @@ T5EncoderModel key                                          engine tensor
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import re
 from dataclasses import dataclass
@@ -30,7 +29,7 @@ from typing import Any, Dict, List, Optional
 import torch
 
 from . import hip
-from .judge import _ensure_ws, _register
+from .context import Context, check_keys
 
 ACTS = {"relu": hip.ACT_RELU, "gelu_new": hip.ACT_GELU_TANH}
 
@@ -121,7 +120,7 @@ def convert_t5(sd: Dict[str, torch.Tensor], dims: T5Dims, act_dtype: torch.dtype
     return out
 
 
-class T5EncoderHIP:
+class T5EncoderHIP(Context):
     """`enc(input_ids [B, Lt] int64, attention_mask [B, Lt]) -> last_hidden_state [B, Lt, d_model] float32`."""
 
     def __init__(self, dims: T5Dims, precision: str = "fp32", device: Optional[str] = None):
@@ -130,20 +129,10 @@ class T5EncoderHIP:
         self.dims = dims
         self.precision = precision
         self.device = torch.device(device) if device is not None else None
-        self._lib = hip.lib(hip.operands_for(precision))
-        self._h = C.c_void_p()
-        self._tensors: Dict[str, torch.Tensor] = {}
-        self._workspace: Optional[torch.Tensor] = None
-        self._loaded = False
         tc = hip.T5Config(precision=hip.precision_code(precision), vocab=dims.vocab_size, d_model=dims.d_model,
                           d_kv=dims.d_kv, heads=dims.num_heads, d_ff=dims.d_ff, layers=dims.num_layers,
                           max_len=dims.max_len, act=ACTS[dims.dense_act_fn], ln_eps=dims.layer_norm_epsilon)
-        hip.check(self._lib.samaudio_t5_create(C.byref(tc), C.byref(self._h)))
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.samaudio_t5_destroy(self._h)
-            self._h = None
+        super().__init__(hip.lib(hip.operands_for(precision)), "samaudio_t5", tc, device=self.device)
 
     @property
     def act_dtype(self) -> torch.dtype:
@@ -158,16 +147,11 @@ class T5EncoderHIP:
         pref = re.compile(r"^(text_encoder\.)?(model\.)?(?=shared\.|encoder\.)")
         sd = {pref.sub("", k): v for k, v in state_dict.items()}
         sd.pop("encoder.embed_tokens.weight", None)
-        want = set(expected_keys(self.dims))
-        missing, unexpected = sorted(want - set(sd)), sorted(set(sd) - want)
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Missing keys: {missing}, unexpected_keys: {unexpected}")
+        missing, unexpected = check_keys(expected_keys(self.dims), sd, strict)
         if not missing:
             with torch.cuda.device(self.device):
-                _register(self._lib.samaudio_t5_set_tensor, self._h, self._tensors,
-                          convert_t5(sd, self.dims, self.act_dtype, self.device))
-                hip.check(self._lib.samaudio_t5_finalize(self._h))
-            self._loaded = True
+                self.register(convert_t5(sd, self.dims, self.act_dtype, self.device))
+                self.finalize()
         return missing, unexpected
 
     @torch.inference_mode()
@@ -191,8 +175,7 @@ class T5EncoderHIP:
             out = torch.empty(rows, tokens, self.dims.d_model, device=self.device, dtype=torch.float32)
             if rows == 0 or tokens == 0:
                 return out
-            need = self._lib.samaudio_t5_workspace_bytes(self._h, rows, tokens)
-            _ensure_ws(self, need, lambda p, b: self._lib.samaudio_t5_set_workspace(self._h, p, b))
+            self.ensure_workspace(rows, tokens)
             hip.check(self._lib.samaudio_t5_encode(self._h, hip.ptr(ids), hip.ptr(mask), rows, tokens, hip.ptr(out),
                                                    hip.current_stream_ptr()))
         return out

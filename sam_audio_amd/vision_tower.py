@@ -28,7 +28,6 @@ then adds the split twins "L{i}.wqkv.x3", ".wo.x3", ".w1.x3", ".w2.x3" and "pool
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 import re
 from typing import Dict, List, Optional, Tuple
@@ -37,7 +36,7 @@ import torch
 
 from . import hip
 from .config import PE_VISION_CONFIGS, PEVisionConfig
-from .judge import _ensure_ws, _register
+from .context import Context, check_keys
 from .weights import x3_tower_weight
 
 POOL_TYPES = {"tok": 0, "avg": 1, "attn": 2}
@@ -153,7 +152,7 @@ def convert_vision(sd: Dict[str, torch.Tensor], cfg: PEVisionConfig, act_dtype: 
     return out
 
 
-class PEVisionTower:
+class PEVisionTower(Context):
     """`pe.CLIP`'s image side: `tower.encode_image(frames [N,3,S,S] float, normalize=bool) -> [N, output_dim]`; also
     callable (`tower(frames, normalize=...)`), which is the signature `PerceptionEncoder(tower=...)` expects.
     `tower.encode_frames(frames [N,3,H,W] uint8, mode, normalize=bool)` is the same on raw frames: resize, rounding and
@@ -173,7 +172,7 @@ class PEVisionTower:
         # epilogue at the same time, so alone the kernel alternates between an MFMA phase and an HBM write burst; two
         # streams interleave the two.  Frames are independent: bitwise equal to one stream (tests/test_vit_gpu.py).
         self.streams = streams
-        self._side = None          # (handle, workspace holder, torch stream) of the second context
+        self._side = None          # (context, torch stream) of the second stream, once a batch was split
         if cfg is None:
             if name not in PE_VISION_CONFIGS:
                 raise ValueError(f"unknown PE vision config {name!r}; known: {sorted(PE_VISION_CONFIGS)}")
@@ -187,11 +186,6 @@ class PEVisionTower:
             hip.CLS_X3_VIT if x3_classes == "auto" else hip.class_mask(x3_classes))
         if self.x3_classes & ~hip.CLS_X3_VIT:
             raise ValueError("x3_classes: the vision tower takes qkv, wo, w13, w2 and attn only")
-        self._lib = hip.lib(hip.operands_for(precision))
-        self._h = C.c_void_p()
-        self._tensors: Dict[str, torch.Tensor] = {}
-        self._workspace: Optional[torch.Tensor] = None
-        self._loaded = False
         vc = hip.VitConfig(
             precision=hip.precision_code(precision), image_size=cfg.image_size, patch_size=cfg.patch_size,
             width=cfg.width, layers=cfg.layers, heads=cfg.heads, mlp_width=cfg.mlp_width, output_dim=cfg.output_dim,
@@ -199,21 +193,13 @@ class PEVisionTower:
             use_ln_post=int(cfg.use_ln_post), pool_type=POOL_TYPES[cfg.pool_type], pool_heads=cfg.attn_pooler_heads,
             act=ACTS[cfg.act], ln_eps=cfg.ln_eps)
         self._vc = vc
-        hip.check(self._lib.samaudio_vit_create(C.byref(vc), C.byref(self._h)))
-        self._set_options(self._h)
+        super().__init__(hip.lib(hip.operands_for(precision)), "samaudio_vit", vc, device=self.device)
+        self._set_options(self)
 
-    def _set_options(self, handle):
+    def _set_options(self, ctx: Context):
         """x3 precisions: the compensated classes, BEFORE finalize (it resolves the twins) - on the main and the side context"""
         if self.x3_classes:
-            hip.check(self._lib.samaudio_vit_set_option(handle, hip.OPT_X3_CLASSES, self.x3_classes))
-
-    def __del__(self):
-        if getattr(self, "_side", None):
-            self._lib.samaudio_vit_destroy(self._side[0])
-            self._side = None
-        if getattr(self, "_h", None):
-            self._lib.samaudio_vit_destroy(self._h)
-            self._h = None
+            ctx.set_option(hip.OPT_X3_CLASSES, self.x3_classes)
 
     @property
     def act_dtype(self) -> torch.dtype:
@@ -242,41 +228,30 @@ class PEVisionTower:
             sd = {pref.sub("", k): v for k, v in state_dict.items() if pref.match(k)}
         else:
             sd = dict(state_dict)
-        want = set(expected_keys(self.cfg))
-        missing = sorted(want - set(sd))
-        unexpected = sorted(set(sd) - want)
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Missing keys: {missing}, unexpected_keys: {unexpected}")
+        missing, unexpected = check_keys(expected_keys(self.cfg), sd, strict)
         if not missing:
             with torch.cuda.device(self.device):
-                _register(self._lib.samaudio_vit_set_tensor, self._h, self._tensors,
-                          convert_vision(sd, self.cfg, self.act_dtype, self.device,
-                                         hip.half_dtype(self.precision) if self.x3_classes else None, self.x3_classes))
-                hip.check(self._lib.samaudio_vit_finalize(self._h))
-            self._loaded = True
+                self.register(convert_vision(sd, self.cfg, self.act_dtype, self.device,
+                                             hip.half_dtype(self.precision) if self.x3_classes else None, self.x3_classes))
+                self.finalize()
         return missing, unexpected
 
     def _side_context(self):
         if self._side is None:
-            class _Holder:   # owns the second context's workspace (judge._ensure_ws contract: .device, ._workspace)
-                pass
-            holder = _Holder()
-            holder.device, holder._workspace = self.device, None
-            h = C.c_void_p()
-            hip.check(self._lib.samaudio_vit_create(C.byref(self._vc), C.byref(h)))
-            self._set_options(h)
-            _register(self._lib.samaudio_vit_set_tensor, h, {}, self._tensors)   # borrowed: the same device tensors
-            hip.check(self._lib.samaudio_vit_finalize(h))
-            self._side = (h, holder, torch.cuda.Stream(device=self.device))
+            side = Context(self._lib, "samaudio_vit", self._vc, device=self.device)
+            self._set_options(side)
+            side.register(self._tensors, borrowed=True)   # the same device tensors
+            side.finalize()
+            self._side = (side, torch.cuda.Stream(device=self.device))
         return self._side
 
-    def _encode_on(self, handle, owner, x, normalize, feats, tokens, mode=None, video=None):
+    def _encode_on(self, ctx: Context, x, normalize, feats, tokens, mode=None, video=None):
         """One context's encode of the frames `x`: float [n,3,S,S] (samaudio_vit_encode), or - `mode` a hip.RESIZE_* code - raw uint8
         [n,3,H,W] (samaudio_vit_encode_frames), or - `video` = (mask or None, pick i32 [n] on the device or None) - the frames `pick` of
         the uint8 video `x` under its mask (samaudio_vit_encode_video)."""
         n = x.shape[0] if video is None or video[1] is None else video[1].shape[0]
-        need = self._lib.samaudio_vit_workspace_bytes(handle, n)
-        _ensure_ws(owner, need, lambda p, b: self._lib.samaudio_vit_set_workspace(handle, p, b))
+        ctx.ensure_workspace(n)
+        handle = ctx._h
         tail = (int(bool(normalize)), hip.ptr(feats), hip.ptr(tokens), hip.current_stream_ptr())
         if mode is None:
             hip.check(self._lib.samaudio_vit_encode(handle, hip.ptr(x), n, *tail))
@@ -300,7 +275,7 @@ class PEVisionTower:
                 import threading
                 if video is not None and video[1] is None:
                     video = (video[0], torch.arange(n, device=self.device, dtype=torch.int32))
-                h2, holder, side = self._side_context()
+                ctx2, side = self._side_context()
                 k = n // 2
                 main = torch.cuda.current_stream(self.device)
                 side.wait_stream(main)
@@ -309,20 +284,20 @@ class PEVisionTower:
                 def second():
                     try:
                         with torch.inference_mode(), torch.cuda.device(self.device), torch.cuda.stream(side):
-                            self._encode_on(h2, holder, part(k, n)[0], normalize, feats[k:], None if tokens is None else tokens[k:],
+                            self._encode_on(ctx2, part(k, n)[0], normalize, feats[k:], None if tokens is None else tokens[k:],
                                             mode, part(k, n)[1])
                     except BaseException as exc:   # re-raised on the caller's thread
                         errors.append(exc)
                 th = threading.Thread(target=second)
                 th.start()
-                self._encode_on(self._h, self, part(0, k)[0], normalize, feats[:k], None if tokens is None else tokens[:k], mode,
+                self._encode_on(self, part(0, k)[0], normalize, feats[:k], None if tokens is None else tokens[:k], mode,
                                 part(0, k)[1])
                 th.join()
                 main.wait_stream(side)
                 if errors:
                     raise errors[0]
             else:
-                self._encode_on(self._h, self, x, normalize, feats, tokens, mode, video)
+                self._encode_on(self, x, normalize, feats, tokens, mode, video)
         return (feats, tokens) if return_tokens else feats
 
     @torch.inference_mode()

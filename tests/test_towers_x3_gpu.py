@@ -72,13 +72,11 @@ def test_masked_groupnorm_silu_split3(gpu, prec):
 
 # ---------------------------------------------------------------------------------------------------- 2, 3: one transformer
 def _encode(m, z, mask, gpu):
-    from sam_audio_amd.judge import _ensure_ws
     rows, T, _ = z.shape
     D = m.config.transformer.hidden_size
     hidden = torch.empty(rows, T + 1, D, device=gpu)
     pm = mask.to(gpu).to(torch.uint8).contiguous() if mask is not None else None
-    need = m._lib.samaudio_judge_workspace_bytes(m._h, rows, 1, T)
-    _ensure_ws(m, need, lambda p, n: m._lib.samaudio_judge_set_workspace(m._h, p, n))
+    m.ensure_workspace(rows, 1, T)
     zd = z.to(gpu).contiguous()
     hip.check(m._lib.samaudio_judge_encode(m._h, 0, hip.ptr(zd), hip.ptr(pm), rows, T, hip.ptr(hidden), util.stream()))
     return hidden.cpu()
@@ -126,7 +124,7 @@ def test_peav_x3_per_class_masks(gpu, prec):
     (2 rows, T = 50 with lengths 50 / 9: S = 51 is no multiple of 64 and the second row has a masked tail).  Only the twins of the
     classes that are switched on are registered; finalize takes that, and the result is inside the bound of the full-mask test above
     (the classes left in fp32 are exact, so a subset cannot need a wider one)."""
-    from sam_audio_amd.judge import convert_judge, convert_judge_x3, _register
+    from sam_audio_amd.judge import convert_judge, convert_judge_x3
     tc = PEAVTransformerConfig(**G.TINY_TC)
     cfg, sd, z, mask = _transformer_case(tc, 2, 50, [50, 9])
     last, pooled = _oracle_transformer(sd, tc, z, mask)
@@ -138,7 +136,7 @@ def test_peav_x3_per_class_masks(gpu, prec):
         hip.check(m._lib.samaudio_judge_set_option(m._h, hip.OPT_X3_CLASSES, classes))
         tensors = convert_judge(sd, cfg, torch.float32, gpu)
         tensors.update(convert_judge_x3(tensors, cfg, HALF[prec], classes))
-        _register(m._lib.samaudio_judge_set_tensor, m._h, m._tensors, tensors)
+        m.register(tensors)
         hip.check(m._lib.samaudio_judge_finalize(m._h))
         hidden = _encode(m, z, mask, gpu)
         util.report(f"peav x3 classes {classes:#x} pooled {prec}", hidden[:, 0], pooled, _bar(pooled))
@@ -325,7 +323,7 @@ def test_judge_x3_workspace_is_exactly_what_the_plan_takes(gpu, prec):
 def test_tower_x3_option_errors(gpu):
     """No launch: the option on a 16-bit context and a non-tower bit are SAMAUDIO_ERR_ARG; finalize without a twin of a class that is
     switched on is SAMAUDIO_ERR_WEIGHT and names the twin."""
-    from sam_audio_amd.judge import SAMAudioJudgeModel, PEAudioFrame, convert_judge, _register
+    from sam_audio_amd.judge import SAMAudioJudgeModel, PEAudioFrame, convert_judge
     cfg = _cfg()
     tm = G.text_tower(cfg)
     lib = hip.lib()
@@ -345,7 +343,7 @@ def test_tower_x3_option_errors(gpu):
     # a missing twin
     assert lib.samaudio_judge_set_option(m32._h, hip.OPT_X3_CLASSES, hip.CLS["w2"]) == 0
     sd = init_judge_state_dict(cfg, seed=9, with_codec=False)
-    _register(lib.samaudio_judge_set_tensor, m32._h, m32._tensors, convert_judge(sd, cfg, torch.float32, gpu))
+    m32.register(convert_judge(sd, cfg, torch.float32, gpu))
     assert lib.samaudio_judge_finalize(m32._h) == hip.ERR_WEIGHT
     assert "t.L0.w2.x3" in lib.samaudio_last_error().decode()
     assert lib.samaudio_judge_set_option(m32._h, hip.OPT_X3_CLASSES, 0) == 0

@@ -333,7 +333,6 @@ def test_option_value_0_is_the_fp32_tower_bit_for_bit(gpu):
 def test_vit_x3_option_errors(gpu):
     """No launch: the option on a 16-bit context, another option and a foreign bit are SAMAUDIO_ERR_ARG; finalize without a twin of a
     class that is switched on is SAMAUDIO_ERR_WEIGHT and names the twin; the option un-finalizes a context."""
-    from sam_audio_amd.judge import _register
     cfg, sd, x, _, _ = _case("pe-tiny", False)
     lib = hip.lib()
     t16 = PEVisionTower(cfg, precision="bf16", device=str(gpu))
@@ -346,7 +345,7 @@ def test_vit_x3_option_errors(gpu):
     assert lib.samaudio_vit_set_option(None, hip.OPT_X3_CLASSES, 0) == hip.ERR_ARG
     # a missing twin: the fp32 tensors alone, class w2 on
     assert lib.samaudio_vit_set_option(t32._h, hip.OPT_X3_CLASSES, hip.CLS["w2"]) == 0
-    _register(lib.samaudio_vit_set_tensor, t32._h, t32._tensors, convert_vision(sd, cfg, torch.float32, gpu))
+    t32.register(convert_vision(sd, cfg, torch.float32, gpu))
     assert lib.samaudio_vit_finalize(t32._h) == hip.ERR_WEIGHT
     assert "L0.w2.x3" in lib.samaudio_last_error().decode()
     assert lib.samaudio_vit_set_option(t32._h, hip.OPT_X3_CLASSES, hip.CLS["qkv"]) == 0

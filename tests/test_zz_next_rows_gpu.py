@@ -83,7 +83,6 @@ def test_peav_transformer_matches_oracle(gpu, prec, masked):
     """One PE-AV transformer (input projection, class token, masked-GroupNorm ResNet block, layers, output
     projection) through the samaudio_judge_encode hook against oracle peav_transformer, which tests/test_judge_oracle.py
     pins to the Hugging Face PeAudioEncoder on this very network (same seeds as gen_golden_judge.pin_transformer)."""
-    from sam_audio_amd.judge import _ensure_ws
     from sam_audio_amd.synthetic import init_peav_state_dict
     tc = PEAVTransformerConfig(**G.TINY_TC)
     g = torch.Generator().manual_seed(5)
@@ -101,8 +100,7 @@ def test_peav_transformer_matches_oracle(gpu, prec, masked):
     m = _judge(cfg, sd, prec, gpu)
     hidden = torch.empty(3, 22, tc.hidden_size, device=gpu)
     pm = mask.to(gpu).to(torch.uint8).contiguous() if masked else None
-    need = m._lib.samaudio_judge_workspace_bytes(m._h, 3, 1, 21)
-    _ensure_ws(m, need, lambda p, n: m._lib.samaudio_judge_set_workspace(m._h, p, n))
+    m.ensure_workspace(3, 1, 21)
     zd = z.to(gpu).contiguous()
     hip.check(m._lib.samaudio_judge_encode(m._h, 0, hip.ptr(zd), hip.ptr(pm), 3, 21, hip.ptr(hidden), util.stream()))
     valid = (mask if masked else torch.ones_like(mask))[..., None]

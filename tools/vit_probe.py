@@ -72,7 +72,7 @@ for _ in range(rounds):
 print(f"{cfg.vision_encoder.name}, {n} frames, {rounds} rounds alternating {' / '.join(precs)} in one process (device events, ms per encode)")
 for p in precs:
     t = encs[p].tower
-    ctx = [t._workspace] + ([t._side[1]._workspace] if t._side else [])
+    ctx = [t._workspace] + ([t._side[0]._workspace] if t._side else [])
     ws = " + ".join(f"{w.numel() / 2 ** 30:.2f}" for w in ctx if w is not None)
     med = statistics.median(times[p])
     print(f"  {p:7s} {' '.join(f'{x:8.2f}' for x in times[p])}   median {med:8.2f} ms, {rate(med)}; workspace {ws} GiB "
