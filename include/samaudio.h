@@ -246,7 +246,8 @@ int samaudio_set_ode_stages(samaudio_ctx* ctx, void* stages, size_t bytes);
  * The context's stage buffers (samaudio_ode_stage_bytes answers for these methods: the K rows, the candidate state, the per-row
  * control block, the per-stage time table and the norm partials) are the caller's as for rk4: missing or too small or overlapping =
  * SAMAUDIO_ERR_WORKSPACE with the state untouched; a library built without the kernels (the CPU launcher emulation) = SAMAUDIO_ERR_STATE;
- * a window table set (samaudio_set_windows) = SAMAUDIO_ERR_STATE.  stats_host: HOST array, one entry per row.  A row that fails (status
+ * a window table set (samaudio_set_windows) without a group table = SAMAUDIO_ERR_STATE; with one (samaudio_set_window_groups) the
+ * unit of step control is the group, not the row.  stats_host: HOST array, one entry per row.  A row that fails (status
  * 2: a rejection drove its step below 10 ulp(t); 3: max_num_steps trial steps) stops where it is while the other rows go on; the call
  * still returns SAMAUDIO_OK and the caller reads the status. */
 typedef struct {
@@ -280,6 +281,18 @@ int samaudio_ode_solve_adaptive(samaudio_ctx* ctx, float* state, int method, flo
  * windows off, and so does every later samaudio_prepare / samaudio_prepare_latent: a stale table never meets a new batch.  A library
  * built without the kernel (the CPU launcher emulation) answers SAMAUDIO_ERR_STATE. */
 int samaudio_set_windows(samaudio_ctx* ctx, const int32_t* next_row_device, int rows, int overlap_frames);
+/* Step control PER CLIP for samaudio_ode_solve_adaptive over window rows (tests/ode_windowed_adaptive_ref.py
+ * is the statement).  groups_device [n_groups, 3] i32 ON THE DEVICE: first engine row, window count, row stride of each group - the
+ * window rows of one (clip, candidate); owner_mask_device [rows, frames] u8 ON THE DEVICE: 1 where the row OWNS the frame - the frame
+ * is valid and lies before the stride (frames - overlap), or the row is its clip's last window - so every valid frame of a clip is
+ * owned by exactly one row.  While both are set, an adaptive solve carries one time, one step, one error norm (over the group's owned
+ * frames, each counted once: partials added in window order, chunk order within a row) and one accept / reject decision per group,
+ * written identically to every row of the group; a clip's result then does not depend on which clips share the call.
+ * Valid only after samaudio_set_windows (SAMAUDIO_ERR_STATE otherwise); n_groups outside [1, rows], a null mask or a misaligned
+ * table = SAMAUDIO_ERR_ARG.  Both arrays are borrowed until replaced; their contents are the caller's responsibility - a row index
+ * outside [0, rows) counts as absent, rows in no group are not stepped.  groups_device = NULL clears them, and so do
+ * samaudio_set_windows (NULL or not) and every samaudio_prepare / samaudio_prepare_latent. */
+int samaudio_set_window_groups(samaudio_ctx* ctx, const int32_t* groups_device, int n_groups, const uint8_t* owner_mask_device);
 /* kernel-level hook: the blend above on out [rows, frames, channels] f32 in place.  SAMAUDIO_ERR_ARG before any launch for a null
  * pointer, rows < 1, frames < 2, overlap outside [1, frames / 2], channels % 4 != 0, out not aligned to 16 bytes. */
 int samaudio_op_window_blend(float* out, const int32_t* next_row, int rows, int frames, int overlap, int channels,
@@ -970,6 +983,16 @@ int samaudio_op_ode_error(const float* y, const float* ynew, const float* const*
 int samaudio_op_ode_control(void* ctl, int mode, int method, float t0, float t1, const samaudio_ode_adaptive* opt, const float* partials,
                             const float* partials_b, int chunks, const uint8_t* mask, int frames, int channels, float* times,
                             int32_t* active, int rows, samaudio_stream stream);
+/* ode_control_groups_kernel, one lane per group of rows (samaudio_set_window_groups): samaudio_op_ode_control's arguments, then
+ *   groups [n_groups, 3] device i32 = first row, row count, row stride.  A group's sum = its rows' partials added in window order,
+ *   chunk order within a row, in one f32 accumulator; n_valid = the masked frames of all its rows * channels; the decision is
+ *   ode_control_kernel's, and every row of the group ends with the same 64 control bytes and time-table column.  Row indices outside
+ *   [0, rows) are skipped.  groups NULL (n_groups == rows): every row is its own group, bit for bit samaudio_op_ode_control.
+ *   *active = rows of groups running afterwards.  More than 256 groups: lanes loop. */
+int samaudio_op_ode_control_groups(void* ctl, int mode, int method, float t0, float t1, const samaudio_ode_adaptive* opt,
+                                   const float* partials, const float* partials_b, int chunks, const uint8_t* mask, int frames,
+                                   int channels, float* times, int32_t* active, int rows, const int32_t* groups, int n_groups,
+                                   samaudio_stream stream);
 /* ode_commit_kernel: rows with accepted_now: y <- ynew, k_first <- k_last */
 int samaudio_op_ode_commit(float* y, const float* ynew, float* k_first, const float* k_last, const void* ctl, int rows,
                            int64_t row_elems, samaudio_stream stream);

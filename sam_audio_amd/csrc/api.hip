@@ -124,6 +124,10 @@ int samaudio_set_windows(samaudio_ctx* ctx, const int32_t* next_row_device, int 
   return SA_ENTRY(ctx, "null context", ctx->engine->set_windows(next_row_device, rows, overlap_frames));
 }
 
+int samaudio_set_window_groups(samaudio_ctx* ctx, const int32_t* groups_device, int n_groups, const uint8_t* owner_mask_device) {
+  return SA_ENTRY(ctx, "null context", ctx->engine->set_window_groups(groups_device, n_groups, owner_mask_device));
+}
+
 int samaudio_codec_encode(samaudio_ctx* ctx, const float* wav, int items, int64_t samples, float* latent,
                           samaudio_stream stream) {
   return SA_ENTRY(ctx, "null context", ctx->engine->codec_encode(wav, items, samples, latent, (hipStream_t)stream));
@@ -936,6 +940,25 @@ int samaudio_op_ode_control(void* ctl, int mode, int method, float t0, float t1,
   if (!sa::launch_ode_control) return not_built("ode_control");
   return hip_ret(sa::launch_ode_control((sa::OdeRowCtl*)ctl, mode, a, partials, partials_b, chunks, mask, frames, channels, times,
                                         (int*)active, rows, (hipStream_t)stream), "ode_control");
+}
+
+int samaudio_op_ode_control_groups(void* ctl, int mode, int method, float t0, float t1, const samaudio_ode_adaptive* opt,
+                                   const float* partials, const float* partials_b, int chunks, const uint8_t* mask, int frames,
+                                   int channels, float* times, int32_t* active, int rows, const int32_t* groups, int n_groups,
+                                   samaudio_stream stream) {
+  if (!ctl || !opt || !times || !active) return bad("ode_control_groups: null argument");
+  sa::OdeControlArgs a;
+  if (!sa::ode_control_args(method, t0, t1, *opt, a)) return bad("ode_control_groups: the method must be dopri5 or bosh3");
+  if (mode < sa::ODE_CTL_RESET || mode > sa::ODE_CTL_STEP) return bad("ode_control_groups: mode");
+  if (rows < 1 || frames < 1 || channels < 1) return bad("ode_control_groups: rows, frames, channels < 1");
+  if (mode != sa::ODE_CTL_RESET && (!partials || chunks < 1)) return bad("ode_control_groups: partials");
+  if (mode == sa::ODE_CTL_INIT1 && !partials_b) return bad("ode_control_groups: the initial-step rule reads two sets of partials");
+  if (groups ? n_groups < 1 : n_groups != rows) return bad("ode_control_groups: n_groups (>= 1; rows when the table is null)");
+  if (!aligned_to(ctl, 4) || !aligned_to(times, 4) || !aligned_to(active, 4) || !aligned_to(groups, 4))
+    return bad("ode_control_groups: alignment");
+  if (!sa::launch_ode_control_groups) return not_built("ode_control_groups");
+  return hip_ret(sa::launch_ode_control_groups((sa::OdeRowCtl*)ctl, mode, a, partials, partials_b, chunks, mask, frames, channels, times,
+                                               (int*)active, rows, groups, n_groups, (hipStream_t)stream), "ode_control_groups");
 }
 
 int samaudio_op_ode_commit(float* y, const float* ynew, float* k_first, const float* k_last, const void* ctl, int rows,

@@ -39,6 +39,10 @@ class Engine {
   // windowed solve (samaudio_set_windows): while a successor table is set, every field evaluation ends with window_blend_kernel on its
   // output.  next_row: device i32 [rows], borrowed; null switches windows off, and so does every prepare
   Status set_windows(const int32_t* next_row, int rows, int overlap);
+  // step control per clip for an adaptive solve over windows (samaudio_set_window_groups): groups [n_groups, 3]
+  // device i32 (first row, window count, row stride) and the ownership mask [rows, frames] u8, both borrowed; only while a successor
+  // table is set; null clears, and so do set_windows and every prepare
+  Status set_window_groups(const int32_t* groups, int n_groups, const uint8_t* owner_mask);
   Status codec_encode(const float* wav, int items, int64_t samples, float* latent, hipStream_t st);
   // `pairs`: latent is the ODE state [items / 2, frames, 2 * codec_dim] - item 2b = the first codec_dim channels of row b (target),
   // 2b + 1 the second (residual): reference model.py:291-295 without the transposed copy
@@ -146,6 +150,9 @@ class Engine {
   size_t stages_bytes_ = 0;
   const int32_t* win_next_ = nullptr;   // samaudio_set_windows: the successor table of the prepared rows (null: no windows)
   int win_overlap_ = 0;
+  const int32_t* win_groups_ = nullptr;   // samaudio_set_window_groups: the rows that share one step control (null: per row)
+  const uint8_t* win_owner_ = nullptr;    // ... and the frames each row contributes to its group's norms
+  int win_n_groups_ = 0;
   bool sentinel_on_ = false;   // SAMAUDIO_OPT_SENTINEL
   float* sentinel_dev_ = nullptr;   // [SAMAUDIO_SENTINEL_SLOTS][2] slots + [kSentinelPartials][2] partials (debug_device_alloc)
   // fold the scan of a tensor into `slot` (no-op unless the sentinel is on); fmt as launch_sentinel

@@ -909,6 +909,9 @@ Status Engine::prepare(int rows, int T, int Lt, const float* feats, const float*
                        const uint8_t* pad_mask, hipStream_t st, int cand, bool latent_feats) {
   win_next_ = nullptr;   // a successor table (samaudio_set_windows) belongs to the rows it was set for: it never meets a new batch
   win_overlap_ = 0;
+  win_groups_ = nullptr;   // and so do the group table and the ownership mask (samaudio_set_window_groups)
+  win_owner_ = nullptr;
+  win_n_groups_ = 0;
   if (!dit_ready_) return fail(SAMAUDIO_ERR_STATE, "prepare: DiT weights not finalized");
   if (rows <= 0 || T <= 0 || !feats) return fail(SAMAUDIO_ERR_ARG, "prepare: bad shape");
   if (cand < 1 || rows % cand) return fail(SAMAUDIO_ERR_ARG, "prepare: rows must be a multiple of candidates");
@@ -1348,6 +1351,9 @@ Status Engine::eval_field(const float* noisy, const float* time, int nt, float* 
 Status Engine::set_windows(const int32_t* next_row, int rows, int overlap) {
   win_next_ = nullptr;
   win_overlap_ = 0;
+  win_groups_ = nullptr;   // groups are groups of window rows: they go with the table
+  win_owner_ = nullptr;
+  win_n_groups_ = 0;
   if (!next_row) return Status{};
   if (!prepared_) return fail(SAMAUDIO_ERR_STATE, "set_windows: call samaudio_prepare first");
   if (rows != rows_) return fail(SAMAUDIO_ERR_ARG, "set_windows: rows is not the prepared row count");
@@ -1357,6 +1363,22 @@ Status Engine::set_windows(const int32_t* next_row, int rows, int overlap) {
   if (!launch_window_blend) return fail(SAMAUDIO_ERR_STATE, "set_windows: this build has no window_blend_kernel");
   win_next_ = next_row;
   win_overlap_ = overlap;
+  return Status{};
+}
+
+Status Engine::set_window_groups(const int32_t* groups, int n_groups, const uint8_t* owner_mask) {
+  win_groups_ = nullptr;
+  win_owner_ = nullptr;
+  win_n_groups_ = 0;
+  if (!groups) return Status{};
+  if (!prepared_ || !win_next_) return fail(SAMAUDIO_ERR_STATE, "set_window_groups: call samaudio_set_windows first");
+  if (n_groups < 1 || n_groups > rows_) return fail(SAMAUDIO_ERR_ARG, "set_window_groups: n_groups must be in [1, rows]");
+  if (!owner_mask) return fail(SAMAUDIO_ERR_ARG, "set_window_groups: the ownership mask is missing");
+  if (reinterpret_cast<uintptr_t>(groups) & 3) return fail(SAMAUDIO_ERR_ARG, "set_window_groups: the table must be aligned to 4 bytes");
+  if (!launch_ode_control_groups) return fail(SAMAUDIO_ERR_STATE, "set_window_groups: this build has no ode_control_groups_kernel");
+  win_groups_ = groups;
+  win_owner_ = owner_mask;
+  win_n_groups_ = n_groups;
   return Status{};
 }
 
@@ -1537,6 +1559,7 @@ bool ode_control_args(int method, float t0, float t1, const samaudio_ode_adaptiv
 // of them on the device.  One trial step = the stage evaluations of all rows (per-row times: eval_field with n_time = rows), the error
 // norms, the controller, the commit, then ONE host read: the number of rows still running.  Rows that have ended ride along - the stage
 // kernel hands their state through, the field evaluates it at their own time, and nothing of theirs is written - until the last row ends.
+// With windows and a group table set the unit of step control is the group instead of the row (section 10.11).
 Status Engine::ode_solve_adaptive(float* y, int method, float t0, float t1, const samaudio_ode_adaptive* opt,
                                   samaudio_ode_row_stats* stats, hipStream_t st) {
   if (!prepared_) return fail(SAMAUDIO_ERR_STATE, "ode_solve_adaptive: call samaudio_prepare first");
@@ -1549,7 +1572,9 @@ Status Engine::ode_solve_adaptive(float* y, int method, float t0, float t1, cons
       opt->first_step != opt->first_step)
     return fail(SAMAUDIO_ERR_ARG, "ode_solve_adaptive: safety > 0, ifactor >= 1, 0 < dfactor < 1, max_num_steps >= 1");
   if (cfg_.latent_channels % 4) return fail(SAMAUDIO_ERR_ARG, "ode_solve_adaptive: latent_channels % 4 != 0");
-  if (win_next_) return fail(SAMAUDIO_ERR_STATE, "ode_solve_adaptive: windows are set (rows of one clip must share their times)");
+  if (win_next_ && !win_groups_)
+    return fail(SAMAUDIO_ERR_STATE, "ode_solve_adaptive: windows are set (rows of one clip must share their times: "
+                                    "samaudio_set_window_groups gives them step control per clip)");
   if (!launch_ode_stage_rows || !launch_ode_error || !launch_ode_control || !launch_ode_commit)
     return fail(SAMAUDIO_ERR_STATE, "ode_solve_adaptive: dopri5 / bosh3 are not available in this build (no ode_*_rows kernels)");
   const int rows = rows_, T = frames_, C2 = cfg_.latent_channels, S = tab->stages;
@@ -1566,8 +1591,17 @@ Status Engine::ode_solve_adaptive(float* y, int method, float t0, float t1, cons
   const int chunks = ode_chunks(T, C2);
   OdeControlArgs ca{};
   ode_control_args(method, t0, t1, *opt, ca);
+  // windows with a group table: the same launches, with the norm over the frames a row OWNS and one
+  // controller lane per (clip, candidate) that hands all its window rows the same time, step and decision
+  const bool grouped = win_next_ && win_groups_;
+  const uint8_t* const norm_mask = grouped ? win_owner_ : d_.pad_mask;
 
   auto control = [&](int mode) {
+    if (grouped)
+      return op("ode_control_groups", (2.0 * sizeof(OdeRowCtl) + 4.0 * chunks) * rows, 0, st, [&] {
+        return launch_ode_control_groups(b.ctl, mode, ca, b.part, b.part_b, chunks, norm_mask, T, C2, b.times, b.active, rows,
+                                         win_groups_, win_n_groups_, st);
+      });
     return op("ode_control", (2.0 * sizeof(OdeRowCtl) + 4.0 * chunks) * rows, 0, st, [&] {
       return launch_ode_control(b.ctl, mode, ca, b.part, b.part_b, chunks, d_.pad_mask, T, C2, b.times, b.active, rows, st);
     });
@@ -1588,7 +1622,7 @@ Status Engine::ode_solve_adaptive(float* y, int method, float t0, float t1, cons
   };
   auto norm = [&](const OdeSrcArgs& a, const float* ynew, int use_h, float* part) {
     return op("ode_error", (a.n_src + (ynew ? 2.0 : 1.0)) * n * 4, 2.0 * (a.n_src + 4) * n, st, [&] {
-      return launch_ode_error(y, ynew, a, b.ctl, d_.pad_mask, opt->rtol, opt->atol, use_h, part, rows, T, C2, st);
+      return launch_ode_error(y, ynew, a, b.ctl, norm_mask, opt->rtol, opt->atol, use_h, part, rows, T, C2, st);
     });
   };
   auto field = [&](const float* in, int slot, float* out) {

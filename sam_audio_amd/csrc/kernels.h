@@ -327,6 +327,15 @@ __attribute__((weak)) hipError_t launch_ode_error(const float* y, const float* y
 __attribute__((weak)) hipError_t launch_ode_control(OdeRowCtl* ctl, int mode, const OdeControlArgs& a, const float* partials,
                                                     const float* partials_b, int chunks, const unsigned char* mask, int frames,
                                                     int channels, float* times, int* active, int rows, hipStream_t st);
+// step control per group of rows: one thread per group; groups [n_groups, 3] device i32 = first row, row
+// count, row stride (null: n_groups == rows, every row its own group - launch_ode_control's arithmetic).  A group's norm adds the
+// partials of its rows in window order, chunk order within a row; n_valid = the masked frames of all its rows * channels; every row
+// of a group is left with the same control block and time-table column.  Row indices outside [0, rows) are skipped.
+// *active = rows of the groups still running
+__attribute__((weak)) hipError_t launch_ode_control_groups(OdeRowCtl* ctl, int mode, const OdeControlArgs& a, const float* partials,
+                                                           const float* partials_b, int chunks, const unsigned char* mask, int frames,
+                                                           int channels, float* times, int* active, int rows, const int* groups,
+                                                           int n_groups, hipStream_t st);
 // rows with accepted_now: y <- ynew, k_first <- k_last
 __attribute__((weak)) hipError_t launch_ode_commit(float* y, const float* ynew, float* k_first, const float* k_last, const OdeRowCtl* ctl,
                                                    int rows, long row_elems, hipStream_t st);

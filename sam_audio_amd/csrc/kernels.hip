@@ -929,6 +929,65 @@ __device__ inline void ode_row_begin_trial(OdeRowCtl& c, const OdeControlArgs& a
   for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = c.t + a.c[i] * c.h;
 }
 
+// what a running row does with the sums of its norm partials (`ss`; `ss_b`: INIT1's second norm): the two halves of the initial-step
+// rule, or the accept / reject decision and the next trial.  The times of the next trial go to column r of the table.
+__device__ inline void ode_row_decide(OdeRowCtl& c, const int mode, const OdeControlArgs& a, const float ss, const float ss_b,
+                                      float* times, const int rows, const int r) {
+#pragma clang fp contract(off)
+  const float n = (float)(c.n_valid > 0 ? c.n_valid : 1);
+  const float norm = sqrtf(ss / n);
+  if (mode == ODE_CTL_INIT1) {   // d0 = |y0 / scale|, d1 = |f0 / scale|: the explicit-Euler probe step h0
+    const float d0 = norm, d1 = sqrtf(ss_b / n);
+    float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+    h0 = fminf(h0, a.t1 - a.t0);
+    c.d1 = d1;
+    c.h0 = c.h = h0;
+    times[rows + r] = a.t0 + h0;
+  } else if (mode == ODE_CTL_INIT2) {   // d2 = |(f1 - f0) / scale| / h0
+    const float d2 = norm / c.h0;
+    const float h1 = (c.d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, c.h0 * 1e-3f)
+                                                      : powf(0.01f / fmaxf(c.d1, d2), 1.f / (float)(a.order + 1));
+    c.h_abs = fminf(fminf(100.f * c.h0, h1), a.t1 - a.t0);
+    ode_row_begin_trial(c, a, times, rows, r);
+  } else {
+    const float expo = -1.f / (float)(a.order + 1);
+    c.err = norm;
+    c.h_abs = c.h;
+    if (norm < 1.f) {
+      float factor = norm == 0.f ? a.ifactor : fminf(a.ifactor, a.safety * powf(norm, expo));
+      if (c.step_rejected) factor = fminf(1.f, factor);
+      c.h_abs *= factor;
+      c.h_prev = c.h;
+      c.t = c.t_new;
+      c.accepted += 1;
+      c.accepted_now = 1;
+      c.step_rejected = 0;
+      if (c.t - a.t1 >= 0.f) c.status = ODE_ROW_FINISHED;
+    } else {   // (a NaN norm lands here: fmaxf drops it and the step shrinks by dfactor until it underflows)
+      c.h_abs *= fmaxf(a.dfactor, a.safety * powf(norm, expo));
+      c.rejected += 1;
+      c.accepted_now = 0;
+      c.step_rejected = 1;
+    }
+    if (c.status == ODE_ROW_RUNNING) ode_row_begin_trial(c, a, times, rows, r);
+  }
+  if (c.status != ODE_ROW_RUNNING)   // a row that stops rides along at its own time
+    for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = c.t;
+}
+
+// a row (or a group's leader row) at the start of a solve; `valid` = the frames its norms count
+__device__ inline void ode_row_reset(OdeRowCtl& c, const OdeControlArgs& a, const int valid, const int channels, float* times,
+                                     const int rows, const int r) {
+  c = OdeRowCtl{};
+  c.t = c.t_new = a.t0;
+  c.n_valid = valid * channels;
+  for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = a.t0;
+  if (a.first_step > 0.f) {
+    c.h_abs = a.first_step;
+    ode_row_begin_trial(c, a, times, rows, r);
+  }
+}
+
 __global__ __launch_bounds__(256) void ode_control_kernel(OdeRowCtl* ctl, const int mode, const OdeControlArgs a,
                                                           const float* __restrict__ partials, const float* __restrict__ partials_b,
                                                           const int chunks, const unsigned char* __restrict__ mask, const int frames,
@@ -939,67 +998,103 @@ __global__ __launch_bounds__(256) void ode_control_kernel(OdeRowCtl* ctl, const 
   for (int r = threadIdx.x; r < rows; r += 256) {
     OdeRowCtl c = ctl[r];
     if (mode == ODE_CTL_RESET) {
-      c = OdeRowCtl{};
-      c.t = c.t_new = a.t0;
       int valid = frames;
       if (mask) {
         valid = 0;
         for (int f = 0; f < frames; ++f) valid += mask[(long)r * frames + f] != 0;
       }
-      c.n_valid = valid * channels;
-      for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = a.t0;
-      if (a.first_step > 0.f) {
-        c.h_abs = a.first_step;
-        ode_row_begin_trial(c, a, times, rows, r);
-      }
+      ode_row_reset(c, a, valid, channels, times, rows, r);
     } else if (c.status == ODE_ROW_RUNNING) {
       float ss = 0.f, ss_b = 0.f;
       for (int k = 0; k < chunks; ++k) ss += partials[(long)r * chunks + k];
-      const float n = (float)(c.n_valid > 0 ? c.n_valid : 1);
-      const float norm = sqrtf(ss / n);
-      if (mode == ODE_CTL_INIT1) {   // d0 = |y0 / scale|, d1 = |f0 / scale|: the explicit-Euler probe step h0
+      if (mode == ODE_CTL_INIT1)
         for (int k = 0; k < chunks; ++k) ss_b += partials_b[(long)r * chunks + k];
-        const float d0 = norm, d1 = sqrtf(ss_b / n);
-        float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
-        h0 = fminf(h0, a.t1 - a.t0);
-        c.d1 = d1;
-        c.h0 = c.h = h0;
-        times[rows + r] = a.t0 + h0;
-      } else if (mode == ODE_CTL_INIT2) {   // d2 = |(f1 - f0) / scale| / h0
-        const float d2 = norm / c.h0;
-        const float h1 = (c.d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, c.h0 * 1e-3f)
-                                                          : powf(0.01f / fmaxf(c.d1, d2), 1.f / (float)(a.order + 1));
-        c.h_abs = fminf(fminf(100.f * c.h0, h1), a.t1 - a.t0);
-        ode_row_begin_trial(c, a, times, rows, r);
-      } else {
-        const float expo = -1.f / (float)(a.order + 1);
-        c.err = norm;
-        c.h_abs = c.h;
-        if (norm < 1.f) {
-          float factor = norm == 0.f ? a.ifactor : fminf(a.ifactor, a.safety * powf(norm, expo));
-          if (c.step_rejected) factor = fminf(1.f, factor);
-          c.h_abs *= factor;
-          c.h_prev = c.h;
-          c.t = c.t_new;
-          c.accepted += 1;
-          c.accepted_now = 1;
-          c.step_rejected = 0;
-          if (c.t - a.t1 >= 0.f) c.status = ODE_ROW_FINISHED;
-        } else {   // (a NaN norm lands here: fmaxf drops it and the step shrinks by dfactor until it underflows)
-          c.h_abs *= fmaxf(a.dfactor, a.safety * powf(norm, expo));
-          c.rejected += 1;
-          c.accepted_now = 0;
-          c.step_rejected = 1;
-        }
-        if (c.status == ODE_ROW_RUNNING) ode_row_begin_trial(c, a, times, rows, r);
-      }
-      if (c.status != ODE_ROW_RUNNING)   // a row that stops rides along at its own time
-        for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = c.t;
+      ode_row_decide(c, mode, a, ss, ss_b, times, rows, r);
     } else {
       c.accepted_now = 0;
     }
     ctl[r] = c;
     mine += c.status == ODE_ROW_RUNNING;
+  }
+  running[threadIdx.x] = mine;
+  for (int o = 128; o > 0; o >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < o) running[threadIdx.x] += running[threadIdx.x + o];
+  }
+  if (threadIdx.x == 0) *active = running[0];
+}
+
+// Step control per GROUP of rows (the window rows of one clip and candidate in a windowed solve): one lane per
+// group.  groups [n_groups, 3] i32 = first row, row count, row stride; null: every row is a group of its own, which is
+// ode_control_kernel's arithmetic.  A group is ONE integration: its norm is the sum of its rows' partials - rows in window order,
+// chunks in order within a row, one accumulator, no atomics - over n_valid = the masked frames of all its rows * channels (`mask`
+// is the ownership mask there: every frame of the clip is counted in exactly one row), and every row of the group receives the
+// same control block and the same column of the time table.  A row index outside [0, rows) is absent: a bad table groups wrong rows
+// but never reaches outside the arrays.  *active = rows (not groups) still running.
+__global__ __launch_bounds__(256) void ode_control_groups_kernel(OdeRowCtl* ctl, const int mode, const OdeControlArgs a,
+                                                                 const float* __restrict__ partials,
+                                                                 const float* __restrict__ partials_b, const int chunks,
+                                                                 const unsigned char* __restrict__ mask, const int frames,
+                                                                 const int channels, float* times, int* active, const int rows,
+                                                                 const int* __restrict__ groups, const int n_groups) {
+#pragma clang fp contract(off)
+  __shared__ int running[256];
+  int mine = 0;
+  for (int g = threadIdx.x; g < n_groups; g += 256) {
+    const int first = groups ? groups[3 * g] : g;
+    int count = groups ? groups[3 * g + 1] : 1;
+    const int stride = groups ? groups[3 * g + 2] : 1;
+    if (count > rows) count = rows;
+    auto row_of = [&](int w) {   // -1: absent
+      const long r = (long)first + (long)w * stride;
+      return r >= 0 && r < rows ? (int)r : -1;
+    };
+    int lead = -1, present = 0;
+    for (int w = 0; w < count; ++w) {
+      const int r = row_of(w);
+      if (r < 0) continue;
+      if (lead < 0) lead = r;
+      ++present;
+    }
+    if (lead < 0) continue;
+    OdeRowCtl c = ctl[lead];
+    if (mode == ODE_CTL_RESET) {
+      int valid = 0;
+      for (int w = 0; w < count; ++w) {
+        const int r = row_of(w);
+        if (r < 0) continue;
+        if (mask) {
+          for (int f = 0; f < frames; ++f) valid += mask[(long)r * frames + f] != 0;
+        } else {
+          valid += frames;
+        }
+      }
+      ode_row_reset(c, a, valid, channels, times, rows, lead);
+    } else if (c.status == ODE_ROW_RUNNING) {
+      float ss = 0.f, ss_b = 0.f;
+      for (int w = 0; w < count; ++w) {
+        const int r = row_of(w);
+        if (r < 0) continue;
+        for (int k = 0; k < chunks; ++k) ss += partials[(long)r * chunks + k];
+      }
+      if (mode == ODE_CTL_INIT1)
+        for (int w = 0; w < count; ++w) {
+          const int r = row_of(w);
+          if (r < 0) continue;
+          for (int k = 0; k < chunks; ++k) ss_b += partials_b[(long)r * chunks + k];
+        }
+      ode_row_decide(c, mode, a, ss, ss_b, times, rows, lead);
+    } else {
+      c.accepted_now = 0;
+    }
+    for (int w = 0; w < count; ++w) {   // the leader's block and its column of the time table, to every row of the group
+      const int r = row_of(w);
+      if (r < 0) continue;
+      ctl[r] = c;
+      if (r != lead)
+        for (int i = 0; i < a.n_times; ++i) times[(long)i * rows + r] = times[(long)i * rows + lead];
+    }
+    mine += c.status == ODE_ROW_RUNNING ? present : 0;
   }
   running[threadIdx.x] = mine;
   for (int o = 128; o > 0; o >>= 1) {
@@ -1017,6 +1112,18 @@ hipError_t launch_ode_control(OdeRowCtl* ctl, int mode, const OdeControlArgs& a,
   if (mode == ODE_CTL_INIT1 && !partials_b) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ode_control_kernel, dim3(1), dim3(256), 0, st, ctl, mode, a, partials, partials_b, chunks, mask, frames, channels,
                      times, active, rows);
+  return hipGetLastError();
+}
+
+hipError_t launch_ode_control_groups(OdeRowCtl* ctl, int mode, const OdeControlArgs& a, const float* partials, const float* partials_b,
+                                     int chunks, const unsigned char* mask, int frames, int channels, float* times, int* active,
+                                     int rows, const int* groups, int n_groups, hipStream_t st) {
+  if (rows < 1 || mode < ODE_CTL_RESET || mode > ODE_CTL_STEP || a.n_times < 2 || a.n_times > kOdeMaxSrc) return hipErrorInvalidValue;
+  if (mode != ODE_CTL_RESET && (!partials || chunks < 1)) return hipErrorInvalidValue;
+  if (mode == ODE_CTL_INIT1 && !partials_b) return hipErrorInvalidValue;
+  if (groups ? n_groups < 1 : n_groups != rows) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ode_control_groups_kernel, dim3(1), dim3(256), 0, st, ctl, mode, a, partials, partials_b, chunks, mask, frames,
+                     channels, times, active, rows, groups, n_groups);
   return hipGetLastError();
 }
 

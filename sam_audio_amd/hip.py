@@ -336,6 +336,7 @@ _PROTOS = {
     "samaudio_ode_stage_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "samaudio_set_ode_stages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "samaudio_set_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "samaudio_set_window_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "samaudio_op_window_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "samaudio_codec_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "samaudio_codec_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -403,6 +404,9 @@ _PROTOS = {
     "samaudio_op_ode_control": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(OdeAdaptive), C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_void_p]),
+    "samaudio_op_ode_control_groups": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(OdeAdaptive), C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_int, C.c_void_p]),
     "samaudio_op_ode_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "samaudio_op_repeat_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "samaudio_op_repeat_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),

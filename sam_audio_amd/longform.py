@@ -72,6 +72,26 @@ class WindowPlan:
         w = min(t // self.stride, self.counts[clip] - 1)
         return w, t - w * self.stride
 
+    # ---------------------------------------------------------------- step control per clip
+    def groups(self) -> List[Tuple[int, int, int]]:
+        """Per (clip, candidate), in the stitched latent's row order: (first engine row, window count, row stride) of its window
+        rows - the rows (first[b] + w) * candidates + c, w < n_b - which an adaptive solve steps as one integration."""
+        return [((self.first[b]) * self.candidates + c, n, self.candidates)
+                for b, n in enumerate(self.counts) for c in range(self.candidates)]
+
+    def owner_mask(self) -> List[List[bool]]:
+        """Per engine row and frame of the row: whether the row OWNS the frame - the frame is valid and lies before the stride, or
+        the row is its clip's last window.  That is `source`'s rule, so the owned frames are the ones the stitch reads, and every
+        valid frame of a clip is owned by exactly one row: a norm over owned frames counts each frame of the clip once."""
+        L, S = self.row_frames, self.stride
+        mask = []
+        for b, n in enumerate(self.counts):
+            for w in range(n):
+                valid = self.valid_frames(b, w)
+                row = [j < valid and (j < S or w == n - 1) for j in range(L)]
+                mask.extend(list(row) for _ in range(self.candidates))
+        return mask
+
     # ---------------------------------------------------------------- index tensors (host lists; the model uploads them once)
     def gather_index(self) -> Tuple[List[int], List[List[int]], List[List[bool]]]:
         """Per window row: the clip it belongs to, the whole-clip frame of each of its `row_frames` frames (clamped into the batch) and

@@ -64,13 +64,15 @@ def ode_adaptive(ode_opt: Dict[str, Any], windowed: bool = False):
     so the two agree to O(tolerance), no closer.
     rtol, atol: required, positive.  options: first_step (default: scipy's select_initial_step, one more field evaluation), safety
     (0.9), ifactor (10), dfactor (0.2), max_num_steps (trial steps per row).  Everything else - other keys, missing tolerances, a
-    windowed solve - is a ValueError."""
+    windowed solve (`windowed`: window_seconds= without separate()'s step_control="clip", which steps per clip instead of per row:
+    DESIGN.md section 10.11) - is a ValueError."""
     method = ode_opt.get("method", "midpoint")
     if method not in ODE_ADAPTIVE_METHODS:
         raise ValueError(f"ode method {method!r} is not an adaptive method of the HIP path ({' | '.join(ODE_ADAPTIVE_METHODS)})")
     if windowed:
         raise ValueError(f"window_seconds= with the adaptive method {method!r}: the rows of one clip share their blended frames and "
-                         "must share their times, which per-row step control does not give them; use a fixed-grid method")
+                         "must share their times, which per-row step control does not give them; pass step_control=\"clip\" to "
+                         "separate() (step control per clip, DESIGN.md section 10.11) or use a fixed-grid method")
     unknown = sorted(set(ode_opt) - {"method", "rtol", "atol", "options"})
     if unknown:
         raise ValueError(f"ode_opt: unsupported {unknown} for {method!r} (method | rtol | atol | options)")
@@ -92,6 +94,21 @@ def ode_adaptive(ode_opt: Dict[str, Any], windowed: bool = False):
     if not (safety > 0 and ifactor >= 1 and 0 < dfactor < 1 and steps >= 1):
         raise ValueError("ode_opt['options']: safety > 0, ifactor >= 1, 0 < dfactor < 1 and max_num_steps >= 1 are required")
     return ODE_ADAPTIVE_METHODS[method], hip.OdeAdaptive(rtol, atol, first, safety, ifactor, dfactor, min(steps, 2 ** 31 - 1))
+
+
+STEP_CONTROLS = (None, "row", "clip")
+
+
+def check_step_control(step_control: Optional[str], ode_opt: Dict[str, Any]) -> bool:
+    """separate()'s `step_control`: None | "row" (the unit of an adaptive method's step control is the engine row: section 10.9) |
+    "clip" (the window rows of one clip and candidate share one time, step, error norm and decision: section 10.11).  True for
+    "clip"; ValueError for another value, and for "clip" with a fixed-grid method, which has no step control."""
+    if step_control not in STEP_CONTROLS:
+        raise ValueError(f"step_control={step_control!r}: None | 'row' | 'clip'")
+    if step_control == "clip" and not is_adaptive(ode_opt):
+        raise ValueError(f"step_control='clip' with the fixed-grid method {ode_opt.get('method', 'midpoint')!r}: only the adaptive "
+                         f"methods ({' | '.join(ODE_ADAPTIVE_METHODS)}) control their step")
+    return step_control == "clip"
 
 
 def _field_stand_in(t, y):
@@ -721,22 +738,27 @@ class SAMAudio(Context):
         return [dict(accepted=s.accepted, rejected=s.rejected, t=s.t, last_h=s.last_h, status=hip.ODE_ROW_STATUS[s.status],
                      evaluations=s.evaluations) for s in stats]
 
-    def _set_ode_stats(self, groups: List[List[dict]], state: torch.Tensor) -> None:
+    def _set_ode_stats(self, groups: List[List[dict]], state: torch.Tensor, names: Optional[List[str]] = None,
+                       windows: Optional[List[int]] = None) -> None:
         """`last_ode_stats` of an adaptive solve: per row accepted / rejected / t / last_h / status, and `evaluations`, the field
         launches of the solve (summed over the row groups of a streams > 1 solve).  A row that failed raises RuntimeError; nothing of
         the solve is rolled back, and the state as the solve left it is kept in `last_latent` before raising: finished rows are
-        complete there, a failed row holds its state at the `t` of its statistics."""
+        complete there, a failed row holds its state at the `t` of its statistics.  `names`: what an entry is called in that
+        error ("row i" by default; the clip and candidate of a solve with step control per clip), `windows`: the window counts per
+        clip of such a solve, added to the statistics."""
         self.last_latent = state
         rows = [dict(r) for g in groups for r in g]
         evaluations = sum(g[0]["evaluations"] for g in groups if g)
         for r in rows:
             del r["evaluations"]
         self.last_ode_stats = {"rows": rows, "evaluations": evaluations}
+        if windows is not None:
+            self.last_ode_stats["windows"] = list(windows)
         for i, r in enumerate(rows):
             if r["status"] != "finished":
                 why = ("its step fell below 10 ulp(t)" if r["status"] == "step_underflow"
                        else "it used up options['max_num_steps'] trial steps")
-                raise RuntimeError(f"adaptive ODE solve: row {i} stopped at t = {r['t']:.6g} after {r['accepted']} accepted and "
+                raise RuntimeError(f"adaptive ODE solve: {names[i] if names else f'row {i}'} stopped at t = {r['t']:.6g} after {r['accepted']} accepted and "
                                    f"{r['rejected']} rejected steps ({why}); try a looser rtol / atol (the state every row "
                                    "reached is in model.last_latent, the statistics in model.last_ode_stats)")
 
@@ -850,7 +872,7 @@ class SAMAudio(Context):
                  ode_opt: Dict[str, Any] = DFLT_ODE_OPT, reranking_candidates: int = 1,
                  predict_spans: bool = False, output_sampling_rate: Optional[int] = None,
                  window_seconds: Optional[float] = None, window_overlap_seconds: Optional[float] = None,
-                 seed: Optional[int] = None) -> SeparationResult:
+                 seed: Optional[int] = None, step_control: Optional[str] = None) -> SeparationResult:
         """Reference model.py:247-338.  `reranking_candidates > 1` draws that many ODE solutions per clip and lets
         `visual_ranker` / `text_ranker` pick one (model.py:306-330); `predict_spans` runs `span_predictor` first
         (model.py:259-268; mind quirk Q13 below).  `output_sampling_rate`: when set and different from the codec's rate, the chosen
@@ -859,7 +881,15 @@ class SAMAudio(Context):
         `ode_opt`: torchdiffeq's shape.  The fixed-grid methods (`ode_grid`) or {"method": "dopri5" | "bosh3", "rtol": r, "atol": a,
         "options": {...}} (`ode_adaptive`): embedded pairs with per-row step control, pinned to scipy's RK45 / RK23 and unpinned vs
         torchdiffeq.  An adaptive solve leaves `last_ode_stats` and raises RuntimeError when a row fails (the
-        state every row reached is then in `last_latent`); it does not combine with `window_seconds`.
+        state every row reached is then in `last_latent`); it combines with `window_seconds` only under `step_control="clip"`.
+        `step_control` (None | "row" | "clip"; None = "row"; this build's own definition): the unit of an
+        adaptive method's step control.  "row": every engine row on its own, which window rows cannot be - ValueError together with
+        `window_seconds`.  "clip": the window rows of one (clip, candidate) carry ONE time, step, error norm - over the clip's valid
+        frames, each counted once, whichever windows hold it - and accept / reject decision, so a clip's result does not depend on the
+        clips beside it.  `last_ode_stats["rows"]` then has one entry per (clip, candidate) in the stitched latent's row order, and
+        `last_ode_stats["windows"]` the window counts per clip; a failed one raises the RuntimeError above, naming clip and candidate,
+        with `last_window_latent` / `last_window_plan` set.  Without windows, or when every clip fits one window, a clip is a row and
+        "clip" is the per-row path: no table, no other launch.  ValueError with a fixed-grid method.
         `window_seconds` / `window_overlap_seconds` (both or neither; this build's own definition): clips longer
         than the window are solved as overlapping windows of that length - rows of ONE batch whose overlapping frames are cross-faded
         after every evaluation of the vector field, so they hold the same bits through the whole solve; the latent is stitched by index
@@ -878,8 +908,9 @@ class SAMAudio(Context):
                 raise ValueError("seed and noise are mutually exclusive: a seed stands for the noise it generates")
             from .noise import check_seed
             seed = check_seed(seed)
-        if is_adaptive(ode_opt):   # before anything runs: the tolerances, the options, and no windows
-            ode_adaptive(ode_opt, windowed=window_seconds is not None)
+        by_clip = check_step_control(step_control, ode_opt)   # before anything runs
+        if is_adaptive(ode_opt):   # before anything runs: the tolerances, the options, and no windows unless stepped per clip
+            ode_adaptive(ode_opt, windowed=window_seconds is not None and not by_clip)
         if not (self._has_dit and self._has_codec):
             raise RuntimeError("load_state_dict() first")
         if (window_seconds is None) != (window_overlap_seconds is None):
@@ -891,7 +922,7 @@ class SAMAudio(Context):
             window = (longform.seconds_to_frames(window_seconds, c.sample_rate, c.hop_length),
                       longform.seconds_to_frames(window_overlap_seconds, c.sample_rate, c.hop_length))
             longform.check_window(*window, self.cfg.transformer.max_positions)
-        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans, window, seed)
+        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans, window, seed)   # (windows + adaptive: per clip)
         if output_sampling_rate is None or int(output_sampling_rate) == self.sample_rate:
             return res
         from . import audio
@@ -1018,18 +1049,36 @@ class SAMAudio(Context):
         self._prepare(*cond_rows, anchors_validated=validated, candidates=cand, latent=True)
         linked = any(s >= 0 for s in plan.next_row)   # clips that all fit one window: plain rows, no table, no extra launch
         table = torch.tensor(plan.next_row, dtype=torch.int32, device=dev) if linked else None
+        # an adaptive method over linked rows (separate() has checked step_control="clip"): one step control per (clip, candidate),
+        # whose norms count the frames a row owns.  Unlinked rows are clips: the per-row solve as it is
+        adaptive = is_adaptive(ode_opt)
+        groups = plan.groups()
+        gtable = torch.tensor(groups, dtype=torch.int32, device=dev) if linked and adaptive else None
+        owner = torch.tensor(plan.owner_mask(), dtype=torch.uint8, device=dev) if linked and adaptive else None
+        row_stats = None
         try:
             if linked:
                 hip.check(self._lib.samaudio_set_windows(self._ctx, hip.ptr(table), plan.rows, plan.overlap))
-            rows = self.solve(wnoise, ode_opt)
+            if gtable is not None:
+                hip.check(self._lib.samaudio_set_window_groups(self._ctx, hip.ptr(gtable), len(groups), hip.ptr(owner)))
+            if adaptive:
+                method, params = ode_adaptive(ode_opt)
+                rows = wnoise.to(dev, torch.float32).clone().contiguous()
+                row_stats = self._solve_adaptive(None, rows, method, params)
+            else:
+                rows = self.solve(wnoise, ode_opt)
         finally:
-            if linked:   # the table is this call's: the context does not keep the pointer
+            if linked:   # the tables are this call's: the context does not keep the pointers (clearing the windows clears the groups)
+                hip.check(self._lib.samaudio_set_window_groups(self._ctx, None, 0, None))
                 hip.check(self._lib.samaudio_set_windows(self._ctx, None, 0, 0))
         srow, soff, have = plan.stitch_index()
         latent = rows[torch.tensor(srow, device=dev), torch.tensor(soff, device=dev)]   # frame t from window min(t // S, n - 1)
         if not all(map(all, have)):   # padding frames behind the last window's row: zero
             latent.masked_fill_(~torch.tensor(have, device=dev)[:, :, None], 0)
         self.last_window_latent, self.last_window_plan = rows, plan
+        if row_stats is not None:   # one entry per (clip, candidate): every row of a group holds the group's counters
+            names = [f"clip {b}, candidate {c}" for b in range(B) for c in range(cand)]
+            self._set_ode_stats([[row_stats[first] for first, _, _ in groups]], latent, names=names, windows=plan.counts)
         return latent
 
     def _rerank(self, batch: Batch, target_wavs: List[torch.Tensor], sizes: List[int], cand: int) -> torch.Tensor:
