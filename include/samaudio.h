@@ -309,6 +309,24 @@ int samaudio_codec_decode(samaudio_ctx* ctx, const float* latent, int items, int
  * f32 -> wav [2 * rows, frames * hop]: waveform 2b = channels [0, codec_dim) of row block b (target), 2b + 1 the rest (residual). */
 int samaudio_codec_decode_pairs(samaudio_ctx* ctx, const float* state, int rows, int frames, float* wav, samaudio_stream stream);
 
+/* The same three in time tiles (no reference counterpart).  The codec is a stack of convolutions: a latent
+ * frame depends on samaudio_codec_halo_frames(ctx, decode) frames of input either side of it and no more (the reach, derived from the
+ * layers the engine launches, rounded up to whole frames).  Tile k of `tile_frames` = L frames is one pass over frames
+ * [max(0, kL - h), min(T, (k + 1) L + h)) of every item that writes rows [kL, min(T, (k + 1) L)) only, straight into the caller's
+ * tensor; T = frames (samples / hop) is the padded length, as in the whole pass.  Results equal the untiled call's bit for bit.
+ * The workspace a call needs is samaudio_workspace_bytes(ctx, 0, 0, 0, items_per_pass, samaudio_codec_tile_samples(ctx, frames,
+ * tile_frames, decode)): it does not grow with the clip (tile_samples: the longest segment in samples; < 0 when frames or
+ * tile_frames < 1).  tile_frames >= frames is the untiled call, launch for launch.  tile_frames < 1: SAMAUDIO_ERR_ARG; a workspace
+ * too small for one segment of one item (of one pair): SAMAUDIO_ERR_WORKSPACE. */
+int samaudio_codec_halo_frames(samaudio_ctx* ctx, int decode);
+int64_t samaudio_codec_tile_samples(samaudio_ctx* ctx, int frames, int tile_frames, int decode);
+int samaudio_codec_encode_tiled(samaudio_ctx* ctx, const float* wav, int items, int64_t samples, int tile_frames, float* latent,
+                                samaudio_stream stream);
+int samaudio_codec_decode_tiled(samaudio_ctx* ctx, const float* latent, int items, int frames, int tile_frames, float* wav,
+                                samaudio_stream stream);
+int samaudio_codec_decode_pairs_tiled(samaudio_ctx* ctx, const float* state, int rows, int frames, int tile_frames, float* wav,
+                                      samaudio_stream stream);
+
 /* ---- reranking and span prediction ------------------------------------------ */
 
 /* One PE-AV transformer (perception_models core.audio_visual_encoder.transformer.Transformer, un-vendored; the

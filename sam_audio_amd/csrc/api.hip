@@ -144,6 +144,29 @@ int samaudio_codec_decode_pairs(samaudio_ctx* ctx, const float* state, int rows,
   return ret(ctx->engine->codec_decode(state, 2 * rows, frames, wav, (hipStream_t)stream, true));
 }
 
+int samaudio_codec_halo_frames(samaudio_ctx* ctx, int decode) { return ctx ? ctx->engine->codec_halo_frames(decode != 0) : -1; }
+
+int64_t samaudio_codec_tile_samples(samaudio_ctx* ctx, int frames, int tile_frames, int decode) {
+  return ctx ? ctx->engine->codec_tile_samples(frames, tile_frames, decode != 0) : -1;
+}
+
+int samaudio_codec_encode_tiled(samaudio_ctx* ctx, const float* wav, int items, int64_t samples, int tile_frames, float* latent,
+                                samaudio_stream stream) {
+  return SA_ENTRY(ctx, "null context", ctx->engine->codec_encode_tiled(wav, items, samples, tile_frames, latent, (hipStream_t)stream));
+}
+
+int samaudio_codec_decode_tiled(samaudio_ctx* ctx, const float* latent, int items, int frames, int tile_frames, float* wav,
+                                samaudio_stream stream) {
+  return SA_ENTRY(ctx, "null context", ctx->engine->codec_decode_tiled(latent, items, frames, tile_frames, wav, (hipStream_t)stream));
+}
+
+int samaudio_codec_decode_pairs_tiled(samaudio_ctx* ctx, const float* state, int rows, int frames, int tile_frames, float* wav,
+                                      samaudio_stream stream) {
+  if (!ctx) return bad("null context");
+  if (rows <= 0) return bad("codec_decode_pairs_tiled: rows");
+  return ret(ctx->engine->codec_decode_tiled(state, 2 * rows, frames, tile_frames, wav, (hipStream_t)stream, true));
+}
+
 void samaudio_debug_force_gemm_variant(int variant) { sa::gemm_force_variant(variant); }
 void samaudio_debug_set_flag(int flag, int value) { sa::set_debug_flag(flag, value); }
 int samaudio_debug_poison_lds(samaudio_stream stream) {

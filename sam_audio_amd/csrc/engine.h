@@ -47,6 +47,13 @@ class Engine {
   // `pairs`: latent is the ODE state [items / 2, frames, 2 * codec_dim] - item 2b = the first codec_dim channels of row b (target),
   // 2b + 1 the second (residual): reference model.py:291-295 without the transposed copy
   Status codec_decode(const float* latent, int items, int frames, float* wav, hipStream_t st, bool pairs = false);
+  // The same in time tiles of `tile_frames` latent frames: tile k is one pass over its frames plus
+  // codec_halo_frames on each side where the clip has them, of which only the tile's own rows are written.  The scratch is sized by
+  // the longest segment (codec_tile_samples), not by the clip; a tile that covers the clip is the untiled call.
+  Status codec_encode_tiled(const float* wav, int items, int64_t samples, int tile_frames, float* latent, hipStream_t st);
+  Status codec_decode_tiled(const float* latent, int items, int frames, int tile_frames, float* wav, hipStream_t st, bool pairs = false);
+  int codec_halo_frames(bool decode) const;   // the direction's reach in whole latent frames, from the layers it launches
+  int64_t codec_tile_samples(int frames, int tile_frames, bool decode) const;   // the longest segment in samples; < 0: bad argument
 
   // Per-kernel timing with HIP events on the launch stream (bench.py's roofline leg): between begin and end
   // every GEMM launch is bracketed by an event pair; end synchronises and folds them per tile variant.
@@ -79,6 +86,12 @@ class Engine {
   size_t codec_bytes(int items, int64_t samples) const;
   int codec_chunk(int items, int64_t samples, bool pairs) const;   // items per pass in this workspace (whole pairs); 0: not even one
   Status codec_carve(bool decode, int n, int64_t samples, CodecBufs& cb);   // one pass's buffers out of the workspace
+  // One pass: frames [t0, t1) of clips of T frames run through every layer, rows [keep0, keep1) of the result are written (the whole
+  // pass: {0, T, 0, T, T}).  encode_pass / decode_pass hold the launches of both the untiled and the tiled calls
+  struct CodecSeg { long t0, t1, keep0, keep1, T; };
+  static CodecSeg codec_tile(long T, long L, long h, long k);
+  Status encode_pass(const float* wav, int i0, int n, const CodecSeg& g, float* latent, hipStream_t st);
+  Status decode_pass(const float* latent, int i0, int n, const CodecSeg& g, float* wav, hipStream_t st, bool pairs);
   // The kind of a GEMM launch.  F32: exact fp32 inside a 16-bit context (SAMAUDIO_OPT_F32_CLASSES - the caller hands fp32 A / W / out_act
   // pointers).  X3: a SAMAUDIO_OPT_X3_CLASSES launch inside an fp32 context (16-bit A / W over K' = 3K, fp32 outputs; linear builds it),
   // both operands split over the whole K (A rows [lo | hi | hi], W rows [W_hi | W_lo | W_hi]: the launch may share operand tiles,

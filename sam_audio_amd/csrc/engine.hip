@@ -1751,6 +1751,75 @@ Status Engine::res_units(const StageW& sw, SBuf& sb, int n, const float* next_al
   return Status{};
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Time tiles.  The codec is a stack of convolutions, so latent frame f of either direction depends on a
+// bounded range of input frames: a pass over the segment [a - h, b + h) of a clip computes frames [a, b) as the whole pass does.
+// ---------------------------------------------------------------------------------------------------
+static long floor_div(long a, long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+static long ceil_div(long a, long b) { return -floor_div(-a, b); }
+
+// The reach of one direction in whole latent frames, walked backwards over the layers codec_encode / codec_decode launch.  While
+// walking, rows [f * per - lo, f * per + hi] of the current layer's input - `per` rows to the frame - feed the outputs of frame f.
+int Engine::codec_halo_frames(bool decode) const {
+  long lo = 0, hi = 0, per = 1, need = 0;
+  auto see = [&] { need = std::max(need, std::max(ceil_div(lo, per), ceil_div(hi - (per - 1), per))); };
+  auto same = [&](int taps, int dil) { lo += (long)(taps / 2) * dil; hi += (long)(taps / 2) * dil; };
+  auto units = [&] {   // the three residual units of a stage, last first: k1 behind the dilated k7
+    for (int dil : {9, 3, 1}) { same(1, 1); same(7, dil); }
+  };
+  if (!decode) {
+    same(1, 1);   // quantizer.in_proj
+    same(3, 1);
+    see();
+    for (int i = 3; i >= 0; --i) {
+      // strided convolution k = 2s, pad (s + 1) / 2: output row q reads input rows [q s - pad, q s - pad + 2s)
+      const long s = cfg_.enc_rates[i], pad = (s + 1) / 2;
+      lo = lo * s + pad; hi = hi * s + 2 * s - 1 - pad; per *= s;
+      units();
+      see();
+    }
+    same(7, 1);
+    see();
+  } else {
+    per = codec_hop(cfg_);
+    hi = per - 1;   // the frame's own samples
+    same(7, 1);     // k7 + tanh
+    see();
+    for (int i = 3; i >= 0; --i) {
+      units();
+      see();
+      // transposed convolution as codec_decode indexes it: output row o = q s + r - pad (0 <= r < s) reads input rows q - 1 and q
+      const long s = cfg_.dec_rates[i], pad = (s + 1) / 2;
+      lo = 1 - floor_div(pad - lo, s); hi = floor_div(hi + pad, s); per /= s;
+      see();
+    }
+    same(7, 1);
+    same(1, 1);   // quantizer.out_proj
+    see();
+  }
+  return (int)need;
+}
+
+// tile k of a clip of T frames in tiles of L: it keeps [kL, min(T, (k + 1) L)) of a pass over [max(0, kL - h), min(T, (k + 1) L + h))
+Engine::CodecSeg Engine::codec_tile(long T, long L, long h, long k) {
+  CodecSeg g;
+  g.keep0 = k * L; g.keep1 = std::min(T, (k + 1) * L);
+  g.t0 = std::max(0L, g.keep0 - h); g.t1 = std::min(T, g.keep1 + h);
+  g.T = T;
+  return g;
+}
+
+int64_t Engine::codec_tile_samples(int frames, int tile_frames, bool decode) const {
+  if (frames < 1 || tile_frames < 1) return -1;
+  const long T = frames, L = tile_frames, h = codec_halo_frames(decode);
+  long longest = 0;
+  for (long k = 0; k * L < T; ++k) {
+    const CodecSeg g = codec_tile(T, L, h, k);
+    longest = std::max(longest, g.t1 - g.t0);
+  }
+  return longest * codec_hop(cfg_);
+}
+
 Status Engine::codec_encode(const float* wav, int items, int64_t S, float* latent, hipStream_t st) {
   if (!enc_ready_) return fail(SAMAUDIO_ERR_STATE, "codec_encode: codec weights not finalized");
   const long hop = codec_hop(cfg_);
@@ -1759,15 +1828,42 @@ Status Engine::codec_encode(const float* wav, int items, int64_t S, float* laten
   if (chunk < 1) return fail(SAMAUDIO_ERR_WORKSPACE, "codec_encode: workspace too small");
   prepared_ = false;  // the codec scratch aliases the DiT scratch
   phase_ = Phase::Codec;
+  const long T = S / hop;
+  const CodecSeg whole{0, T, 0, T, T};
+  for (int i0 = 0; i0 < items; i0 += chunk)
+    SA_TRY(encode_pass(wav, i0, items - i0 < chunk ? items - i0 : chunk, whole, latent, st));
+  return Status{};
+}
+
+Status Engine::codec_encode_tiled(const float* wav, int items, int64_t S, int tile_frames, float* latent, hipStream_t st) {
+  if (tile_frames < 1) return fail(SAMAUDIO_ERR_ARG, "codec_encode_tiled: tile_frames < 1");
+  const long hop = codec_hop(cfg_);
+  if (S <= 0 || S % hop || tile_frames >= S / hop) return codec_encode(wav, items, S, latent, st);   // one tile: the whole pass
+  if (!enc_ready_) return fail(SAMAUDIO_ERR_STATE, "codec_encode: codec weights not finalized");
+  if (!wav || !latent || items <= 0) return fail(SAMAUDIO_ERR_ARG, "codec_encode_tiled: bad argument");
+  const long T = S / hop, L = tile_frames, h = codec_halo_frames(false);
+  const int chunk = codec_chunk(items, codec_tile_samples((int)T, tile_frames, false), false);
+  if (chunk < 1) return fail(SAMAUDIO_ERR_WORKSPACE, "codec_encode_tiled: workspace too small for one segment");
+  prepared_ = false;
+  phase_ = Phase::Codec;
+  for (int i0 = 0; i0 < items; i0 += chunk)
+    for (long k = 0; k * L < T; ++k)
+      SA_TRY(encode_pass(wav, i0, items - i0 < chunk ? items - i0 : chunk, codec_tile(T, L, h, k), latent, st));
+  return Status{};
+}
+
+// One pass over frames [g.t0, g.t1) of the n waveforms from item i0 on; `wav` / `latent`: the whole tensors, clips of g.T frames.  Only the last
+// launch knows about the kept rows [g.keep0, g.keep1): it computes those and writes them to their place in `latent`.
+Status Engine::encode_pass(const float* wav, int i0, int n, const CodecSeg& g, float* latent, hipStream_t st) {
+  const long hop = codec_hop(cfg_), S = (g.t1 - g.t0) * hop;
   const int CL = cfg_.codec_latent, CD = cfg_.codec_dim;
-  for (int i0 = 0; i0 < items; i0 += chunk) {
-    const int n = items - i0 < chunk ? items - i0 : chunk;
+  {
     CodecBufs cb;
     SA_TRY(codec_carve(false, n, S, cb));
     SBuf* const sb = cb.sb;
     // waveform -> [n][HALO + S + HALO][8] (channel 0), zero halos
     SA_HIP(hipMemsetAsync(cb.in8, 0, (size_t)n * (S + 2 * HALO) * 8 * esz_, st));
-    SA_HIP(launch_to_act(wav + (long)i0 * S, S, 1, 0, cb.in8, 0, bf16_, n, S, 1, 8, HALO, st));
+    SA_HIP(launch_to_act(wav + ((long)i0 * g.T + g.t0) * hop, g.T * hop, 1, 0, cb.in8, 0, bf16_, n, S, 1, 8, HALO, st));
     for (int i = 0; i < 5; ++i) {
       SA_HIP(launch_zero_halo(sb[i].act, bf16_, n, sb[i].T, sb[i].C, HALO, st));
       SA_HIP(launch_zero_halo(sb[i].tmp, bf16_, n, sb[i].T, sb[i].C, HALO, st));
@@ -1800,7 +1896,8 @@ Status Engine::codec_encode(const float* wav, int items, int64_t S, float* laten
       SA_TRY(codec_gemm(p, st));
       p = conv_same(cb.eout, T, CL, 1, 1, enc_.proj_w, CL, CD, n);  // quantizer.in_proj, mean half only
       p.bias = enc_.proj_b;
-      p.out_f32 = latent + (long)i0 * T * CD; p.f32_bstride = T * CD; p.f32_ld = CD; p.f32_off = 0;
+      p.a_off += (g.keep0 - g.t0) * CL; p.M = (int)(g.keep1 - g.keep0);   // (the whole pass: every row)
+      p.out_f32 = latent + ((long)i0 * g.T + g.keep0) * CD; p.f32_bstride = g.T * CD; p.f32_ld = CD; p.f32_off = 0;
       SA_TRY(codec_gemm(p, st));
     }
   }
@@ -1817,9 +1914,38 @@ Status Engine::codec_decode(const float* latent, int items, int T0, float* wav, 
     return fail(SAMAUDIO_ERR_WORKSPACE, pairs ? "codec_decode: workspace too small for one (target, residual) pair" : "codec_decode: workspace too small");
   prepared_ = false;
   phase_ = Phase::Codec;
+  const CodecSeg whole{0, T0, 0, T0, T0};
+  for (int i0 = 0; i0 < items; i0 += chunk)
+    SA_TRY(decode_pass(latent, i0, items - i0 < chunk ? items - i0 : chunk, whole, wav, st, pairs));
+  return Status{};
+}
+
+Status Engine::codec_decode_tiled(const float* latent, int items, int T0, int tile_frames, float* wav, hipStream_t st, bool pairs) {
+  if (tile_frames < 1) return fail(SAMAUDIO_ERR_ARG, "codec_decode_tiled: tile_frames < 1");
+  if (T0 <= 0 || tile_frames >= T0) return codec_decode(latent, items, T0, wav, st, pairs);   // one tile: the whole pass
+  if (!codec_ready_) return fail(SAMAUDIO_ERR_STATE, "codec_decode: codec weights not finalized");
+  if (!latent || !wav || items <= 0) return fail(SAMAUDIO_ERR_ARG, "codec_decode_tiled: bad argument");
+  if (pairs && items % 2) return fail(SAMAUDIO_ERR_ARG, "codec_decode: the state layout holds (target, residual) pairs");
+  const long T = T0, L = tile_frames, h = codec_halo_frames(true);
+  const int chunk = codec_chunk(items, codec_tile_samples(T0, tile_frames, true), pairs);
+  if (chunk < 1)
+    return fail(SAMAUDIO_ERR_WORKSPACE, pairs ? "codec_decode_tiled: workspace too small for one segment of one (target, residual) pair"
+                                              : "codec_decode_tiled: workspace too small for one segment");
+  prepared_ = false;
+  phase_ = Phase::Codec;
+  for (int i0 = 0; i0 < items; i0 += chunk)
+    for (long k = 0; k * L < T; ++k)
+      SA_TRY(decode_pass(latent, i0, items - i0 < chunk ? items - i0 : chunk, codec_tile(T, L, h, k), wav, st, pairs));
+  return Status{};
+}
+
+// One pass over frames [g.t0, g.t1) of the n waveforms from item i0 on; `latent` / `wav`: the whole tensors, clips of g.T frames.
+// Only the last launch knows about the kept rows [g.keep0, g.keep1): it computes their samples and writes them to their place in `wav`.
+Status Engine::decode_pass(const float* latent, int i0, int n, const CodecSeg& g, float* wav, hipStream_t st, bool pairs) {
+  const long hop = codec_hop(cfg_), T0 = g.t1 - g.t0;
+  const int64_t S = (int64_t)T0 * hop;
   const int CL = cfg_.codec_latent, CD = cfg_.codec_dim;
-  for (int i0 = 0; i0 < items; i0 += chunk) {
-    const int n = items - i0 < chunk ? items - i0 : chunk;
+  {
     CodecBufs cb;
     SA_TRY(codec_carve(true, n, S, cb));
     SBuf* const sb = cb.sb;
@@ -1833,10 +1959,10 @@ Status Engine::codec_decode(const float* latent, int items, int T0, float* wav, 
     if (pairs) {   // items (2b, 2b + 1) = channels [0, CD) / [CD, 2 CD) of state row block b: two strided gathers, no transposed copy
       const long item = (long)(T0 + 2 * HALO) * CD;
       for (int sgn = 0; sgn < 2; ++sgn)
-        SA_HIP(launch_to_act(latent + (long)(i0 / 2) * T0 * 2 * CD, (long)T0 * 2 * CD, 2L * CD, sgn * CD, (char*)lat + (size_t)sgn * item * esz_,
+        SA_HIP(launch_to_act(latent + ((long)(i0 / 2) * g.T + g.t0) * 2 * CD, g.T * 2 * CD, 2L * CD, sgn * CD, (char*)lat + (size_t)sgn * item * esz_,
                              2 * item, bf16_, n / 2, T0, CD, CD, HALO, st));
     } else
-    SA_HIP(launch_to_act(latent + (long)i0 * T0 * CD, (long)T0 * CD, CD, 0, lat, 0, bf16_, n, T0, CD, CD, HALO, st));
+    SA_HIP(launch_to_act(latent + ((long)i0 * g.T + g.t0) * CD, g.T * CD, CD, 0, lat, 0, bf16_, n, T0, CD, CD, HALO, st));
     {
       GemmParams p = conv_same(lat, T0, CD, 1, 1, dec_.proj_w, CD, CL, n);  // quantizer.out_proj
       p.bias = dec_.proj_b;
@@ -1870,8 +1996,10 @@ Status Engine::codec_decode(const float* latent, int items, int T0, float* wav, 
       GemmParams p = conv_same(sb[4].act, T, C, 7, 1, dec_.out_w, dec_.out_kpad, 1, n);
       p.bias = dec_.out_b;
       p.act = ACT_TANH; p.f32_act = 1;
-      p.out_f32 = wav + (long)i0 * T; p.f32_bstride = T; p.f32_ld = 1; p.f32_off = 0;
-      SA_TRY(codec_gemm(p, st, 2.0 * T * 7 * C * n));
+      const long M = (g.keep1 - g.keep0) * hop;   // (the whole pass: every row)
+      p.a_off += (g.keep0 - g.t0) * hop * C; p.M = (int)M;
+      p.out_f32 = wav + ((long)i0 * g.T + g.keep0) * hop; p.f32_bstride = g.T * hop; p.f32_ld = 1; p.f32_off = 0;
+      SA_TRY(codec_gemm(p, st, 2.0 * M * 7 * C * n));
     }
   }
   return Status{};

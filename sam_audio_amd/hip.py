@@ -340,6 +340,12 @@ _PROTOS = {
     "samaudio_op_window_blend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "samaudio_codec_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "samaudio_codec_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # the codec in time tiles
+    "samaudio_codec_halo_frames": (C.c_int, [C.c_void_p, C.c_int]),
+    "samaudio_codec_tile_samples": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "samaudio_codec_encode_tiled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "samaudio_codec_decode_tiled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "samaudio_codec_decode_pairs_tiled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "samaudio_profile_begin": (C.c_int, [C.c_void_p]),
     "samaudio_sentinel_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_void_p]),
     "samaudio_debug_force_gemm_variant": (None, [C.c_int]),

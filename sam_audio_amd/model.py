@@ -216,8 +216,13 @@ class SAMAudio(Context):
     def __init__(self, cfg: SAMAudioConfig, precision: str = "fp16x3", device: Optional[str] = None,
                  text_encoder: Optional[Callable] = None, streams: int = 1, f32_classes="auto",
                  weight_layout: str = "auto", prefetch_rows: Optional[int] = None, x3_classes="auto",
-                 codec_decode: str = "auto", tower_precision: Optional[str] = None, frame_transform: Optional[str] = None):
-        """`frame_transform`: `PerceptionEncoder(frame_transform=...)` of the vision encoder that load_state_dict builds - None (default)
+                 codec_decode: str = "auto", tower_precision: Optional[str] = None, frame_transform: Optional[str] = None,
+                 codec_tile_seconds: Optional[float] = None):
+        """`codec_tile_seconds` (None = off, the default; this build's own definition): separate() runs the
+        DAC-VAE - the mixture's encode and the decode of (target, residual) pairs - in time tiles of this length, each with the
+        codec's own reach of context either side, so the codec scratch is sized by the tile and not by the clip.  The results are
+        bitwise those of the untiled codec.  separate(codec_tile_seconds=...) overrides it for one call.
+        `frame_transform`: `PerceptionEncoder(frame_transform=...)` of the vision encoder that load_state_dict builds - None (default)
         = its default "torch"; "hip" resizes, rounds and normalises uint8 videos inside the tower's first kernel.
         `tower_precision`: the precision of the PE-Core vision tower that load_state_dict builds when the checkpoint carries one.
         None (default) = hip.tower_precision(precision): plain 16-bit operands beside an x3 DiT.  "fp16x3" / "bf16x3" opt the tower
@@ -249,6 +254,10 @@ class SAMAudio(Context):
             if frame_transform not in FRAME_TRANSFORMS:
                 raise ValueError(f"frame_transform must be one of {FRAME_TRANSFORMS}, not {frame_transform!r}")
         self.frame_transform = frame_transform
+        self._codec_tile_frames(codec_tile_seconds, cfg)   # (ValueError below one frame)
+        self.codec_tile_seconds = codec_tile_seconds
+        # per direction ("encode" / "decode") of the last tiled codec call: tile_frames, halo_frames, tiles, passes
+        self.last_codec_tiles: Dict[str, Dict[str, int]] = {}
         # precision "fp16x3" (and "bf16x3"): fp32 storage and fp32 small classes, the six big GEMM classes of the layers on
         # compensated 16-bit operands (samaudio.h SAMAUDIO_OPT_X3_CLASSES; `x3_classes`: names or a mask, "auto" = all six)
         self.x3_classes = 0 if not hip.is_x3(precision) else (
@@ -351,7 +360,7 @@ class SAMAudio(Context):
     @classmethod
     def from_pretrained(cls, model_id: str, map_location: str = "cpu", strict: bool = True,
                         precision: str = "fp16x3", device: Optional[str] = None, tower_precision: Optional[str] = None,
-                        frame_transform: Optional[str] = None, **model_kwargs):
+                        frame_transform: Optional[str] = None, codec_tile_seconds: Optional[float] = None, **model_kwargs):
         """Local directory with the reference's `config.json` + `checkpoint.pt`
         (reference base.py:17-62; hub download needs network access this build does not have).
 
@@ -359,7 +368,7 @@ class SAMAudio(Context):
         (default) = hip.tower_precision(precision): plain 16-bit operands beside an x3 DiT.  "fp16x3" / "bf16x3" opt the Judge and
         the vision tower into their compensated modes (fp32 storage, the big contractions on hi/lo-split 16-bit operands; DESIGN.md
         sections 10.1 and 10.2).
-        `frame_transform`: see SAMAudio(...)."""
+        `frame_transform`, `codec_tile_seconds`: see SAMAudio(...)."""
         if not os.path.isdir(model_id):
             raise FileNotFoundError(f"{model_id}: only local checkpoint directories are supported offline")
         with open(os.path.join(model_id, "config.json")) as fin:
@@ -368,7 +377,7 @@ class SAMAudio(Context):
             if key in config:
                 config[key] = value
         model = cls(SAMAudioConfig(**config), precision=precision, device=device, tower_precision=tower_precision,
-                    frame_transform=frame_transform)
+                    frame_transform=frame_transform, codec_tile_seconds=codec_tile_seconds)
         sd = torch.load(os.path.join(model_id, "checkpoint.pt"), weights_only=True, map_location=map_location)
         model.load_state_dict(sd, strict=strict)
         # the reference builds its T5 encoder and rankers in __init__ from hub ids (model.py:82,94-95); offline they
@@ -586,9 +595,44 @@ class SAMAudio(Context):
         rem = wavs.size(-1) % hop
         return wavs if rem == 0 else torch.nn.functional.pad(wavs, (0, hop - rem), mode="reflect")
 
-    def encode_audio(self, audios: torch.Tensor) -> torch.Tensor:
+    @staticmethod
+    def _codec_tile_frames(seconds: Optional[float], cfg: SAMAudioConfig) -> Optional[int]:
+        """`codec_tile_seconds` in latent frames, as longform.py turns seconds into frames; None stays None (no tiles)"""
+        if seconds is None:
+            return None
+        from . import longform
+        frames = longform.seconds_to_frames(seconds, cfg.audio_codec.sample_rate, cfg.audio_codec.hop_length)
+        if frames < 1:
+            raise ValueError(f"codec_tile_seconds={seconds!r} is less than one latent frame "
+                             f"({cfg.audio_codec.hop_length} samples at {cfg.audio_codec.sample_rate} Hz)")
+        return frames
+
+    def _codec_segment(self, frames: int, tile_frames: int, decode: bool) -> int:
+        """the samples of the longest segment a pass over tiles of `tile_frames` runs (samaudio_codec_tile_samples): what the
+        workspace of a tiled call is sized by"""
+        if int(tile_frames) < 1:
+            raise ValueError(f"tile_frames={tile_frames!r}: a codec tile holds at least one latent frame")
+        return int(self._lib.samaudio_codec_tile_samples(self._ctx, frames, int(tile_frames), int(decode)))
+
+    def _codec_tiles_record(self, ctx, own: Context, items: int, frames: int, tile_frames: int, segment: int, decode: bool,
+                            pairs: bool = False) -> Dict[str, int]:
+        """what a tiled call on `ctx` in `own`'s workspace runs: the engine takes as many items per pass as the workspace holds
+        segments of (samaudio_workspace_bytes is linear in the items; a pass holds whole pairs)"""
+        from .context import _aligned
+        usable = _aligned(own._workspace)[1]
+        one = self._lib.samaudio_workspace_bytes(ctx, 0, 0, 0, 1, segment)
+        per_item = self._lib.samaudio_workspace_bytes(ctx, 0, 0, 0, 2, segment) - one
+        chunk = min(items, (usable - (one - per_item)) // per_item)
+        if pairs and chunk > 1:
+            chunk &= ~1
+        return dict(tile_frames=int(tile_frames), halo_frames=int(self._lib.samaudio_codec_halo_frames(ctx, int(decode))),
+                    tiles=-(-frames // int(tile_frames)) if tile_frames < frames else 1, passes=-(-items // chunk))
+
+    def encode_audio(self, audios: torch.Tensor, tile_frames: Optional[int] = None) -> torch.Tensor:
         """audios [B,1,Tw] -> mean latent, channels-last [B, T, codebook_dim] (reference codec.py:65-78;
-        the reference returns [B, C, T] and transposes at model.py:183)."""
+        the reference returns [B, C, T] and transposes at model.py:183).
+        `tile_frames` (None: one pass over the whole waveforms): in time tiles of that many latent frames -
+        the same bits from a workspace sized by the tile; `last_codec_tiles["encode"]` says what ran."""
         if not self._has_codec:
             raise RuntimeError("audio_codec weights are not loaded")
         wav = self._pad_to_hop(audios.to(self.device, torch.float32)).squeeze(1).contiguous()
@@ -596,18 +640,29 @@ class SAMAudio(Context):
         frames = samples // self.cfg.audio_codec.hop_length
         z = torch.empty(items, frames, self.cfg.audio_codec.codebook_dim, device=self.device)
         with torch.cuda.device(self.device):
+            if tile_frames is not None:
+                segment = self._codec_segment(frames, tile_frames, False)
+                self._ensure_workspace(0, 0, 0, self._codec_chunk(items), segment)
+                hip.check(self._lib.samaudio_codec_encode_tiled(self._ctx, hip.ptr(wav), items, samples, int(tile_frames), hip.ptr(z),
+                                                                hip.current_stream_ptr()))
+                self.last_codec_tiles["encode"] = self._codec_tiles_record(self._ctx, self, items, frames, tile_frames, segment, False)
+                return z
             self._ensure_workspace(0, 0, 0, self._codec_chunk(items), samples)
             hip.check(self._lib.samaudio_codec_encode(self._ctx, hip.ptr(wav), items, samples, hip.ptr(z),
                                                       hip.current_stream_ptr()))
         return z
 
     def decode_audio(self, latents: torch.Tensor, lane: Optional[_Lane] = None,
-                     out: Optional[torch.Tensor] = None, pairs: bool = False) -> torch.Tensor:
+                     out: Optional[torch.Tensor] = None, pairs: bool = False, tile_frames: Optional[int] = None,
+                     record: Optional[list] = None) -> torch.Tensor:
         """latents channels-last [N, T, codebook_dim] -> [N, T*hop] (reference codec.py:86-89).  `lane`: run on that
         lane's context (and on the current stream); `out`: a contiguous [N, T*hop] fp32 destination.
         `pairs`: `latents` is the ODE state [rows, T, 2*codebook_dim]; waveform 2b = the first codebook_dim channels of row
         block b (target), 2b + 1 the rest (residual) - reference model.py:291-295, gathered inside the engine instead of a
-        transposed copy."""
+        transposed copy.
+        `tile_frames` (None: one pass over the whole latents): in time tiles of that many latent frames -
+        the same bits from a workspace sized by the tile; `last_codec_tiles["decode"]` says what ran (`record`: a list that takes
+        the entry instead - the row groups of `streams` > 1 each decode their own rows)."""
         if not self._has_codec:
             raise RuntimeError("audio_codec weights are not loaded")
         lat = latents.to(self.device, torch.float32).contiguous()
@@ -618,18 +673,29 @@ class SAMAudio(Context):
         samples = frames * self.cfg.audio_codec.hop_length
         wav = out if out is not None else torch.empty(items, samples, device=self.device)
         assert wav.shape == (items, samples) and wav.is_contiguous() and wav.dtype == torch.float32
+        # (tiles: every workspace below is sized for the longest segment instead of the whole waveform)
+        span = samples if tile_frames is None else self._codec_segment(frames, tile_frames, True)
         with torch.cuda.device(self.device):
-            self._ensure_workspace(0, 0, 0, self._codec_chunk(items), samples, lane=lane)
+            self._ensure_workspace(0, 0, 0, self._codec_chunk(items), span, lane=lane)
             ctx = self._ctx if lane is None else lane._ctx
+            own = lane if lane is not None else self
             if self.codec_decode == "16":
                 # the 16-bit codec context of this owner, on the owner's workspace (sized for the fp32 context's codec pass, which
                 # needs more; stream order keeps the two contexts' uses of it apart)
-                own = lane if lane is not None else self
                 if own._codec16 is None:
                     own._codec16 = _Codec16(self)
                 ctx = own._codec16._ctx
-                own.lend_workspace(own._codec16, 0, 0, 1, self._codec_chunk(items), samples)
-            if pairs:
+                own.lend_workspace(own._codec16, 0, 0, 1, self._codec_chunk(items), span)
+            if tile_frames is not None:
+                fn = self._lib.samaudio_codec_decode_pairs_tiled if pairs else self._lib.samaudio_codec_decode_tiled
+                hip.check(fn(ctx, hip.ptr(lat), items // 2 if pairs else items, frames, int(tile_frames), hip.ptr(wav),
+                             hip.current_stream_ptr()))
+                rec = self._codec_tiles_record(ctx, own, items, frames, tile_frames, span, True, pairs)
+                if record is not None:
+                    record.append(rec)
+                else:
+                    self.last_codec_tiles["decode"] = rec
+            elif pairs:
                 hip.check(self._lib.samaudio_codec_decode_pairs(ctx, hip.ptr(lat), items // 2, frames, hip.ptr(wav),
                                                                 hip.current_stream_ptr()))
             else:
@@ -769,8 +835,9 @@ class SAMAudio(Context):
 
     def _solve_concurrent(self, noise: torch.Tensor, ode_opt: Dict[str, Any], cond: List[Optional[torch.Tensor]],
                           groups: int, decode: bool = False, anchors_validated: bool = False, candidates: int = 1,
-                          latent: bool = False):
-        """prepare + ODE solve (+ DAC-VAE decode of target and residual when `decode`) of `groups` contiguous row groups,
+                          latent: bool = False, codec_tile: Optional[int] = None):
+        """`codec_tile`: the time tile of the groups' decodes in latent frames (None: whole waveforms).
+        prepare + ODE solve (+ DAC-VAE decode of target and residual when `decode`) of `groups` contiguous row groups,
         each on its own engine context and HIP stream, driven by one host thread per group (the C calls release the GIL).
         Rows are independent, so the result equals the single-stream one bit for bit.  Returns the
         latent state, and with `decode` also the waveforms [rows, 2, samples] (model.py:291-295)."""
@@ -797,6 +864,7 @@ class SAMAudio(Context):
         self._apply_options(groups)
         main = torch.cuda.current_stream(self.device)
         errors: List[BaseException] = []
+        tile_recs: List[Dict[str, int]] = []   # tiled decodes: one entry per group
 
         def work(i: int, lane: Optional[_Lane]):
             try:
@@ -825,7 +893,8 @@ class SAMAudio(Context):
                         hip.check(self._lib.samaudio_ode_solve(ctx, hip.ptr(state[sl]), method, g, len(grid),
                                                                hip.current_stream_ptr()))
                     if decode:   # waveforms (2b, 2b+1) = (target, residual) of row b, gathered from the state inside the engine
-                        self.decode_audio(state[sl], lane=lane, out=wavs[2 * rr.start: 2 * rr.stop], pairs=True)
+                        self.decode_audio(state[sl], lane=lane, out=wavs[2 * rr.start: 2 * rr.stop], pairs=True,
+                                          tile_frames=codec_tile, record=tile_recs)
             except BaseException as exc:  # re-raised on the caller's thread
                 errors.append(exc)
 
@@ -844,6 +913,8 @@ class SAMAudio(Context):
                 main.wait_stream(lane.stream)
         if errors:
             raise errors[0]
+        if tile_recs:   # the groups' passes add up; tile, halo and tile count are the same for all
+            self.last_codec_tiles["decode"] = dict(tile_recs[0], passes=sum(r["passes"] for r in tile_recs))
         if adaptive:
             self._set_ode_stats(group_stats, state)
         return (state, wavs.view(rows, 2, -1)) if decode else state
@@ -872,8 +943,11 @@ class SAMAudio(Context):
                  ode_opt: Dict[str, Any] = DFLT_ODE_OPT, reranking_candidates: int = 1,
                  predict_spans: bool = False, output_sampling_rate: Optional[int] = None,
                  window_seconds: Optional[float] = None, window_overlap_seconds: Optional[float] = None,
-                 seed: Optional[int] = None, step_control: Optional[str] = None) -> SeparationResult:
-        """Reference model.py:247-338.  `reranking_candidates > 1` draws that many ODE solutions per clip and lets
+                 seed: Optional[int] = None, step_control: Optional[str] = None,
+                 codec_tile_seconds: Optional[float] = None) -> SeparationResult:
+        """Reference model.py:247-338.  `codec_tile_seconds` (None = the model's setting, see SAMAudio(...)):
+        the mixture's encode and the decode of the pairs run in time tiles of that length on every path below - the same bits, a
+        codec scratch sized by the tile; `last_codec_tiles` says what ran.  The rerankers and the span predictor see whole clips.  `reranking_candidates > 1` draws that many ODE solutions per clip and lets
         `visual_ranker` / `text_ranker` pick one (model.py:306-330); `predict_spans` runs `span_predictor` first
         (model.py:259-268; mind quirk Q13 below).  `output_sampling_rate`: when set and different from the codec's rate, the chosen
         target and residual of every clip are resampled to it on the device (sam_audio_amd/audio.py resample: what the reference's
@@ -922,7 +996,8 @@ class SAMAudio(Context):
             window = (longform.seconds_to_frames(window_seconds, c.sample_rate, c.hop_length),
                       longform.seconds_to_frames(window_overlap_seconds, c.sample_rate, c.hop_length))
             longform.check_window(*window, self.cfg.transformer.max_positions)
-        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans, window, seed)   # (windows + adaptive: per clip)
+        tile = self._codec_tile_frames(self.codec_tile_seconds if codec_tile_seconds is None else codec_tile_seconds, self.cfg)
+        res = self._separate(batch, noise, ode_opt, reranking_candidates, predict_spans, window, seed, tile)   # (windows + adaptive: per clip)
         if output_sampling_rate is None or int(output_sampling_rate) == self.sample_rate:
             return res
         from . import audio
@@ -932,8 +1007,11 @@ class SAMAudio(Context):
                                     noise=res.noise)
 
     def _separate(self, batch: Batch, noise: Optional[torch.Tensor], ode_opt: Dict[str, Any], reranking_candidates: int,
-                  predict_spans: bool, window: Optional[tuple] = None, seed: Optional[int] = None) -> SeparationResult:
+                  predict_spans: bool, window: Optional[tuple] = None, seed: Optional[int] = None,
+                  codec_tile: Optional[int] = None) -> SeparationResult:
+        """`codec_tile`: the codec's time tile in latent frames (None: whole waveforms), handed to every codec call below"""
         cand = int(reranking_candidates)
+        self.last_codec_tiles = {}
         with torch.cuda.device(self.device):
             # Nothing of torch's own arithmetic runs between the first and the last kernel of a step: the noise is drawn first
             # (model.py:274-275: `torch.randn_like` on the model device), features = (z | z) (model.py:182-184), the sample-major
@@ -949,7 +1027,7 @@ class SAMAudio(Context):
             if noise is None:
                 noise = torch.randn(B * cand, T, C2, device=self.device)         # model.py:274-275
             assert tuple(noise.shape) == (B * cand, T, C2), "noise must be [B*candidates, T, 256]"
-            z = self.encode_audio(batch.audios)                                  # [B, T, 128]
+            z = self.encode_audio(batch.audios, tile_frames=codec_tile)          # [B, T, 128]
             assert z.shape[:2] == (B, T) and 2 * z.size(2) == C2
             text, text_mask = self._text(batch)
             video = None
@@ -982,7 +1060,7 @@ class SAMAudio(Context):
                 # each group also decodes its own rows on its stream: the codec's HBM-bound convolutions of one group run
                 # beside the other group's kernels instead of after both solves
                 latent, wavs = self._solve_concurrent(noise, ode_opt, cond, groups, decode=True, anchors_validated=validated,
-                                                      candidates=cand, latent=True)
+                                                      candidates=cand, latent=True, codec_tile=codec_tile)
             else:
                 self._apply_options(1)
                 self._prepare(*cond, anchors_validated=validated, candidates=cand, latent=True)
@@ -991,7 +1069,7 @@ class SAMAudio(Context):
             # [Bc, T, 2C] -> waveforms (2b, 2b+1) = (target, residual) of row b (model.py:291-295)
             Bc = latent.size(0)
             if wavs is None:
-                wavs = self.decode_audio(latent, pairs=True).view(Bc, 2, -1)
+                wavs = self.decode_audio(latent, pairs=True, tile_frames=codec_tile).view(Bc, 2, -1)
             # codec.py:91-97, from the batch's host copy of the frame counts: slicing by device scalars would block on the GPU
             sizes = [n * hop for n in (getattr(batch, "sizes_host", None) or [int(v) for v in batch.sizes.tolist()])]
             target = self.unbatch(wavs[:, 0].view(B, cand, -1), sizes)
